@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py - controller-steps/s of the fused MPC random-shooting plan step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line.
+`--full` adds everything listed below (kernel-only loop and correctness gate against the golden vector, device-RNG and
+foreign-draw legs, config 5, roofline, collective and strong-scaling figures, CPU baseline).  `--dump-outputs DIR`
+writes what the last timed step returned to its caller as DIR/<name>.npy (float64): with the same arguments the
+inputs are the same from run to run, so two builds can be compared output for output.
 
 Workload (BASELINE.json config 2, the configuration `metric` is quoted on): HalfCheetah-shaped
 synthetic inputs, n_candidates = 2000 per GPU, horizon 30, mean-ensemble of 5 MLPs
@@ -17,7 +23,7 @@ sharded over the ranks, 2000 per GPU (weak scaling: N = 8 is BASELINE.json's con
 16000-candidate plan per step); `value` then counts 2000-candidate controller steps,
 value = N * plan_steps_per_s, and `config.plan_steps_per_s` states the plans themselves.
 
-Beside it, in `config`: the same loop with `rng="device"` (candidates drawn on the GPU) and the
+With `--full`, beside it, in `config`: the same loop with `rng="device"` (candidates drawn on the GPU) and the
 kernel-only loop over candidates resident in HBM (memset + kernel [+ all-reduce]) - the three modes of
 SURVEY.md H5.  Extra objects: `roofline` (fp32 MFMA roofline of the rollout kernel, HIP events around
 each launch on the launch stream) and `cpu_baseline` (the NumPy oracle = CPU restatement of the reference
@@ -112,15 +118,27 @@ def _self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
-def _timed_calls(fn, steps, warmup, sync):
+def _timed_calls(fn, steps, warmup, sync, last=None):
+    """Seconds for `steps` calls of fn after `warmup` untimed ones; `last` (a list) receives what the final timed call returned."""
     for _ in range(warmup):
         fn()
     sync()
+    r = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        fn()
+        r = fn()
     sync()
-    return time.perf_counter() - t0
+    dt = time.perf_counter() - t0
+    if last is not None:
+        last.append(r)
+    return dt
+
+
+def _dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, as float64 (the outputs are a few numbers per step: no sampling needed)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
 
 
 def main():
@@ -128,7 +146,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel-only loop + golden-vector gate, device-RNG and foreign-draw legs, "
+                         "config 5, roofline, collective / strong-scaling figures (N > 1), CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (chosen actions, best index and return) as DIR/<name>.npy")
     ap.add_argument("--no-e2e", action="store_true",
                     help="profiling runs: only the kernel-only loop (candidates resident in HBM), so that the "
                          "kernel statistics hold the timed plan launches and nothing else; `value` is then that loop")
@@ -230,14 +253,17 @@ def main():
         if world > 1:
             dist.all_reduce(best, op=dist.ReduceOp.MAX)
 
-    # correctness gate: the first plan must pick the reference planner's candidate
-    resident_step()
-    torch.cuda.synchronize()
-    ret0, idx0 = _lib.key_decode(int(best.cpu()[0]))
+    full = args.full
+    # correctness gate (--full): the first plan must pick the reference planner's candidate
+    ret0 = idx0 = None
     index_match = None
-    if gold_glob is not None:
-        index_match = bool(idx0 == int(gold_glob["best"][0]))
-        assert index_match, "plan picked candidate %d, reference picked %d" % (idx0, int(gold_glob["best"][0]))
+    if full:
+        resident_step()
+        torch.cuda.synchronize()
+        ret0, idx0 = _lib.key_decode(int(best.cpu()[0]))
+        if gold_glob is not None:
+            index_match = bool(idx0 == int(gold_glob["best"][0]))
+            assert index_match, "plan picked candidate %d, reference picked %d" % (idx0, int(gold_glob["best"][0]))
     # Clocks: after idle time the MI355X needs some tens of milliseconds of back-to-back work to reach its ~2.39 GHz (2.0 -
     # 2.15 GHz over the first launches, tools/timeline*.py), and the fractions below are quoted against the peak-clock number.
     # A short run (the driver's 20 steps are 30 ms) measured the ramp, not the kernel: round 3 read 649.7 steps/s there and
@@ -250,23 +276,30 @@ def main():
                 native.plan_rs(obs0, bufs[1], 1, N_CAND, HORIZON, 1.0, spec, cand_offset=lo, best_key=best)
             torch.cuda.synchronize()
 
-    clock_warm()
-    resident_s = max_over_ranks(_timed_calls(resident_step, args.steps, args.warmup, sync))
-    native.ctx.launch_status()          # raises if any launch flagged a problem
+    # ---- kernel-only loop, timed (--full; without it only as the headline of --no-e2e) ------------------------------------
+    resident_s = None
+    resident_key = None
+    if full or args.no_e2e:
+        clock_warm()
+        resident_s = max_over_ranks(_timed_calls(resident_step, args.steps, args.warmup, sync))
+        resident_key = int(best.cpu()[0])   # the last timed plan's key (all-reduced at N > 1)
+        native.ctx.launch_status()          # raises if any launch flagged a problem
 
-    # ---- kernel duration: HIP events around each launch on the launch stream (every rank: min / max over ranks at N > 1) -----
-    k2 = min(args.steps, 100)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(k2)]
-    clock_warm()
-    for i in range(k2):
-        evs[i][0].record()
-        native.plan_rs(obs0, bufs[i % len(bufs)], 1, N_CAND, HORIZON, 1.0, spec, cand_offset=lo, best_key=best)
-        evs[i][1].record()
-    torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    # ---- kernel duration (--full): HIP events around each launch on the launch stream (every rank: min / max over ranks at N > 1) -----
+    kern_ms = None
     kern_ms_ranks = None
     collective = None
-    if world > 1:
+    if full:
+        k2 = min(args.steps, 100)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(k2)]
+        clock_warm()
+        for i in range(k2):
+            evs[i][0].record()
+            native.plan_rs(obs0, bufs[i % len(bufs)], 1, N_CAND, HORIZON, 1.0, spec, cand_offset=lo, best_key=best)
+            evs[i][1].record()
+        torch.cuda.synchronize()
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    if full and world > 1:
         t = torch.zeros((world,), dtype=torch.float64, device=dev)
         t[rank] = kern_ms
         dist.all_reduce(t)
@@ -296,11 +329,12 @@ def main():
                               "on the launch stream | host wall clock incl. the stream synchronisation" % k3}
         dist.barrier()
 
-    # ---- completed controller steps through the drop-in MPCController ------------------------------------------
+    # ---- completed controller steps through the drop-in MPCController (plain run: parity mode only) --------------------
     e2e = {}
     e2e_index_match = None
+    headline_out = None                 # what the last timed parity-mode step returned to its caller
     if not args.no_e2e:
-        for mode in ("numpy", "device"):
+        for mode in (("numpy", "device") if full else ("numpy",)):
             ctrl = cases.product_controller(case, model=model, env=env, rng=mode)
             np.random.seed(0)                   # every rank alike: the shards are slices of ONE candidate tensor
             torch.manual_seed(0)
@@ -312,16 +346,20 @@ def main():
             ctrl.get_actions(obs_np)
             ctrl.get_actions(obs_np)
             clock_warm()
-            if mode == "numpy" and gold_glob is not None:
+            if full and mode == "numpy" and gold_glob is not None:
                 e2e_index_match = bool(first_index == int(gold_glob["best"][0]))
                 assert e2e_index_match, "get_actions picked %d, reference picked %d" % (first_index, int(gold_glob["best"][0]))
-            e2e[mode] = max_over_ranks(_timed_calls(lambda: ctrl.get_actions(obs_np), args.steps, args.warmup, sync))
+            last = []
+            e2e[mode] = max_over_ranks(_timed_calls(lambda: ctrl.get_actions(obs_np), args.steps, args.warmup, sync, last))
             if mode == "numpy":
+                if last[0] is not None:
+                    headline_out = {"actions": np.array(last[0][0]), "best_index": np.array(ctrl.last_plan["best_index"]),
+                                    "best_return": np.array(ctrl.last_plan["best_return"])}
                 e2e["draw_ahead_hits"] = int(ctrl.draw_ahead_stats()["hits"])
                 e2e["native_step"] = ctrl._cstep is not None
                 if ctrl._cstep is not None:
                     e2e["native_step_stage_us"] = {k: round(v, 1) for k, v in ctrl._cstep.stats()["stage_us"].items()}
-            if mode == "numpy":
+            if full and mode == "numpy":
                 # the mode an in-process env sees (n_parallel = 1: samplers/vectorized_env_executor.py:45 ->
                 # envs/mujoco_env.py:85-87 reset noise; samplers/utils.py rollout()): somebody else consumes the global
                 # generator between two plans, so the block drawn ahead is stale and the step draws synchronously
@@ -345,7 +383,7 @@ def main():
     # policies/mpc_controller.py get_cem_action_device).  n = 4000 is the WHOLE plan at every N (strong scaling: 4000 / N per
     # rank - at N = 8 the 500-candidate shard the member fan of csrc/l2a_mfma.h exists for).  Bounded: <= ~0.5 s.
     c5 = None
-    if not args.no_e2e:
+    if full and not args.no_e2e:
         case5 = cases.CASES["c5_hc_cem_n4000_h30_e5"]
         ctrl5 = cases.product_controller(case5, model=model, env=env, rng="device")
         torch.manual_seed(0)                    # every rank alike: the ranks sample the same normals and keep their slice
@@ -363,7 +401,7 @@ def main():
 
     # ---- strong scaling of THIS plan (n_glob candidates): rank 0 alone runs the whole plan on its one GPU ------------
     strong = None
-    if world > 1:
+    if full and world > 1:
         full_ms = None
         if rank == 0:
             a_full = torch.rand((HORIZON, n_glob, ACT_DIM), generator=gen, device=dev) * 2.0 - 1.0
@@ -387,9 +425,9 @@ def main():
                       "note": "the SAME %d-candidate plan on one GPU (rank 0 alone) vs sharded over %d GPUs incl. the "
                               "all-reduce; kernel-only loops" % (n_glob, world)}
 
-    # ---- CPU baseline: the NumPy oracle on this box's host cores (N = 1, rank 0) ---------------
+    # ---- CPU baseline (--full): the NumPy oracle on this box's host cores (N = 1, rank 0) ---------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import make_reward
         from oracle.planner import rollout_returns
         case1 = cases.CASES["c2_hc_rs_n2000_h30_e5"]
@@ -463,15 +501,16 @@ def main():
                                     "read both (at N = 1 they coincide)",
                 "candidates_per_plan": n_glob,
                 "plan_steps_per_s": round(plan_steps, 3),
-                "kernel_only_plan_steps_per_s": round(args.steps / resident_s, 3),
-                "kernel_only_ms_per_step": round(1e3 * resident_s / args.steps, 4),
+                "kernel_only_plan_steps_per_s": None if resident_s is None else round(args.steps / resident_s, 3),
+                "kernel_only_ms_per_step": None if resident_s is None else round(1e3 * resident_s / args.steps, 4),
                 "mlp_steps_per_ms": round(world * N_CAND * HORIZON * ENSEMBLE / ms_per_step, 1),
                 "collective": "int64 MAX all-reduce of 1 key per plan step" if world > 1 else "none",
                 "backend": backend, "collective_ranks": collective_ranks,
                 "action_index_match_vs_reference": index_match if e2e_index_match is None else
                                                    bool(index_match and e2e_index_match),
-                "best_index": idx0, "best_return": round(ret0, 4),
+                "best_index": idx0, "best_return": None if ret0 is None else round(ret0, 4),
                 "host_rng_threads": fast_rng.threads(),
+                "full": full,
                 "clock_warm": "0.15 s of untimed kernel launches in front of every timed leg (the board's clock ramp; since round 4 - "
                               "BENCH_r01..r03 were measured without it and read 2 - 3 % lower on short runs)",
             },
@@ -485,7 +524,8 @@ def main():
                                                 else "torch.distributed behind the C step's reduce callback")
             if e2e.get("native_step_stage_us"):
                 out["config"]["native_step_stage_us"] = e2e["native_step_stage_us"]
-            out["config"]["host_path_us_per_step"] = round(1e3 * (ms_per_step - 1e3 * resident_s / args.steps), 1)
+            if resident_s is not None:
+                out["config"]["host_path_us_per_step"] = round(1e3 * (ms_per_step - 1e3 * resident_s / args.steps), 1)
         if "foreign" in e2e:
             out["config"]["get_actions_parity_foreign_draw_plan_steps_per_s"] = round(args.steps / e2e["foreign"], 3)
             out["config"]["foreign_draw_note"] = ("one np.random.uniform() consumed between calls (an in-process env reset): "
@@ -543,6 +583,11 @@ def main():
             }
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if args.dump_outputs:
+            if headline_out is None:        # --no-e2e: the kernel-only loop's last plan (key all-reduced at N > 1)
+                ret_k, idx_k = _lib.key_decode(resident_key)
+                headline_out = {"best_index": np.array([idx_k]), "best_return": np.array([ret_k])}
+            _dump_outputs(args.dump_outputs, headline_out)
         print(json.dumps(out), flush=True)
 
     if world > 1:

@@ -18,5 +18,5 @@ echo "== same with the Python path (L2A_NATIVE_STEP=0)"
 L2A_NATIVE_STEP=0 timeout 600 python tools/probe_step.py $WL --calls=300 > $OUT/probe_steps_python.jsonl 2>> $OUT/probe_steps.err; echo "probe rc=$?"
 cut -c1-400 $OUT/probe_steps_python.jsonl
 echo "== bench"
-timeout 600 python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 cat $OUT/bench.json; tail -5 $OUT/bench.err

@@ -15,7 +15,7 @@ echo "== pytest -m gpu"
 timeout 1200 python -m pytest tests -m gpu -q --timeout 300 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
 tail -25 $OUT/pytest_gpu.log
 echo "== bench"
-timeout 600 python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 cat $OUT/bench.json; tail -5 $OUT/bench.err
 echo "== rocprof kernel trace"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o trace -- python $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-e2e > $GRAFT_REPO_ROOT/$OUT/prof_bench.json 2> $GRAFT_REPO_ROOT/$OUT/prof.err); echo "rocprof rc=$?"
@@ -82,7 +82,7 @@ timeout 300 python tools/bench_rng.py > $OUT/rng.jsonl 2>&1; echo "rng rc=$?"
 timeout 300 python tools/probe_e2e.py > $OUT/probe_c2.jsonl 2> $OUT/probe.err; echo "probe c2 rc=$?"
 timeout 300 python tools/probe_e2e.py c5_hc_cem_n4000_h30_e5 > $OUT/probe_c5.jsonl 2>> $OUT/probe.err; echo "probe c5 rc=$?"
 echo "== N = 2 code path: two gloo ranks sharing this GPU (self-launch; numbers meaningless)"
-L2A_BENCH_SHARE_GPU=1 L2A_SPLIT=0 timeout 600 python bench.py --gpus 2 --steps 10 --warmup 3 > $OUT/bench_share2.json 2> $OUT/bench_share2.err; echo "share2 rc=$?"
+L2A_BENCH_SHARE_GPU=1 L2A_SPLIT=0 timeout 600 python bench.py --full --gpus 2 --steps 10 --warmup 3 > $OUT/bench_share2.json 2> $OUT/bench_share2.err; echo "share2 rc=$?"
 echo "== round 6: member fan (config-5 shards), the stationary-cluster probe, two planners on the blocking path"
 timeout 200 python tools/timeline.py c5_hc_cem_n4000_h30_e5 n=500 > $OUT/timeline_c5shard_fan.txt 2>&1; echo "timeline fan rc=$?"
 timeout 200 python tools/timeline.py c3_ant_rs_n2000_h20_pb5 > $OUT/timeline_c3.txt 2>&1; echo "timeline c3 (rest launch: shared tiles) rc=$?"
