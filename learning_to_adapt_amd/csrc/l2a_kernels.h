@@ -131,9 +131,14 @@ __host__ __device__ inline void l2a_pack_decode(long long idx, int KG, int* k, i
 // ------------------------------------------------------------------------------------------
 // shared device helpers
 // ------------------------------------------------------------------------------------------
+// max(x, f) that propagates NaN like np.maximum / torch.relu (IEEE 754-2019 maximum, one v_maximum3_f32): fmaxf is
+// maxNum, fmaxf(NaN, 0) = 0, and would let a diverged candidate (inf + -inf in a pre-activation) look finite.
+// Equal to fmaxf on every non-NaN input, signed zeros included (max(-0, +0) = +0).
+__device__ __forceinline__ float l2a_max_nan(float x, float f) { return __builtin_elementwise_maximum(x, f); }
+
 __device__ __forceinline__ float l2a_act1(float x, int kind) {
     switch (kind) {
-        case L2A_ACT_RELU: return fmaxf(x, 0.0f);
+        case L2A_ACT_RELU: return l2a_max_nan(x, 0.0f);
         case L2A_ACT_TANH: return tanhf(x);
         case L2A_ACT_SIGMOID: return 1.0f / (1.0f + expf(-x));
         case L2A_ACT_SWISH: return x / (1.0f + expf(-x));
@@ -143,8 +148,8 @@ __device__ __forceinline__ float l2a_act1(float x, int kind) {
 
 __device__ __forceinline__ f32x4 l2a_act4(f32x4 v, int kind) {
     if (kind == L2A_ACT_RELU) {
-        v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f);
-        v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+        v.x = l2a_max_nan(v.x, 0.0f); v.y = l2a_max_nan(v.y, 0.0f);
+        v.z = l2a_max_nan(v.z, 0.0f); v.w = l2a_max_nan(v.w, 0.0f);
         return v;
     }
     if (kind == L2A_ACT_IDENTITY) return v;
@@ -153,7 +158,8 @@ __device__ __forceinline__ f32x4 l2a_act4(f32x4 v, int kind) {
     return v;
 }
 
-// (orderable_u32(ret) << 31) | (0x7fffffff - index); NaN sorts above +inf like np.argmax.
+// (orderable_u32(ret) << 31) | (0x7fffffff - index); NaN sorts above +inf like np.argmax, and -0 packs as +0
+// (np.argmax holds them equal: the first index wins).
 __host__ __device__ inline unsigned long long l2a_key_pack(float ret, int index) {
     unsigned int u;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -162,6 +168,7 @@ __host__ __device__ inline unsigned long long l2a_key_pack(float ret, int index)
     union { float f; unsigned int u; } cv; cv.f = ret; u = cv.u;
 #endif
     unsigned int ord;
+    if (ret == 0.0f) u = 0u;
     if (ret != ret) ord = 0xffffffffu;
     else ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ((unsigned long long)ord << 31) | (unsigned long long)(0x7fffffffu - (unsigned int)index);

@@ -396,7 +396,7 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_lstm_mfma_k(const L2ALstmPara
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - p.rw.ctrl_coef * asq_prev[nt];
+            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq_prev[nt] : 0.0f);
             float psq = 0.0f;
 #pragma unroll
             for (int c = 0; c < OT; ++c) {
@@ -421,7 +421,8 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_lstm_mfma_k(const L2ALstmPara
 #pragma unroll
                 for (int ii = 0; ii < 4; ++ii) {
                     const int dim = 16 * c + 4 * qq + ii;
-                    if (dim == p.rw.vel_index) plin += p.rw.w_vel * d[ii] * p.rw.inv_dt;
+                    if (p.rw.w_vel != 0.0f && dim == p.rw.vel_index)     // d + (obs - obs): next - obs (l2a_mfma.h)
+                        plin += p.rw.w_vel * (d[ii] + (st[nt][c][ii] - st[nt][c][ii])) * p.rw.inv_dt;
                     const bool in_dist = (p.rw.dist_coef != 0.0f) && (dim >= p.rw.dist_index) &&
                                          (dim < p.rw.dist_index + 3) && (dim < obs_dim);
                     psq += in_dist ? nx[ii] * nx[ii] : 0.0f;

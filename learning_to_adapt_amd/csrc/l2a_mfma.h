@@ -97,12 +97,13 @@ __device__ __forceinline__ f32x4 l2a_ldw(__amdgpu_buffer_rsrc_t rs, int voff, in
 
 // Activation.  GACT == false covers relu and identity branch-free as max(x, floor) with floor = 0
 // or -inf: the generic path (tanh / sigmoid / swish) inlines ~10 KiB of code per call site, and
-// jumping around it in every epilogue cost ~2k cycles per layer in instruction fetch.
+// jumping around it in every epilogue cost ~2k cycles per layer in instruction fetch.  The max
+// propagates NaN (l2a_max_nan), so max(NaN, -inf) = NaN keeps the identity exact.
 template <bool GACT>
 __device__ __forceinline__ f32x4 l2a_actv(f32x4 v, int kind, float floor) {
     if (GACT) return l2a_act4(v, kind);
-    v.x = fmaxf(v.x, floor); v.y = fmaxf(v.y, floor);
-    v.z = fmaxf(v.z, floor); v.w = fmaxf(v.w, floor);
+    v.x = l2a_max_nan(v.x, floor); v.y = l2a_max_nan(v.y, floor);
+    v.z = l2a_max_nan(v.z, floor); v.w = l2a_max_nan(v.w, floor);
     return v;
 }
 
@@ -1256,7 +1257,8 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
         disc_pow *= p.discount;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - p.rw.ctrl_coef * asq_t[nt];
+            // (a term whose coefficient is zero is left out, as RewardSpec.evaluate leaves it out: 0 x inf would be NaN)
+            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq_t[nt] : 0.0f);
             float psq = 0.0f;
 #pragma unroll
             for (int c = 0; c < OT; ++c) {
@@ -1273,11 +1275,21 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                         d[ii] = (fabsf(q) < INFINITY) ? qc : q;
                     }
                 }
-                const f32x4 nx = st[nt][c] + d;
+                f32x4 nx = st[nt][c] + d;
+                if (c == OT - 1) {
+                    // the state's padding lanes stay exact zeros: a diverged candidate's delta carries inf x 0 = NaN there
+                    // (zero weight columns, zero denormalisation), which the next step's zero weight rows would spread
+                    // over the whole candidate - where the oracle stays at +-inf
+#pragma unroll
+                    for (int ii = 0; ii < 4; ++ii)
+                        if (16 * c + 4 * qq + ii >= obs_dim) nx[ii] = 0.0f;
+                }
 #pragma unroll
                 for (int ii = 0; ii < 4; ++ii) {
                     const int dim = 16 * c + 4 * qq + ii;
-                    if (dim == p.rw.vel_index) plin += p.rw.w_vel * d[ii] * p.rw.inv_dt;
+                    // next - obs as the oracle has it: d + (obs - obs) is d for a finite obs (bit for bit), NaN for +-inf
+                    if (p.rw.w_vel != 0.0f && dim == p.rw.vel_index)
+                        plin += p.rw.w_vel * (d[ii] + (st[nt][c][ii] - st[nt][c][ii])) * p.rw.inv_dt;
                     const bool in_dist = (p.rw.dist_coef != 0.0f) && (dim >= p.rw.dist_index) &&
                                          (dim < p.rw.dist_index + 3) && (dim < obs_dim);
                     psq += in_dist ? nx[ii] * nx[ii] : 0.0f;

@@ -458,12 +458,13 @@ __device__ __forceinline__ void l2a_lstm_micro_body(const L2ALstmParams& p, cons
                 const f32x4 d = s * osd + omu;
                 const f32x4 nx = st + d;
                 // reward in the 16-candidate kernel's order: quarter partials r_qq (lanes b = qq < 4), (r0 + r1) + (r2 + r3)
-                float plin = ((qq == 0) ? p.rw.alive : 0.0f) - p.rw.ctrl_coef * asq;
+                float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
                 float psq = 0.0f;
                 const int vi = p.rw.vel_index;
                 const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
-                const float dvel = l2a_from_row(dsel, vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
-                if (qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+                const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
+                const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
+                if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
 #pragma unroll
                 for (int ii = 0; ii < 4; ++ii) {
                     const int dim = 4 * b + ii;
@@ -875,14 +876,18 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
                     d[ii] = (fabsf(q) < INFINITY) ? qc : q;
                 }
             }
-            const f32x4 nx = st + d;
+            f32x4 nx = st + d;
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii)      // padding lanes stay exact zeros, also for a diverged candidate (l2a_mfma.h)
+                if (4 * b + ii >= obs_dim) nx[ii] = 0.0f;
             // reward in the 16-candidate kernel's order: quarter partials r_qq (lanes b = qq < 4), (r0 + r1) + (r2 + r3)
-            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - p.rw.ctrl_coef * asq;
+            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
             float psq = 0.0f;
             const int vi = p.rw.vel_index;
             const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
-            const float dvel = l2a_from_row(dsel, vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
-            if (qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+            const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
+            const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
+            if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii) {
                 const int dim = 4 * b + ii;

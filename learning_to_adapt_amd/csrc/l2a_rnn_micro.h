@@ -484,12 +484,13 @@ __device__ __forceinline__ void l2a_rnn_micro_body(const L2ALstmParams& p, const
             s = l2a_act4(s + bias, p.output_act);
             const f32x4 d = s * osd + omu;
             const f32x4 nx4 = st + d;
-            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - p.rw.ctrl_coef * asq;
+            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
             float psq = 0.0f;
             const int vi = p.rw.vel_index;
             const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
-            const float dvel = l2a_from_row(dsel, vi >> 4);
-            if (qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+            const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
+            const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);  // d + (obs - obs): next - obs (l2a_mfma.h)
+            if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii) {
                 const int dim = 4 * b + ii;

@@ -154,8 +154,11 @@ __global__ void __launch_bounds__(256) l2a_rnn_valu_k(const L2ALstmParams p) {
         if (s == 0) {
             float asq = 0.0f;
             for (int k = 0; k < act_dim; ++k) asq = fmaf(arow[k], arow[k], asq);
-            float r = p.rw.alive - p.rw.ctrl_coef * asq;
-            if (p.rw.w_vel != 0.0f) r += p.rw.w_vel * ds[j * obs_dim + p.rw.vel_index] * p.rw.inv_dt;
+            float r = p.rw.alive - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
+            if (p.rw.w_vel != 0.0f) {       // d + (obs - obs): next - obs, NaN for an infinite obs (l2a_mfma.h)
+                const float so = ss[j * obs_dim + p.rw.vel_index];
+                r += p.rw.w_vel * (ds[j * obs_dim + p.rw.vel_index] + (so - so)) * p.rw.inv_dt;
+            }
             if (p.rw.dist_coef != 0.0f) {
                 float sq = 0.0f;
                 for (int d = p.rw.dist_index; d < p.rw.dist_index + 3 && d < obs_dim; ++d) {

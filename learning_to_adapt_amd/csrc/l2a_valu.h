@@ -128,11 +128,12 @@ __global__ void __launch_bounds__(256) l2a_rollout_valu_k(const L2AKParams p) {
             const int c = tid;
             float asq = 0.0f;
             for (int k = 0; k < act_dim; ++k) asq = fmaf(av[k * L2A_VT + c], av[k * L2A_VT + c], asq);
-            float r = p.rw.alive - p.rw.ctrl_coef * asq;
+            float r = p.rw.alive - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
             if (p.rw.w_vel != 0.0f) {
+                const float so = st[p.rw.vel_index * L2A_VT + c];
                 float d = ds[p.rw.vel_index * L2A_VT + c];
                 if (e_loop > 1) d = d / (float)e_loop;
-                r += p.rw.w_vel * d * p.rw.inv_dt;
+                r += p.rw.w_vel * (d + (so - so)) * p.rw.inv_dt;    // next - obs: NaN for an infinite obs (l2a_mfma.h)
             }
             if (p.rw.dist_coef != 0.0f) {
                 float sq = 0.0f;

@@ -67,6 +67,10 @@ def test_key_roundtrip_and_order():
     # NaN sorts above everything (np.argmax picks the first NaN)
     assert lib.l2a_key_encode(ctypes.c_float(float("nan")), 3) > lib.l2a_key_encode(ctypes.c_float(float("inf")), 0)
     assert lib.l2a_key_encode(ctypes.c_float(-1e30), 0) > 0    # 0 is the "no candidate" sentinel
+    # -0 and +0 are equal for np.argmax: the lower index wins whichever sign it carries
+    assert lib.l2a_key_encode(ctypes.c_float(-0.0), 0) > lib.l2a_key_encode(ctypes.c_float(0.0), 1)
+    assert lib.l2a_key_encode(ctypes.c_float(0.0), 0) > lib.l2a_key_encode(ctypes.c_float(-0.0), 1)
+    assert lib.l2a_key_encode(ctypes.c_float(-0.0), 5) > lib.l2a_key_encode(ctypes.c_float(-1e-45), 0)
 
 
 def test_pack_layer_is_a_padded_permutation():
