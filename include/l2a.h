@@ -313,6 +313,21 @@ int l2a_cem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, int n
  * returns are ordered as np.argmax orders them (a NaN is the maximum, the first one wins): a diverged plan reports NaN.  */
 int l2a_cem_pick(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m,
                  int D, int act_dim, int reference, float* out, void* stream);
+/* l2a_cem_refit_sample: l2a_cem_refit followed by l2a_cem_sample in ONE launch - iteration i's `returns` [m, n] and samples
+ * `a_clip_in` [n, m, D] in, iteration i + 1's samples out - bit-identical to the two calls (mean, std, elite_rows, a_clip, a_raw,
+ * seq; injected z or Philox z under (seed, offset); both readings).  mean_in [m, D]: the mean iteration i sampled with, read only;
+ * NULL (or == mean) updates `mean` in place.  The launch is one workgroup per (horizon step, candidate slice, statistics group):
+ * each ranks its group's returns itself, refits the act_dim dimensions of its step and samples them - no wait between
+ * workgroups.  Several slices per step only when neither mean_in nor a_clip_in is also an output (pass distinct buffers, e.g.
+ * ping-pong pairs, for the fast path); a_raw and seq must not alias a_clip_in.  Shapes beyond the launch's LDS budget (the
+ * pooled elite rows' values or 2 n + 4096 words) run the two calls instead, inside this call; the same argument checks as they
+ * have (n * 4 bytes within the LDS of a workgroup, at most 8192 elite rows per statistics group). */
+int l2a_cem_refit_sample(l2a_ctx* ctx, const float* returns, const float* a_clip_in, int n, int m, int h, int act_dim,
+                         int num_elites, int reference, float alpha, const float* z, unsigned long long seed,
+                         unsigned long long offset, const float* low, const float* high, int lo, int hi, int* elite_rows,
+                         const float* mean_in, float* mean, float* std, float* a_clip, float* a_raw, float* seq, void* stream);
+/* 1 when l2a_cem_refit_sample runs this shape as its one launch, 0 when it runs the two calls instead (or the shape is invalid). */
+int l2a_cem_refit_sample_fused(const l2a_ctx* ctx, int n, int m, int h, int act_dim, int num_elites, int reference);
 
 /* ---- sharded plans: the one collective ------------------------------------------------------
  * Candidates are independent, so G GPUs (one process and one context each) plan disjoint shards of one candidate
@@ -514,6 +529,28 @@ int l2a_controller_create_device(l2a_model* model, int m, int n, int h, const do
                                  const l2a_reward* reward, unsigned long long seed, l2a_controller** out);
 int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
                                       double discount, const l2a_reward* reward, unsigned long long seed, l2a_controller** out);
+/* ---- the CEM controller step as one call (device mode) -------------------------------------------------------------------
+ * `MPCController.get_cem_action_device` (policies/mpc_controller.py; the reference's `get_cem_action`, :71-106, with the normals
+ * drawn on the device): the whole plan step on the launch stream - l2a_cem_sample for iteration 0, then per iteration the fused
+ * rollout and ONE l2a_cem_refit_sample (the last iteration: l2a_cem_refit), l2a_cem_pick, and ONE read-back of the packed result.
+ * The normals of iteration `it` of the controller's s-th step are the Philox stream (seed) at offset (s * iters + it) * n * m * D,
+ * D = h * act_dim - with the same seed a step equals get_cem_action_device bit for bit (action, index, return, final mean / std).
+ *   iters       CEM iterations per step (`num_cem_iters`)
+ *   num_elites  max(int(n * percent_elites), 1), computed by the caller as the reference does
+ *   reference   1 = the reference's reading (unclipped rollouts, candidate-major rows, the pooled rank mask of :101); 0 = fixed
+ * Steps through l2a_controller_step / _begin / _finish / _stats / _destroy (action_out = the first action of each env's best
+ * candidate of the last iteration, as float64; L2A_STEP_UNSPLIT when a tile-split launch lost its partner and the step was repeated
+ * unsplit with the same offsets - same bits).  One GPU, MLP models.  The launch status word is per context, and a CEM step reads
+ * and clears it: a CEM step never shares the context with another controller's step in flight.  l2a_controller_begin of a CEM
+ * controller returns L2A_ESTATE while any other controller on the context is between _begin and _finish, and that of an RS or
+ * recurrent controller returns L2A_ESTATE while a CEM step is - nothing is launched or consumed then, and the step in flight
+ * finishes with its solo result.
+ * l2a_cem_controller_result: after a finished step, the final mean / std (host fp32 [m, D] each, or NULL) and every iteration's
+ * returns of that step (host fp32 [iters, m, n], or NULL; one synchronous copy).                                                */
+int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
+                                     double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
+                                     int reference, unsigned long long seed, l2a_controller** out);
+int l2a_cem_controller_result(l2a_controller* controller, float* mean_out, float* std_out, float* returns_out);
 void l2a_controller_destroy(l2a_controller* controller);
 int l2a_controller_step(l2a_controller* controller, const double* obs, double* action_out, long long* index_out,
                         float* return_out, void* stream);

@@ -34,12 +34,13 @@ EXPORTED_SYMBOLS = (
     "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
     "l2a_packed_layer_floats", "l2a_pack_layer_host", "l2a_micro_layout_floats", "l2a_micro_pack_layer_host",
     "l2a_comm_unique_id", "l2a_comm_init", "l2a_comm_destroy", "l2a_allreduce_best", "l2a_plan_payload",
-    "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick",
+    "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick", "l2a_cem_refit_sample", "l2a_cem_refit_sample_fused",
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_controller_create", "l2a_controller_create_sharded", "l2a_controller_create_sharded_device", "l2a_lstm_controller_create", "l2a_controller_create_device", "l2a_lstm_controller_create_device",
     "l2a_controller_destroy", "l2a_controller_step", "l2a_controller_begin", "l2a_lstm_controller_begin", "l2a_controller_finish",
     "l2a_lstm_controller_step", "l2a_controller_rearm", "l2a_controller_actions", "l2a_controller_stats",
+    "l2a_cem_controller_create_device", "l2a_cem_controller_result",
 )
 
 
@@ -197,6 +198,12 @@ def load():
     lib.l2a_cem_refit.restype = i32
     lib.l2a_cem_pick.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.l2a_cem_pick.restype = i32
+    if hasattr(lib, "l2a_cem_refit_sample"):
+        lib.l2a_cem_refit_sample.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, c.c_ulonglong, c.c_ulonglong, vp, vp,
+                                             i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.l2a_cem_refit_sample.restype = i32
+        lib.l2a_cem_refit_sample_fused.argtypes = [vp, i32, i32, i32, i32, i32, i32]
+        lib.l2a_cem_refit_sample_fused.restype = i32
     lib.l2a_lstm_plan_rs_sync.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardSpec), i32, vp, vp, vp, vp]
     lib.l2a_lstm_plan_rs_sync.restype = i32
     lib.l2a_lstm_plan_rs_chunk.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, c.c_double, c.POINTER(RewardSpec), i32,
@@ -251,6 +258,12 @@ def load():
         lib.l2a_controller_actions.restype = vp
         lib.l2a_controller_stats.argtypes = [vp, dp, i32]
         lib.l2a_controller_stats.restype = i32
+    if hasattr(lib, "l2a_cem_controller_create_device"):
+        lib.l2a_cem_controller_create_device.argtypes = [vp, i32, i32, i32, vp, vp, c.c_double, c.POINTER(RewardSpec), i32, i32, f32, i32,
+                                                         c.c_ulonglong, c.POINTER(vp)]
+        lib.l2a_cem_controller_create_device.restype = i32
+        lib.l2a_cem_controller_result.argtypes = [vp, vp, vp, vp]
+        lib.l2a_cem_controller_result.restype = i32
     _lib = lib
     return lib
 

@@ -23,6 +23,7 @@
 
 #include "l2a_host.h"
 
+#include <atomic>
 #include <cstring>
 #include <string>
 
@@ -132,6 +133,14 @@ __global__ void __launch_bounds__(256) l2a_cem_rank_k(const float* returns, int 
 // slice of the rows (independent loads, 4 in flight), the slices meet in LDS in a fixed order; two passes (mean, then
 // the squared deviations).  grid (ceil(D / 32), groups).
 #define L2A_CEM_MAXROWS 8192
+// mean = alpha * mean + (1 - alpha) * elite_mean with its roundings written out (no contraction left to the compiler): the pooled
+// (reference) reading rounds through one fma, fma(mean, alpha, (1 - alpha) mu); the per-env (fixed) reading rounds both products
+// and their sum.  l2a_cem_stats_k and l2a_cem_refit_sample_k both use it - the two stay bit-identical by construction.
+__device__ __forceinline__ float cem_mean_update(float mean, float alpha, float mu, bool pooled) {
+#pragma clang fp contract(off)
+    const float keep = (1.0f - alpha) * mu;
+    return pooled ? fmaf(mean, alpha, keep) : mean * alpha + keep;
+}
 __global__ void __launch_bounds__(256) l2a_cem_stats_k(const float* a_clip, const int* elite_rows, int m, int D, int k,
                                                        int reference, float alpha, float* mean, float* std) {
     __shared__ int rows[L2A_CEM_MAXROWS];
@@ -171,14 +180,274 @@ __global__ void __launch_bounds__(256) l2a_cem_stats_k(const float* a_clip, cons
     if (!live || sl != 0) return;
     if (reference) {
         for (int i = 0; i < m; ++i) {
-            mean[i * D + d] = mean[i * D + d] * alpha + (1.0f - alpha) * mu;
+            mean[i * D + d] = cem_mean_update(mean[i * D + d], alpha, mu, true);
             std[i * D + d] = sd;
         }
     } else {
-        mean[grp * D + d] = mean[grp * D + d] * alpha + (1.0f - alpha) * mu;
+        mean[grp * D + d] = cem_mean_update(mean[grp * D + d], alpha, mu, false);
         std[grp * D + d] = sd;
     }
 }
+
+// ---- l2a_cem_refit_sample_k: iteration i's returns -> iteration i + 1's candidates in ONE launch ---------------------------------
+// Workgroup (t, s, grp): horizon step t, candidate slice s, statistics group grp (all envs pooled = 1 group in the reference's
+// reading, one env per group in the fixed one).  Every workgroup ranks its group's returns itself (no inter-workgroup traffic, no
+// wait), owns the act_dim dimensions of step t - their elite statistics, redundantly per slice - and writes the samples of those
+// dimensions for candidates [s n / S, (s + 1) n / S) of its envs.  Bit-identical to l2a_cem_rank_k + l2a_cem_stats_k +
+// l2a_cem_sample_k:
+//   rank  : the same stable descending order (NaN -> -inf, ties to the lower index) without the n x k comparisons of the counting
+//           rank - the returns are binned by value (a monotone map: a higher bin holds only smaller values), the rank of j is the
+//           population of the bins above its own plus an exact count inside its bin (ties, however many, are compared one by one)
+//   stats : the elite rows' values of step t are staged in LDS once, then summed in l2a_cem_stats_k's order exactly (8 row slices,
+//           four accumulators at +8 / +16 / +24, slice totals added w = 0..7, two passes)
+//   sample: l2a_cem_sample_k's arithmetic and Philox numbering on the new mean / std held in LDS
+// Slices (S > 1) read the previous mean and a_clip from buffers the launch does not write (the entry point takes S = 1 when they alias).
+#define L2A_CRS_THREADS 512
+#define L2A_CRS_BINS 2048
+
+struct CemRefitSampleParams {
+    const float* returns;       // [m, n]
+    const float* a_clip_in;     // [n, m, D]: the samples whose returns these are
+    const float* mean_in;       // [m, D]: the mean they were drawn with
+    const float* z;             // [n, m, D] or null (Philox)
+    unsigned long long seed, offset;
+    const float* low;
+    const float* high;
+    int n, m, h, act_dim, k, reference, lo, hi, slices;
+    float alpha;
+    int* elite_rows;            // [m * k] (written by the slice-0 workgroups of step 0)
+    float* mean;                // [m, D]
+    float* std;
+    float* a_clip;              // [n, m, D]
+    float* a_raw;               // [n, m, D] or null
+    float* seq;                 // [h, m * (hi - lo), act_dim] or null
+};
+
+// descending bin of a value: 0 holds the largest; monotone (v1 < v2 => bin(v1) >= bin(v2)), equal values share a bin
+__device__ __forceinline__ int crs_bin(float v, float vmin, float scale) {
+    if (v == __builtin_inff()) return 0;
+    if (v == -__builtin_inff()) return L2A_CRS_BINS - 1;
+    const float t = (v - vmin) * scale;
+    const int b = (t > 0.0f) ? (t < (float)(L2A_CRS_BINS - 1) ? (int)t : L2A_CRS_BINS - 1) : 0;
+    return L2A_CRS_BINS - 1 - b;
+}
+
+__global__ void __launch_bounds__(L2A_CRS_THREADS) l2a_cem_refit_sample_k(const CemRefitSampleParams p) {
+    extern __shared__ int crs_lds[];
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x, s = blockIdx.y, grp = blockIdx.z;
+    const int n = p.n, m = p.m, k = p.k, A = p.act_dim, D = p.h * A;
+    const int gm = p.reference ? m : 1;                 // envs of this statistics group
+    const int cnt = gm * k;                             // elite rows of the group
+    int* rows = crs_lds;                                // [cnt]
+    float* nm = reinterpret_cast<float*>(rows + cnt);   // [gm, A] the group's new mean of step t
+    float* ns = nm + gm * A;                            // [A]
+    float* part = ns + A;                               // [8, A]
+    float* red = part + 8 * A;                          // [4 * 8] wave minima / maxima
+    int* sc = reinterpret_cast<int*>(red + 32);         // [L2A_CRS_THREADS] scan
+    float* vals = reinterpret_cast<float*>(sc + L2A_CRS_THREADS);   // union: [n] returns | [n] bin lists | bins | fill
+    int* list = reinterpret_cast<int*>(vals + n);
+    int* start = list + n;                              // [BINS]
+    int* fill = start + L2A_CRS_BINS;                   // [BINS]
+    float* E = vals;                                    // union: [cnt, A] elite values of step t
+    const int lane = tid & 63, wv = tid >> 6;
+
+    for (int q = tid; q < cnt; q += L2A_CRS_THREADS) rows[q] = 0;       // (every entry is written below; never a stray row id)
+    for (int ii = 0; ii < gm; ++ii) {
+        const int i = p.reference ? ii : grp;
+        // finite minimum / maximum (the bins) and minimum / maximum of everything above -inf (one tie class?)
+        float lmin = __builtin_inff(), lmax = -__builtin_inff(), umin = __builtin_inff(), umax = -__builtin_inff();
+        int lninf = 0;
+        for (int c = tid; c < n; c += L2A_CRS_THREADS) {
+            float x = p.returns[(long long)i * n + c];
+            x = (x != x) ? -__builtin_inff() : x;       // l2a_cem_rank_k: NaN sorts last
+            vals[c] = x;
+            if (x == -__builtin_inff()) lninf = 1;
+            else {
+                umin = fminf(umin, x); umax = fmaxf(umax, x);
+                if (x != __builtin_inff()) { lmin = fminf(lmin, x); lmax = fmaxf(lmax, x); }
+            }
+        }
+        for (int b = tid; b < L2A_CRS_BINS; b += L2A_CRS_THREADS) fill[b] = 0;
+        for (int o = 32; o >= 1; o >>= 1) {
+            lmin = fminf(lmin, __shfl_xor(lmin, o)); lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+            umin = fminf(umin, __shfl_xor(umin, o)); umax = fmaxf(umax, __shfl_xor(umax, o));
+        }
+        if (lane == 0) { red[wv] = lmin; red[8 + wv] = lmax; red[16 + wv] = umin; red[24 + wv] = umax; }
+        const bool any_ninf = __syncthreads_or(lninf) != 0;
+        float vmin = red[0], vmax = red[8], wmin = red[16], wmax = red[24];
+        for (int w = 1; w < L2A_CRS_THREADS / 64; ++w) {
+            vmin = fminf(vmin, red[w]); vmax = fmaxf(vmax, red[8 + w]); wmin = fminf(wmin, red[16 + w]); wmax = fmaxf(wmax, red[24 + w]);
+        }
+        // every value above -inf equal (a constant reward) - or none (every rollout diverged): no bins needed at all
+        const bool uniform = !(wmin < wmax);
+        // Ties of the two classes degenerate returns are made of, ranked by index order without comparisons: the -inf values
+        // (diverged rollouts) sort after everything else, and in a uniform env everything above -inf is one tie.  Each thread
+        // walks a contiguous index range; an exclusive scan of the ranges' class counts gives each range its first ranks.
+        if (uniform || any_ninf) {
+            const int per = (n + L2A_CRS_THREADS - 1) / L2A_CRS_THREADS;
+            const int c0 = tid * per < n ? tid * per : n, c1 = (tid + 1) * per < n ? (tid + 1) * per : n;
+            int ninf = 0;
+            for (int c = c0; c < c1; ++c) ninf += (vals[c] == -__builtin_inff()) ? 1 : 0;
+            const int packed = ninf | ((c1 - c0 - ninf) << 16);         // (n < 65536: n floats fit a workgroup's LDS)
+            sc[tid] = packed;
+            __syncthreads();
+            for (int o = 1; o < L2A_CRS_THREADS; o <<= 1) {
+                const int add = tid >= o ? sc[tid - o] : 0;
+                __syncthreads();
+                sc[tid] += add;
+                __syncthreads();
+            }
+            const int above = sc[L2A_CRS_THREADS - 1] >> 16;           // values above -inf in the env
+            int ra = above + ((sc[tid] - packed) & 0xffff), rb = (sc[tid] - packed) >> 16;
+            __syncthreads();
+            for (int c = c0; c < c1; ++c) {
+                int rank = -1;
+                if (vals[c] == -__builtin_inff()) rank = ra++;
+                else if (uniform) rank = rb++;
+                if (rank < 0) continue;
+                if (p.reference) { if (c < k) rows[ii * k + c] = rank * m + i; }   // position rank_i(c) of env i is an elite (:101)
+                else if (rank < k) rows[rank] = c * m + i;                         // candidate c is among env i's top k
+            }
+        }
+        if (!uniform) {         // the values above -inf: value bins, and an exact count inside the bin
+            const float range = vmax - vmin;            // (no finite value: -inf, scale 0 - one bin, still exact)
+            const float scale = (range > 0.0f) ? (float)(L2A_CRS_BINS - 1) / range : 0.0f;
+            for (int c = tid; c < n; c += L2A_CRS_THREADS)
+                if (vals[c] != -__builtin_inff()) atomicAdd(&fill[crs_bin(vals[c], vmin, scale)], 1);
+            __syncthreads();
+            // exclusive scan of the bin populations: 4 bins per thread, Hillis-Steele over the threads
+            constexpr int PER = L2A_CRS_BINS / L2A_CRS_THREADS;
+            int loc[PER], run = 0;
+#pragma unroll
+            for (int q = 0; q < PER; ++q) { loc[q] = run; run += fill[tid * PER + q]; }
+            sc[tid] = run;
+            __syncthreads();
+            for (int o = 1; o < L2A_CRS_THREADS; o <<= 1) {
+                const int add = tid >= o ? sc[tid - o] : 0;
+                __syncthreads();
+                sc[tid] += add;
+                __syncthreads();
+            }
+            const int base = sc[tid] - run;
+#pragma unroll
+            for (int q = 0; q < PER; ++q) { start[tid * PER + q] = base + loc[q]; fill[tid * PER + q] = base + loc[q]; }
+            __syncthreads();
+            for (int c = tid; c < n; c += L2A_CRS_THREADS)
+                if (vals[c] != -__builtin_inff()) list[atomicAdd(&fill[crs_bin(vals[c], vmin, scale)], 1)] = c;
+            __syncthreads();
+            // rank of j = candidates that sort before it: every one in a higher bin, and the ones of its own bin that do
+            const int work = p.reference ? k : n;
+            for (int j = tid; j < work; j += L2A_CRS_THREADS) {
+                const float v = vals[j];
+                if (v == -__builtin_inff()) continue;   // (ranked above)
+                const int b = crs_bin(v, vmin, scale);
+                const int b0 = start[b], b1 = fill[b];  // (after the scatter fill[b] is the bin's end)
+                int rank = b0;
+                for (int q = b0; q < b1; ++q) {
+                    const int c = list[q];
+                    const float w = vals[c];
+                    rank += (w > v || (w == v && c < j)) ? 1 : 0;
+                }
+                if (p.reference) rows[ii * k + j] = rank * m + i;     // position rank_i(j) of env i is an elite (:101)
+                else if (rank < k) rows[rank] = j * m + i;            // candidate j is among env i's top k
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0 && s == 0)
+        for (int q = tid; q < cnt; q += L2A_CRS_THREADS) p.elite_rows[(p.reference ? 0 : grp * k) + q] = rows[q];
+    // the elite rows' values of step t, once
+    for (int e = tid; e < cnt * A; e += L2A_CRS_THREADS) {
+        const int q = e / A, kk = e - q * A;
+        E[e] = p.a_clip_in[(long long)rows[q] * D + t * A + kk];
+    }
+    __syncthreads();
+    const bool st = tid < 8 * A;
+    const int sl = st ? tid / A : 0, kk0 = st ? tid - sl * A : 0;
+    float mu = 0.0f, sd = 0.0f;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (st) {
+            const float* col = E + kk0;
+            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+            int q = sl;
+            for (; q + 24 < cnt; q += 32) {
+                const float x0 = col[q * A], x1 = col[(q + 8) * A];
+                const float x2 = col[(q + 16) * A], x3 = col[(q + 24) * A];
+                if (pass == 0) { s0 += x0; s1 += x1; s2 += x2; s3 += x3; }
+                else { s0 = fmaf(x0 - mu, x0 - mu, s0); s1 = fmaf(x1 - mu, x1 - mu, s1);
+                       s2 = fmaf(x2 - mu, x2 - mu, s2); s3 = fmaf(x3 - mu, x3 - mu, s3); }
+            }
+            for (; q < cnt; q += 8) {
+                const float x0 = col[q * A];
+                if (pass == 0) s0 += x0; else s0 = fmaf(x0 - mu, x0 - mu, s0);
+            }
+            part[sl * A + kk0] = (s0 + s1) + (s2 + s3);
+        }
+        __syncthreads();
+        if (st) {
+            float tot = 0.0f;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) tot += part[w * A + kk0];
+            if (pass == 0) mu = tot / (float)cnt; else sd = sqrtf(tot / (float)cnt);
+        }
+        __syncthreads();
+    }
+    if (st && sl == 0) {
+        const int d = t * A + kk0;
+        for (int ii = 0; ii < gm; ++ii) {
+            const int i = p.reference ? ii : grp;
+            const float nmv = cem_mean_update(p.mean_in[i * D + d], p.alpha, mu, p.reference != 0);
+            nm[ii * A + kk0] = nmv;
+            if (s == 0) { p.mean[i * D + d] = nmv; p.std[i * D + d] = sd; }
+        }
+        ns[kk0] = sd;
+    }
+    __syncthreads();
+    // the samples of step t for this slice's candidates (l2a_cem_sample_k)
+    const int j0 = (int)((long long)s * n / p.slices), j1 = (int)((long long)(s + 1) * n / p.slices);
+    const int total = (j1 - j0) * gm * A;
+    for (int w = tid; w < total; w += L2A_CRS_THREADS) {
+        const int kk = w % A, r = w / A;
+        const int ii = r % gm, j = j0 + r / gm;
+        const int i = p.reference ? ii : grp;
+        const long long g = (long long)j * m + i;
+        const int d = t * A + kk;
+        const long long e = g * D + d;
+        const float z = p.z ? p.z[e] : philox_normal(p.seed, p.offset + (unsigned long long)e);
+        const float a = nm[ii * A + kk] + z * ns[kk];                                 // :86
+        const float c = fminf(fmaxf(a, p.low[kk]), p.high[kk]);                         // :87
+        p.a_clip[e] = c;
+        if (p.a_raw) p.a_raw[e] = a;
+        if (p.seq) {
+            const long long prow = p.reference ? g : (long long)i * n + j;
+            const long long cand = prow % n, blk = prow / n;
+            if (cand >= p.lo && cand < p.hi) {
+                const long long nsel = p.hi - p.lo;
+                p.seq[((long long)t * (m * nsel) + blk * nsel + (cand - p.lo)) * A + kk] = p.reference ? a : c;
+            }
+        }
+    }
+}
+
+// LDS bytes of one l2a_cem_refit_sample_k workgroup
+size_t crs_lds_bytes(int n, int m, int k, int act_dim, int reference) {
+    const size_t gm = reference ? (size_t)m : 1, cnt = gm * (size_t)k;
+    const size_t fixed = cnt + gm * act_dim + act_dim + 8 * (size_t)act_dim + 32 + L2A_CRS_THREADS;
+    const size_t bins = 2 * (size_t)n + 2 * L2A_CRS_BINS, elite = cnt * (size_t)act_dim;
+    return 4 * (fixed + (bins > elite ? bins : elite));
+}
+
+// Does l2a_cem_refit_sample run this shape as one launch (else: l2a_cem_refit + l2a_cem_sample inside the call)?
+bool crs_fused(const l2a_ctx* ctx, int n, int m, int h, int act_dim, int k, int reference) {
+    const long long total = (long long)n * m * h * act_dim;
+    return crs_lds_bytes(n, m, k, act_dim, reference) <= (size_t)ctx->lds_per_block && 8 * act_dim <= L2A_CRS_THREADS &&
+           total <= 0x7fffffffLL;
+}
+
+// the dynamic-LDS limit l2a_cem_refit_sample_k has been raised to, per device
+#define L2A_CRS_DEVICES 64
+std::atomic<int> crs_smem_set[L2A_CRS_DEVICES];
 
 // np.argmax's order (the reference's `np.argmax(returns, axis=1)`, mpc_controller.py:128-129): a NaN is the maximum, the first
 // NaN wins; otherwise the largest value, ties to the lowest index.  A diverged rollout therefore surfaces as a NaN best return
@@ -279,6 +548,68 @@ int l2a_cem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, int n
                        stream, a_clip, elite_rows, m, D, num_elites, reference ? 1 : 0, alpha, mean, std);
     L2A_HIP(ctx, hipGetLastError());
     return L2A_OK;
+}
+
+int l2a_cem_refit_sample(l2a_ctx* ctx, const float* returns, const float* a_clip_in, int n, int m, int h, int act_dim, int num_elites,
+                         int reference, float alpha, const float* z, unsigned long long seed, unsigned long long offset, const float* low,
+                         const float* high, int lo, int hi, int* elite_rows, const float* mean_in, float* mean, float* std, float* a_clip,
+                         float* a_raw, float* seq, void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    if (!returns || !a_clip_in || !elite_rows || !mean || !std || !low || !high || !a_clip)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_refit_sample: null pointer");
+    if (n < 1 || m < 1 || h < 1 || act_dim < 1 || lo < 0 || hi < lo || hi > n || num_elites < 1 || num_elites > n)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_refit_sample: bad n / m / h / act_dim / num_elites / shard");
+    if ((long long)(reference ? m : 1) * num_elites > L2A_CEM_MAXROWS)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_refit_sample: more than 8192 elite rows per statistics group");
+    if ((size_t)n * sizeof(float) > (size_t)ctx->lds_per_block)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_refit_sample: more candidates than an env's returns fit in LDS");
+    if (!mean_in) mean_in = mean;
+    l2a_device_guard guard(ctx->device);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    const size_t smem = crs_lds_bytes(n, m, num_elites, act_dim, reference);
+    if (!crs_fused(ctx, n, m, h, act_dim, num_elites, reference)) {
+        // shapes the fused launch does not take: the two calls it replaces (same bits)
+        if (mean_in != mean)
+            L2A_HIP(ctx, hipMemcpyAsync(mean, mean_in, sizeof(float) * (size_t)m * h * act_dim, hipMemcpyDeviceToDevice, stream));
+        int rc = l2a_cem_refit(ctx, returns, a_clip_in, n, m, h * act_dim, num_elites, reference, alpha, elite_rows, mean, std, stream_v);
+        if (rc != L2A_OK) return rc;
+        return l2a_cem_sample(ctx, z, seed, offset, mean, std, low, high, n, m, h, act_dim, reference, lo, hi, a_clip, a_raw, seq,
+                              stream_v);
+    }
+    const int groups = reference ? 1 : m;
+    // candidate slices: about one workgroup per CU; in place (the previous mean or samples are overwritten) one slice
+    int slices = 1;
+    if (mean_in != mean && a_clip_in != a_clip) {
+        const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+        slices = l2a_ceil_div(cus, h * groups);
+        const int most = n / 64 > 1 ? n / 64 : 1;
+        slices = slices < most ? slices : most;
+        slices = slices > 1 ? slices : 1;
+    }
+    if (smem > 48 * 1024 && ctx->device >= 0 && ctx->device < L2A_CRS_DEVICES && (int)smem > crs_smem_set[ctx->device].load()) {
+        // raised once per device to the largest size launched so far (a race between two threads only repeats the call)
+        L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_cem_refit_sample_k),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        crs_smem_set[ctx->device].store((int)smem);
+    } else if (smem > 48 * 1024 && (ctx->device < 0 || ctx->device >= L2A_CRS_DEVICES)) {
+        L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_cem_refit_sample_k),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    }
+    CemRefitSampleParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.returns = returns; p.a_clip_in = a_clip_in; p.mean_in = mean_in; p.z = z; p.seed = seed; p.offset = offset;
+    p.low = low; p.high = high; p.n = n; p.m = m; p.h = h; p.act_dim = act_dim; p.k = num_elites; p.reference = reference ? 1 : 0;
+    p.lo = lo; p.hi = hi; p.slices = slices; p.alpha = alpha; p.elite_rows = elite_rows; p.mean = mean; p.std = std;
+    p.a_clip = a_clip; p.a_raw = a_raw; p.seq = (hi > lo) ? seq : nullptr;
+    hipLaunchKernelGGL(l2a_cem_refit_sample_k, dim3((unsigned)h, (unsigned)slices, (unsigned)groups), dim3(L2A_CRS_THREADS),
+                       (unsigned)smem, stream, p);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
+}
+
+int l2a_cem_refit_sample_fused(const l2a_ctx* ctx, int n, int m, int h, int act_dim, int num_elites, int reference) {
+    if (!ctx || n < 1 || m < 1 || h < 1 || act_dim < 1 || num_elites < 1 || num_elites > n) return 0;
+    return crs_fused(ctx, n, m, h, act_dim, num_elites, reference) ? 1 : 0;
 }
 
 int l2a_cem_pick(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m, int D,

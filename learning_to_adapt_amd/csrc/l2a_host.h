@@ -46,6 +46,9 @@ struct l2a_ctx {
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 0;
     int num_cu = 0;
+    // controller steps between l2a_controller_begin and _finish on this context: CEM steps and RS / recurrent steps (the launch
+    // status word is per context - a CEM step does not share it with any other step in flight, l2a_step.hip)
+    int cem_steps_in_flight = 0, rs_steps_in_flight = 0;
     int lds_per_block = 0;
     int clock_khz = 0;
     std::string arch;

@@ -76,6 +76,29 @@ struct l2a_controller {
     hipEvent_t payload_ev = nullptr;
     unsigned long long digest = 0;
     size_t glob_floats = 0;                     // h * m * n * act_dim: the WHOLE plan's candidate tensor (the device stream's step)
+    // CEM plan (l2a_cem_controller_create_device): K iterations of rollout -> l2a_cem_refit_sample, one read-back per step
+    struct cem_state* cem = nullptr;
+};
+
+// Device-mode CEM (`MPCController.get_cem_action_device`, policies/mpc_controller.py): the whole plan step on the launch stream -
+// l2a_cem_sample for iteration 0, then per iteration the rollout and ONE l2a_cem_refit_sample (the last iteration: l2a_cem_refit),
+// l2a_cem_pick, and one copy of the packed result to page-locked memory.  Philox offsets (calls + it) * n * m * D, as the Python path.
+struct cem_state {
+    int iters = 0, k = 0, reference = 1, D = 0;
+    float alpha = 0.1f;
+    unsigned long long iter_calls = 0;          // CEM iterations planned so far (the Philox stream's position)
+    float* mean[2] = {nullptr, nullptr};        // [m, D] ping-pong (the fused launch reads one and writes the other)
+    float* std = nullptr;                       // [m, D]
+    float* a_clip[2] = {nullptr, nullptr};      // [n, m, D] ping-pong
+    float* a_raw = nullptr;                     // [n, m, D]
+    float* seq = nullptr;                       // [h, m * n, act_dim]
+    int* rows = nullptr;                        // [m * k]
+    float* rets = nullptr;                      // [iters, m, n]: every iteration's returns of the latest step
+    float* lowhigh = nullptr;                   // [2][act_dim] fp32 bounds
+    float* packed_dev = nullptr;                // l2a_cem_pick's buffer: m x (act_dim + 2), mean [m, D], std [m, D]
+    float* packed_host = nullptr;               // page-locked
+    hipEvent_t done = nullptr;
+    int cur = 0;                                // the buffers of the last iteration
 };
 
 extern "C" unsigned long long l2a_mt19937_state_digest(const void* addr);      // csrc/l2a_rng.c
@@ -118,6 +141,14 @@ __global__ void __launch_bounds__(256) l2a_uniform_fill_shard_k(unsigned long lo
 namespace {
 
 int fail(l2a_ctx* ctx, int code, const std::string& msg) { return l2a_fail(ctx, code, msg); }
+
+// A step enters / leaves flight: the context counts its CEM and its other steps in flight.
+void set_in_flight(l2a_controller* c, bool on) {
+    if (c->in_flight == on) return;
+    c->in_flight = on;
+    int& n = c->cem ? c->ctx->cem_steps_in_flight : c->ctx->rs_steps_in_flight;
+    n += on ? 1 : -1;
+}
 
 // page-locked / device words of a sharded controller (both RNG modes)
 hipError_t alloc_sharded(l2a_controller* c) {
@@ -262,8 +293,15 @@ int launch_sharded(l2a_controller* c, bool first) {
 
 // First half of a step: everything that touches the generator (take / draw, re-arm), the staging and the launch.  Returns
 // L2A_OK (plan in flight), L2A_STEP_MISS (nothing consumed or launched) or a negative code.
+int cem_begin(l2a_controller* c, const double* obs, void* stream);
+int cem_finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out);
+
 int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
+    if (c->cem) return cem_begin(c, obs, stream);
     l2a_ctx* ctx = c->ctx;
+    if (ctx->cem_steps_in_flight > 0)
+        return fail(ctx, L2A_ESTATE, "l2a_controller_begin: a CEM step of another controller is in flight on this context (it reads and "
+                                     "clears the context's launch status word: finish it first)");
     if (!obs) return fail(ctx, L2A_EINVAL, "l2a_controller_begin: null obs");
     if (c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_begin: the previous step was not finished (l2a_controller_finish)");
     const double t0 = l2a_now_us();
@@ -317,7 +355,7 @@ int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0
         ctx->stamps_us[0] = t0;
         const int rc = launch_sharded(c, true);
         if (rc != L2A_OK) return rc;
-        c->in_flight = true;
+        set_in_flight(c, true);
         return L2A_OK;
     }
     l2a_after_launch_fn hook = c->device_rng ? nullptr : (drew ? kick_arm : kick_next);
@@ -329,17 +367,18 @@ int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0
         rc = l2a_lstm_plan_rs_sync_hook(c->rnn, c->obs32, c0, h0, c->dev[slot], c->m, c->n, c->h, c->discount, &c->rw, 0, nullptr,
                                         c1, h1, stream, hook, c, &c->pending);
     if (rc != L2A_OK) return rc;
-    c->in_flight = true;
+    set_in_flight(c, true);
     return L2A_OK;
 }
 
 // Second half: wait for the keys (a launch that lost its tile-split partner is repeated unsplit - same bits; the generator is not
 // touched again), decode, gather the winners' float64 first actions.
 int finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out) {
+    if (c->cem) return cem_finish(c, action_out, index_out, return_out);
     l2a_ctx* ctx = c->ctx;
     if (!action_out) return fail(ctx, L2A_EINVAL, "l2a_controller_finish: null action_out");
     if (!c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_finish: no step is in flight (l2a_controller_begin)");
-    c->in_flight = false;
+    set_in_flight(c, false);
     const int slot = c->slot;
     unsigned long long keys[L2A_MAIL_KEYS];
     int result = c->result;
@@ -424,6 +463,124 @@ int finish(l2a_controller* c, double* action_out, long long* index_out, float* r
     return result;
 }
 
+// ---- CEM (device mode) ---------------------------------------------------------------------------------------------------------
+// The iteration-0 distribution: mean 0, std 1 (get_cem_action_device's zero_() / fill_(1.0)).
+__global__ void __launch_bounds__(256) l2a_cem_init_k(int md, float* __restrict__ mean, float* __restrict__ std) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < md) { mean[e] = 0.0f; std[e] = 1.0f; }
+}
+
+// Everything of one CEM plan step, in stream order on `stream`; nothing on the host waits.
+int cem_launch(l2a_controller* c) {
+    l2a_ctx* ctx = c->ctx;
+    cem_state* q = c->cem;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    const int m = c->m, n = c->n, h = c->h, A = c->act_dim, D = q->D;
+    const unsigned long long per_iter = (unsigned long long)n * m * D;
+    l2a_device_guard guard(ctx->device);
+    std::memcpy(c->obs_map_host, c->obs32, sizeof(float) * (size_t)m * c->obs_dim);
+    hipLaunchKernelGGL(l2a_cem_init_k, dim3((unsigned)l2a_ceil_div(m * D, 256)), dim3(256), 0, stream, m * D, q->mean[0], q->std);
+    L2A_HIP(ctx, hipGetLastError());
+    const float* low = q->lowhigh;
+    const float* high = q->lowhigh + A;
+    int cur = 0;
+    int rc = l2a_cem_sample(ctx, nullptr, c->seed, q->iter_calls * per_iter, q->mean[0], q->std, low, high, n, m, h, A, q->reference, 0, n,
+                            q->a_clip[0], q->reference ? q->a_raw : nullptr, q->seq, c->stream);
+    if (rc != L2A_OK) return rc;
+    ctx->stamps_us[1] = l2a_now_us();
+    for (int it = 0; it < q->iters; ++it) {
+        float* rets = q->rets + (size_t)it * m * n;
+        rc = l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n, h, c->discount, &c->rw, 0, rets, c->keys_dev, c->stream);
+        if (rc != L2A_OK) return rc;
+        if (it + 1 < q->iters) {
+            rc = l2a_cem_refit_sample(ctx, rets, q->a_clip[cur], n, m, h, A, q->k, q->reference, q->alpha, nullptr, c->seed,
+                                      (q->iter_calls + it + 1) * per_iter, low, high, 0, n, q->rows, q->mean[cur], q->mean[cur ^ 1], q->std,
+                                      q->a_clip[cur ^ 1], q->reference ? q->a_raw : nullptr, q->seq, c->stream);
+            cur ^= 1;
+        } else {
+            rc = l2a_cem_refit(ctx, rets, q->a_clip[cur], n, m, D, q->k, q->reference, q->alpha, q->rows, q->mean[cur], q->std, c->stream);
+        }
+        if (rc != L2A_OK) return rc;
+    }
+    rc = l2a_cem_pick(ctx, q->rets + (size_t)(q->iters - 1) * m * n, q->reference ? q->a_raw : q->a_clip[cur], q->mean[cur], q->std, n, m,
+                      D, A, q->reference, q->packed_dev, c->stream);
+    if (rc != L2A_OK) return rc;
+    q->cur = cur;
+    const size_t words = (size_t)m * (A + 2) + 2 * (size_t)m * D;
+    L2A_HIP(ctx, hipMemcpyAsync(q->packed_host, q->packed_dev, sizeof(float) * words, hipMemcpyDeviceToHost, stream));
+    L2A_HIP(ctx, hipEventRecord(q->done, stream));
+    ctx->stamps_us[2] = l2a_now_us();
+    return L2A_OK;
+}
+
+int cem_begin(l2a_controller* c, const double* obs, void* stream) {
+    l2a_ctx* ctx = c->ctx;
+    if (!obs) return fail(ctx, L2A_EINVAL, "l2a_controller_begin: null obs");
+    if (c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_begin: the previous step was not finished (l2a_controller_finish)");
+    if (ctx->cem_steps_in_flight + ctx->rs_steps_in_flight > 0)
+        return fail(ctx, L2A_ESTATE, "l2a_controller_begin: another controller's step is in flight on this context (a CEM step reads and "
+                                     "clears the context's launch status word: finish the other step first)");
+    c->t_begin = l2a_now_us();
+    c->t_taken = c->t_begin;
+    const int no = c->m * c->obs_dim;
+    for (int i = 0; i < no; ++i) c->obs32[i] = (float)obs[i];
+    c->stream = stream;
+    c->result = L2A_OK;
+    const int rc = cem_launch(c);
+    if (rc != L2A_OK) return rc;
+    ctx->stamps_us[3] = l2a_now_us();
+    set_in_flight(c, true);
+    return L2A_OK;
+}
+
+// Wait for the packed result; a launch flagged invalid (a tile-split partner that was not co-resident) repeats the whole step unsplit
+// with the same Philox offsets - the same bits - as get_cem_action_device's retry does.
+int cem_finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out) {
+    l2a_ctx* ctx = c->ctx;
+    if (!action_out) return fail(ctx, L2A_EINVAL, "l2a_controller_finish: null action_out");
+    if (!c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_finish: no step is in flight (l2a_controller_begin)");
+    set_in_flight(c, false);
+    cem_state* q = c->cem;
+    int result = c->result;
+    l2a_device_guard guard(ctx->device);
+    for (int attempt = 0; ; ++attempt) {
+        L2A_HIP(ctx, hipEventSynchronize(q->done));
+        ctx->stamps_us[4] = l2a_now_us();
+        if (*ctx->status_host == 0) break;
+        *ctx->status_host = 0;
+        if (attempt == 1 || ctx->split_policy == 0)
+            return fail(ctx, L2A_ESPLIT, "l2a_controller_step: the rollout was flagged invalid with the tile split disabled");
+        (void)l2a_set_split(ctx, 0);
+        c->relaunches += 1;
+        result = L2A_STEP_UNSPLIT;
+        const int rc = cem_launch(c);
+        if (rc != L2A_OK) return rc;
+    }
+    const double t2 = l2a_now_us();
+    const int A = c->act_dim, W = A + 2;
+    for (int i = 0; i < c->m; ++i) {
+        const float* r = q->packed_host + (size_t)i * W;
+        int idx = 0;
+        std::memcpy(&idx, r + A + 1, sizeof(int));
+        for (int k = 0; k < A; ++k) action_out[(size_t)i * A + k] = (double)r[k];
+        if (index_out) index_out[i] = idx;
+        if (return_out) return_out[i] = r[A];
+    }
+    q->iter_calls += (unsigned long long)q->iters;
+    const double t3 = l2a_now_us();
+    c->steps += 1;
+    c->calls += 1;
+    const double* st = ctx->stamps_us;
+    c->stage_us[0] = 0.0;
+    c->stage_us[1] = st[1] - c->t_taken;        // observation staging + iteration 0's sampling launch
+    c->stage_us[2] = st[2] - st[1];             // the iterations' launch calls
+    c->stage_us[3] = 0.0;
+    c->stage_us[4] = st[4] - st[3];             // wait for the packed result
+    c->stage_us[5] = t3 - t2;                   // decode
+    c->stage_us[6] = t3 - c->t_begin;           // whole step
+    return result;
+}
+
 int step(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, double* action_out,
          long long* index_out, float* return_out, void* stream) {
     if (!obs || !action_out) return fail(c->ctx, L2A_EINVAL, "l2a_controller_step: null obs / action_out");
@@ -500,11 +657,90 @@ int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, cons
     return create(ctx, nullptr, model, obs_dim, act_dim, units, m, n, h, low, high, discount, reward, nullptr, 1, out, true, seed);
 }
 
+int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                     const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
+                                     unsigned long long seed, l2a_controller** out) {
+    if (!model) return L2A_EINVAL;
+    l2a_ctx* ctx = nullptr;
+    int obs_dim = 0, act_dim = 0;
+    l2a_model_facts(model, &ctx, &obs_dim, &act_dim);
+    if (!out) return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: out is null");
+    *out = nullptr;
+    if (!low || !high || !reward) return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: null low / high / reward");
+    if (m < 1 || m > L2A_MAIL_KEYS || (long long)m * obs_dim > L2A_MAIL_OBS || n < 1 || h < 1 || act_dim < 1 || act_dim > 16)
+        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, "
+                                     "h >= 1, 1 <= act_dim <= 16");
+    if (iters < 1 || num_elites < 1 || num_elites > n)
+        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: needs iters >= 1 and 1 <= num_elites <= n");
+    if ((long long)(reference ? m : 1) * num_elites > 8192 || (size_t)n * sizeof(float) > (size_t)ctx->lds_per_block)
+        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: more elite rows or candidates than l2a_cem_refit takes");
+    const long long D = (long long)h * act_dim;
+    if ((long long)n * m * D > 0x7fffffffLL || (long long)iters * m * n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: too many samples");
+    l2a_controller* c = new (std::nothrow) l2a_controller();
+    cem_state* q = c ? new (std::nothrow) cem_state() : nullptr;
+    if (!q) { delete c; return fail(ctx, L2A_EHIP, "l2a_cem_controller_create_device: out of memory"); }
+    c->ctx = ctx; c->mlp = model; c->cem = q;
+    c->m = m; c->n = n; c->h = h; c->obs_dim = obs_dim; c->act_dim = act_dim;
+    c->discount = discount; c->rw = *reward;
+    for (int k = 0; k < act_dim; ++k) { c->low[k] = low[k]; c->high[k] = high[k]; }
+    c->device_rng = true; c->seed = seed; c->lo = 0; c->hi = n;
+    q->iters = iters; q->k = num_elites; q->reference = reference ? 1 : 0; q->D = (int)D; q->alpha = alpha;
+    l2a_device_guard guard(ctx->device);
+    const size_t md = (size_t)m * D, nmd = (size_t)n * md, words = (size_t)m * (act_dim + 2) + 2 * md;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&c->obs_map_host), sizeof(float) * L2A_MAIL_OBS, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&c->obs_map_dev), c->obs_map_host, 0);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->keys_dev), sizeof(unsigned long long) * (size_t)m);
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        e = hipMalloc(reinterpret_cast<void**>(&q->mean[s]), sizeof(float) * md);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->a_clip[s]), sizeof(float) * nmd);
+    }
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->std), sizeof(float) * md);
+    if (e == hipSuccess && q->reference) e = hipMalloc(reinterpret_cast<void**>(&q->a_raw), sizeof(float) * nmd);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->seq), sizeof(float) * nmd);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->rows), sizeof(int) * (size_t)m * num_elites);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->rets), sizeof(float) * (size_t)iters * m * n);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->lowhigh), sizeof(float) * 2 * act_dim);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->packed_dev), sizeof(float) * words);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&q->packed_host), sizeof(float) * words, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&q->done, hipEventDisableTiming);
+    if (e == hipSuccess) {
+        float lh[32] = {0};
+        for (int k = 0; k < act_dim; ++k) { lh[k] = (float)low[k]; lh[act_dim + k] = (float)high[k]; }
+        e = hipMemcpy(q->lowhigh, lh, sizeof(float) * 2 * act_dim, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        const std::string msg = std::string("l2a_cem_controller_create_device: ") + hipGetErrorString(e);
+        l2a_controller_destroy(c);
+        return fail(ctx, L2A_EHIP, msg);
+    }
+    *out = c;
+    return L2A_OK;
+}
+
+int l2a_cem_controller_result(l2a_controller* c, float* mean_out, float* std_out, float* returns_out) {
+    if (!c) return L2A_EINVAL;
+    if (!c->cem) return fail(c->ctx, L2A_EINVAL, "l2a_cem_controller_result: not a CEM controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_cem_controller_result: a step is in flight (l2a_controller_finish)");
+    if (c->steps == 0) return fail(c->ctx, L2A_ESTATE, "l2a_cem_controller_result: no step has finished yet");
+    cem_state* q = c->cem;
+    const size_t md = (size_t)c->m * q->D;
+    const float* tail = q->packed_host + (size_t)c->m * (c->act_dim + 2);
+    if (mean_out) std::memcpy(mean_out, tail, sizeof(float) * md);
+    if (std_out) std::memcpy(std_out, tail + md, sizeof(float) * md);
+    if (returns_out) {
+        l2a_device_guard guard(c->ctx->device);
+        L2A_HIP(c->ctx, hipMemcpy(returns_out, q->rets, sizeof(float) * (size_t)q->iters * c->m * c->n, hipMemcpyDeviceToHost));
+    }
+    return L2A_OK;
+}
+
 void l2a_controller_destroy(l2a_controller* c) {
     if (!c) return;
     if (c->chain) l2a_ahead_destroy(c->chain);                // joins the producer: no upload is in flight afterwards
     l2a_device_guard guard(c->ctx->device);
     if (c->in_flight) (void)hipDeviceSynchronize();           // a step begun and never finished: its launch still reads these buffers
+    set_in_flight(c, false);
     for (int s = 0; s < 2; ++s) {
         if (c->pin[s]) (void)hipHostFree(c->pin[s]);
         if (c->dev[s]) (void)hipFree(c->dev[s]);
@@ -517,6 +753,18 @@ void l2a_controller_destroy(l2a_controller* c) {
     if (c->payload_host) (void)hipHostFree(c->payload_host);
     if (c->payload_ev) (void)hipEventDestroy(c->payload_ev);
     if (c->side) (void)hipStreamDestroy(c->side);
+    if (cem_state* q = c->cem) {
+        for (int s = 0; s < 2; ++s) {
+            if (q->mean[s]) (void)hipFree(q->mean[s]);
+            if (q->a_clip[s]) (void)hipFree(q->a_clip[s]);
+        }
+        float* dev_bufs[] = {q->std, q->a_raw, q->seq, q->rets, q->lowhigh, q->packed_dev};
+        for (float* b : dev_bufs) if (b) (void)hipFree(b);
+        if (q->rows) (void)hipFree(q->rows);
+        if (q->packed_host) (void)hipHostFree(q->packed_host);
+        if (q->done) (void)hipEventDestroy(q->done);
+        delete q;
+    }
     delete c;
 }
 

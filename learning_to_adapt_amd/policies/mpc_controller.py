@@ -26,7 +26,10 @@ mode: the NEXT controller step's candidates are drawn on a private copy of the g
 GPU runs the current plan and adopted only if the global generator is still in exactly that state -
 ``policies/draw_ahead.py``; numbers, order and the state left behind are the reference's), ``native_step`` (parity-mode
 random shooting on one GPU: the whole step - adopt the block drawn ahead by a C thread, launch, wait, decode, gather - is ONE
-C call, ``l2a_controller_step``, ``policies/native_step.py``; a step that finds no valid block falls back to the path above).
+C call, ``l2a_controller_step``, ``policies/native_step.py``; a step that finds no valid block falls back to the path above),
+``native_cem_step`` (off by default: ``rng="device"`` CEM on one GPU through the C controller,
+``l2a_cem_controller_create_device`` - bit-identical to ``get_cem_action_device``, ``policies/native_cem_step.py``; every other
+case keeps the Python path).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -67,6 +70,7 @@ class MPCController(Policy, Serializable):
             pipeline_chunks=5,
             draw_ahead=True,
             native_step=True,
+            native_cem_step=False,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -87,6 +91,7 @@ class MPCController(Policy, Serializable):
         self.pipeline_chunks = int(pipeline_chunks)
         self.draw_ahead = bool(draw_ahead)
         self.native_step = bool(native_step)
+        self.native_cem_step = bool(native_cem_step)
 
         self.unwrapped_env = innermost_env(env)
 
@@ -101,6 +106,7 @@ class MPCController(Policy, Serializable):
         self._ahead = None          # DrawAhead chain (parity mode), created on first use
         self._cstep = None          # NativeStep (l2a_controller): the whole parity-mode step in one C call
         self._cstep_no = None       # request key the C controller was found ineligible for
+        self._cemstep = None        # NativeCemStep (CEM l2a_controller, rng="device"): the whole CEM plan step in one C call
         self._cem_first_chunk = 4   # horizon steps of the first chunk of a pipelined CEM rollout (0: equal chunks)
         self.last_plan = None       # diagnostics of the latest fused plan (returns, keys, ...)
 
@@ -1077,9 +1083,60 @@ class MPCController(Policy, Serializable):
         self.last_plan = dict(best_index=best_index, best_return=best_return, cem_mean=mean_h, cem_std=std_h)
         return out
 
+    def _native_cem_step(self, observations):
+        """``rng="device"`` CEM on one GPU through the C controller (``l2a_cem_controller_create_device``): the same Philox offsets as
+        ``get_cem_action_device``, so the two paths can take turns only while they agree on the stream position - the C controller
+        is built where the Python path's counter is 0 for this seed and dropped when the Python path has planned since.  Returns the
+        actions, or None when the C controller does not apply (parity mode, sharded plan, recurrent model, a test hook replaced the
+        normals or the launch path, a forked child)."""
+        if self.rng != "device" or not self._native_step_stock():
+            return None
+        if getattr(self._cem_normal_device, "__func__", None) is not MPCController._cem_normal_device:
+            return None
+        if self._dist()[1] > 1:
+            return None
+        native = self.dynamics_model.planner_model()
+        if hasattr(native, "units") or not hasattr(native.lib, "l2a_cem_controller_create_device"):
+            return None
+        n, m, h = self.n_candidates, len(observations), self.horizon
+        if m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16:
+            return None
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        if self._bufs.get("cem_seed") != seed:
+            self._bufs["cem_seed"], self._bufs["cem_calls"] = seed, 0
+        num_elites = max(int(n * self.percent_elites), 1)
+        key = (id(native), native.handle.value, m, n, h, float(self.discount), seed, self.cem_mode, int(self.num_cem_iters),
+               num_elites, float(self.alpha))
+        st = self._cemstep
+        if st is not None and (st.pid != os.getpid() or st.key != key or st.calls != self._bufs["cem_calls"]):
+            if st.pid != os.getpid():
+                return None                 # (a forked child: the parent's HIP objects did not come along)
+            st.close()
+            st = self._cemstep = None
+        if st is None:
+            if self._bufs["cem_calls"] != 0:
+                return None                 # the Python path has planned with this seed: its stream position is not the C one's
+            from .native_cem_step import NativeCemStep
+            st = NativeCemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
+                               self.num_cem_iters, num_elites, self.alpha, self.cem_mode == "reference", seed)
+            st.key, st.calls = key, 0
+            self._cemstep = st
+        self._check_blocks(m)
+        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        st.calls += int(self.num_cem_iters)
+        self._bufs["cem_calls"] = st.calls
+        mean, std, rets = st.result()
+        self.last_plan = dict(best_index=st.idx.copy(), best_return=st.ret.copy(), cem_mean=mean, cem_std=std,
+                              cem_trace=[dict(returns=rets[it]) for it in range(rets.shape[0])])
+        return st.act.copy()
+
     def get_cem_action(self, observations):
         if not self._fusable():
             raise _lib.L2AError("CEM planning needs a fusable closed-form reward (env.reward_spec)")
+        if self.native_cem_step:
+            out = self._native_cem_step(observations)
+            if out is not None:
+                return out
         if self.rng == "device":
             return self.get_cem_action_device(observations)
         n = self.n_candidates
