@@ -2,7 +2,12 @@
 that share a GPU) and run the sharded controller step end to end - launch, payload packed on the device
 (`l2a_plan_payload`), the collective, the relaunch protocol - through `MPCController.get_actions` /
 `RNNMPCController.get_actions`.  `tests/test_distributed_cpu.py` runs the same host paths with the launch replaced by the
-oracle; here nothing is replaced.  What the driver's multi-GPU run meets is what ran here, except RCCL for gloo.
+oracle; here nothing is replaced.
+
+What runs here is the UNSPLIT launch geometry: `L2A_SPLIT=0` (below) is needed because a tile's two workgroups may not be
+co-resident while several processes share the GPU, and it switches the member fan off as well.  A rank that owns its GPU launches
+config 4's shard on the tile split and config 5's on the member fan; that geometry - real processes and a real collective given
+up for it - is tests/test_sharded_emulation_gpu.py.  RCCL with more than one rank runs nowhere in the suite.
 
 Reference semantics preserved: `np.argmax` first-max over ALL candidates (policies/mpc_controller.py:128-129)."""
 
