@@ -358,6 +358,28 @@ int l2a_allreduce_best(l2a_ctx* ctx, unsigned long long* best_key, int m, void* 
 #define L2A_DIGEST_MASK 0x7fffffffffffull
 int l2a_plan_payload(l2a_ctx* ctx, const unsigned long long* best_key, int m, unsigned long long digest,
                      unsigned long long* payload, void* stream);
+/* Sharded CEM: the ranks' returns of one iteration travel through the SAME collective - no second collective kind, no second
+ * callback type.  A rank contributes m * n + 3 u64 words per iteration:
+ *   [i * n + j]  (1ull << 32) | the RAW bits of its fp32 return of env i's global candidate j when lo <= j < hi, else 0.  Only the
+ *                owner contributes a non-zero word, so MAX returns it exactly: NaN payloads, -0.0 and +-inf survive bit for bit
+ *   [m * n]      1 when this context's launch status word is set (read on the device, as l2a_plan_payload does)
+ *   [m * n + 1]  digest & L2A_DIGEST_MASK, [m * n + 2]  L2A_DIGEST_MASK - (digest & L2A_DIGEST_MASK)
+ * Every word is below 2^33: signed 64-bit MAX (torch.int64) reduces them correctly.  After the in-place MAX all-reduce every
+ * rank holds every candidate's return, the any-rank flag and the digest check.
+ *   l2a_cem_shard_pack   : ONE launch writes ALL m * n + 3 words (zeros outside the shard - no memset in front); returns_local
+ *                          [m, hi - lo] (may be NULL when hi == lo: more ranks than candidates - zeros and the three tail words)
+ *   l2a_cem_shard_unpack : ONE launch decodes the reduced words into the fp32 table returns_out [m, n] that l2a_cem_refit_sample
+ *                          and l2a_cem_pick read, and ACCUMULATES into verdict (device u32 [3], NOT reset by the call - the caller
+ *                          zeroes it once per plan step): [0] |= the flag word, [1] += the number of zero words ("holes": a
+ *                          candidate nobody contributed, decoded as 0.0f), [2] |= 1 when words[m * n + 1] + words[m * n + 2] !=
+ *                          L2A_DIGEST_MASK
+ *   l2a_cem_word_encode / _decode : the word of a return on the host; _decode returns 0 for an absent (zero) word, else 1.   */
+int l2a_cem_shard_pack(l2a_ctx* ctx, const float* returns_local, int m, int n, int lo, int hi, unsigned long long digest,
+                       unsigned long long* words_out, void* stream);
+int l2a_cem_shard_unpack(l2a_ctx* ctx, const unsigned long long* words, int m, int n, float* returns_out,
+                         unsigned int* verdict, void* stream);
+unsigned long long l2a_cem_word_encode(float ret);
+int l2a_cem_word_decode(unsigned long long word, float* ret);
 
 /* ---- recurrent planner (ReBAL) --------------------------------------------------------------
  * Single-layer LSTM dynamics model: `RNNDynamicsModel` (dynamics/rnn_dynamics.py:11-100) built by
@@ -540,7 +562,8 @@ int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, cons
  *   reference   1 = the reference's reading (unclipped rollouts, candidate-major rows, the pooled rank mask of :101); 0 = fixed
  * Steps through l2a_controller_step / _begin / _finish / _stats / _destroy (action_out = the first action of each env's best
  * candidate of the last iteration, as float64; L2A_STEP_UNSPLIT when a tile-split launch lost its partner and the step was repeated
- * unsplit with the same offsets - same bits).  One GPU, MLP models.  The launch status word is per context, and a CEM step reads
+ * unsplit with the same offsets - same bits).  MLP models; one GPU (sharded: l2a_cem_controller_create_sharded_device below).
+ * The launch status word is per context, and a CEM step reads
  * and clears it: a CEM step never shares the context with another controller's step in flight.  l2a_controller_begin of a CEM
  * controller returns L2A_ESTATE while any other controller on the context is between _begin and _finish, and that of an RS or
  * recurrent controller returns L2A_ESTATE while a CEM step is - nothing is launched or consumed then, and the step in flight
@@ -550,6 +573,22 @@ int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, cons
 int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
                                      double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
                                      int reference, unsigned long long seed, l2a_controller** out);
+/* The same step for ONE rank of a plan sharded over `world` GPUs (config 5: 8 x 500 of 4000 candidates): every rank samples ALL
+ * n rows of the same Philox stream (the stream does not depend on `world`), rolls out candidates [lo, hi) = [rank n / world,
+ * (rank + 1) n / world) and, per iteration, packs its returns (l2a_cem_shard_pack), runs the collective - `reduce`, or
+ * l2a_allreduce_best on m * n + 3 words over the context's communicator when `reduce` is NULL - unpacks the gathered table
+ * (l2a_cem_shard_unpack) and refits on it: `iters` collectives per step, all in stream order, no host wait between iterations,
+ * ONE read-back of the packed result and the verdict.  The digest fingerprints seed, stream position, m, n, h, iters, num_elites,
+ * reference, alpha and world.  _finish decides from the REDUCED verdict only (identical on every rank, so the ranks never disagree
+ * on the number of collectives): a digest mismatch or a hole fails the step with L2A_ESTATE on every rank and the stream position
+ * does not advance; a flag makes every rank switch to l2a_set_split(ctx, 0) and repeat the whole step once with the same offsets
+ * (L2A_STEP_UNSPLIT, one relaunch; flagged again: L2A_ESPLIT).  With the same seed every rank's step equals the unsharded
+ * controller's bit for bit, and l2a_cem_controller_result returns the GATHERED [iters, m, n] tables.  The in-flight exclusion
+ * rules above apply unchanged.                                                                                                   */
+int l2a_cem_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
+                                             double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
+                                             int reference, unsigned long long seed, int rank, int world, l2a_reduce_fn reduce,
+                                             void* reduce_arg, l2a_controller** out);
 int l2a_cem_controller_result(l2a_controller* controller, float* mean_out, float* std_out, float* returns_out);
 void l2a_controller_destroy(l2a_controller* controller);
 int l2a_controller_step(l2a_controller* controller, const double* obs, double* action_out, long long* index_out,

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("L2A_LIB_PATH") or os.path.join(_HERE, "libl2a_hip.so"
 
 # include/l2a.h
 L2A_OK = 0
+L2A_ESTATE = -4
 L2A_ESPLIT = -5
 L2A_STEP_MISS = 1
 L2A_STEP_UNSPLIT = 2
@@ -41,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "l2a_controller_destroy", "l2a_controller_step", "l2a_controller_begin", "l2a_lstm_controller_begin", "l2a_controller_finish",
     "l2a_lstm_controller_step", "l2a_controller_rearm", "l2a_controller_actions", "l2a_controller_stats",
     "l2a_cem_controller_create_device", "l2a_cem_controller_result",
+    "l2a_cem_shard_pack", "l2a_cem_shard_unpack", "l2a_cem_word_encode", "l2a_cem_word_decode", "l2a_cem_controller_create_sharded_device",
 )
 
 
@@ -264,6 +266,18 @@ def load():
         lib.l2a_cem_controller_create_device.restype = i32
         lib.l2a_cem_controller_result.argtypes = [vp, vp, vp, vp]
         lib.l2a_cem_controller_result.restype = i32
+    if hasattr(lib, "l2a_cem_controller_create_sharded_device"):
+        lib.l2a_cem_shard_pack.argtypes = [vp, vp, i32, i32, i32, i32, c.c_ulonglong, vp, vp]
+        lib.l2a_cem_shard_pack.restype = i32
+        lib.l2a_cem_shard_unpack.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+        lib.l2a_cem_shard_unpack.restype = i32
+        lib.l2a_cem_word_encode.argtypes = [f32]
+        lib.l2a_cem_word_encode.restype = c.c_ulonglong
+        lib.l2a_cem_word_decode.argtypes = [c.c_ulonglong, c.POINTER(f32)]
+        lib.l2a_cem_word_decode.restype = i32
+        lib.l2a_cem_controller_create_sharded_device.argtypes = [vp, i32, i32, i32, vp, vp, c.c_double, c.POINTER(RewardSpec), i32, i32, f32, i32,
+                                                                 c.c_ulonglong, i32, i32, vp, vp, c.POINTER(vp)]
+        lib.l2a_cem_controller_create_sharded_device.restype = i32
     _lib = lib
     return lib
 

@@ -1,5 +1,5 @@
 // l2a_cem.hip - the cross-entropy-method planner's per-iteration work around the fused rollout, on the device
-// (include/l2a.h: l2a_cem_sample, l2a_cem_refit).  gfx950 only.
+// (include/l2a.h: l2a_cem_sample, l2a_cem_refit, l2a_cem_shard_pack / _unpack).  gfx950 only.
 //
 // Reference: `MPCController.get_cem_action` (policies/mpc_controller.py:71-106).  Per iteration the reference draws
 // n * m * h * act_dim standard normals on the host (:85), forms a = mean + z * std (:86), clips (:87), rolls the
@@ -499,6 +499,62 @@ __global__ void __launch_bounds__(256) l2a_cem_pick_k(const float* returns, cons
     if (threadIdx.x == 0) { out[i * W + act_dim] = returns[(long long)i * n + j]; out[i * W + act_dim + 1] = __int_as_float(j); }
 }
 
+
+// ---- sharded CEM: every rank's returns of one iteration gathered by the plan's ONE collective kind, the int64 MAX all-reduce ------
+// A rank contributes m * n + 3 words: word i * n + j = (1 << 32) | the RAW bits of its return of env i's candidate j when it owns
+// j (lo <= j < hi), else 0 - only the owner's word is non-zero, so MAX hands it to every rank exactly (NaN payloads, -0.0, +-inf
+// included; every word is below 2^33, so a signed MAX reduces them alike); behind them [launch flag | digest | MASK - digest] as
+// l2a_plan_payload_k packs them.
+#define L2A_CEM_WORD_PRESENT (1ull << 32)
+
+// One launch writes ALL m * n + 3 words (zeros outside the shard: no memset in front).  returns_local [m, hi - lo].
+__global__ void __launch_bounds__(256) l2a_cem_shard_pack_k(const float* __restrict__ returns_local, int m, int n, int lo, int hi,
+                                                            const unsigned int* status, unsigned long long digest,
+                                                            unsigned long long* __restrict__ words) {
+    const long long total = (long long)m * n;
+    const int n_local = hi - lo;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int i = (int)(e / n), j = (int)(e - (long long)i * n);
+        unsigned long long w = 0ull;
+        if (j >= lo && j < hi) w = L2A_CEM_WORD_PRESENT | (unsigned long long)__float_as_uint(returns_local[(long long)i * n_local + (j - lo)]);
+        words[e] = w;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // the status word lives in host-mapped memory; the rollout in front ORed into it with system scope and has completed
+        const unsigned int st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const unsigned long long d = digest & L2A_DIGEST_MASK;
+        words[total] = st ? 1ull : 0ull;
+        words[total + 1] = d;
+        words[total + 2] = L2A_DIGEST_MASK - d;
+    }
+}
+
+// One launch decodes the reduced words into the fp32 table [m, n] the refit and the pick read, and ACCUMULATES into verdict [3]:
+// [0] |= any rank's flag, [1] += zero words ("holes": a candidate nobody contributed, decoded as 0.0f), [2] |= the digest pair
+// does not add up (ranks built differently, or out of step).
+__global__ void __launch_bounds__(256) l2a_cem_shard_unpack_k(const unsigned long long* __restrict__ words, int m, int n,
+                                                              float* __restrict__ returns_out, unsigned int* verdict) {
+    const long long total = (long long)m * n;
+    int holes = 0;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const unsigned long long w = words[e];
+        holes += (w == 0ull) ? 1 : 0;
+        returns_out[e] = (w == 0ull) ? 0.0f : __uint_as_float((unsigned int)w);
+    }
+    for (int o = 32; o >= 1; o >>= 1) holes += __shfl_xor(holes, o);
+    if ((threadIdx.x & 63) == 0 && holes > 0) atomicAdd(&verdict[1], (unsigned int)holes);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (words[total] != 0ull) atomicOr(&verdict[0], 1u);
+        if (words[total + 1] + words[total + 2] != L2A_DIGEST_MASK) atomicOr(&verdict[2], 1u);
+    }
+}
+
+// workgroups of the two launches above: a grid-stride loop, at most four workgroups per CU
+unsigned cem_shard_blocks(const l2a_ctx* ctx, long long total) {
+    const long long want = (total + 255) / 256, most = 4LL * (ctx->num_cu > 0 ? ctx->num_cu : 256);
+    return (unsigned)(want < 1 ? 1 : (want < most ? want : most));
+}
+
 }  // namespace
 
 extern "C" {
@@ -623,6 +679,44 @@ int l2a_cem_pick(l2a_ctx* ctx, const float* returns, const float* cand, const fl
     const long long copy_blocks = (2LL * m * D + 255) / 256;
     hipLaunchKernelGGL(l2a_cem_pick_k, dim3((unsigned)(m + copy_blocks)), dim3(256), 0, stream, returns, cand, mean, std, n, m, D,
                        act_dim, reference ? 1 : 0, out);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
+}
+
+
+unsigned long long l2a_cem_word_encode(float ret) {
+    unsigned int bits = 0;
+    std::memcpy(&bits, &ret, sizeof(bits));
+    return L2A_CEM_WORD_PRESENT | (unsigned long long)bits;
+}
+
+int l2a_cem_word_decode(unsigned long long word, float* ret) {
+    const unsigned int bits = word ? (unsigned int)word : 0u;      // an absent word decodes as 0.0f, like the kernel
+    if (ret) std::memcpy(ret, &bits, sizeof(bits));
+    return word ? 1 : 0;
+}
+
+int l2a_cem_shard_pack(l2a_ctx* ctx, const float* returns_local, int m, int n, int lo, int hi, unsigned long long digest,
+                       unsigned long long* words_out, void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    if (m < 1 || n < 1 || lo < 0 || hi < lo || hi > n) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_shard_pack: bad m / n / shard");
+    if (!words_out || (hi > lo && !returns_local)) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_shard_pack: null pointer");
+    if ((long long)m * n > 0x3fffffffLL) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_shard_pack: too many candidates");
+    l2a_device_guard guard(ctx->device);
+    hipLaunchKernelGGL(l2a_cem_shard_pack_k, dim3(cem_shard_blocks(ctx, (long long)m * n)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream_v), returns_local, m, n, lo, hi, ctx->status_dev, digest, words_out);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
+}
+
+int l2a_cem_shard_unpack(l2a_ctx* ctx, const unsigned long long* words, int m, int n, float* returns_out, unsigned int* verdict,
+                         void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    if (m < 1 || n < 1 || (long long)m * n > 0x3fffffffLL) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_shard_unpack: bad m / n");
+    if (!words || !returns_out || !verdict) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_shard_unpack: null pointer");
+    l2a_device_guard guard(ctx->device);
+    hipLaunchKernelGGL(l2a_cem_shard_unpack_k, dim3(cem_shard_blocks(ctx, (long long)m * n)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream_v), words, m, n, returns_out, verdict);
     L2A_HIP(ctx, hipGetLastError());
     return L2A_OK;
 }

@@ -99,6 +99,13 @@ struct cem_state {
     float* packed_host = nullptr;               // page-locked
     hipEvent_t done = nullptr;
     int cur = 0;                                // the buffers of the last iteration
+    // one rank of a sharded plan (l2a_cem_controller_create_sharded_device): rollouts of candidates [lo, hi), every iteration's
+    // returns gathered by the int64 MAX all-reduce of m * n + 3 words (l2a_cem_shard_pack / _unpack)
+    bool sharded = false;
+    float* rets_local = nullptr;                // [m, hi - lo]: this rank's returns of the iteration under way
+    unsigned long long* words = nullptr;        // [m * n + 3]
+    unsigned int* verdict_dev = nullptr;        // [3] behind packed_dev's floats: flag | holes | digest mismatch, accumulated per step
+    unsigned long long digest = 0;
 };
 
 extern "C" unsigned long long l2a_mt19937_state_digest(const void* addr);      // csrc/l2a_rng.c
@@ -470,6 +477,24 @@ __global__ void __launch_bounds__(256) l2a_cem_init_k(int md, float* __restrict_
     if (e < md) { mean[e] = 0.0f; std[e] = 1.0f; }
 }
 
+// What every rank of a sharded CEM step must share: how the controller was built and where its Philox stream stands.
+unsigned long long cem_digest(const l2a_controller* c) {
+    const cem_state* q = c->cem;
+    unsigned int alpha_bits = 0;
+    std::memcpy(&alpha_bits, &q->alpha, sizeof(alpha_bits));
+    const unsigned long long v[] = {c->seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n, (unsigned long long)c->h,
+                                    (unsigned long long)q->iters, (unsigned long long)q->k, (unsigned long long)q->reference,
+                                    (unsigned long long)alpha_bits, (unsigned long long)c->world};
+    unsigned long long d = 0x9E3779B97F4A7C15ull;
+    for (unsigned long long x : v) {            // splitmix64's finaliser over the running value
+        d = (d ^ x) + 0x9E3779B97F4A7C15ull;
+        d = (d ^ (d >> 30)) * 0xBF58476D1CE4E5B9ull;
+        d = (d ^ (d >> 27)) * 0x94D049BB133111EBull;
+        d ^= d >> 31;
+    }
+    return d;
+}
+
 // Everything of one CEM plan step, in stream order on `stream`; nothing on the host waits.
 int cem_launch(l2a_controller* c) {
     l2a_ctx* ctx = c->ctx;
@@ -484,17 +509,36 @@ int cem_launch(l2a_controller* c) {
     const float* low = q->lowhigh;
     const float* high = q->lowhigh + A;
     int cur = 0;
-    int rc = l2a_cem_sample(ctx, nullptr, c->seed, q->iter_calls * per_iter, q->mean[0], q->std, low, high, n, m, h, A, q->reference, 0, n,
+    // (sharded: every rank samples all n rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
+    const int lo = c->lo, hi = c->hi, n_local = hi - lo;
+    if (q->sharded) L2A_HIP(ctx, hipMemsetAsync(q->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
+    int rc = l2a_cem_sample(ctx, nullptr, c->seed, q->iter_calls * per_iter, q->mean[0], q->std, low, high, n, m, h, A, q->reference, lo, hi,
                             q->a_clip[0], q->reference ? q->a_raw : nullptr, q->seq, c->stream);
     if (rc != L2A_OK) return rc;
     ctx->stamps_us[1] = l2a_now_us();
     for (int it = 0; it < q->iters; ++it) {
         float* rets = q->rets + (size_t)it * m * n;
-        rc = l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n, h, c->discount, &c->rw, 0, rets, c->keys_dev, c->stream);
-        if (rc != L2A_OK) return rc;
+        if (!q->sharded) {
+            rc = l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n, h, c->discount, &c->rw, 0, rets, c->keys_dev, c->stream);
+            if (rc != L2A_OK) return rc;
+        } else {
+            // this rank's rollouts -> words -> the ONE collective -> every rank's returns in the iteration's slot of `rets`
+            if (n_local > 0) {
+                rc = l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n_local, h, c->discount, &c->rw, lo, q->rets_local, c->keys_dev, c->stream);
+                if (rc != L2A_OK) return rc;
+            }
+            rc = l2a_cem_shard_pack(ctx, q->rets_local, m, n, lo, hi, q->digest, q->words, c->stream);
+            if (rc != L2A_OK) return rc;
+            const int words = m * n + 3;
+            rc = c->reduce ? c->reduce(c->reduce_arg, q->words, words, c->stream)
+                           : l2a_allreduce_best(ctx, q->words, words, c->stream);       // RCCL: uint64 MAX over xGMI
+            if (rc != L2A_OK) return c->reduce ? fail(ctx, L2A_EHIP, "l2a_controller_step: the caller's reduce function failed") : rc;
+            rc = l2a_cem_shard_unpack(ctx, q->words, m, n, rets, q->verdict_dev, c->stream);
+            if (rc != L2A_OK) return rc;
+        }
         if (it + 1 < q->iters) {
             rc = l2a_cem_refit_sample(ctx, rets, q->a_clip[cur], n, m, h, A, q->k, q->reference, q->alpha, nullptr, c->seed,
-                                      (q->iter_calls + it + 1) * per_iter, low, high, 0, n, q->rows, q->mean[cur], q->mean[cur ^ 1], q->std,
+                                      (q->iter_calls + it + 1) * per_iter, low, high, lo, hi, q->rows, q->mean[cur], q->mean[cur ^ 1], q->std,
                                       q->a_clip[cur ^ 1], q->reference ? q->a_raw : nullptr, q->seq, c->stream);
             cur ^= 1;
         } else {
@@ -506,7 +550,7 @@ int cem_launch(l2a_controller* c) {
                       D, A, q->reference, q->packed_dev, c->stream);
     if (rc != L2A_OK) return rc;
     q->cur = cur;
-    const size_t words = (size_t)m * (A + 2) + 2 * (size_t)m * D;
+    const size_t words = (size_t)m * (A + 2) + 2 * (size_t)m * D + (q->sharded ? 3 : 0);      // (sharded: + the verdict's three words)
     L2A_HIP(ctx, hipMemcpyAsync(q->packed_host, q->packed_dev, sizeof(float) * words, hipMemcpyDeviceToHost, stream));
     L2A_HIP(ctx, hipEventRecord(q->done, stream));
     ctx->stamps_us[2] = l2a_now_us();
@@ -526,10 +570,40 @@ int cem_begin(l2a_controller* c, const double* obs, void* stream) {
     for (int i = 0; i < no; ++i) c->obs32[i] = (float)obs[i];
     c->stream = stream;
     c->result = L2A_OK;
+    if (cem_state* q = c->cem; q->sharded) q->digest = cem_digest(c);
     const int rc = cem_launch(c);
     if (rc != L2A_OK) return rc;
     ctx->stamps_us[3] = l2a_now_us();
     set_in_flight(c, true);
+    return L2A_OK;
+}
+
+// The sharded step's wait.  The REDUCED verdict alone decides - it is the same on every rank, so the ranks never disagree on the
+// number of collectives.  This rank's own status word travelled in its words; it is consumed here and never consulted.
+int cem_finish_sharded(l2a_controller* c, int* result) {
+    l2a_ctx* ctx = c->ctx;
+    cem_state* q = c->cem;
+    for (int attempt = 0; ; ++attempt) {
+        L2A_HIP(ctx, hipEventSynchronize(q->done));
+        ctx->stamps_us[4] = l2a_now_us();
+        *ctx->status_host = 0;
+        unsigned int verdict[3];
+        std::memcpy(verdict, q->packed_host + (size_t)c->m * (c->act_dim + 2) + 2 * (size_t)c->m * q->D, sizeof(verdict));
+        if (verdict[2] != 0)
+            return fail(ctx, L2A_ESTATE, "sharded CEM needs identically built controllers in step on every rank (same seed, step count, "
+                                         "m, n, h, iters, num_elites, mode, alpha and world): the ranks' digests differ");
+        if (verdict[1] != 0)
+            return fail(ctx, L2A_ESTATE, "sharded CEM: " + std::to_string(verdict[1]) + " returns of this step were contributed by no rank "
+                                         "(the collective did not reduce over every rank of the plan)");
+        if (verdict[0] == 0) break;
+        // SOME rank's launch lost its tile-split partner: all ranks repeat the whole step unsplit, together (same offsets, same bits)
+        if (attempt == 1) return fail(ctx, L2A_ESPLIT, "l2a_controller_step: some rank's rollout was flagged invalid twice");
+        (void)l2a_set_split(ctx, 0);
+        c->relaunches += 1;
+        *result = L2A_STEP_UNSPLIT;
+        const int rc = cem_launch(c);
+        if (rc != L2A_OK) return rc;
+    }
     return L2A_OK;
 }
 
@@ -543,7 +617,11 @@ int cem_finish(l2a_controller* c, double* action_out, long long* index_out, floa
     cem_state* q = c->cem;
     int result = c->result;
     l2a_device_guard guard(ctx->device);
-    for (int attempt = 0; ; ++attempt) {
+    if (q->sharded) {
+        const int rc = cem_finish_sharded(c, &result);
+        if (rc != L2A_OK) return rc;
+    }
+    for (int attempt = 0; !q->sharded; ++attempt) {      // (unsharded: this context's own status word)
         L2A_HIP(ctx, hipEventSynchronize(q->done));
         ctx->stamps_us[4] = l2a_now_us();
         if (*ctx->status_host == 0) break;
@@ -657,37 +735,46 @@ int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, cons
     return create(ctx, nullptr, model, obs_dim, act_dim, units, m, n, h, low, high, discount, reward, nullptr, 1, out, true, seed);
 }
 
-int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
-                                     const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
-                                     unsigned long long seed, l2a_controller** out) {
+// Both CEM controllers: the unsharded one is rank 0 of a world of 1 without the collective's buffers.
+static int cem_create(const std::string& who, l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                      const l2a_reward* reward, int iters, int num_elites, float alpha, int reference, unsigned long long seed,
+                      bool sharded, int rank, int world, l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out) {
     if (!model) return L2A_EINVAL;
     l2a_ctx* ctx = nullptr;
     int obs_dim = 0, act_dim = 0;
     l2a_model_facts(model, &ctx, &obs_dim, &act_dim);
-    if (!out) return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: out is null");
+    if (sharded && (world < 1 || rank < 0 || rank >= world)) return fail(ctx, L2A_EINVAL, who + ": bad rank / world");
+    if (sharded && !reduce && (!ctx->comm || ctx->comm_world != world || ctx->comm_rank != rank))
+        return fail(ctx, L2A_ESTATE, who + ": no reduce function and no communicator of this rank / world (l2a_comm_init)");
+    if (!out) return fail(ctx, L2A_EINVAL, who + ": out is null");
     *out = nullptr;
-    if (!low || !high || !reward) return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: null low / high / reward");
+    if (!low || !high || !reward) return fail(ctx, L2A_EINVAL, who + ": null low / high / reward");
     if (m < 1 || m > L2A_MAIL_KEYS || (long long)m * obs_dim > L2A_MAIL_OBS || n < 1 || h < 1 || act_dim < 1 || act_dim > 16)
-        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, "
+        return fail(ctx, L2A_EINVAL, who + ": needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, "
                                      "h >= 1, 1 <= act_dim <= 16");
     if (iters < 1 || num_elites < 1 || num_elites > n)
-        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: needs iters >= 1 and 1 <= num_elites <= n");
+        return fail(ctx, L2A_EINVAL, who + ": needs iters >= 1 and 1 <= num_elites <= n");
     if ((long long)(reference ? m : 1) * num_elites > 8192 || (size_t)n * sizeof(float) > (size_t)ctx->lds_per_block)
-        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: more elite rows or candidates than l2a_cem_refit takes");
+        return fail(ctx, L2A_EINVAL, who + ": more elite rows or candidates than l2a_cem_refit takes");
     const long long D = (long long)h * act_dim;
-    if ((long long)n * m * D > 0x7fffffffLL || (long long)iters * m * n > 0x7fffffffLL)
-        return fail(ctx, L2A_EINVAL, "l2a_cem_controller_create_device: too many samples");
+    if ((long long)n * m * D > 0x7fffffffLL || (long long)iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
+        return fail(ctx, L2A_EINVAL, who + ": too many samples");
     l2a_controller* c = new (std::nothrow) l2a_controller();
     cem_state* q = c ? new (std::nothrow) cem_state() : nullptr;
-    if (!q) { delete c; return fail(ctx, L2A_EHIP, "l2a_cem_controller_create_device: out of memory"); }
+    if (!q) { delete c; return fail(ctx, L2A_EHIP, who + ": out of memory"); }
     c->ctx = ctx; c->mlp = model; c->cem = q;
     c->m = m; c->n = n; c->h = h; c->obs_dim = obs_dim; c->act_dim = act_dim;
     c->discount = discount; c->rw = *reward;
     for (int k = 0; k < act_dim; ++k) { c->low[k] = low[k]; c->high[k] = high[k]; }
-    c->device_rng = true; c->seed = seed; c->lo = 0; c->hi = n;
+    c->device_rng = true; c->seed = seed;
+    c->rank = rank; c->world = world; c->reduce = reduce; c->reduce_arg = reduce_arg;
+    c->lo = (int)((long long)rank * n / world);                 // contiguous candidate ranges (MPCController._shard_range)
+    c->hi = (int)((long long)(rank + 1) * n / world);
+    q->sharded = sharded;
+    const size_t n_local = (size_t)(c->hi - c->lo), n_alloc = n_local > 0 ? n_local : 1;
     q->iters = iters; q->k = num_elites; q->reference = reference ? 1 : 0; q->D = (int)D; q->alpha = alpha;
     l2a_device_guard guard(ctx->device);
-    const size_t md = (size_t)m * D, nmd = (size_t)n * md, words = (size_t)m * (act_dim + 2) + 2 * md;
+    const size_t md = (size_t)m * D, nmd = (size_t)n * md, words = (size_t)m * (act_dim + 2) + 2 * md + (sharded ? 3 : 0);
     hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&c->obs_map_host), sizeof(float) * L2A_MAIL_OBS, hipHostMallocMapped);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&c->obs_map_dev), c->obs_map_host, 0);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->keys_dev), sizeof(unsigned long long) * (size_t)m);
@@ -697,25 +784,43 @@ int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, cons
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->std), sizeof(float) * md);
     if (e == hipSuccess && q->reference) e = hipMalloc(reinterpret_cast<void**>(&q->a_raw), sizeof(float) * nmd);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->seq), sizeof(float) * nmd);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->seq), sizeof(float) * n_alloc * md);     // [h, m * n_local, act_dim]
+    if (e == hipSuccess && sharded) e = hipMalloc(reinterpret_cast<void**>(&q->rets_local), sizeof(float) * (size_t)m * n_alloc);
+    if (e == hipSuccess && sharded) e = hipMalloc(reinterpret_cast<void**>(&q->words), sizeof(unsigned long long) * ((size_t)m * n + 3));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->rows), sizeof(int) * (size_t)m * num_elites);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->rets), sizeof(float) * (size_t)iters * m * n);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->lowhigh), sizeof(float) * 2 * act_dim);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->packed_dev), sizeof(float) * words);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&q->packed_host), sizeof(float) * words, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&q->done, hipEventDisableTiming);
+    if (e == hipSuccess && sharded) q->verdict_dev = reinterpret_cast<unsigned int*>(q->packed_dev + (words - 3));
     if (e == hipSuccess) {
         float lh[32] = {0};
         for (int k = 0; k < act_dim; ++k) { lh[k] = (float)low[k]; lh[act_dim + k] = (float)high[k]; }
         e = hipMemcpy(q->lowhigh, lh, sizeof(float) * 2 * act_dim, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
-        const std::string msg = std::string("l2a_cem_controller_create_device: ") + hipGetErrorString(e);
+        const std::string msg = std::string(who + ": ") + hipGetErrorString(e);
         l2a_controller_destroy(c);
         return fail(ctx, L2A_EHIP, msg);
     }
     *out = c;
     return L2A_OK;
+}
+
+int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                     const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
+                                     unsigned long long seed, l2a_controller** out) {
+    return cem_create("l2a_cem_controller_create_device", model, m, n, h, low, high, discount, reward, iters, num_elites, alpha, reference,
+                      seed, false, 0, 1, nullptr, nullptr, out);
+}
+
+int l2a_cem_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                             const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
+                                             unsigned long long seed, int rank, int world, l2a_reduce_fn reduce, void* reduce_arg,
+                                             l2a_controller** out) {
+    return cem_create("l2a_cem_controller_create_sharded_device", model, m, n, h, low, high, discount, reward, iters, num_elites, alpha,
+                      reference, seed, true, rank, world, reduce, reduce_arg, out);
 }
 
 int l2a_cem_controller_result(l2a_controller* c, float* mean_out, float* std_out, float* returns_out) {
@@ -761,6 +866,8 @@ void l2a_controller_destroy(l2a_controller* c) {
         float* dev_bufs[] = {q->std, q->a_raw, q->seq, q->rets, q->lowhigh, q->packed_dev};
         for (float* b : dev_bufs) if (b) (void)hipFree(b);
         if (q->rows) (void)hipFree(q->rows);
+        if (q->rets_local) (void)hipFree(q->rets_local);
+        if (q->words) (void)hipFree(q->words);
         if (q->packed_host) (void)hipHostFree(q->packed_host);
         if (q->done) (void)hipEventDestroy(q->done);
         delete q;

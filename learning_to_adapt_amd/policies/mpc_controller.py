@@ -27,9 +27,9 @@ GPU runs the current plan and adopted only if the global generator is still in e
 ``policies/draw_ahead.py``; numbers, order and the state left behind are the reference's), ``native_step`` (parity-mode
 random shooting on one GPU: the whole step - adopt the block drawn ahead by a C thread, launch, wait, decode, gather - is ONE
 C call, ``l2a_controller_step``, ``policies/native_step.py``; a step that finds no valid block falls back to the path above),
-``native_cem_step`` (off by default: ``rng="device"`` CEM on one GPU through the C controller,
-``l2a_cem_controller_create_device`` - bit-identical to ``get_cem_action_device``, ``policies/native_cem_step.py``; every other
-case keeps the Python path).
+``native_cem_step`` (off by default: ``rng="device"`` CEM through the C controller, ``l2a_cem_controller_create_device`` -
+sharded over torch.distributed ranks: ``l2a_cem_controller_create_sharded_device``, one rank each - bit-identical to
+``get_cem_action_device``, ``policies/native_cem_step.py``; every other case keeps the Python path).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -107,6 +107,7 @@ class MPCController(Policy, Serializable):
         self._cstep = None          # NativeStep (l2a_controller): the whole parity-mode step in one C call
         self._cstep_no = None       # request key the C controller was found ineligible for
         self._cemstep = None        # NativeCemStep (CEM l2a_controller, rng="device"): the whole CEM plan step in one C call
+        self._cemstep_no = None     # key of a sharded CEM controller that could not be built (the collective's dry run failed)
         self._cem_first_chunk = 4   # horizon steps of the first chunk of a pipelined CEM rollout (0: equal chunks)
         self.last_plan = None       # diagnostics of the latest fused plan (returns, keys, ...)
 
@@ -1084,19 +1085,22 @@ class MPCController(Policy, Serializable):
         return out
 
     def _native_cem_step(self, observations):
-        """``rng="device"`` CEM on one GPU through the C controller (``l2a_cem_controller_create_device``): the same Philox offsets as
-        ``get_cem_action_device``, so the two paths can take turns only while they agree on the stream position - the C controller
-        is built where the Python path's counter is 0 for this seed and dropped when the Python path has planned since.  Returns the
-        actions, or None when the C controller does not apply (parity mode, sharded plan, recurrent model, a test hook replaced the
-        normals or the launch path, a forked child)."""
+        """``rng="device"`` CEM through the C controller (``l2a_cem_controller_create_device``; at ``world > 1`` this rank's
+        ``l2a_cem_controller_create_sharded_device``, whose per-iteration gather of the returns is the int64 MAX all-reduce of
+        ``m * n + 3`` words through ``_reduce_payload`` - or the library's communicator, ``L2A_NATIVE_COMM=1``): the same Philox
+        offsets as ``get_cem_action_device``, so the two paths can take turns only while they agree on the stream position - the C
+        controller is built where the Python path's counter is 0 for this seed and dropped when the Python path has planned since.
+        Returns the actions, or None when the C controller does not apply (parity mode, recurrent model, a test hook replaced the
+        normals or the launch path, a backend that cannot reduce the words, a forked child)."""
         if self.rng != "device" or not self._native_step_stock():
             return None
         if getattr(self._cem_normal_device, "__func__", None) is not MPCController._cem_normal_device:
             return None
-        if self._dist()[1] > 1:
-            return None
+        rank, world = self._dist()
         native = self.dynamics_model.planner_model()
         if hasattr(native, "units") or not hasattr(native.lib, "l2a_cem_controller_create_device"):
+            return None
+        if world > 1 and not hasattr(native.lib, "l2a_cem_controller_create_sharded_device"):
             return None
         n, m, h = self.n_candidates, len(observations), self.horizon
         if m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16:
@@ -1106,7 +1110,7 @@ class MPCController(Policy, Serializable):
             self._bufs["cem_seed"], self._bufs["cem_calls"] = seed, 0
         num_elites = max(int(n * self.percent_elites), 1)
         key = (id(native), native.handle.value, m, n, h, float(self.discount), seed, self.cem_mode, int(self.num_cem_iters),
-               num_elites, float(self.alpha))
+               num_elites, float(self.alpha), rank, world)
         st = self._cemstep
         if st is not None and (st.pid != os.getpid() or st.key != key or st.calls != self._bufs["cem_calls"]):
             if st.pid != os.getpid():
@@ -1117,8 +1121,25 @@ class MPCController(Policy, Serializable):
             if self._bufs["cem_calls"] != 0:
                 return None                 # the Python path has planned with this seed: its stream position is not the C one's
             from .native_cem_step import NativeCemStep
+            shard = None
+            if world > 1:
+                if self._cemstep_no == key:
+                    return None
+                # every rank builds its controller in the same plan step, so the dry run of the collective the callback will issue
+                # every iteration is symmetric (`_native_step_build`): a backend that cannot MAX-reduce int64 words on this device
+                # keeps the Python path
+                own = os.environ.get("L2A_NATIVE_COMM", "0") == "1" and torch.distributed.get_backend() != "gloo"
+                if own:
+                    self._native_comm(native, rank, world)
+                else:
+                    try:
+                        self._reduce_payload(torch.zeros((m * n + 3,), dtype=torch.int64, device=native.device))
+                    except Exception:
+                        self._cemstep_no = key
+                        return None
+                shard = (rank, world, None if own else self._reduce_payload)
             st = NativeCemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
-                               self.num_cem_iters, num_elites, self.alpha, self.cem_mode == "reference", seed)
+                               self.num_cem_iters, num_elites, self.alpha, self.cem_mode == "reference", seed, shard=shard)
             st.key, st.calls = key, 0
             self._cemstep = st
         self._check_blocks(m)
@@ -1128,6 +1149,8 @@ class MPCController(Policy, Serializable):
         mean, std, rets = st.result()
         self.last_plan = dict(best_index=st.idx.copy(), best_return=st.ret.copy(), cem_mean=mean, cem_std=std,
                               cem_trace=[dict(returns=rets[it]) for it in range(rets.shape[0])])
+        if world > 1:
+            self.last_plan["shard"] = self._shard_range(n, rank, world)
         return st.act.copy()
 
     def get_cem_action(self, observations):

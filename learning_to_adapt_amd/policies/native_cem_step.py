@@ -5,6 +5,11 @@ Per step the C controller enqueues iteration 0's sampling, then per iteration th
 (iteration i's returns -> iteration i + 1's candidates), the pick of the best candidate, and one read-back; the Python path makes
 three ctypes calls and a torch call per iteration.  Same Philox offsets as the Python path: with the same seed and the same number
 of iterations planned so far the result is bit-identical.
+
+``shard=(rank, world, reduce)`` builds ONE rank of a plan sharded over ``world`` GPUs (``l2a_cem_controller_create_sharded_device``):
+the rank rolls out its slice of the candidates and every iteration's returns are gathered by an int64 MAX all-reduce of
+``m * n + 3`` words - ``reduce(tensor)`` in place (torch.distributed), or the library's own RCCL communicator when ``reduce`` is
+None.  Every rank's step equals the unsharded one bit for bit.
 """
 
 import ctypes
@@ -13,10 +18,11 @@ import os
 import numpy as np
 
 from .. import _lib
+from .native_step import make_reduce_cb
 
 
 class NativeCemStep(object):
-    def __init__(self, native, m, n, h, low, high, discount, reward, iters, num_elites, alpha, reference, seed):
+    def __init__(self, native, m, n, h, low, high, discount, reward, iters, num_elites, alpha, reference, seed, shard=None):
         lib = native.lib
         self.lib, self.ctx, self.native = lib, native.ctx, native
         self.m, self.n, self.h, self.iters = int(m), int(n), int(h), int(iters)
@@ -24,11 +30,22 @@ class NativeCemStep(object):
         low = np.ascontiguousarray(low, dtype=np.float64)
         high = np.ascontiguousarray(high, dtype=np.float64)
         handle = ctypes.c_void_p()
-        rc = lib.l2a_cem_controller_create_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                                                  float(discount), ctypes.byref(reward), self.iters, int(num_elites), float(alpha),
-                                                  1 if reference else 0, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                                  ctypes.byref(handle))
-        self.ctx.check(rc, "l2a_cem_controller_create_device")
+        self.reduce_error = None
+        self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
+        seed = ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if shard is None:
+            rc = lib.l2a_cem_controller_create_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
+                                                      float(discount), ctypes.byref(reward), self.iters, int(num_elites), float(alpha),
+                                                      1 if reference else 0, seed, ctypes.byref(handle))
+            self.ctx.check(rc, "l2a_cem_controller_create_device")
+        else:
+            rank, world, reduce = shard
+            cb = make_reduce_cb(self, lib, native, reduce)
+            rc = lib.l2a_cem_controller_create_sharded_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
+                                                              float(discount), ctypes.byref(reward), self.iters, int(num_elites),
+                                                              float(alpha), 1 if reference else 0, seed, int(rank), int(world), cb, None,
+                                                              ctypes.byref(handle))
+            self.ctx.check(rc, "l2a_cem_controller_create_sharded_device")
         self.handle = handle
         self.pid = os.getpid()
         self.obs = np.empty((self.m, native.obs_dim), dtype=np.float64)
@@ -37,6 +54,7 @@ class NativeCemStep(object):
         self.ret = np.empty((self.m,), dtype=np.float32)
         self._p = (self.obs.ctypes.data, self.act.ctypes.data, self.idx.ctypes.data, self.ret.ctypes.data)
         self.steps = 0
+        self._stats = (ctypes.c_double * 16)()
 
     def step(self, observations, stream):
         """One plan step; ``self.act`` / ``self.idx`` / ``self.ret`` hold the result afterwards."""
@@ -46,6 +64,9 @@ class NativeCemStep(object):
         if rc == _lib.L2A_STEP_UNSPLIT:         # the C side has switched the context to the unsplit geometry (same bits)
             self.ctx.split_degraded = True
         elif rc != _lib.L2A_OK:
+            if self.reduce_error is not None:
+                exc, self.reduce_error = self.reduce_error, None
+                raise exc
             self.ctx.check(rc, "l2a_controller_step (CEM)")
         self.steps += 1
         return rc
@@ -59,6 +80,11 @@ class NativeCemStep(object):
                                                           rets.ctypes.data if rets is not None else None),
                        "l2a_cem_controller_result")
         return mean, std, rets
+
+    def stats(self):
+        self.ctx.check(self.lib.l2a_controller_stats(self.handle, self._stats, 16), "l2a_controller_stats")
+        v = list(self._stats)
+        return dict(stage_us=dict(sample=v[1], launch=v[2], wait=v[4], decode=v[5], call=v[6]), steps=int(v[7]), relaunches=int(v[8]))
 
     def close(self):
         if getattr(self, "handle", None):

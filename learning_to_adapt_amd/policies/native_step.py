@@ -30,6 +30,36 @@ def _alias_int64(ptr, words, device):
     return torch.as_tensor(_DevWords(ptr, words), device=device)
 
 
+def make_reduce_cb(owner, lib, native, reduce):
+    """ctypes callback around ``reduce(tensor)`` for a sharded C controller (``l2a_reduce_fn``; None: the library's own RCCL
+    communicator is used).  The collective runs on a tensor torch allocated itself (what every backend is used to); the library's
+    words are copied in and out on the same stream (two tiny copies) - the alias of the library's buffer never reaches the process
+    group.  The callback is kept alive on ``owner`` (``_reduce_cb``); an exception raised by ``reduce`` is parked in
+    ``owner.reduce_error`` - it must not unwind through the C frame - and the C step fails."""
+    owner._reduce_cb = None
+    owner.reduce_error = None
+    if reduce is None:
+        return None
+    owner._payload = None
+
+    def _cb(arg, ptr, words, stream, _reduce=reduce):
+        try:
+            if owner._payload is None or owner._payload[0] != (ptr, words):
+                import torch
+                alias = _alias_int64(ptr, words, native.device)
+                owner._payload = ((ptr, words), alias, torch.empty_like(alias))
+            _, alias, own = owner._payload
+            own.copy_(alias)
+            _reduce(own)
+            alias.copy_(own)
+            return 0
+        except Exception as exc:          # an exception must not unwind through the C frame
+            owner.reduce_error = exc
+            return -1
+    owner._reduce_cb = lib.REDUCE_FN(_cb)    # (kept alive with the controller)
+    return ctypes.cast(owner._reduce_cb, ctypes.c_void_p)
+
+
 class NativeStep(object):
     def __init__(self, native, recurrent, m, n, h, low, high, discount, reward, device_seed=None, shard=None):
         """``device_seed``: None = parity mode (NumPy's global generator, candidates drawn ahead by a C thread); an integer =
@@ -48,7 +78,7 @@ class NativeStep(object):
         if self.device_rng and shard is not None and not self.recurrent:
             self.addr, self.lock = None, None
             rank, world, reduce = shard
-            cb = self._make_reduce_cb(lib, native, reduce)
+            cb = make_reduce_cb(self, lib, native, reduce)
             rc = lib.l2a_controller_create_sharded_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
                                                           float(discount), ctypes.byref(reward),
                                                           ctypes.c_ulonglong(int(device_seed) & 0xFFFFFFFFFFFFFFFF), int(rank), int(world),
@@ -65,7 +95,7 @@ class NativeStep(object):
             self.lock = fast_rng._global_lock()
             if shard is not None and not self.recurrent:
                 rank, world, reduce = shard
-                cb = self._make_reduce_cb(lib, native, reduce)
+                cb = make_reduce_cb(self, lib, native, reduce)
                 rc = lib.l2a_controller_create_sharded(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
                                                        float(discount), ctypes.byref(reward), self.addr, fast_rng.threads(),
                                                        int(rank), int(world), cb, None, ctypes.byref(handle))
@@ -84,32 +114,6 @@ class NativeStep(object):
         self.misses_in_row = 0
         self.cooldown = 0
         self._stats = (ctypes.c_double * 16)()
-
-    def _make_reduce_cb(self, lib, native, reduce):
-        """ctypes callback around ``reduce(tensor)`` (None: the library's own RCCL communicator is used).  The collective runs on
-        a tensor torch allocated itself (what every backend is used to); the library's words are copied in and out on the same
-        stream (two tiny copies) - the alias of the library's buffer never reaches the process group."""
-        self._reduce_cb = None
-        if reduce is None:
-            return None
-        self._payload = None
-
-        def _cb(arg, ptr, words, stream, _reduce=reduce):
-            try:
-                if self._payload is None or self._payload[0] != (ptr, words):
-                    import torch
-                    alias = _alias_int64(ptr, words, native.device)
-                    self._payload = ((ptr, words), alias, torch.empty_like(alias))
-                _, alias, own = self._payload
-                own.copy_(alias)
-                _reduce(own)
-                alias.copy_(own)
-                return 0
-            except Exception as exc:          # an exception must not unwind through the C frame
-                self.reduce_error = exc
-                return -1
-        self._reduce_cb = lib.REDUCE_FN(_cb)    # (kept alive with the controller)
-        return ctypes.cast(self._reduce_cb, ctypes.c_void_p)
 
     def step(self, observations, stream, state=None):
         """One controller step.  Returns True (``self.act`` / ``self.idx`` / ``self.ret`` hold the result; when no valid block of
