@@ -81,6 +81,13 @@ def load():
         raise L2AError(
             "%s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
+    # PyTorch-ROCm brings its own HIP runtime and has to be in the process FIRST: loaded behind libl2a_hip.so (which pulls in the
+    # system's), the process holds two runtimes and l2a_init finds "no ROCm-capable device" once torch has opened the GPU
+    # (`build()` followed by `smoke()` in one interpreter did).  Importing torch touches no device.
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass            # plain C-ABI use without PyTorch
     lib = ctypes.CDLL(LIB_PATH)
     c = ctypes
     vp, i32, f32 = c.c_void_p, c.c_int, c.c_float

@@ -2,7 +2,9 @@
 kinds drawn from a seeded generator; every candidate's return is compared with the oracle (rel 1e-4)
 and the arg-max key with the returns the kernel itself wrote (bit exact).  Covers the corners between
 the hand-picked golden cases: obs/act dims that straddle 16-feature tiles, every MFMA-eligible hidden
-width and depth, odd ensembles under all tile-split policies, ragged candidate counts."""
+width and depth, odd ensembles under all tile-split policies, ragged candidate counts.  Coverage per compiled kernel
+instance (every unit x (OT, KG0) x variant, on the shapes at its bounds) lives in tests/test_gpu_instance_matrix.py; this sweep
+is the random complement to that table."""
 
 import os
 
