@@ -542,6 +542,32 @@ int l2a_controller_create_sharded(l2a_model* model, int m, int n, int h, const d
 int l2a_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
                                          double discount, const l2a_reward* reward, unsigned long long seed, int rank, int world,
                                          l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out);
+/* The sharded step of the RECURRENT planner (`RNNMPCController` at N > 1; run_scripts/run_rebal.py's plan over several GPUs): shard,
+ * collective and failure protocol are those of l2a_controller_create_sharded / _sharded_device above, unchanged - rank r rolls out
+ * candidates [r n / world, (r + 1) n / world) of every env with l2a_lstm_plan_rs (cand_offset = lo); parity mode: every rank consumes
+ * the generator for ALL h*n*m rows; device mode: every rank fills its slice of the SAME Philox stream, so the plan does not depend on
+ * the number of ranks; ONE MAX all-reduce of the m + 3 words of l2a_plan_payload per launch, one page-locked read-back; a digest
+ * mismatch fails the step with L2A_ESTATE on every rank, a reduced flag makes every rank repeat the step unsplit once
+ * (L2A_STEP_UNSPLIT; flagged again: L2A_ESPLIT); a rank with an empty shard (world > n) contributes the neutral key and still joins.
+ * Steps through l2a_lstm_controller_step / l2a_lstm_controller_begin / l2a_controller_finish / _stats / _destroy; action_out = the
+ * float64 first action of the GLOBAL winner (parity: the value NumPy drew; device: the fp32 stream value as float64).
+ * With c_next / h_next the controller's own state is advanced as well, in stream order BEHIND the collective:
+ *   state' = cell(obs, fp32 first action of the GLOBAL winner of each env, state)
+ * - the winner usually belongs to another rank, so the action is looked up through the REDUCED keys on the device, without a host
+ * round trip and without a second collective: parity mode in an fp32 table of the whole plan's first horizon step [m * n, act_dim]
+ * (the cast the candidate tensor gets, uploaded with every block), device mode in the stream itself (l2a_philox_uniform - the bits
+ * the owning rank rolled out).  One LSTM layer: l2a_lstm_advance's kernel; other cells: a gather and one step of the rollout kernel
+ * (never tile-split).  The index decoded from a key is clamped to [0, n): a flagged launch or a neutral key may hold anything, and
+ * the state written from it is overwritten by the relaunch (launch, payload, collective, advance, read-back - in that order again)
+ * or discarded with the failed step.  c_next / h_next are valid after L2A_OK / L2A_STEP_DREW / L2A_STEP_UNSPLIT and invalid after a
+ * negative return; with the same inputs they equal the unsharded controller's (l2a_lstm_controller_create[_device]) bit for bit.
+ * No mailbox; the in-flight exclusion rules of the CEM controllers below apply as for every RS / recurrent step.                   */
+int l2a_lstm_controller_create_sharded(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
+                                       double discount, const l2a_reward* reward, void* np_state_addr, int rng_threads, int rank,
+                                       int world, l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out);
+int l2a_lstm_controller_create_sharded_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
+                                              double discount, const l2a_reward* reward, unsigned long long seed, int rank, int world,
+                                              l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out);
 /* The same step with the candidates drawn ON THE DEVICE (`MPCController(rng="device")`: statistically equivalent to the reference's
  * draw, not its numbers; NumPy's generator is not touched): every step a Philox4x32-10 kernel fills the candidate tensor from the
  * counter-based stream (seed, steps so far) in front of the plan, and the winners' first actions are recomputed on the host from

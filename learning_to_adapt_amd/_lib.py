@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_controller_create", "l2a_controller_create_sharded", "l2a_controller_create_sharded_device", "l2a_lstm_controller_create", "l2a_controller_create_device", "l2a_lstm_controller_create_device",
+    "l2a_lstm_controller_create_sharded", "l2a_lstm_controller_create_sharded_device",
     "l2a_controller_destroy", "l2a_controller_step", "l2a_controller_begin", "l2a_lstm_controller_begin", "l2a_controller_finish",
     "l2a_lstm_controller_step", "l2a_controller_rearm", "l2a_controller_actions", "l2a_controller_stats",
     "l2a_cem_controller_create_device", "l2a_cem_controller_result",
@@ -267,6 +268,11 @@ def load():
         lib.l2a_controller_actions.restype = vp
         lib.l2a_controller_stats.argtypes = [vp, dp, i32]
         lib.l2a_controller_stats.restype = i32
+    if hasattr(lib, "l2a_lstm_controller_create_sharded"):       # the sharded recurrent step (absent from older variant libraries)
+        lib.l2a_lstm_controller_create_sharded.argtypes = lib.l2a_controller_create_sharded.argtypes
+        lib.l2a_lstm_controller_create_sharded.restype = i32
+        lib.l2a_lstm_controller_create_sharded_device.argtypes = lib.l2a_controller_create_sharded_device.argtypes
+        lib.l2a_lstm_controller_create_sharded_device.restype = i32
     if hasattr(lib, "l2a_cem_controller_create_device"):
         lib.l2a_cem_controller_create_device.argtypes = [vp, i32, i32, i32, vp, vp, c.c_double, c.POINTER(RewardSpec), i32, i32, f32, i32,
                                                          c.c_ulonglong, c.POINTER(vp)]

@@ -124,6 +124,13 @@ extern "C" L2A_HIDDEN int l2a_lstm_plan_rs_sync_hook(l2a_lstm* md, const float* 
                                                      const l2a_reward* reward, int cand_offset, unsigned long long* keys_host_out,
                                                      float* c_next, float* h_next, void* stream, l2a_after_launch_fn hook,
                                                      void* hook_arg, l2a_mail_pending* pending = nullptr);
+// The state advance of a SHARDED recurrent step (l2a_step.hip), enqueued behind the collective: state' = cell(obs, first action of
+// the GLOBAL winner of each env, state).  `keys` [m] (device): the reduced arg-max keys; the index decoded from a key is clamped to
+// [0, n).  `table` (device fp32 [m * n, act_dim]): the whole plan's first horizon step - or NULL: the action is recomputed from the
+// Philox stream (seed, offset; l2a_philox_uniform, lowr = [2][16] low | range), bit-equal to what the owning rank rolled out.
+extern "C" L2A_HIDDEN int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, const unsigned long long* keys, const float* table,
+                                                int n, unsigned long long seed, unsigned long long offset, const float* lowr,
+                                                const float* c0, const float* h0, float* c_next, float* h_next, int m, void* stream);
 extern "C" L2A_HIDDEN void l2a_model_facts(const l2a_model* md, l2a_ctx** ctx, int* obs_dim, int* act_dim);
 extern "C" L2A_HIDDEN void l2a_lstm_facts(const l2a_lstm* md, l2a_ctx** ctx, int* obs_dim, int* act_dim, int* units);
 inline double l2a_now_us() {

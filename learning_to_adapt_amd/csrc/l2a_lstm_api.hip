@@ -12,6 +12,7 @@
 #include "l2a_rnn_mfma.h"
 #include "l2a_micro_pack.h"
 #include "l2a_micro_launch.h"
+#include "l2a_philox.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -57,6 +58,20 @@ __global__ void l2a_gather_best_k(const unsigned long long* best_key, const floa
     idx = idx < 0 ? 0 : (idx >= n ? n - 1 : idx);
     for (int d = threadIdx.x; d < act_dim; d += blockDim.x)      // any action width (the generic cells take act_dim > 64)
         out[i * act_dim + d] = actions[((long long)i * n + idx) * act_dim + d];
+}
+
+// The same gather for a plan whose candidates are the counter-based stream (device-RNG mode, sharded: the winner usually belongs to
+// another rank's slice, which this rank never filled): out[i] = element ((i * n + index(best_key[i])) * act_dim + d) of the step's
+// stream - l2a_philox_uniform, the function the fill kernels and the host decode use, so the bits the owning rank rolled out.
+__global__ void l2a_gather_best_philox_k(const unsigned long long* best_key, int m, int n, int act_dim, unsigned long long seed,
+                                         unsigned long long offset, const float* lowr, float* out) {
+    const int i = blockIdx.x;
+    if (i >= m) return;
+    const unsigned int low = (unsigned int)(best_key[i] & 0x7fffffffull);
+    int idx = (int)(0x7fffffffu - low);
+    idx = idx < 0 ? 0 : (idx >= n ? n - 1 : idx);
+    for (int d = threadIdx.x; d < act_dim; d += blockDim.x)
+        out[i * act_dim + d] = l2a_philox_uniform(seed, offset + ((unsigned long long)i * n + idx) * act_dim + d, lowr[d], lowr[16 + d]);
 }
 
 namespace {
@@ -676,6 +691,41 @@ int l2a_lstm_plan_rs_sync_hook(l2a_lstm* md, const float* obs_host, const float*
     rc = l2a_mail_end(ctx, tk, m, publish, rc, stream, keys_host_out, "l2a_lstm_plan_rs_sync");
     ctx->stamps_us[4] = l2a_now_us();
     return rc;
+}
+
+int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, const unsigned long long* keys, const float* table, int n,
+                          unsigned long long seed, unsigned long long offset, const float* lowr, const float* c0, const float* h0,
+                          float* c_next, float* h_next, int m, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    if (!obs || !keys || (!table && !lowr) || !c0 || !h0 || !c_next || !h_next)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_advance_keys: null pointer");
+    if (m < 1 || m > L2A_MAIL_KEYS || n < 1) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_advance_keys: needs 1 <= m <= 64, n >= 1");
+    if (!table && md->act_dim > 16) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_advance_keys: the stream's bounds hold 16 action dimensions");
+    if (c_next == c0 || h_next == h0) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_advance_keys: the next state must not alias the current one");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    // one LSTM layer, actions in a table: the advance kernel gathers through the keys itself (as behind the unsharded plan)
+    if (table && advance_kernel_ok(md)) return launch_advance(md, obs, nullptr, keys, table, n, 0, c0, h0, c_next, h_next, m, stream);
+    if (!md->adv_buf)
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->adv_buf), sizeof(float) * L2A_MAIL_KEYS * (md->act_dim + md->obs_dim)));
+    float* act_sel = md->adv_buf;
+    if (table)
+        hipLaunchKernelGGL(l2a_gather_best_k, dim3((unsigned)m), dim3(64), 0, stream, keys, table, m, n, 0, md->act_dim, act_sel);
+    else
+        hipLaunchKernelGGL(l2a_gather_best_philox_k, dim3((unsigned)m), dim3(64), 0, stream, keys, m, n, md->act_dim, seed, offset, lowr,
+                           act_sel);
+    L2A_HIP(ctx, hipGetLastError());
+    if (advance_kernel_ok(md)) return launch_advance(md, obs, act_sel, nullptr, nullptr, 0, 0, c0, h0, c_next, h_next, m, stream);
+    // generic cells / stacks: one step of the rollout kernel on the gathered actions - never tile-split (see the comment in
+    // l2a_lstm_plan_rs_sync_hook: a flag raised here would be noticed one step late)
+    L2ALstmParams q;
+    fill(md, q);
+    q.obs0 = obs; q.c0 = c0; q.h0 = h0; q.actions = act_sel;
+    q.state_out = md->adv_buf + (size_t)L2A_MAIL_KEYS * md->act_dim; q.c_out = c_next; q.h_out = h_next;
+    q.obs_per_row = 1; q.hid_per_row = 1;
+    q.m = 1; q.n = m; q.h = 1; q.discount = 1.0;
+    return launch(md, q, stream_v, false);
 }
 
 int l2a_lstm_plan_rs_chunk(l2a_lstm* md, const float* state, const float* c, const float* h, int per_row,

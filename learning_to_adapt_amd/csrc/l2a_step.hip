@@ -76,6 +76,10 @@ struct l2a_controller {
     hipEvent_t payload_ev = nullptr;
     unsigned long long digest = 0;
     size_t glob_floats = 0;                     // h * m * n * act_dim: the WHOLE plan's candidate tensor (the device stream's step)
+    // sharded RECURRENT plan, parity mode: the whole plan's first horizon step as fp32 [m * n, act_dim] - the cast of c64[slot] the
+    // candidate tensor gets - so that the state advance behind the collective finds the GLOBAL winner's first action on the device
+    float* tab_pin[2] = {nullptr, nullptr};
+    float* tab_dev[2] = {nullptr, nullptr};
     // CEM plan (l2a_cem_controller_create_device): K iterations of rollout -> l2a_cem_refit_sample, one read-back per step
     struct cem_state* cem = nullptr;
 };
@@ -168,6 +172,16 @@ hipError_t alloc_sharded(l2a_controller* c) {
     return e;
 }
 
+// Sharded recurrent plan: the first-step table of block `slot` - float64 -> fp32 as the candidate tensor's rows are cast
+// (csrc/l2a_rng.c), so for candidates in [lo, hi) it holds the planned values bit for bit - enqueued for upload on `stream`.
+hipError_t upload_table(l2a_controller* c, int slot, hipStream_t stream) {
+    const size_t count = (size_t)c->m * c->n * c->act_dim;
+    const double* src = c->c64[slot];
+    float* dst = c->tab_pin[slot];
+    for (size_t i = 0; i < count; ++i) dst[i] = (float)src[i];
+    return hipMemcpyAsync(c->tab_dev[slot], dst, count * sizeof(float), hipMemcpyHostToDevice, stream);
+}
+
 // Producer thread, after the block's draw: one H2D copy on the side stream, completed before the block is marked ready - the
 // consumer neither waits on an event nor launches behind an unfinished copy.
 int upload_block(void* arg, int slot) {
@@ -176,8 +190,11 @@ int upload_block(void* arg, int slot) {
         if (hipSetDevice(c->ctx->device) != hipSuccess) { c->upload_err = "hipSetDevice on the producer thread failed"; return -1; }
         c->producer_bound = true;
     }
-    if (c->hi == c->lo) return 0;                               // more ranks than candidates: this rank rolls nothing out
-    hipError_t e = hipMemcpyAsync(c->dev[slot], c->pin[slot], c->act_floats * sizeof(float), hipMemcpyHostToDevice, c->side);
+    const bool table = c->tab_dev[slot] != nullptr;
+    if (c->hi == c->lo && !table) return 0;                     // more ranks than candidates: this rank rolls nothing out
+    hipError_t e = table ? upload_table(c, slot, c->side) : hipSuccess;
+    if (e == hipSuccess && c->hi > c->lo)
+        e = hipMemcpyAsync(c->dev[slot], c->pin[slot], c->act_floats * sizeof(float), hipMemcpyHostToDevice, c->side);
     if (e == hipSuccess) e = hipStreamSynchronize(c->side);
     if (e != hipSuccess) { c->upload_err = std::string("uploading a candidate block: ") + hipGetErrorString(e); return -1; }
     return 0;
@@ -249,6 +266,11 @@ int create(l2a_ctx* ctx, l2a_model* mlp, l2a_lstm* rnn, int obs_dim, int act_dim
             c->c64[s] = static_cast<double*>(std::malloc(sizeof(double) * (size_t)m * n * act_dim));
             if (!c->c64[s]) e = hipErrorOutOfMemory;
         }
+        if (e == hipSuccess && sharded && rnn) {
+            const size_t bytes = sizeof(float) * (size_t)m * n * act_dim;
+            e = hipHostMalloc(reinterpret_cast<void**>(&c->tab_pin[s]), bytes, hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->tab_dev[s]), bytes);
+        }
     }
     if (e == hipSuccess) {
         // rows of the reference's draw: h * n * m (mpc_controller.py:114), row r <-> candidate r % n; the whole env-major tensor
@@ -279,8 +301,10 @@ int launch_sharded(l2a_controller* c, bool first) {
     std::memcpy(c->obs_map_host, c->obs32, sizeof(float) * (size_t)c->m * c->obs_dim);
     ctx->stamps_us[1] = l2a_now_us();
     if (n_local > 0) {
-        const int rc = l2a_plan_rs(c->mlp, c->obs_map_dev, c->dev[c->slot], c->m, n_local, c->h, c->discount, &c->rw, c->lo, nullptr,
-                                   c->keys_dev, c->stream);
+        const int rc = c->mlp ? l2a_plan_rs(c->mlp, c->obs_map_dev, c->dev[c->slot], c->m, n_local, c->h, c->discount, &c->rw, c->lo,
+                                            nullptr, c->keys_dev, c->stream)
+                              : l2a_lstm_plan_rs(c->rnn, c->obs_map_dev, c->c0, c->h0, c->dev[c->slot], c->m, n_local, c->h, c->discount,
+                                                 &c->rw, c->lo, nullptr, c->keys_dev, c->stream);
         if (rc != L2A_OK) return rc;
     } else {
         L2A_HIP(ctx, hipMemsetAsync(c->keys_dev, 0, sizeof(unsigned long long) * (size_t)c->m, stream));    // the neutral key
@@ -293,6 +317,15 @@ int launch_sharded(l2a_controller* c, bool first) {
     rc = c->reduce ? c->reduce(c->reduce_arg, c->payload_dev, c->m + 3, c->stream)
                    : l2a_allreduce_best(ctx, c->payload_dev, c->m + 3, c->stream);       // RCCL: uint64 MAX over xGMI
     if (rc != L2A_OK) return c->reduce ? fail(ctx, L2A_EHIP, "l2a_controller_step: the caller's reduce function failed") : rc;
+    if (c->rnn && c->c1) {
+        // the controller's own state moves on with the GLOBAL winner's first action (rnn_mpc_controller.py:63), in stream order behind
+        // the collective: the reduced keys index the whole plan's first step - the fp32 table of this block (parity mode) or the
+        // Philox stream itself (device mode) - with the index clamped: the keys of a flagged launch, a neutral key or a placeholder
+        // may hold anything, and the state written from them is overwritten by the relaunch or dropped with the failed step
+        rc = l2a_lstm_advance_keys(c->rnn, c->obs_map_dev, c->payload_dev, c->device_rng ? nullptr : c->tab_dev[c->slot], c->n, c->seed,
+                                   c->offset, c->lowr_dev, c->c0, c->h0, c->c1, c->h1, c->m, c->stream);
+        if (rc != L2A_OK) return rc;
+    }
     L2A_HIP(ctx, hipMemcpyAsync(c->payload_host, c->payload_dev, sizeof(unsigned long long) * (size_t)(c->m + 3), hipMemcpyDeviceToHost, stream));
     L2A_HIP(ctx, hipEventRecord(c->payload_ev, stream));
     return L2A_OK;
@@ -311,6 +344,11 @@ int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0
                                      "clears the context's launch status word: finish it first)");
     if (!obs) return fail(ctx, L2A_EINVAL, "l2a_controller_begin: null obs");
     if (c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_begin: the previous step was not finished (l2a_controller_finish)");
+    if (c->sharded && c->rnn) {         // (unsharded: l2a_lstm_plan_rs_sync_hook checks the same) - before anything is consumed
+        if ((!c1) != (!h1)) return fail(ctx, L2A_EINVAL, "l2a_lstm_controller_begin: pass c_next and h_next together");
+        if (c1 && (c1 == c0 || h1 == h0))
+            return fail(ctx, L2A_EINVAL, "l2a_lstm_controller_begin: the next state must not alias the current one");
+    }
     const double t0 = l2a_now_us();
     int slot = 0;
     bool drew = false;
@@ -343,6 +381,7 @@ int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0
         if (c->hi > c->lo)
             L2A_HIP(ctx, hipMemcpyAsync(c->dev[slot], c->pin[slot], c->act_floats * sizeof(float), hipMemcpyHostToDevice,
                                         reinterpret_cast<hipStream_t>(stream)));
+        if (c->tab_dev[slot]) L2A_HIP(ctx, upload_table(c, slot, reinterpret_cast<hipStream_t>(stream)));
         drew = true;
         c->sync_draws += 1;
     } else {
@@ -717,6 +756,34 @@ int l2a_lstm_controller_create(l2a_lstm* model, int m, int n, int h, const doubl
     return create(ctx, nullptr, model, obs_dim, act_dim, units, m, n, h, low, high, discount, reward, np_state_addr, rng_threads, out);
 }
 
+int l2a_lstm_controller_create_sharded(l2a_lstm* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                       const l2a_reward* reward, void* np_state_addr, int rng_threads, int rank, int world,
+                                       l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out) {
+    if (!model) return L2A_EINVAL;
+    l2a_ctx* ctx = nullptr;
+    int obs_dim = 0, act_dim = 0, units = 0;
+    l2a_lstm_facts(model, &ctx, &obs_dim, &act_dim, &units);
+    if (world < 1 || rank < 0 || rank >= world) return fail(ctx, L2A_EINVAL, "l2a_lstm_controller_create_sharded: bad rank / world");
+    if (!reduce && (!ctx->comm || ctx->comm_world != world || ctx->comm_rank != rank))
+        return fail(ctx, L2A_ESTATE, "l2a_lstm_controller_create_sharded: no reduce function and no communicator of this rank / world (l2a_comm_init)");
+    return create(ctx, nullptr, model, obs_dim, act_dim, units, m, n, h, low, high, discount, reward, np_state_addr, rng_threads, out,
+                  false, 0, rank, world, reduce, reduce_arg, true);
+}
+
+int l2a_lstm_controller_create_sharded_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
+                                              double discount, const l2a_reward* reward, unsigned long long seed, int rank, int world,
+                                              l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out) {
+    if (!model) return L2A_EINVAL;
+    l2a_ctx* ctx = nullptr;
+    int obs_dim = 0, act_dim = 0, units = 0;
+    l2a_lstm_facts(model, &ctx, &obs_dim, &act_dim, &units);
+    if (world < 1 || rank < 0 || rank >= world) return fail(ctx, L2A_EINVAL, "l2a_lstm_controller_create_sharded_device: bad rank / world");
+    if (!reduce && (!ctx->comm || ctx->comm_world != world || ctx->comm_rank != rank))
+        return fail(ctx, L2A_ESTATE, "l2a_lstm_controller_create_sharded_device: no reduce function and no communicator of this rank / world (l2a_comm_init)");
+    return create(ctx, nullptr, model, obs_dim, act_dim, units, m, n, h, low, high, discount, reward, nullptr, 1, out, true, seed, rank,
+                  world, reduce, reduce_arg, true);
+}
+
 int l2a_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
                                  const l2a_reward* reward, unsigned long long seed, l2a_controller** out) {
     if (!model) return L2A_EINVAL;
@@ -850,6 +917,8 @@ void l2a_controller_destroy(l2a_controller* c) {
         if (c->pin[s]) (void)hipHostFree(c->pin[s]);
         if (c->dev[s]) (void)hipFree(c->dev[s]);
         std::free(c->c64[s]);
+        if (c->tab_pin[s]) (void)hipHostFree(c->tab_pin[s]);
+        if (c->tab_dev[s]) (void)hipFree(c->tab_dev[s]);
     }
     if (c->lowr_dev) (void)hipFree(c->lowr_dev);
     if (c->obs_map_host) (void)hipHostFree(c->obs_map_host);

@@ -64,9 +64,11 @@ class NativeStep(object):
     def __init__(self, native, recurrent, m, n, h, low, high, discount, reward, device_seed=None, shard=None):
         """``device_seed``: None = parity mode (NumPy's global generator, candidates drawn ahead by a C thread); an integer =
         ``rng="device"``: the candidates come from the library's counter-based Philox stream under that seed, drawn on the GPU.
-        ``shard``: None, or ``(rank, world, reduce)`` - the sharded step (``l2a_controller_create_sharded``, MLP models, parity
-        mode): ``reduce`` = None runs the step's one collective over the library's own RCCL communicator (``l2a_comm_init``),
-        else a callable ``reduce(payload)`` that MAX-all-reduces the int64 CUDA tensor it is handed in place (torch.distributed)."""
+        ``shard``: None, or ``(rank, world, reduce)`` - the sharded step (``l2a_controller_create_sharded[_device]``; recurrent
+        models: ``l2a_lstm_controller_create_sharded[_device]``, which also advance the hidden state with the GLOBAL winner's
+        action behind the collective): ``reduce`` = None runs the step's one collective over the library's own RCCL communicator
+        (``l2a_comm_init``), else a callable ``reduce(payload)`` that MAX-all-reduces the int64 CUDA tensor it is handed in place
+        (torch.distributed)."""
         lib = native.lib
         self.lib, self.ctx, self.native, self.recurrent = lib, native.ctx, native, bool(recurrent)
         self.m, self.n, self.h = int(m), int(n), int(h)
@@ -75,14 +77,16 @@ class NativeStep(object):
         handle = ctypes.c_void_p()
         self.device_rng = device_seed is not None
         self.reduce_error = None
-        if self.device_rng and shard is not None and not self.recurrent:
+        if shard is not None and self.recurrent and not hasattr(lib, "l2a_lstm_controller_create_sharded"):
+            raise _lib.L2AError("this libl2a_hip.so has no sharded recurrent controller step")
+        if self.device_rng and shard is not None:
             self.addr, self.lock = None, None
             rank, world, reduce = shard
             cb = make_reduce_cb(self, lib, native, reduce)
-            rc = lib.l2a_controller_create_sharded_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                                                          float(discount), ctypes.byref(reward),
-                                                          ctypes.c_ulonglong(int(device_seed) & 0xFFFFFFFFFFFFFFFF), int(rank), int(world),
-                                                          cb, None, ctypes.byref(handle))
+            create = lib.l2a_lstm_controller_create_sharded_device if self.recurrent else lib.l2a_controller_create_sharded_device
+            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount), ctypes.byref(reward),
+                        ctypes.c_ulonglong(int(device_seed) & 0xFFFFFFFFFFFFFFFF), int(rank), int(world), cb, None,
+                        ctypes.byref(handle))
         elif self.device_rng:
             self.addr, self.lock = None, None
             create = lib.l2a_lstm_controller_create_device if self.recurrent else lib.l2a_controller_create_device
@@ -93,12 +97,13 @@ class NativeStep(object):
             if self.addr is None:
                 raise _lib.L2AError("np.random's global generator is not the legacy MT19937")
             self.lock = fast_rng._global_lock()
-            if shard is not None and not self.recurrent:
+            if shard is not None:
                 rank, world, reduce = shard
                 cb = make_reduce_cb(self, lib, native, reduce)
-                rc = lib.l2a_controller_create_sharded(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                                                       float(discount), ctypes.byref(reward), self.addr, fast_rng.threads(),
-                                                       int(rank), int(world), cb, None, ctypes.byref(handle))
+                create = lib.l2a_lstm_controller_create_sharded if self.recurrent else lib.l2a_controller_create_sharded
+                rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount),
+                            ctypes.byref(reward), self.addr, fast_rng.threads(), int(rank), int(world), cb, None,
+                            ctypes.byref(handle))
             else:
                 create = lib.l2a_lstm_controller_create if self.recurrent else lib.l2a_controller_create
                 rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount),
