@@ -313,6 +313,12 @@ int l2a_cem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, int n
  * returns are ordered as np.argmax orders them (a NaN is the maximum, the first one wins): a diverged plan reports NaN.  */
 int l2a_cem_pick(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m,
                  int D, int act_dim, int reference, float* out, void* stream);
+/* l2a_cem_pick_act: l2a_cem_pick - the same launch, the same `out` bit for bit - that also writes the winners' first actions as a
+ * dense `act_out` [m, act_dim] (device fp32): act_out[i] holds the bits of out[i * (act_dim + 2) ..], the unclipped first action of
+ * row i * n + j (reference = 1) or the clipped one of row j * m + i (0), j = 0 when every return of env i is NaN or -inf.  It is what
+ * l2a_lstm_advance reads behind a recurrent CEM plan: pick, advance, one read-back - no gather launch, no host wait in between.     */
+int l2a_cem_pick_act(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m,
+                     int D, int act_dim, int reference, float* out, float* act_out, void* stream);
 /* l2a_cem_refit_sample: l2a_cem_refit followed by l2a_cem_sample in ONE launch - iteration i's `returns` [m, n] and samples
  * `a_clip_in` [n, m, D] in, iteration i + 1's samples out - bit-identical to the two calls (mean, std, elite_rows, a_clip, a_raw,
  * seq; injected z or Philox z under (seed, offset); both readings).  mean_in [m, D]: the mean iteration i sampled with, read only;
@@ -588,7 +594,8 @@ int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, cons
  *   reference   1 = the reference's reading (unclipped rollouts, candidate-major rows, the pooled rank mask of :101); 0 = fixed
  * Steps through l2a_controller_step / _begin / _finish / _stats / _destroy (action_out = the first action of each env's best
  * candidate of the last iteration, as float64; L2A_STEP_UNSPLIT when a tile-split launch lost its partner and the step was repeated
- * unsplit with the same offsets - same bits).  MLP models; one GPU (sharded: l2a_cem_controller_create_sharded_device below).
+ * unsplit with the same offsets - same bits).  MLP models (recurrent: l2a_lstm_cem_controller_create_device below); one GPU
+ * (sharded: l2a_cem_controller_create_sharded_device below).
  * The launch status word is per context, and a CEM step reads
  * and clears it: a CEM step never shares the context with another controller's step in flight.  l2a_controller_begin of a CEM
  * controller returns L2A_ESTATE while any other controller on the context is between _begin and _finish, and that of an RS or
@@ -615,6 +622,33 @@ int l2a_cem_controller_create_sharded_device(l2a_model* model, int m, int n, int
                                              double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
                                              int reference, unsigned long long seed, int rank, int world, l2a_reduce_fn reduce,
                                              void* reduce_arg, l2a_controller** out);
+/* The CEM step of the RECURRENT planner (`RNNMPCController(use_cem=True, rng="device")`; run_scripts/run_rebal.py's plan with
+ * use_cem): the sequence, the Philox offsets (s * iters + it) * n * m * D, the failure protocol and the argument limits (m <= 64,
+ * act_dim <= 16, the LDS checks of refit and sample) are those of l2a_cem_controller_create_device / _sharded_device above, for any
+ * model l2a_lstm_create or l2a_rnn_create builds (LSTM, GRU, BasicRNN, stacks).  Every iteration's rollout is l2a_lstm_plan_rs from
+ * the caller's state c0 / h0 (device fp32 [m, state width]; cand_offset 0 over n, sharded: lo over this rank's hi - lo), the pick is
+ * l2a_cem_pick_act, and with c_next / h_next the controller's own state is advanced behind it, in front of the read-back:
+ *   state' = cell(obs, fp32 first action of each env's best candidate, state)               (l2a_lstm_advance)
+ * Sharded, every rank holds every sample row and - after each iteration's collective - every return, so the pick and the advance
+ * are local and identical on all ranks: no further collective, no key lookup; a rank with an empty shard (world > n) skips the
+ * rollout and still packs, reduces, refits, picks and advances.
+ * Steps through l2a_lstm_controller_step / l2a_lstm_controller_begin (c0, h0, c_next, h_next) / l2a_controller_finish / _stats /
+ * _destroy and l2a_cem_controller_result.  l2a_controller_step / _begin on a recurrent CEM controller, and the l2a_lstm_* step
+ * functions on an MLP CEM controller, return L2A_EINVAL: nothing is launched, nothing consumed.  c_next / h_next: both NULL = plan
+ * only; one of them NULL, or an output aliasing c0 / h0, is L2A_EINVAL.  c0 / h0 are read by every iteration's rollout and by the
+ * advance: they stay valid and unwritten until _finish.  A flagged step repeats the WHOLE sequence unsplit, the advance included -
+ * from the same c0 / h0 with the same offsets, so c_next / h_next are simply rewritten; they are invalid after a negative return and
+ * after L2A_OK / L2A_STEP_UNSPLIT equal what l2a_lstm_advance gives for the returned action, bit for bit.  With the same seed every
+ * rank's step equals the unsharded controller's bit for bit, the state included - as long as every shard width selects the same
+ * rollout kernel: ranks whose widths select a VALU kernel against a matrix-core kernel agree to fp32 tolerance only (l2a_set_micro).
+ * The in-flight exclusion rules above apply unchanged; the digest also carries the controller kind.                               */
+int l2a_lstm_cem_controller_create_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
+                                          double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
+                                          int reference, unsigned long long seed, l2a_controller** out);
+int l2a_lstm_cem_controller_create_sharded_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
+                                                  double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
+                                                  int reference, unsigned long long seed, int rank, int world, l2a_reduce_fn reduce,
+                                                  void* reduce_arg, l2a_controller** out);
 int l2a_cem_controller_result(l2a_controller* controller, float* mean_out, float* std_out, float* returns_out);
 void l2a_controller_destroy(l2a_controller* controller);
 int l2a_controller_step(l2a_controller* controller, const double* obs, double* action_out, long long* index_out,

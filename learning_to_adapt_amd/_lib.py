@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "l2a_lstm_controller_step", "l2a_controller_rearm", "l2a_controller_actions", "l2a_controller_stats",
     "l2a_cem_controller_create_device", "l2a_cem_controller_result",
     "l2a_cem_shard_pack", "l2a_cem_shard_unpack", "l2a_cem_word_encode", "l2a_cem_word_decode", "l2a_cem_controller_create_sharded_device",
+    "l2a_cem_pick_act", "l2a_lstm_cem_controller_create_device", "l2a_lstm_cem_controller_create_sharded_device",
 )
 
 
@@ -291,6 +292,13 @@ def load():
         lib.l2a_cem_controller_create_sharded_device.argtypes = [vp, i32, i32, i32, vp, vp, c.c_double, c.POINTER(RewardSpec), i32, i32, f32, i32,
                                                                  c.c_ulonglong, i32, i32, vp, vp, c.POINTER(vp)]
         lib.l2a_cem_controller_create_sharded_device.restype = i32
+    if hasattr(lib, "l2a_lstm_cem_controller_create_device"):
+        lib.l2a_cem_pick_act.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+        lib.l2a_cem_pick_act.restype = i32
+        lib.l2a_lstm_cem_controller_create_device.argtypes = lib.l2a_cem_controller_create_device.argtypes
+        lib.l2a_lstm_cem_controller_create_device.restype = i32
+        lib.l2a_lstm_cem_controller_create_sharded_device.argtypes = lib.l2a_cem_controller_create_sharded_device.argtypes
+        lib.l2a_lstm_cem_controller_create_sharded_device.restype = i32
     _lib = lib
     return lib
 

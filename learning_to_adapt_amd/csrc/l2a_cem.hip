@@ -463,9 +463,10 @@ __device__ __forceinline__ bool l2a_argmax_better(float x, int c, float best, in
 // returns (np.argmax's order, NaN included), the first action of that candidate as the rollout saw it, its return; behind them
 // the final mean / std.
 // out: [m][act_dim + 2] floats (action | return | index as the bit pattern of an int32), then mean [m, D], std [m, D].
+// act_out (nullable): the winners' first actions once more as a dense [m, act_dim] - what l2a_lstm_advance reads (the same bits).
 // grid (m + ceil(2 m D / 256)): block i < m is env i.
 __global__ void __launch_bounds__(256) l2a_cem_pick_k(const float* returns, const float* cand, const float* mean, const float* std,
-                                                      int n, int m, int D, int act_dim, int reference, float* out) {
+                                                      int n, int m, int D, int act_dim, int reference, float* out, float* act_out) {
     const int W = act_dim + 2;
     if ((int)blockIdx.x >= m) {
         const long long e = (long long)(blockIdx.x - m) * 256 + threadIdx.x;
@@ -495,7 +496,11 @@ __global__ void __launch_bounds__(256) l2a_cem_pick_k(const float* returns, cons
     if (j < 0 || j >= n) j = 0;                         // (all returns NaN / -inf)
     // reference: the sample memory read as [m, n, D] (:92-96), row i * n + j; fixed: candidate j of env i is sample row j * m + i
     const long long row = reference ? (long long)i * n + j : (long long)j * m + i;
-    if ((int)threadIdx.x < act_dim) out[i * W + threadIdx.x] = cand[row * D + threadIdx.x];
+    if ((int)threadIdx.x < act_dim) {
+        const float a = cand[row * D + threadIdx.x];
+        out[i * W + threadIdx.x] = a;
+        if (act_out) act_out[i * act_dim + threadIdx.x] = a;
+    }
     if (threadIdx.x == 0) { out[i * W + act_dim] = returns[(long long)i * n + j]; out[i * W + act_dim + 1] = __int_as_float(j); }
 }
 
@@ -668,19 +673,31 @@ int l2a_cem_refit_sample_fused(const l2a_ctx* ctx, int n, int m, int h, int act_
     return crs_fused(ctx, n, m, h, act_dim, num_elites, reference) ? 1 : 0;
 }
 
-int l2a_cem_pick(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m, int D,
-                 int act_dim, int reference, float* out, void* stream_v) {
+// Both picks: `act_out` null is l2a_cem_pick.
+static int cem_pick(const char* who, l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n,
+                    int m, int D, int act_dim, int reference, float* out, float* act_out, void* stream_v) {
     if (!ctx) return L2A_EINVAL;
-    if (!returns || !cand || !mean || !std || !out) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_pick: null pointer");
+    if (!returns || !cand || !mean || !std || !out) return l2a_fail(ctx, L2A_EINVAL, std::string(who) + ": null pointer");
     if (n < 1 || m < 1 || D < 1 || act_dim < 1 || act_dim > D || act_dim > 256)
-        return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_pick: bad n / m / D / act_dim");
+        return l2a_fail(ctx, L2A_EINVAL, std::string(who) + ": bad n / m / D / act_dim");
     l2a_device_guard guard(ctx->device);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     const long long copy_blocks = (2LL * m * D + 255) / 256;
     hipLaunchKernelGGL(l2a_cem_pick_k, dim3((unsigned)(m + copy_blocks)), dim3(256), 0, stream, returns, cand, mean, std, n, m, D,
-                       act_dim, reference ? 1 : 0, out);
+                       act_dim, reference ? 1 : 0, out, act_out);
     L2A_HIP(ctx, hipGetLastError());
     return L2A_OK;
+}
+
+int l2a_cem_pick(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m, int D,
+                 int act_dim, int reference, float* out, void* stream_v) {
+    return cem_pick("l2a_cem_pick", ctx, returns, cand, mean, std, n, m, D, act_dim, reference, out, nullptr, stream_v);
+}
+
+int l2a_cem_pick_act(l2a_ctx* ctx, const float* returns, const float* cand, const float* mean, const float* std, int n, int m, int D,
+                     int act_dim, int reference, float* out, float* act_out, void* stream_v) {
+    if (ctx && !act_out) return l2a_fail(ctx, L2A_EINVAL, "l2a_cem_pick_act: null act_out");
+    return cem_pick("l2a_cem_pick_act", ctx, returns, cand, mean, std, n, m, D, act_dim, reference, out, act_out, stream_v);
 }
 
 

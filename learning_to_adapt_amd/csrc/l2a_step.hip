@@ -87,6 +87,8 @@ struct l2a_controller {
 // Device-mode CEM (`MPCController.get_cem_action_device`, policies/mpc_controller.py): the whole plan step on the launch stream -
 // l2a_cem_sample for iteration 0, then per iteration the rollout and ONE l2a_cem_refit_sample (the last iteration: l2a_cem_refit),
 // l2a_cem_pick, and one copy of the packed result to page-locked memory.  Philox offsets (calls + it) * n * m * D, as the Python path.
+// A recurrent controller (l2a_lstm_cem_controller_create_device) rolls out with l2a_lstm_plan_rs from the caller's c0 / h0, picks with
+// l2a_cem_pick_act and, with c_next / h_next, enqueues l2a_lstm_advance on the picked actions in front of the read-back.
 struct cem_state {
     int iters = 0, k = 0, reference = 1, D = 0;
     float alpha = 0.1f;
@@ -103,6 +105,7 @@ struct cem_state {
     float* packed_host = nullptr;               // page-locked
     hipEvent_t done = nullptr;
     int cur = 0;                                // the buffers of the last iteration
+    float* act_dev = nullptr;                   // recurrent: the winners' first actions [m, act_dim] (l2a_cem_pick_act -> l2a_lstm_advance)
     // one rank of a sharded plan (l2a_cem_controller_create_sharded_device): rollouts of candidates [lo, hi), every iteration's
     // returns gathered by the int64 MAX all-reduce of m * n + 3 words (l2a_cem_shard_pack / _unpack)
     bool sharded = false;
@@ -333,11 +336,11 @@ int launch_sharded(l2a_controller* c, bool first) {
 
 // First half of a step: everything that touches the generator (take / draw, re-arm), the staging and the launch.  Returns
 // L2A_OK (plan in flight), L2A_STEP_MISS (nothing consumed or launched) or a negative code.
-int cem_begin(l2a_controller* c, const double* obs, void* stream);
+int cem_begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream);
 int cem_finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out);
 
 int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
-    if (c->cem) return cem_begin(c, obs, stream);
+    if (c->cem) return cem_begin(c, obs, c0, h0, c1, h1, stream);
     l2a_ctx* ctx = c->ctx;
     if (ctx->cem_steps_in_flight > 0)
         return fail(ctx, L2A_ESTATE, "l2a_controller_begin: a CEM step of another controller is in flight on this context (it reads and "
@@ -523,7 +526,7 @@ unsigned long long cem_digest(const l2a_controller* c) {
     std::memcpy(&alpha_bits, &q->alpha, sizeof(alpha_bits));
     const unsigned long long v[] = {c->seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n, (unsigned long long)c->h,
                                     (unsigned long long)q->iters, (unsigned long long)q->k, (unsigned long long)q->reference,
-                                    (unsigned long long)alpha_bits, (unsigned long long)c->world};
+                                    (unsigned long long)alpha_bits, (unsigned long long)c->world, (unsigned long long)(c->rnn ? 1 : 0)};
     unsigned long long d = 0x9E3779B97F4A7C15ull;
     for (unsigned long long x : v) {            // splitmix64's finaliser over the running value
         d = (d ^ x) + 0x9E3779B97F4A7C15ull;
@@ -558,12 +561,17 @@ int cem_launch(l2a_controller* c) {
     for (int it = 0; it < q->iters; ++it) {
         float* rets = q->rets + (size_t)it * m * n;
         if (!q->sharded) {
-            rc = l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n, h, c->discount, &c->rw, 0, rets, c->keys_dev, c->stream);
+            rc = c->mlp ? l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n, h, c->discount, &c->rw, 0, rets, c->keys_dev, c->stream)
+                        : l2a_lstm_plan_rs(c->rnn, c->obs_map_dev, c->c0, c->h0, q->seq, m, n, h, c->discount, &c->rw, 0, rets, c->keys_dev,
+                                           c->stream);
             if (rc != L2A_OK) return rc;
         } else {
             // this rank's rollouts -> words -> the ONE collective -> every rank's returns in the iteration's slot of `rets`
             if (n_local > 0) {
-                rc = l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n_local, h, c->discount, &c->rw, lo, q->rets_local, c->keys_dev, c->stream);
+                rc = c->mlp ? l2a_plan_rs(c->mlp, c->obs_map_dev, q->seq, m, n_local, h, c->discount, &c->rw, lo, q->rets_local, c->keys_dev,
+                                          c->stream)
+                            : l2a_lstm_plan_rs(c->rnn, c->obs_map_dev, c->c0, c->h0, q->seq, m, n_local, h, c->discount, &c->rw, lo,
+                                               q->rets_local, c->keys_dev, c->stream);
                 if (rc != L2A_OK) return rc;
             }
             rc = l2a_cem_shard_pack(ctx, q->rets_local, m, n, lo, hi, q->digest, q->words, c->stream);
@@ -585,9 +593,17 @@ int cem_launch(l2a_controller* c) {
         }
         if (rc != L2A_OK) return rc;
     }
-    rc = l2a_cem_pick(ctx, q->rets + (size_t)(q->iters - 1) * m * n, q->reference ? q->a_raw : q->a_clip[cur], q->mean[cur], q->std, n, m,
-                      D, A, q->reference, q->packed_dev, c->stream);
+    const float* last = q->rets + (size_t)(q->iters - 1) * m * n;
+    const float* cand = q->reference ? q->a_raw : q->a_clip[cur];
+    rc = c->rnn ? l2a_cem_pick_act(ctx, last, cand, q->mean[cur], q->std, n, m, D, A, q->reference, q->packed_dev, q->act_dev, c->stream)
+                : l2a_cem_pick(ctx, last, cand, q->mean[cur], q->std, n, m, D, A, q->reference, q->packed_dev, c->stream);
     if (rc != L2A_OK) return rc;
+    if (c->rnn && c->c1) {
+        // the controller's own state moves on with the winners' first actions (rnn_mpc_controller.py:63), in stream order behind the
+        // pick: sharded, every rank holds every sample row and every return, so pick and advance are local and alike on all ranks
+        rc = l2a_lstm_advance(c->rnn, c->obs_map_dev, q->act_dev, c->c0, c->h0, m, c->c1, c->h1, c->stream);
+        if (rc != L2A_OK) return rc;
+    }
     q->cur = cur;
     const size_t words = (size_t)m * (A + 2) + 2 * (size_t)m * D + (q->sharded ? 3 : 0);      // (sharded: + the verdict's three words)
     L2A_HIP(ctx, hipMemcpyAsync(q->packed_host, q->packed_dev, sizeof(float) * words, hipMemcpyDeviceToHost, stream));
@@ -596,9 +612,14 @@ int cem_launch(l2a_controller* c) {
     return L2A_OK;
 }
 
-int cem_begin(l2a_controller* c, const double* obs, void* stream) {
+int cem_begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
     l2a_ctx* ctx = c->ctx;
     if (!obs) return fail(ctx, L2A_EINVAL, "l2a_controller_begin: null obs");
+    if (c->rnn) {                       // before anything is launched
+        if ((!c1) != (!h1)) return fail(ctx, L2A_EINVAL, "l2a_lstm_controller_begin: pass c_next and h_next together");
+        if (c1 && (c1 == c0 || h1 == h0))
+            return fail(ctx, L2A_EINVAL, "l2a_lstm_controller_begin: the next state must not alias the current one");
+    }
     if (c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_begin: the previous step was not finished (l2a_controller_finish)");
     if (ctx->cem_steps_in_flight + ctx->rs_steps_in_flight > 0)
         return fail(ctx, L2A_ESTATE, "l2a_controller_begin: another controller's step is in flight on this context (a CEM step reads and "
@@ -607,7 +628,7 @@ int cem_begin(l2a_controller* c, const double* obs, void* stream) {
     c->t_taken = c->t_begin;
     const int no = c->m * c->obs_dim;
     for (int i = 0; i < no; ++i) c->obs32[i] = (float)obs[i];
-    c->stream = stream;
+    c->c0 = c0; c->h0 = h0; c->c1 = c1; c->h1 = h1; c->stream = stream;
     c->result = L2A_OK;
     if (cem_state* q = c->cem; q->sharded) q->digest = cem_digest(c);
     const int rc = cem_launch(c);
@@ -803,13 +824,16 @@ int l2a_lstm_controller_create_device(l2a_lstm* model, int m, int n, int h, cons
 }
 
 // Both CEM controllers: the unsharded one is rank 0 of a world of 1 without the collective's buffers.
-static int cem_create(const std::string& who, l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
-                      const l2a_reward* reward, int iters, int num_elites, float alpha, int reference, unsigned long long seed,
-                      bool sharded, int rank, int world, l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out) {
-    if (!model) return L2A_EINVAL;
+// (`model` or `rnn`: the feed-forward and the recurrent controllers differ in the rollout call and in the advance behind the pick)
+static int cem_create(const std::string& who, l2a_model* model, l2a_lstm* rnn, int m, int n, int h, const double* low, const double* high,
+                      double discount, const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
+                      unsigned long long seed, bool sharded, int rank, int world, l2a_reduce_fn reduce, void* reduce_arg,
+                      l2a_controller** out) {
+    if (!model && !rnn) return L2A_EINVAL;
     l2a_ctx* ctx = nullptr;
-    int obs_dim = 0, act_dim = 0;
-    l2a_model_facts(model, &ctx, &obs_dim, &act_dim);
+    int obs_dim = 0, act_dim = 0, units = 0;
+    if (model) l2a_model_facts(model, &ctx, &obs_dim, &act_dim);
+    else l2a_lstm_facts(rnn, &ctx, &obs_dim, &act_dim, &units);
     if (sharded && (world < 1 || rank < 0 || rank >= world)) return fail(ctx, L2A_EINVAL, who + ": bad rank / world");
     if (sharded && !reduce && (!ctx->comm || ctx->comm_world != world || ctx->comm_rank != rank))
         return fail(ctx, L2A_ESTATE, who + ": no reduce function and no communicator of this rank / world (l2a_comm_init)");
@@ -829,8 +853,8 @@ static int cem_create(const std::string& who, l2a_model* model, int m, int n, in
     l2a_controller* c = new (std::nothrow) l2a_controller();
     cem_state* q = c ? new (std::nothrow) cem_state() : nullptr;
     if (!q) { delete c; return fail(ctx, L2A_EHIP, who + ": out of memory"); }
-    c->ctx = ctx; c->mlp = model; c->cem = q;
-    c->m = m; c->n = n; c->h = h; c->obs_dim = obs_dim; c->act_dim = act_dim;
+    c->ctx = ctx; c->mlp = model; c->rnn = rnn; c->cem = q;
+    c->m = m; c->n = n; c->h = h; c->obs_dim = obs_dim; c->act_dim = act_dim; c->units = units;
     c->discount = discount; c->rw = *reward;
     for (int k = 0; k < act_dim; ++k) { c->low[k] = low[k]; c->high[k] = high[k]; }
     c->device_rng = true; c->seed = seed;
@@ -858,6 +882,7 @@ static int cem_create(const std::string& who, l2a_model* model, int m, int n, in
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->rets), sizeof(float) * (size_t)iters * m * n);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->lowhigh), sizeof(float) * 2 * act_dim);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&q->packed_dev), sizeof(float) * words);
+    if (e == hipSuccess && rnn) e = hipMalloc(reinterpret_cast<void**>(&q->act_dev), sizeof(float) * (size_t)m * act_dim);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&q->packed_host), sizeof(float) * words, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&q->done, hipEventDisableTiming);
     if (e == hipSuccess && sharded) q->verdict_dev = reinterpret_cast<unsigned int*>(q->packed_dev + (words - 3));
@@ -878,16 +903,31 @@ static int cem_create(const std::string& who, l2a_model* model, int m, int n, in
 int l2a_cem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
                                      const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
                                      unsigned long long seed, l2a_controller** out) {
-    return cem_create("l2a_cem_controller_create_device", model, m, n, h, low, high, discount, reward, iters, num_elites, alpha, reference,
-                      seed, false, 0, 1, nullptr, nullptr, out);
+    return cem_create("l2a_cem_controller_create_device", model, nullptr, m, n, h, low, high, discount, reward, iters, num_elites, alpha,
+                      reference, seed, false, 0, 1, nullptr, nullptr, out);
 }
 
 int l2a_cem_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
                                              const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
                                              unsigned long long seed, int rank, int world, l2a_reduce_fn reduce, void* reduce_arg,
                                              l2a_controller** out) {
-    return cem_create("l2a_cem_controller_create_sharded_device", model, m, n, h, low, high, discount, reward, iters, num_elites, alpha,
-                      reference, seed, true, rank, world, reduce, reduce_arg, out);
+    return cem_create("l2a_cem_controller_create_sharded_device", model, nullptr, m, n, h, low, high, discount, reward, iters, num_elites,
+                      alpha, reference, seed, true, rank, world, reduce, reduce_arg, out);
+}
+
+int l2a_lstm_cem_controller_create_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                          const l2a_reward* reward, int iters, int num_elites, float alpha, int reference,
+                                          unsigned long long seed, l2a_controller** out) {
+    return cem_create("l2a_lstm_cem_controller_create_device", nullptr, model, m, n, h, low, high, discount, reward, iters, num_elites, alpha,
+                      reference, seed, false, 0, 1, nullptr, nullptr, out);
+}
+
+int l2a_lstm_cem_controller_create_sharded_device(l2a_lstm* model, int m, int n, int h, const double* low, const double* high,
+                                                  double discount, const l2a_reward* reward, int iters, int num_elites, float alpha,
+                                                  int reference, unsigned long long seed, int rank, int world, l2a_reduce_fn reduce,
+                                                  void* reduce_arg, l2a_controller** out) {
+    return cem_create("l2a_lstm_cem_controller_create_sharded_device", nullptr, model, m, n, h, low, high, discount, reward, iters,
+                      num_elites, alpha, reference, seed, true, rank, world, reduce, reduce_arg, out);
 }
 
 int l2a_cem_controller_result(l2a_controller* c, float* mean_out, float* std_out, float* returns_out) {
@@ -932,7 +972,7 @@ void l2a_controller_destroy(l2a_controller* c) {
             if (q->mean[s]) (void)hipFree(q->mean[s]);
             if (q->a_clip[s]) (void)hipFree(q->a_clip[s]);
         }
-        float* dev_bufs[] = {q->std, q->a_raw, q->seq, q->rets, q->lowhigh, q->packed_dev};
+        float* dev_bufs[] = {q->std, q->a_raw, q->seq, q->rets, q->lowhigh, q->packed_dev, q->act_dev};
         for (float* b : dev_bufs) if (b) (void)hipFree(b);
         if (q->rows) (void)hipFree(q->rows);
         if (q->rets_local) (void)hipFree(q->rets_local);

@@ -1093,17 +1093,23 @@ class MPCController(Policy, Serializable):
         ``m * n + 3`` words through ``_reduce_payload`` - or the library's communicator, ``L2A_NATIVE_COMM=1``): the same Philox
         offsets as ``get_cem_action_device``, so the two paths can take turns only while they agree on the stream position - the C
         controller is built where the Python path's counter is 0 for this seed and dropped when the Python path has planned since.
-        Returns the actions, or None when the C controller does not apply (parity mode, recurrent model, a test hook replaced the
-        normals or the launch path, a backend that cannot reduce the words, a forked child)."""
+        A recurrent planner (``RNNMPCController``) takes ``l2a_lstm_cem_controller_create_device`` / ``_sharded_device``: the
+        rollouts start from the controller's hidden state and the state advance with the chosen actions runs inside the same call
+        (``_native_step_state`` / ``_native_step_done``, as the random-shooting C step does).
+        Returns the actions, or None when the C controller does not apply (parity mode, a library without the recurrent entry
+        points, a test hook replaced the normals or the launch path, a backend that cannot reduce the words, a forked child)."""
+        self._native_step_done(None)        # (recurrent: no advanced state is pending whenever this call falls back)
         if self.rng != "device" or not self._native_step_stock():
             return None
         if getattr(self._cem_normal_device, "__func__", None) is not MPCController._cem_normal_device:
             return None
         rank, world = self._dist()
         native = self.dynamics_model.planner_model()
-        if hasattr(native, "units") or not hasattr(native.lib, "l2a_cem_controller_create_device"):
+        recurrent = hasattr(native, "units")
+        if not hasattr(native.lib, "l2a_lstm_cem_controller_create_device" if recurrent else "l2a_cem_controller_create_device"):
             return None
-        if world > 1 and not hasattr(native.lib, "l2a_cem_controller_create_sharded_device"):
+        if world > 1 and not hasattr(native.lib, "l2a_lstm_cem_controller_create_sharded_device" if recurrent
+                                     else "l2a_cem_controller_create_sharded_device"):
             return None
         n, m, h = self.n_candidates, len(observations), self.horizon
         if m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16:
@@ -1146,7 +1152,9 @@ class MPCController(Policy, Serializable):
             st.key, st.calls = key, 0
             self._cemstep = st
         self._check_blocks(m)
-        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        state, keep = self._native_step_state(native, m)
+        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream, state)
+        self._native_step_done(keep)
         st.calls += int(self.num_cem_iters)
         self._bufs["cem_calls"] = st.calls
         mean, std, rets = st.result()

@@ -10,6 +10,10 @@ of iterations planned so far the result is bit-identical.
 the rank rolls out its slice of the candidates and every iteration's returns are gathered by an int64 MAX all-reduce of
 ``m * n + 3`` words - ``reduce(tensor)`` in place (torch.distributed), or the library's own RCCL communicator when ``reduce`` is
 None.  Every rank's step equals the unsharded one bit for bit.
+
+A recurrent native model (one with ``units``: ``RNNMPCController``) builds ``l2a_lstm_cem_controller_create_device`` /
+``_sharded_device``: every rollout starts from the controller's hidden state and ``step(..., state=(c0, h0, c_next, h_next))``
+also advances that state with the chosen actions, behind the pick and in front of the one read-back.
 """
 
 import ctypes
@@ -27,6 +31,9 @@ class NativeCemStep(object):
         self.lib, self.ctx, self.native = lib, native.ctx, native
         self.m, self.n, self.h, self.iters = int(m), int(n), int(h), int(iters)
         self.D = self.h * native.act_dim
+        self.recurrent = hasattr(native, "units")
+        if self.recurrent and not hasattr(lib, "l2a_lstm_cem_controller_create_device"):
+            raise _lib.L2AError("this libl2a_hip.so has no recurrent CEM controller step")
         low = np.ascontiguousarray(low, dtype=np.float64)
         high = np.ascontiguousarray(high, dtype=np.float64)
         handle = ctypes.c_void_p()
@@ -34,17 +41,20 @@ class NativeCemStep(object):
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         seed = ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF)
         if shard is None:
-            rc = lib.l2a_cem_controller_create_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                                                      float(discount), ctypes.byref(reward), self.iters, int(num_elites), float(alpha),
-                                                      1 if reference else 0, seed, ctypes.byref(handle))
+            create = lib.l2a_lstm_cem_controller_create_device if self.recurrent else lib.l2a_cem_controller_create_device
+            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
+                        float(discount), ctypes.byref(reward), self.iters, int(num_elites), float(alpha),
+                        1 if reference else 0, seed, ctypes.byref(handle))
             self.ctx.check(rc, "l2a_cem_controller_create_device")
         else:
             rank, world, reduce = shard
             cb = make_reduce_cb(self, lib, native, reduce)
-            rc = lib.l2a_cem_controller_create_sharded_device(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                                                              float(discount), ctypes.byref(reward), self.iters, int(num_elites),
-                                                              float(alpha), 1 if reference else 0, seed, int(rank), int(world), cb, None,
-                                                              ctypes.byref(handle))
+            create = (lib.l2a_lstm_cem_controller_create_sharded_device if self.recurrent
+                      else lib.l2a_cem_controller_create_sharded_device)
+            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
+                        float(discount), ctypes.byref(reward), self.iters, int(num_elites),
+                        float(alpha), 1 if reference else 0, seed, int(rank), int(world), cb, None,
+                        ctypes.byref(handle))
             self.ctx.check(rc, "l2a_cem_controller_create_sharded_device")
         self.handle = handle
         self.pid = os.getpid()
@@ -56,11 +66,15 @@ class NativeCemStep(object):
         self.steps = 0
         self._stats = (ctypes.c_double * 16)()
 
-    def step(self, observations, stream):
-        """One plan step; ``self.act`` / ``self.idx`` / ``self.ret`` hold the result afterwards."""
+    def step(self, observations, stream, state=None):
+        """One plan step; ``self.act`` / ``self.idx`` / ``self.ret`` hold the result afterwards.  ``state`` (recurrent):
+        ``(c0, h0, c_next, h_next)`` device pointers; ``c_next`` and ``h_next`` both None plan without advancing the state."""
         np.copyto(self.obs, observations, casting="same_kind")
         p = self._p
-        rc = self.lib.l2a_controller_step(self.handle, p[0], p[1], p[2], p[3], stream)
+        if self.recurrent:
+            rc = self.lib.l2a_lstm_controller_step(self.handle, p[0], state[0], state[1], state[2], state[3], p[1], p[2], p[3], stream)
+        else:
+            rc = self.lib.l2a_controller_step(self.handle, p[0], p[1], p[2], p[3], stream)
         if rc == _lib.L2A_STEP_UNSPLIT:         # the C side has switched the context to the unsplit geometry (same bits)
             self.ctx.split_degraded = True
         elif rc != _lib.L2A_OK:

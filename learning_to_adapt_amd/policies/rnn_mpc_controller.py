@@ -45,6 +45,7 @@ class RNNMPCController(MPCController):
             cem_mode="reference",
             shard_candidates=True,
             pipeline_chunks=3,
+            native_cem_step=False,
     ):
         Serializable.quick_init(self, locals())
         # alpha = 0 makes the shared CEM update `mean * alpha + (1 - alpha) * mean(elites)` the
@@ -54,7 +55,7 @@ class RNNMPCController(MPCController):
                                n_candidates=n_candidates, horizon=horizon, num_cem_iters=num_cem_iters,
                                percent_elites=percent_elites, use_reward_model=use_reward_model, alpha=0.0,
                                rng=rng, cem_mode=cem_mode, shard_candidates=shard_candidates,
-                               pipeline_chunks=pipeline_chunks)
+                               pipeline_chunks=pipeline_chunks, native_cem_step=native_cem_step)
         self._hidden_state = None
 
     # ------------------------------------------------------------------ hidden state: host view + device copy
