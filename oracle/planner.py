@@ -32,19 +32,27 @@ def sample_rs_actions(low, high, n, m, h):
     return flat.reshape((h, n * m, -1))
 
 
-def rollout_returns(dynamics_model, reward_fn, observations, actions, n, discount):
-    """The shared horizon loop (``:116-127`` for RS, ``:92-99`` for CEM).
+def rollout_trace(dynamics_model, reward_fn, observations, actions, n, discount):
+    """The shared horizon loop (``:116-127`` for RS, ``:92-99`` for CEM), keeping what each step hands to the next.
 
-    ``actions``: float64 ``[h, n*m, act_dim]``.  Returns float64 ``[n*m]``.
+    ``actions``: float64 ``[h, n*m, act_dim]``.  Returns ``(returns [n*m], states [h, n*m, obs_dim])`` in float64;
+    ``states[t]`` is the observation after horizon step ``t``.
     """
     h = actions.shape[0]
     total = np.zeros((actions.shape[1],))
     state = np.repeat(np.asarray(observations, dtype=np.float64), n, axis=0)
+    states = []
     for t in range(h):
         nxt = dynamics_model.predict(state, actions[t])
         total += discount ** t * reward_fn(state, actions[t], nxt)
         state = nxt
-    return total
+        states.append(nxt)
+    return total, np.stack(states)
+
+
+def rollout_returns(dynamics_model, reward_fn, observations, actions, n, discount):
+    """The returns of ``rollout_trace``: float64 ``[n*m]``."""
+    return rollout_trace(dynamics_model, reward_fn, observations, actions, n, discount)[0]
 
 
 def rs_plan(dynamics_model, reward_fn, observations, low, high, n, h, discount=1.0,

@@ -29,16 +29,27 @@ def repeat_hidden(hidden, n):
     return np.repeat(hidden, n, axis=0)
 
 
-def rnn_rollout_returns(dynamics_model, reward_fn, observations, hidden, actions, n, discount):
+def rnn_rollout_trace(dynamics_model, reward_fn, observations, hidden, actions, n, discount):
+    """The horizon loop, keeping what each step hands to the next.  Returns ``(returns [n*m], states [h, n*m, obs_dim]
+    float64, hiddens)``: ``states[t]`` / ``hiddens[t]`` are the observation and the hidden state (whatever
+    ``dynamics_model.predict`` returns) after horizon step ``t``."""
     h = actions.shape[0]
     total = np.zeros((actions.shape[1],))
     state = np.repeat(np.asarray(observations, dtype=np.float64), n, axis=0)   # :119 / :95
     hid = repeat_hidden(hidden, n)                                              # :120 / :96
+    states, hiddens = [], []
     for t in range(h):
         nxt, hid = dynamics_model.predict(state, actions[t], hid)               # :123
         total += discount ** t * reward_fn(state, actions[t], nxt)
         state = nxt
-    return total
+        states.append(nxt)
+        hiddens.append(hid)
+    return total, np.stack(states), hiddens
+
+
+def rnn_rollout_returns(dynamics_model, reward_fn, observations, hidden, actions, n, discount):
+    """The returns of ``rnn_rollout_trace``: float64 ``[n*m]`` (``:119-127`` for RS, ``:95-104`` for CEM)."""
+    return rnn_rollout_trace(dynamics_model, reward_fn, observations, hidden, actions, n, discount)[0]
 
 
 def rnn_rs_plan(dynamics_model, reward_fn, observations, hidden, low, high, n, h, discount=1.0,

@@ -239,3 +239,49 @@ def _lstm_rows():
 MLP_ROWS = _mlp_rows() + _micro_rows()
 LSTM_ROWS = _lstm_rows()
 ROWS = MLP_ROWS + LSTM_ROWS
+
+# ---- the generic recurrent kernel: one row per run-time branch -------------------------------------------------------------------
+#
+# l2a_rnn_mfma_k (csrc/l2a_rnn_mfma.h) is not templated over the model: it branches at run time on each layer's width
+# (UT = ceil(U / 16) unit tiles, KGx = ceil(inputs / 16) input k-groups).  A row is the smallest model that reaches a branch;
+# every row also runs on l2a_rnn_valu_k.  ``why`` names the line of l2a_rnn_mfma.h the row is there for.
+GenericRow = namedtuple("GenericRow", "id cell obs_dim act_dim units activation reward why")
+GENERIC_M, GENERIC_N = 2, N_SMALL
+
+
+def _generic(cell, obs_dim, act_dim, units, activation, why, reward="vel"):
+    rid = "%s-%s-o%da%d-%s" % (cell, "x".join(str(u) for u in units), obs_dim, act_dim, activation)
+    return GenericRow(rid, cell, obs_dim, act_dim, tuple(units), activation, reward, why)
+
+
+GENERIC_ROWS = [
+    # width classes (20 + 6 inputs: KGx = 2).  UT = 8: ring of 10 k-groups, tail 2
+    _generic("gru", 20, 6, [120], "tanh", ":339 prod2 and :307 prod1 with TB = 2, UT even"),
+    _generic("rnn", 20, 6, [120], "relu", ":307 prod1 with TB = 2, UT even"),
+    # UT = 9: the last block of two reads a zero tile (:302, :322 skip it); ring of 11, tail 3
+    _generic("gru", 20, 6, [130], "sigmoid", ":339 / :307 TB = 2, UT odd: :322 and :302 skip the zero tile"),
+    _generic("rnn", 20, 6, [130], "tanh", ":307 TB = 2, UT odd: :302 skips the zero tile"),
+    # UT = 17 (41 + 8 inputs: KGx = 4; ring of 21, tail 1): four tiles per call, the last block holds three zero tiles; the GRU
+    # gates stay at two tiles per call with an odd UT
+    _generic("gru", 41, 8, [264], "tanh", ":306 prod1 with TB = 4, three zero tiles; :339 TB = 2 with UT odd", "dist"),
+    _generic("rnn", 41, 8, [264], "swish", ":306 prod1 with TB = 4, three zero tiles"),
+    # a stack of LSTM layers whose top width has U % 4 != 0: a lane's f32x4 of c / h is partly live (:278, :283); rings of 7 and 7
+    _generic("lstm", 20, 6, [72, 23], "tanh", ":262 LSTM blocks, :278 `live` inside an f32x4"),
+    # 16 inputs exactly, one unit tile: a ring of TWO k-groups (:97 clamps the third request), an output layer of ONE (:383)
+    _generic("gru", 9, 7, [16], "tanh", ":97 ring clamp with KGx + UT = 2; :383 output layer of a single k-group"),
+    # three layers of different widths: rings of 5 (tail 1), 12 (tail 0) and 11 (tail 3); the input stride changes per layer (:370)
+    _generic("rnn", 20, 6, [40, 130, 24], "tanh", ":124 ring with no tail (3 + 9 k-groups); :370-372 a new input stride per layer"),
+    # 40 action dims: no prefetch, the actions are read in place (ring of 8, tail 0)
+    _generic("gru", 20, 40, [64], "tanh", ":208 apf off, :234 actions read in place"),
+    # 65 observation dims: five observation tiles for four waves - wave 0 takes tiles 0 and 4; the reward reads dim 64
+    _generic("gru", 65, 3, [48], "tanh", ":380 a fifth observation tile (wave 0: c = 0 and c = 4)"),
+]
+
+
+def generic_rings(row):
+    """KGx + UT of every layer's product and the k-groups of the output layer: the lengths of the operand rings of a row."""
+    kin, out = row.obs_dim + row.act_dim, []
+    for u in row.units:
+        out.append((kin + 15) // 16 + (u + 15) // 16)
+        kin = u
+    return out, (kin + 15) // 16

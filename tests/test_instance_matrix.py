@@ -4,7 +4,11 @@
     unit its instance lives in, and the unit's switch (restated in `instance_matrix.dispatched_instance`) picks that instance;
 (b) the rows cover the literal enumeration of instances minus the explicit UNREACHABLE list - removing a row, or changing a
     policy so that it routes elsewhere, fails here;
-(c) the GPU file runs every row: no row is skipped, deselected by a mark or expected to fail.
+(c) the GPU file runs every row: no row is skipped, deselected by a mark or expected to fail;
+(d) the carry launches of a row (tests/test_gpu_instance_matrix.py: a chunk of one horizon step, a chunk of two, a predict)
+    take the geometry of the row's plan: the launcher's decision does not look at h below 4096, and with m = 1 a predict of
+    the row's n rows is a plan of h = 1;
+(e) GENERIC_ROWS reaches every run-time branch of the generic recurrent kernel it claims, and its oracle stays finite.
 """
 
 import ctypes
@@ -18,10 +22,11 @@ from learning_to_adapt_amd import _lib
 GEOMETRY_FIELDS = ("kernel", "nt", "split", "fan", "whole_instance", "front_workgroups")
 
 
-def _geometry(row):
+def _geometry(row, h=None, micro=None):
     p = row.policy
-    return _lib.plan_geometry(row.obs_dim, row.act_dim, row.hidden, row.E, row.mode, row.m, row.n, row.h,
-                              split=p["split"], fan=p["fan"], micro=p["micro"], cus=256, double=p["double"])
+    return _lib.plan_geometry(row.obs_dim, row.act_dim, row.hidden, row.E, row.mode, row.m, row.n, row.h if h is None else h,
+                              split=p["split"], fan=p["fan"], micro=p["micro"] if micro is None else micro, cus=256,
+                              double=p["double"])
 
 
 def _unit_of(row, g):
@@ -52,6 +57,22 @@ def test_row_routes_to_its_instance(row):
     else:
         assert im.dispatched_instance(family, unit, row.obs_dim, row.act_dim, len(row.hidden), row.activation) == row.instance
     assert row.h == 3 and row.m == 1
+
+
+CARRY_MLP_ROWS = [r for r in im.MLP_ROWS if r.instance.family == "mlp"]
+
+
+@pytest.mark.parametrize("row", CARRY_MLP_ROWS, ids=[r.id for r in CARRY_MLP_ROWS])
+def test_carry_launches_route_to_the_rows_instance(row):
+    """Chunk A is a launch of h = 1, chunk B one of h = 2, and the predict (every row has m = 1: n rows in one block) is
+    h = 1 again (l2a_api.hip: l2a_predict), all with micro = 0: the launcher must pick the geometry of the row's own plan - and
+    with it, by (a), the row's instance.  (A launch with per-row states or a state output never takes the micro tiles whatever the
+    policy says: l2a_api.hip:235.)"""
+    assert row.m == 1
+    for h in (1, 2):
+        g = _geometry(row, h=h, micro=0)
+        assert {k: g[k] for k in GEOMETRY_FIELDS} == row.expect, (row.id, h)
+        assert _unit_of(row, g) == ("mlp", row.instance.unit)
 
 
 def test_rows_cover_every_compiled_instance():
@@ -94,6 +115,10 @@ def test_lstm_rows_meet_the_launcher_conditions():
             assert row.policy["micro"] == 0
             assert row.policy["split"] == (1 if row.instance.variant == "split" else 0)
             assert 2 * tiles <= 256 and row.h < 4096
+            # The carry launches take the same branch: the unit-tile split of :236 reads only the tile count, the split policy
+            # and h < 4096 (chunks of h = 1 and 2 over the same m, n; l2a_lstm_predict is m = 1, n = rows, h = 1 with the default
+            # `allow_split`), and :207 keeps every launch with per-row states or a state output off the micro tiles.
+            assert row.m == 1           # so a predict of m * n rows is the plan's own tile count
 
 
 def test_gpu_file_runs_every_row():
@@ -105,3 +130,51 @@ def test_gpu_file_runs_every_row():
         assert list(args) == list(rows) and all(isinstance(a, im.Row) for a in args)    # plain rows: no marked parameter
         assert list(marks[0].kwargs["ids"]) == [r.id for r in rows]
     assert [m.name for m in gpu.pytestmark] == ["gpu"] if isinstance(gpu.pytestmark, list) else gpu.pytestmark.name == "gpu"
+
+
+def test_gpu_file_runs_the_carry_of_every_row_that_has_one():
+    """The carry checks live inside the two row tests (the row's case is warm there), behind `has_carry`: true for every row
+    but the micro-tile ones, whose kernels the launcher never gives a carry launch."""
+    import inspect
+    import test_gpu_instance_matrix as gpu
+    for row in im.ROWS:
+        assert gpu.has_carry(row) == (row.instance.family not in ("mlp_micro", "lstm_micro")), row.id
+    assert sum(gpu.has_carry(r) for r in im.MLP_ROWS) == len(CARRY_MLP_ROWS) > 0
+    for fn, carry in ((gpu.test_mlp_instance_matches_oracle, "_mlp_carry"), (gpu.test_lstm_instance_matches_oracle, "_lstm_carry")):
+        src = inspect.getsource(fn)
+        assert "if has_carry(row):" in src and src.count(carry + "(ctx, case, row, ") == 2 and "_check_chain(" in src
+
+
+def test_gpu_file_runs_every_generic_row_on_both_kernels():
+    import test_gpu_instance_matrix as gpu
+    marks = {m.args[0]: m for m in gpu.test_generic_recurrent_branches_match_oracle.pytestmark}
+    assert sorted(marks) == ["kernel", "row"] and all(m.name == "parametrize" for m in marks.values())
+    assert list(marks["row"].args[1]) == list(im.GENERIC_ROWS) and list(marks["kernel"].args[1]) == ["mfma", "valu"]
+    assert len({r.id for r in im.GENERIC_ROWS}) == len(im.GENERIC_ROWS)
+
+
+def test_generic_rows_reach_the_branches_they_name():
+    """The run-time switches of l2a_rnn_mfma.h, restated: unit tiles per product call (:306-308, :339-340), the operand ring's
+    tail (:130-133) and clamp (:97), the action prefetch (:208), the observation tiles per wave (:380)."""
+    rows = im.GENERIC_ROWS
+    ut = lambda u: (u + 15) // 16  # noqa: E731
+    for cell in ("gru", "rnn"):
+        classes = {(1 if ut(u) < 8 else 2 if ut(u) < 16 else 4, ut(u) % 2) for r in rows if r.cell == cell for u in r.units}
+        assert {(2, 0), (2, 1), (4, 1)} <= classes, (cell, classes)
+    assert any(r.cell == "lstm" and len(r.units) > 1 and any(u % 4 for u in r.units) for r in rows)
+    rings = [k for r in rows for k in im.generic_rings(r)[0]]
+    assert {k % 4 for k in rings} == {0, 1, 2, 3} and 2 in rings
+    assert any(im.generic_rings(r)[1] == 1 for r in rows)                        # an output layer of one k-group
+    assert any(len(r.units) == 3 and len(set(r.units)) == 3 for r in rows)
+    assert any(r.act_dim > 32 for r in rows) and any(r.obs_dim > 64 for r in rows)
+    assert {"tanh", "relu", "sigmoid", "swish"} <= {r.activation for r in rows}
+    assert all(re.match(r":\d+", r.why) for r in rows)
+
+
+@pytest.mark.parametrize("row", im.GENERIC_ROWS, ids=[r.id for r in im.GENERIC_ROWS])
+def test_generic_rows_keep_the_oracle_finite(row):
+    import numpy as np
+    import test_gpu_instance_matrix as gpu
+    case = gpu._generic_oracle(row)
+    for a in (case.want, case.states) + tuple(x for pair in case.cells for x in pair) + case.pred_want:
+        assert np.all(np.isfinite(a)) and np.max(np.abs(a)) < 1e3, row.id

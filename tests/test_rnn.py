@@ -781,3 +781,135 @@ def test_gpu_rnn_generic_micro_tiles_match_the_16_candidate_kernel_and_the_oracl
     # are sums of up to h rewards of either sign), far inside the bar against the oracle above
     assert float(np.max(np.abs(out[2][0] - out[0][0])) / max(1.0, float(np.max(np.abs(out[0][0]))))) < 2e-6
     assert _tol_returns(out[2][0], out[0][0]) < 1e-4
+
+
+# ------------------------------------------------------------------------------------------ the small-rows state step
+# (rows, units, (obs_dim, act_dim), cell activation): every value of every axis at least twice.  Rows 9, 17 and 64 take a second
+# (third, eighth) turn of the kernel's loop over chunks of eight rows, 7 and 9 leave a chunk ragged; K = inputs + units is and
+# is not a multiple of 4 and of the 8-wide inner step (20, 33, 42, 96, ...); 16 units is ONE workgroup, 512 are thirty-two.
+ADVANCE_CASES = [
+    (1, 16, (3, 1), "tanh"), (7, 16, (16, 1), "relu"), (8, 16, (20, 6), "tanh"), (9, 16, (64, 16), "relu"),
+    (17, 80, (3, 1), "relu"), (64, 80, (16, 1), "tanh"), (1, 80, (20, 6), "relu"), (9, 80, (64, 16), "tanh"),
+    (7, 128, (3, 1), "tanh"), (8, 128, (16, 1), "relu"), (17, 128, (20, 6), "tanh"), (64, 128, (64, 16), "relu"),
+    (8, 512, (3, 1), "relu"), (17, 512, (16, 1), "tanh"), (64, 512, (20, 6), "relu"), (1, 512, (64, 16), "tanh"),
+]
+ADVANCE_GUARD = 16          # rows of sentinel on each side of c_out / h_out
+
+
+def _advance_model(obs_dim, act_dim, units, activation, seed):
+    """One LSTM layer on which `l2a_lstm_advance` runs `l2a_lstm_advance_k`, with `advance_kernel_ok`'s conditions
+    (l2a_lstm_api.hip:274) asserted: not a generic model, units a multiple of 16, not the VALU kernel, the LDS rows fit.
+    `NativeLSTM` (l2a_rnn_create) makes a width outside the tuned kernel's {128, 256, 512} a GENERIC model, whose state step
+    is one step of the rollout kernel; `l2a_lstm_create` keeps it the plain one-layer model that takes the small-rows kernel."""
+    import ctypes
+    from learning_to_adapt_amd import _lib
+    from learning_to_adapt_amd.dynamics.native_lstm import NativeLSTM
+    from learning_to_adapt_amd.utils import synthetic
+    from oracle import OracleLSTMDynamics
+    params = synthetic.make_lstm_set(obs_dim, act_dim, units, seed)
+    norm = synthetic.make_norm(obs_dim, act_dim, -np.ones(act_dim), np.ones(act_dim), seed + 1)
+    native = NativeLSTM(obs_dim, act_dim, units, activation, None)
+    if not native.lib.l2a_lstm_mfma_eligible(obs_dim, act_dim, units):
+        native.close()
+        handle = ctypes.c_void_p()
+        native.ctx.check(native.lib.l2a_lstm_create(native.ctx.handle, obs_dim, act_dim, units, _lib.ACT_CODES[activation],
+                                                    _lib.ACT_CODES[None], ctypes.byref(handle)), "l2a_lstm_create")
+        native.handle = handle
+    native.set_weights(params)
+    native.set_norm(norm)
+    assert units % 16 == 0 and units >= 16
+    assert (obs_dim + act_dim + units) * 8 * 4 + 4 * 64 * 8 * 4 <= 64 * 1024
+    return native, OracleLSTMDynamics(obs_dim, act_dim, params, norm, hidden_nonlinearity=activation, dtype=np.float64)
+
+
+def _guarded(rows, width, dev):
+    full = torch.full((rows + 2 * ADVANCE_GUARD, width), -7.25e5, dtype=torch.float32, device=dev)
+    inner = full[ADVANCE_GUARD:ADVANCE_GUARD + rows]
+    inner.fill_(float("nan"))
+    return full, inner
+
+
+def _read_guarded(full):
+    full = full.cpu().numpy()
+    assert np.all(full[:ADVANCE_GUARD] == np.float32(-7.25e5)) and np.all(full[-ADVANCE_GUARD:] == np.float32(-7.25e5))
+    inner = full[ADVANCE_GUARD:-ADVANCE_GUARD]
+    assert not np.any(np.isnan(inner))
+    return inner
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows,units,dims,activation", ADVANCE_CASES,
+                         ids=["r%d-u%d-o%da%d-%s" % (r, u, d[0], d[1], a) for r, u, d, a in ADVANCE_CASES])
+def test_gpu_rnn_advance_kernel_matches_oracle(rows, units, dims, activation):
+    """`l2a_lstm_advance_k` against the states of `OracleLSTMDynamics.predict` in float64, at predict's own bar
+    (test_gpu_rnn_predict_matches_oracle), beyond one chunk of eight rows and away from 128 / 256 units and 26 inputs."""
+    from learning_to_adapt_amd import _lib
+    obs_dim, act_dim = dims
+    ctx = _lib.Context.get(0)
+    ctx.set_kernel("auto")
+    native, dyn = _advance_model(obs_dim, act_dim, units, activation, 1000 + rows + units + obs_dim)
+    dev = native.device
+    rs = np.random.RandomState(rows * 1000 + units + act_dim)
+    obs = rs.randn(rows, obs_dim).astype(np.float32)
+    act = rs.uniform(-1, 1, (rows, act_dim)).astype(np.float32)
+    hid = LSTMStateTuple(rs.randn(rows, units).astype(np.float32), np.tanh(rs.randn(rows, units)).astype(np.float32))
+    _, want = dyn.predict(obs, act, hid)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+    (c_full, c_out), (h_full, h_out) = _guarded(rows, units, dev), _guarded(rows, units, dev)
+    native.advance(up(obs), up(act), up(hid.c), up(hid.h), c_out=c_out, h_out=h_out)
+    torch.cuda.synchronize()
+    c_got, h_got = _read_guarded(c_full), _read_guarded(h_full)
+    print("advance r%d u%d: |c - want| %.3e, |h - want| %.3e" % (rows, units, np.abs(c_got - want.c).max(), np.abs(h_got - want.h).max()))
+    np.testing.assert_allclose(c_got, want.c, rtol=1e-5, atol=2e-6)
+    np.testing.assert_allclose(h_got, want.h, rtol=1e-5, atol=2e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("units", [128, 80])
+def test_gpu_rnn_blocking_plan_advances_nine_envs_through_the_keys(units):
+    """The gather form of `l2a_lstm_advance_k` behind `l2a_lstm_plan_rs_sync` (the winners' first actions read through the
+    keys, `cand_offset` > 0) with m = 9 - a second chunk of rows - against `l2a_lstm_advance` with the actions picked on the
+    host: bit for bit.  128 units: the tuned kernel plans and publishes the keys; 80: the VALU kernel plans."""
+    from learning_to_adapt_amd import _lib
+    from learning_to_adapt_amd.envs import RewardSpec
+    m, n, h, offset = 9, 5, 3, 13
+    ctx = _lib.Context.get(0)
+    ctx.set_kernel("auto")
+    native, _ = _advance_model(20, 6, units, "tanh", 77 + units)
+    dev = native.device
+    spec = RewardSpec.make(w_vel=1.0, dt=0.05, ctrl_coef=0.05, vel_index=8)
+    rs = np.random.RandomState(units)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+    obs = rs.randn(m, 20).astype(np.float32)
+    acts = up(rs.uniform(-1, 1, (h, m * n, 6)))
+    c0, h0 = up(rs.randn(m, units)), up(np.tanh(rs.randn(m, units)))
+    (c_full, c1), (h_full, h1) = _guarded(m, units, dev), _guarded(m, units, dev)
+    keys = native.plan_rs_sync(obs, c0, h0, acts, m, n, h, 0.97, spec, cand_offset=offset, c_next=c1, h_next=h1)
+    assert keys is not None
+    torch.cuda.synchronize()
+    idx = np.array([_lib.key_decode(k)[1] for k in keys.view(np.int64)]) - offset
+    assert np.all((idx >= 0) & (idx < n)) and len(set(idx.tolist())) > 1, idx      # (not every env picks the same candidate)
+    chosen = acts[0].reshape(m, n, 6)[torch.arange(m), torch.from_numpy(idx).to(dev)].contiguous()
+    c_want, h_want = native.advance(up(obs), chosen, c0, h0)
+    torch.cuda.synchronize()
+    assert np.array_equal(_read_guarded(c_full), c_want.cpu().numpy())
+    assert np.array_equal(_read_guarded(h_full), h_want.cpu().numpy())
+    ctx.launch_status()
+
+
+def test_advance_cases_cover_every_value_twice_and_all_run():
+    """No GPU: ADVANCE_CASES is what the GPU test is parametrised with (plain tuples, no skip / xfail mark), and it covers the
+    rows, units, input widths and activations asked for at least twice each."""
+    marks = test_gpu_rnn_advance_kernel_matches_oracle.pytestmark
+    assert sorted(m.name for m in marks) == ["gpu", "parametrize"]
+    args = [m for m in marks if m.name == "parametrize"][0].args[1]
+    assert list(args) == ADVANCE_CASES and all(type(a) is tuple for a in args) and len(set(ADVANCE_CASES)) == len(ADVANCE_CASES)
+    for axis, values in ((0, (1, 7, 8, 9, 17, 64)), (1, (16, 80, 128, 512)), (2, ((3, 1), (16, 1), (20, 6), (64, 16))),
+                         (3, ("tanh", "relu"))):
+        seen = [c[axis] for c in ADVANCE_CASES]
+        assert set(seen) == set(values) and all(seen.count(v) >= 2 for v in values), (axis, seen)
+    for rows, units, (obs_dim, act_dim), _ in ADVANCE_CASES:        # advance_kernel_ok's arithmetic (l2a_lstm_api.hip:274)
+        assert units % 16 == 0 and units >= 16 and (obs_dim + act_dim + units) * 8 * 4 + 4 * 64 * 8 * 4 <= 64 * 1024
+    ks = {obs_dim + act_dim + units for _, units, (obs_dim, act_dim), _ in ADVANCE_CASES}
+    assert any(k % 4 for k in ks) and any(k % 4 == 0 and k % 8 for k in ks) and any(k % 8 == 0 for k in ks)
+    assert any(rows > 8 for rows, _, _, _ in ADVANCE_CASES)
