@@ -480,6 +480,20 @@ class MPCController(Policy, Serializable):
         ctx.native_comm = (rank, world)
         return True
 
+    def _native_shard(self, native, rank, world, words):
+        """The ``shard`` tuple of a sharded C step (``NativeStep`` / ``NativeCemStep``) whose collective reduces ``words`` int64 words:
+        over the library's own communicator (``L2A_NATIVE_COMM=1``), else through ``_reduce_payload`` - after a dry run of that
+        collective (every rank builds its controller in the same step, so the call is symmetric).  None: the backend cannot
+        MAX-reduce int64 words on this device, and the plan keeps the Python path."""
+        if os.environ.get("L2A_NATIVE_COMM", "0") == "1" and torch.distributed.get_backend() != "gloo":
+            self._native_comm(native, rank, world)
+            return (rank, world, None)
+        try:
+            self._reduce_payload(torch.zeros((words,), dtype=torch.int64, device=native.device))
+        except Exception:
+            return None
+        return (rank, world, self._reduce_payload)
+
     def _native_step_build(self, native, m, key, rank=0, world=1):
         from .native_step import NativeStep
         if self._cstep is not None:
@@ -504,17 +518,9 @@ class MPCController(Policy, Serializable):
             if not hasattr(native.lib, "l2a_lstm_controller_create_sharded" if hasattr(native, "units")
                            else "l2a_controller_create_sharded_device"):
                 return None
-            own = os.environ.get("L2A_NATIVE_COMM", "0") == "1" and torch.distributed.get_backend() != "gloo"
-            if own:
-                self._native_comm(native, rank, world)
-            else:
-                # dry run of the collective the callback will issue every step (every rank builds its controller in the same
-                # step, so the call is symmetric): a backend that cannot MAX-reduce int64 words on this device keeps the Python path
-                try:
-                    self._reduce_payload(torch.zeros((m + 3,), dtype=torch.int64, device=native.device))
-                except Exception:
-                    return None
-            shard = (rank, world, None if own else self._reduce_payload)
+            shard = self._native_shard(native, rank, world, m + 3)
+            if shard is None:
+                return None
         st = NativeStep(native, hasattr(native, "units"), m, self.n_candidates, self.horizon, self.action_space.low,
                         self.action_space.high, self.discount, self._reward_spec,
                         device_seed=(int(torch.initial_seed()) if device else None), shard=shard)
@@ -1134,19 +1140,10 @@ class MPCController(Policy, Serializable):
             if world > 1:
                 if self._cemstep_no == key:
                     return None
-                # every rank builds its controller in the same plan step, so the dry run of the collective the callback will issue
-                # every iteration is symmetric (`_native_step_build`): a backend that cannot MAX-reduce int64 words on this device
-                # keeps the Python path
-                own = os.environ.get("L2A_NATIVE_COMM", "0") == "1" and torch.distributed.get_backend() != "gloo"
-                if own:
-                    self._native_comm(native, rank, world)
-                else:
-                    try:
-                        self._reduce_payload(torch.zeros((m * n + 3,), dtype=torch.int64, device=native.device))
-                    except Exception:
-                        self._cemstep_no = key
-                        return None
-                shard = (rank, world, None if own else self._reduce_payload)
+                shard = self._native_shard(native, rank, world, m * n + 3)
+                if shard is None:
+                    self._cemstep_no = key
+                    return None
             st = NativeCemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
                                self.num_cem_iters, num_elites, self.alpha, self.cem_mode == "reference", seed, shard=shard)
             st.key, st.calls = key, 0

@@ -16,72 +16,26 @@ A recurrent native model (one with ``units``: ``RNNMPCController``) builds ``l2a
 also advances that state with the chosen actions, behind the pick and in front of the one read-back.
 """
 
-import ctypes
-import os
-
 import numpy as np
 
-from .. import _lib
-from .native_step import make_reduce_cb
+from .native_step import StepHandle, _seed
 
 
-class NativeCemStep(object):
+class NativeCemStep(StepHandle):
     def __init__(self, native, m, n, h, low, high, discount, reward, iters, num_elites, alpha, reference, seed, shard=None):
-        lib = native.lib
-        self.lib, self.ctx, self.native = lib, native.ctx, native
-        self.m, self.n, self.h, self.iters = int(m), int(n), int(h), int(iters)
+        self.iters = int(iters)
+        create = "l2a_%scem_controller_create%s_device" % ("lstm_" if hasattr(native, "units") else "", "_sharded" if shard is not None else "")
+        extra = (self.iters, int(num_elites), float(alpha), 1 if reference else 0, _seed(seed))
+        self._open(native, create, m, n, h, low, high, discount, reward, extra, shard)
         self.D = self.h * native.act_dim
-        self.recurrent = hasattr(native, "units")
-        if self.recurrent and not hasattr(lib, "l2a_lstm_cem_controller_create_device"):
-            raise _lib.L2AError("this libl2a_hip.so has no recurrent CEM controller step")
-        low = np.ascontiguousarray(low, dtype=np.float64)
-        high = np.ascontiguousarray(high, dtype=np.float64)
-        handle = ctypes.c_void_p()
-        self.reduce_error = None
-        self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
-        seed = ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF)
-        if shard is None:
-            create = lib.l2a_lstm_cem_controller_create_device if self.recurrent else lib.l2a_cem_controller_create_device
-            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                        float(discount), ctypes.byref(reward), self.iters, int(num_elites), float(alpha),
-                        1 if reference else 0, seed, ctypes.byref(handle))
-            self.ctx.check(rc, "l2a_cem_controller_create_device")
-        else:
-            rank, world, reduce = shard
-            cb = make_reduce_cb(self, lib, native, reduce)
-            create = (lib.l2a_lstm_cem_controller_create_sharded_device if self.recurrent
-                      else lib.l2a_cem_controller_create_sharded_device)
-            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data,
-                        float(discount), ctypes.byref(reward), self.iters, int(num_elites),
-                        float(alpha), 1 if reference else 0, seed, int(rank), int(world), cb, None,
-                        ctypes.byref(handle))
-            self.ctx.check(rc, "l2a_cem_controller_create_sharded_device")
-        self.handle = handle
-        self.pid = os.getpid()
-        self.obs = np.empty((self.m, native.obs_dim), dtype=np.float64)
-        self.act = np.empty((self.m, native.act_dim), dtype=np.float64)
-        self.idx = np.empty((self.m,), dtype=np.int64)
-        self.ret = np.empty((self.m,), dtype=np.float32)
-        self._p = (self.obs.ctypes.data, self.act.ctypes.data, self.idx.ctypes.data, self.ret.ctypes.data)
         self.steps = 0
-        self._stats = (ctypes.c_double * 16)()
 
     def step(self, observations, stream, state=None):
         """One plan step; ``self.act`` / ``self.idx`` / ``self.ret`` hold the result afterwards.  ``state`` (recurrent):
         ``(c0, h0, c_next, h_next)`` device pointers; ``c_next`` and ``h_next`` both None plan without advancing the state."""
         np.copyto(self.obs, observations, casting="same_kind")
-        p = self._p
-        if self.recurrent:
-            rc = self.lib.l2a_lstm_controller_step(self.handle, p[0], state[0], state[1], state[2], state[3], p[1], p[2], p[3], stream)
-        else:
-            rc = self.lib.l2a_controller_step(self.handle, p[0], p[1], p[2], p[3], stream)
-        if rc == _lib.L2A_STEP_UNSPLIT:         # the C side has switched the context to the unsplit geometry (same bits)
-            self.ctx.split_degraded = True
-        elif rc != _lib.L2A_OK:
-            if self.reduce_error is not None:
-                exc, self.reduce_error = self.reduce_error, None
-                raise exc
-            self.ctx.check(rc, "l2a_controller_step (CEM)")
+        rc = self._call(state, stream)
+        self._settle(rc, "l2a_controller_step (CEM)")
         self.steps += 1
         return rc
 
@@ -96,18 +50,5 @@ class NativeCemStep(object):
         return mean, std, rets
 
     def stats(self):
-        self.ctx.check(self.lib.l2a_controller_stats(self.handle, self._stats, 16), "l2a_controller_stats")
-        v = list(self._stats)
+        v = self._stat_slots()
         return dict(stage_us=dict(sample=v[1], launch=v[2], wait=v[4], decode=v[5], call=v[6]), steps=int(v[7]), relaunches=int(v[8]))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            if getattr(self, "pid", None) == os.getpid():
-                self.lib.l2a_controller_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

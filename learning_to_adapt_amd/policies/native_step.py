@@ -60,7 +60,78 @@ def make_reduce_cb(owner, lib, native, reduce):
     return ctypes.cast(owner._reduce_cb, ctypes.c_void_p)
 
 
-class NativeStep(object):
+def _seed(seed):
+    return ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+class StepHandle(object):
+    """What `NativeStep` and `NativeCemStep` (policies/native_cem_step.py) share: the create call, the I/O arrays of a step, the
+    step's return code, the stats call and the teardown."""
+
+    def _open(self, native, create, m, n, h, low, high, discount, reward, extra, shard):
+        """``lib.<create>(model, m, n, h, low, high, discount, reward, *extra[, rank, world, reduce, NULL], &handle)``."""
+        lib = native.lib
+        self.lib, self.ctx, self.native = lib, native.ctx, native
+        self.m, self.n, self.h = int(m), int(n), int(h)
+        self.recurrent = hasattr(native, "units")
+        if not hasattr(lib, create):
+            raise _lib.L2AError("this libl2a_hip.so has no %s" % create)
+        low = np.ascontiguousarray(low, dtype=np.float64)
+        high = np.ascontiguousarray(high, dtype=np.float64)
+        self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
+        cb = make_reduce_cb(self, lib, native, None if shard is None else shard[2])
+        tail = () if shard is None else self.shard + (cb, None)
+        handle = ctypes.c_void_p()
+        rc = getattr(lib, create)(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount),
+                                  ctypes.byref(reward), *extra, *tail, ctypes.byref(handle))
+        self.ctx.check(rc, create)
+        self.handle = handle
+        self.pid = os.getpid()      # a forked child must not tear down the parent's HIP objects (it drops the handle instead)
+        self.obs = np.empty((self.m, native.obs_dim), dtype=np.float64)
+        self.act = np.empty((self.m, native.act_dim), dtype=np.float64)
+        self.idx = np.empty((self.m,), dtype=np.int64)
+        self.ret = np.empty((self.m,), dtype=np.float32)
+        self._p = (self.obs.ctypes.data, self.act.ctypes.data, self.idx.ctypes.data, self.ret.ctypes.data)
+        self._stats = (ctypes.c_double * 16)()
+
+    def _call(self, state, stream):
+        """The whole step in one call.  ``state`` (recurrent): ``(c0, h0, c_next, h_next)`` device pointers."""
+        p = self._p
+        if self.recurrent:
+            return self.lib.l2a_lstm_controller_step(self.handle, p[0], state[0], state[1], state[2], state[3], p[1], p[2], p[3], stream)
+        return self.lib.l2a_controller_step(self.handle, p[0], p[1], p[2], p[3], stream)
+
+    def _raise(self, rc, what):
+        """A failed call: the exception the reduce callback parked (it could not unwind through the C frame), else the library's."""
+        if self.reduce_error is not None:
+            exc, self.reduce_error = self.reduce_error, None
+            raise exc
+        self.ctx.check(rc, what)
+
+    def _settle(self, rc, what):
+        if rc == _lib.L2A_STEP_UNSPLIT:        # the C side has switched the context to the unsplit geometry (same bits)
+            self.ctx.split_degraded = True
+        elif rc != _lib.L2A_OK:
+            self._raise(rc, what)
+
+    def _stat_slots(self):
+        self.ctx.check(self.lib.l2a_controller_stats(self.handle, self._stats, 16), "l2a_controller_stats")
+        return list(self._stats)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self, "pid", None) == os.getpid():
+                self.lib.l2a_controller_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeStep(StepHandle):
     def __init__(self, native, recurrent, m, n, h, low, high, discount, reward, device_seed=None, shard=None):
         """``device_seed``: None = parity mode (NumPy's global generator, candidates drawn ahead by a C thread); an integer =
         ``rng="device"``: the candidates come from the library's counter-based Philox stream under that seed, drawn on the GPU.
@@ -69,56 +140,18 @@ class NativeStep(object):
         action behind the collective): ``reduce`` = None runs the step's one collective over the library's own RCCL communicator
         (``l2a_comm_init``), else a callable ``reduce(payload)`` that MAX-all-reduces the int64 CUDA tensor it is handed in place
         (torch.distributed)."""
-        lib = native.lib
-        self.lib, self.ctx, self.native, self.recurrent = lib, native.ctx, native, bool(recurrent)
-        self.m, self.n, self.h = int(m), int(n), int(h)
-        low = np.ascontiguousarray(low, dtype=np.float64)
-        high = np.ascontiguousarray(high, dtype=np.float64)
-        handle = ctypes.c_void_p()
         self.device_rng = device_seed is not None
-        self.reduce_error = None
-        if shard is not None and self.recurrent and not hasattr(lib, "l2a_lstm_controller_create_sharded"):
-            raise _lib.L2AError("this libl2a_hip.so has no sharded recurrent controller step")
-        if self.device_rng and shard is not None:
-            self.addr, self.lock = None, None
-            rank, world, reduce = shard
-            cb = make_reduce_cb(self, lib, native, reduce)
-            create = lib.l2a_lstm_controller_create_sharded_device if self.recurrent else lib.l2a_controller_create_sharded_device
-            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount), ctypes.byref(reward),
-                        ctypes.c_ulonglong(int(device_seed) & 0xFFFFFFFFFFFFFFFF), int(rank), int(world), cb, None,
-                        ctypes.byref(handle))
-        elif self.device_rng:
-            self.addr, self.lock = None, None
-            create = lib.l2a_lstm_controller_create_device if self.recurrent else lib.l2a_controller_create_device
-            rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount),
-                        ctypes.byref(reward), ctypes.c_ulonglong(int(device_seed) & 0xFFFFFFFFFFFFFFFF), ctypes.byref(handle))
-        else:
-            self.addr = fast_rng._global_addr()
-            if self.addr is None:
-                raise _lib.L2AError("np.random's global generator is not the legacy MT19937")
-            self.lock = fast_rng._global_lock()
-            if shard is not None:
-                rank, world, reduce = shard
-                cb = make_reduce_cb(self, lib, native, reduce)
-                create = lib.l2a_lstm_controller_create_sharded if self.recurrent else lib.l2a_controller_create_sharded
-                rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount),
-                            ctypes.byref(reward), self.addr, fast_rng.threads(), int(rank), int(world), cb, None,
-                            ctypes.byref(handle))
-            else:
-                create = lib.l2a_lstm_controller_create if self.recurrent else lib.l2a_controller_create
-                rc = create(native.handle, self.m, self.n, self.h, low.ctypes.data, high.ctypes.data, float(discount),
-                            ctypes.byref(reward), self.addr, fast_rng.threads(), ctypes.byref(handle))
-        self.ctx.check(rc, "l2a_controller_create")
-        self.handle = handle
-        self.pid = os.getpid()      # a forked child must not tear down the parent's HIP objects (it drops the handle instead)
-        self.obs = np.empty((self.m, native.obs_dim), dtype=np.float64)
-        self.act = np.empty((self.m, native.act_dim), dtype=np.float64)
-        self.idx = np.empty((self.m,), dtype=np.int64)
-        self.ret = np.empty((self.m,), dtype=np.float32)
-        self._p = (self.obs.ctypes.data, self.act.ctypes.data, self.idx.ctypes.data, self.ret.ctypes.data)
+        self.addr = None if self.device_rng else fast_rng._global_addr()
+        self.lock = None if self.device_rng else fast_rng._global_lock()
+        if not self.device_rng and self.addr is None:
+            raise _lib.L2AError("np.random's global generator is not the legacy MT19937")
+        create = "l2a_%scontroller_create%s%s" % ("lstm_" if recurrent else "", "_sharded" if shard is not None else "",
+                                                  "_device" if self.device_rng else "")
+        extra = (_seed(device_seed),) if self.device_rng else (self.addr, fast_rng.threads())
+        self._open(native, create, m, n, h, low, high, discount, reward, extra, shard)
+        self.recurrent = bool(recurrent)
         self.misses_in_row = 0
         self.cooldown = 0
-        self._stats = (ctypes.c_double * 16)()
 
     def step(self, observations, stream, state=None):
         """One controller step.  Returns True (``self.act`` / ``self.idx`` / ``self.ret`` hold the result; when no valid block of
@@ -128,7 +161,7 @@ class NativeStep(object):
         np.copyto(self.obs, observations, casting="same_kind")
         p = self._p
         if self.device_rng:
-            rc = self._call(p, state, stream)
+            rc = self._call(state, stream)
         else:
             # The generator's own lock - no other thread draws between the state compare and the adoption - held around the
             # FIRST half of the step only (take / draw, launch, producer kick: everything that touches the generator,
@@ -138,29 +171,17 @@ class NativeStep(object):
                 rc = self._begin(p, state, stream)
             if rc == _lib.L2A_OK:
                 rc = self.lib.l2a_controller_finish(self.handle, p[1], p[2], p[3])
-        if rc == _lib.L2A_OK or rc == _lib.L2A_STEP_DREW:   # (DREW: no valid block was waiting, the step drew synchronously itself)
-            self.misses_in_row = 0
-            return True
         if rc == _lib.L2A_STEP_MISS:
             return False
-        if rc == _lib.L2A_STEP_UNSPLIT:        # the C side has switched the context to the unsplit geometry (same bits)
-            self.ctx.split_degraded = True
-            self.misses_in_row = 0
-            return True
-        if getattr(self, "reduce_error", None) is not None:
-            exc, self.reduce_error = self.reduce_error, None
-            raise exc
-        self.ctx.check(rc, "l2a_controller_step")
+        if rc != _lib.L2A_OK and rc != _lib.L2A_STEP_DREW:   # (DREW: no valid block was waiting, the step drew synchronously itself)
+            self._settle(rc, "l2a_controller_step")
+        self.misses_in_row = 0
+        return True
 
     def _begin(self, p, state, stream):
         if self.recurrent:
             return self.lib.l2a_lstm_controller_begin(self.handle, p[0], state[0], state[1], state[2], state[3], stream)
         return self.lib.l2a_controller_begin(self.handle, p[0], stream)
-
-    def _call(self, p, state, stream):
-        if self.recurrent:
-            return self.lib.l2a_lstm_controller_step(self.handle, p[0], state[0], state[1], state[2], state[3], p[1], p[2], p[3], stream)
-        return self.lib.l2a_controller_step(self.handle, p[0], p[1], p[2], p[3], stream)
 
     def rearm(self):
         """After a synchronous draw: the chain restarts at the current global state.  Backs off while steps keep missing
@@ -176,23 +197,10 @@ class NativeStep(object):
             self.ctx.check(self.lib.l2a_controller_rearm(self.handle), "l2a_controller_rearm")
 
     def stats(self):
-        self.ctx.check(self.lib.l2a_controller_stats(self.handle, self._stats, 16), "l2a_controller_stats")
-        v = list(self._stats)
+        v = self._stat_slots()
         return dict(stage_us=dict(take=v[0], stage_obs=v[1], launch=v[2], kick=v[3], wait=v[4], decode=v[5], call=v[6]),
                     steps=int(v[7]), relaunches=int(v[8]), sync_draws=int(v[15]), hits=int(v[9]), misses=int(v[10]), produced=int(v[11]),
                     producer_us_per_block=v[12], consumer_wait_us_per_take=v[13], armed=bool(v[14]))
 
     def actions_ptr(self):
         return self.lib.l2a_controller_actions(self.handle)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            if getattr(self, "pid", None) == os.getpid():
-                self.lib.l2a_controller_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
