@@ -75,6 +75,59 @@ typedef struct l2a_reward {
     int reserved;
 } l2a_reward;
 
+/*
+ * Reward program: any closed-form env reward as a short list of terms, scored by a kernel of its own behind the
+ * rollout (l2a_score_trajectory, l2a_plan_rs_program) - for envs whose `reward(obs, act, next_obs)` is not the
+ * formula above.
+ *
+ *   r = bias + sum over terms, in program order, of  coef * v(term)
+ *
+ * A term reads the contiguous range [index, index + len) of one source vector x: the observation (OBS), the
+ * action (ACT), the next observation (NEXT) or DELTA = next - obs.
+ *   LINEAR  (len 1)  v = x[index]
+ *   SQSUM            v = sum_k (x[index + k] - target_k)^2
+ *   NORM             v = sqrt of the same sum
+ *   INRANGE (len 1)  v = 1 when lo <= x[index] <= hi, else 0 (a NaN gives 0, as NumPy's comparison does)
+ * `target` is an offset into `consts` (goal positions, set points: target_k = consts[target + k]) or -1 for zeros.
+ *
+ * Arithmetic (fixed, so that a host can restate it bit for bit - envs/reward_spec.py: RewardProgram.evaluate_f32):
+ * fp32, round to nearest, nothing contracted.  d = x - t; s = s + d * d as a separate multiply and add, k ascending
+ * from s = 0; r = r + coef * v as a separate multiply and add, starting from r = bias; the return R = R + disc_t * r
+ * as a separate multiply and add from R = 0, disc_t = discount ** t carried in float64 by repeated multiplication
+ * and rounded to fp32 once per step (as l2a_plan_rs does).
+ *
+ * Plain C, passed by value, no pointers inside: sizeof(l2a_reward_term) == 32, sizeof(l2a_reward_program) ==
+ * 16 + 16 * 32 + 64 * 4 == 784.
+ */
+#define L2A_PROGRAM_MAX_TERMS 16
+#define L2A_PROGRAM_MAX_CONSTS 64
+#define L2A_SRC_OBS 0
+#define L2A_SRC_ACT 1
+#define L2A_SRC_NEXT 2
+#define L2A_SRC_DELTA 3
+#define L2A_TERM_LINEAR 0
+#define L2A_TERM_SQSUM 1
+#define L2A_TERM_NORM 2
+#define L2A_TERM_INRANGE 3
+typedef struct l2a_reward_term {
+    int kind;
+    int source;
+    int index;
+    int len;
+    int target;
+    float coef;
+    float lo;
+    float hi;
+} l2a_reward_term;
+typedef struct l2a_reward_program {
+    int n_terms;
+    int n_consts;
+    float bias;
+    int reserved;
+    l2a_reward_term terms[L2A_PROGRAM_MAX_TERMS];
+    float consts[L2A_PROGRAM_MAX_CONSTS];
+} l2a_reward_program;
+
 /* ---- context -------------------------------------------------------------------------- */
 /* Create a context on HIP device `device`.  Lazy by design: the reference forks its env
  * workers (samplers/sampler.py:37) before it creates the TF session
@@ -225,6 +278,36 @@ int l2a_plan_rs_chunk(l2a_model* model, const float* state, int state_per_row, c
                       int h_chunk, int t0, double discount, const l2a_reward* reward, int cand_offset,
                       const float* returns_in, float* returns_out, float* state_out, unsigned long long* best_key,
                       void* stream);
+
+/* ---- plans with a reward program ------------------------------------------------------------
+ * l2a_reward_program_check: host only, needs no GPU.  L2A_EINVAL - with a message through l2a_last_error(NULL) - for an
+ * unknown kind or source, a range outside its vector (OBS / NEXT / DELTA: obs_dim, ACT: act_dim), len != 1 on LINEAR /
+ * INRANGE, a target range outside the constant table, counts above the capacities.  Both entries below call it first.
+ *
+ * l2a_score_trajectory: the scoring kernel alone (csrc/l2a_score.hip) - every candidate's discounted return and the
+ * per-env arg-max of trajectories that are already in HBM.
+ *   obs0     device fp32 [m, obs_dim]            observation of each env in front of step 0
+ *   traj     device fp32 [h, m*n, obs_dim]       traj[t] = the state after horizon step t; row r belongs to env r / n
+ *   actions  device fp32 [h, m*n, act_dim]
+ * `obs` of step 0 is obs0[env], of step t > 0 traj[t - 1][r].  returns_out [m, n] or NULL, best_key [m] or NULL (zeroed
+ * on `stream` in front of the launch; keys as l2a_plan_rs packs them: lowest index wins ties, NaN sorts highest,
+ * indices are cand_offset + r % n).  A workgroup's 64 rows of a step must fit the LDS:
+ * 256 * (2 * (obs_dim | 1) + (act_dim | 1)) bytes <= 63 KiB, e.g. obs_dim <= 117 at act_dim 16.
+ *
+ * l2a_plan_rs_program: the plan step for an env with a reward program - `h` one-step launches of the rollout kernels
+ * with the state carried from launch to launch (l2a_plan_rs_chunk's hand-off: traj[t] is launch t's state_out and launch
+ * t + 1's state), then ONE scoring launch; all on `stream`, no host synchronisation inside.  The price of generality is
+ * h launches per plan instead of one and a trajectory that passes through HBM; the rollout kernels themselves are
+ * untouched.  traj_out: device fp32 [h, m*n, obs_dim], or NULL: the library keeps a buffer of its own (grown on demand,
+ * which synchronises `stream`; freed with the model).  The launch status word keeps its meaning: a flagged tile-split
+ * launch anywhere in the chain flags the call (l2a_launch_status) and the caller repeats it unsplit.                */
+int l2a_reward_program_check(const l2a_reward_program* program, int obs_dim, int act_dim);
+int l2a_score_trajectory(l2a_ctx* ctx, const float* obs0, const float* traj, const float* actions, int m, int n, int h,
+                         int obs_dim, int act_dim, double discount, const l2a_reward_program* program, int cand_offset,
+                         float* returns_out, unsigned long long* best_key, void* stream);
+int l2a_plan_rs_program(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                        const l2a_reward_program* program, int cand_offset, float* returns_out,
+                        unsigned long long* best_key, float* traj_out, void* stream);
 
 /* One-step batched prediction: MLPDynamicsModel.predict / MetaMLPDynamicsModel.predict
  * (mlp_dynamics.py:204-222, meta_mlp_dynamics.py:276-294).

@@ -9,7 +9,7 @@ import ctypes
 import json
 import os
 
-from .envs.reward_spec import RewardSpec
+from .envs.reward_spec import RewardProgram, RewardSpec
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # L2A_LIB_PATH: developer override for kernel A/B runs (tools/build_variant.py); the product loads the in-tree build
@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = (
     "l2a_launch_status", "l2a_set_debug_buffer", "l2a_set_spin_limit", "l2a_inject_status",
     "l2a_model_create", "l2a_model_destroy", "l2a_model_set_weights", "l2a_model_set_weights_strided",
     "l2a_model_set_norm", "l2a_model_adapt_sgd", "l2a_model_adapt_sgd_host", "l2a_model_adapt_sgd_raw", "l2a_model_get_weights",
-    "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
+    "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_reward_program_check", "l2a_score_trajectory", "l2a_plan_rs_program", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
     "l2a_packed_layer_floats", "l2a_pack_layer_host", "l2a_micro_layout_floats", "l2a_micro_pack_layer_host",
     "l2a_comm_unique_id", "l2a_comm_init", "l2a_comm_destroy", "l2a_allreduce_best", "l2a_plan_payload",
     "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick", "l2a_cem_refit_sample", "l2a_cem_refit_sample_fused",
@@ -163,6 +163,12 @@ def load():
     lib.l2a_plan_rs_sync.restype = i32
     lib.l2a_plan_rs_chunk.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, c.c_double, c.POINTER(RewardSpec), i32, vp, vp, vp, vp, vp]
     lib.l2a_plan_rs_chunk.restype = i32
+    lib.l2a_reward_program_check.argtypes = [c.POINTER(RewardProgram), i32, i32]
+    lib.l2a_reward_program_check.restype = i32
+    lib.l2a_score_trajectory.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), i32, vp, vp, vp]
+    lib.l2a_score_trajectory.restype = i32
+    lib.l2a_plan_rs_program.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), i32, vp, vp, vp, vp]
+    lib.l2a_plan_rs_program.restype = i32
     lib.l2a_predict.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.l2a_predict.restype = i32
     lib.l2a_key_encode.argtypes = [f32, i32]
@@ -428,6 +434,28 @@ class Context(object):
         rc = self.lib.l2a_plan_payload(self.handle, ctypes.c_void_p(best_key.data_ptr()), int(m), ctypes.c_ulonglong(int(digest)),
                                        ctypes.c_void_p(payload.data_ptr()), stream_ptr)
         self.check(rc, "l2a_plan_payload")
+
+    def score_trajectory(self, obs0, traj, actions, m, n, h, discount, program, cand_offset=0, returns_out=None,
+                         best_key=None, stream_ptr=None):
+        """Score trajectories that are already on the device with a reward program (``l2a_score_trajectory``): ``obs0``
+        ``[m, obs_dim]``, ``traj`` ``[h, m * n, obs_dim]``, ``actions`` ``[h, m * n, act_dim]`` fp32 CUDA tensors."""
+        import torch
+        assert isinstance(program, RewardProgram)
+        for t in (obs0, traj, actions):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        obs_dim, act_dim = int(obs0.shape[-1]), int(actions.shape[-1])
+        assert obs0.numel() == m * obs_dim and traj.numel() == h * m * n * obs_dim and actions.numel() == h * m * n * act_dim
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if stream_ptr is None:
+            stream_ptr = ctypes.c_void_p(torch.cuda.current_stream(obs0.device).cuda_stream)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)    # noqa: E731
+        rc = self.lib.l2a_score_trajectory(self.handle, ptr(obs0), ptr(traj), ptr(actions), int(m), int(n), int(h), obs_dim,
+                                           act_dim, float(discount), ctypes.byref(program), int(cand_offset), ptr(returns_out),
+                                           ptr(best_key), stream_ptr)
+        self.check(rc, "l2a_score_trajectory")
 
     def set_spin_limit(self, polls):
         """Developer / test knob: polls a split workgroup waits for its partner per launch (0 = default)."""

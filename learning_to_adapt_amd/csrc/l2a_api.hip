@@ -59,6 +59,8 @@ struct l2a_model {
     unsigned int launch_nonce = 0;
     float* adapt_scratch = nullptr;               // l2a_model_adapt_sgd: layer inputs and dZ of every task
     long long adapt_scratch_floats = 0;
+    float* prog_buf = nullptr;                    // l2a_plan_rs_program: [returns of the carry launches (rows) | trajectory (h x rows x obs_dim)]
+    long long prog_buf_floats = 0;
     // l2a_model_adapt_sgd_host: two staging slots (host-mapped, read by the kernels directly)
     struct adapt_slot {
         float* stage_host = nullptr;
@@ -783,6 +785,7 @@ void l2a_model_destroy(l2a_model* md) {
     }
     if (md->xbuf) (void)hipFree(md->xbuf);
     if (md->adapt_scratch) (void)hipFree(md->adapt_scratch);
+    if (md->prog_buf) (void)hipFree(md->prog_buf);
     for (auto& sl : md->aslot) {
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.stage_host) (void)hipHostFree(sl.stage_host);
@@ -1345,6 +1348,44 @@ int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, cons
     p.disc0 = d0;
     p.m = m; p.n = n; p.h = h_chunk; p.cand_offset = cand_offset; p.discount = discount; p.rw = *reward;
     return launch_rollout(md, p, stream_v);
+}
+
+// The plan step of an env with a reward program: h one-step carry launches of the rollout kernels - all-zero fused
+// reward, state_out = traj[t], the trajectory slice itself being the hand-off buffer - and one scoring launch
+// (l2a_score.hip).  Stream-ordered throughout.
+int l2a_plan_rs_program(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                        const l2a_reward_program* program, int cand_offset, float* returns_out,
+                        unsigned long long* best_key, float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    int rc = l2a_reward_program_check(program, md->obs_dim, md->act_dim);
+    if (rc != L2A_OK) return fail(ctx, rc, l2a_last_error(nullptr));
+    if (!obs0 || !actions) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: null obs0/actions");
+    if (!best_key && !returns_out) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: nothing to write (best_key and returns_out are null)");
+    if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: m, n and h must be >= 1");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: too many candidates");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    const long long rows = (long long)m * n;
+    const long long need = rows + (traj_out ? 0 : (long long)h * rows * md->obs_dim);
+    if (need > md->prog_buf_floats) {
+        l2a_device_guard guard(ctx->device);
+        if (md->prog_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->prog_buf)); md->prog_buf = nullptr; md->prog_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->prog_buf), (size_t)need * sizeof(float)));
+        md->prog_buf_floats = need;
+    }
+    float* carry_returns = md->prog_buf;            // the chunk launches' required returns_out: all zero rewards, never read
+    float* traj = traj_out ? traj_out : md->prog_buf + rows;
+    l2a_reward zero;
+    std::memset(&zero, 0, sizeof(zero));
+    const long long step_state = rows * md->obs_dim, step_act = rows * md->act_dim;
+    for (int t = 0; t < h; ++t) {
+        rc = l2a_plan_rs_chunk(md, t == 0 ? obs0 : traj + (t - 1) * step_state, t > 0, actions + t * step_act, m, n, 1, 0,
+                               discount, &zero, cand_offset, nullptr, carry_returns, traj + t * step_state, nullptr, stream_v);
+        if (rc != L2A_OK) return rc;
+    }
+    return l2a_score_trajectory(ctx, obs0, traj, actions, m, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset,
+                                returns_out, best_key, stream_v);
 }
 
 int l2a_predict(l2a_model* md, const float* obs, const float* act, int rows, int n_blocks,

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..envs.reward_spec import RewardSpec
+from ..envs.reward_spec import RewardProgram, RewardSpec
 
 
 def _stream_ptr(device=None):
@@ -52,6 +52,7 @@ class NativeModel(object):
         self.ctx.check(rc, "l2a_model_create")
         self.handle = handle
         self._keep = {}     # source tensors kept alive until the stream has consumed them
+        self.program_plans = 0      # calls of plan_rs_program (diagnostics: which plan path a controller took)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -217,6 +218,28 @@ class NativeModel(object):
                                   float(discount), ctypes.byref(reward), int(cand_offset),
                                   _ptr(returns_out), _ptr(best_key), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_plan_rs")
+
+    def plan_rs_program(self, obs0, actions, m, n, h, discount, program, cand_offset=0, returns_out=None, best_key=None,
+                        traj_out=None):
+        """Plan step of an env with a ``RewardProgram`` (``l2a_plan_rs_program``): ``h`` one-step rollout launches that hand
+        the state on through the trajectory buffer, then the scoring kernel.  Arguments as ``plan_rs``; ``traj_out``:
+        optional fp32 CUDA ``[h, m * n, obs_dim]`` that receives every candidate's states."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if traj_out is not None:
+            assert traj_out.is_cuda and traj_out.dtype == torch.float32 and traj_out.is_contiguous()
+            assert traj_out.numel() == h * m * n * self.obs_dim
+        assert isinstance(program, RewardProgram)
+        self.program_plans += 1
+        rc = self.lib.l2a_plan_rs_program(self.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h), float(discount),
+                                          ctypes.byref(program), int(cand_offset), _ptr(returns_out), _ptr(best_key),
+                                          _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_plan_rs_program")
 
     def plan_rs_sync(self, obs_host, actions, m, n, h, discount, reward, cand_offset=0, returns_out=None):
         """Blocking plan step (``l2a_plan_rs_sync``): ``obs_host`` is a HOST array ``[m, obs_dim]``; returns the

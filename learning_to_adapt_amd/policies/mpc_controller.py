@@ -42,7 +42,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..envs.reward_spec import reward_spec_for_env
+from ..envs.reward_spec import RewardProgram, reward_spec_for_env
 from ..utils import fast_rng
 from ..utils.serializable import Serializable
 from .draw_ahead import DrawAhead
@@ -246,6 +246,12 @@ class MPCController(Policy, Serializable):
     def _fusable(self):
         return (self._reward_spec is not None) and hasattr(self.dynamics_model, "planner_model")
 
+    def _program(self):
+        """The env's reward is a ``RewardProgram``: the plan runs through ``l2a_plan_rs_program`` (``_rollout``), and every
+        path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking launch, the horizon-chunked
+        pipelines, the C controllers - declines."""
+        return isinstance(self._reward_spec, RewardProgram)
+
     def _buf(self, key, shape, dtype, device):
         t = self._bufs.get(key)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device:
@@ -365,8 +371,9 @@ class MPCController(Policy, Serializable):
         obs0 = obs_dev if obs_dev is not None else self._upload_obs(observations)
         best = self._buf("best", (m,), torch.int64, dev)
         rets = self._buf("rets", (m, n_local), torch.float32, dev) if want_returns else None
-        native.plan_rs(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
-                       cand_offset=cand_offset, returns_out=rets, best_key=best)
+        plan = native.plan_rs_program if self._program() else native.plan_rs
+        plan(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
+             cand_offset=cand_offset, returns_out=rets, best_key=best)
         return best, rets
 
     def _plan_keys(self, observations, a_dev, n_local, lo, world):
@@ -377,7 +384,7 @@ class MPCController(Policy, Serializable):
         model, CPU test harness)."""
         m = len(observations)
         stock = getattr(self._rollout, "__func__", None) is MPCController._rollout      # not overridden / replaced
-        native = self.dynamics_model.planner_model() if (stock and world == 1 and n_local > 0) else None
+        native = self.dynamics_model.planner_model() if (stock and world == 1 and n_local > 0 and not self._program()) else None
         if native is not None and getattr(native, "sync_max_envs", 0) >= m:
             self._check_blocks(m)
             for _ in range(2):
@@ -535,7 +542,7 @@ class MPCController(Policy, Serializable):
         from ``np.random`` since the last step) draws them itself inside the C call - the reference's draw from the global
         generator - and re-arms the chain behind it."""
         self._cstep_missed = False
-        if self.use_cem or not self._native_step_stock():
+        if self.use_cem or self._program() or not self._native_step_stock():
             if self._cstep is not None:     # built earlier, bypassed now (a harness replaced the launch path): no idle C chain
                 self._cstep.close()
                 self._cstep = None
@@ -734,7 +741,7 @@ class MPCController(Policy, Serializable):
 
     # ------------------------------------------------------------------ parity mode, pipelined over the horizon
     def _can_pipeline(self, h, n_local):
-        return (self.pipeline_chunks > 1 and h >= 6 and n_local > 0
+        return (self.pipeline_chunks > 1 and h >= 6 and n_local > 0 and not self._program()
                 and hasattr(self.dynamics_model.planner_model(), "plan_rs_chunk"))
 
     def _plan_pipelined(self, observations, n, m, h, lo, hi, world, redraw=True):
@@ -932,7 +939,7 @@ class MPCController(Policy, Serializable):
     def _can_pipeline_cem(self, m, world, n):
         """Single env, single rank: the host prepares horizon chunk k + 1 (``a = mean + z * std``, clip, cast,
         transpose of its steps) while the GPU rolls out chunk k."""
-        return (m == 1 and world == 1 and self._cem_chunks(self.horizon) > 1
+        return (m == 1 and world == 1 and self._cem_chunks(self.horizon) > 1 and not self._program()
                 and hasattr(self.dynamics_model.planner_model(), "plan_rs_chunk"))
 
     def _cem_rollout_pipelined(self, observations, z, a, a_st, mean2, std2, reference, relaunch=False):
@@ -1105,7 +1112,7 @@ class MPCController(Policy, Serializable):
         Returns the actions, or None when the C controller does not apply (parity mode, a library without the recurrent entry
         points, a test hook replaced the normals or the launch path, a backend that cannot reduce the words, a forked child)."""
         self._native_step_done(None)        # (recurrent: no advanced state is pending whenever this call falls back)
-        if self.rng != "device" or not self._native_step_stock():
+        if self.rng != "device" or self._program() or not self._native_step_stock():
             return None
         if getattr(self._cem_normal_device, "__func__", None) is not MPCController._cem_normal_device:
             return None
@@ -1163,7 +1170,7 @@ class MPCController(Policy, Serializable):
 
     def get_cem_action(self, observations):
         if not self._fusable():
-            raise _lib.L2AError("CEM planning needs a fusable closed-form reward (env.reward_spec)")
+            raise _lib.L2AError("CEM planning needs a fusable closed-form reward (env.reward_spec: a RewardSpec or a RewardProgram)")
         if self.native_cem_step:
             out = self._native_cem_step(observations)
             if out is not None:
