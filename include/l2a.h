@@ -24,6 +24,7 @@ extern "C" {
 typedef struct l2a_ctx l2a_ctx;
 typedef struct l2a_model l2a_model;
 typedef struct l2a_lstm l2a_lstm;
+typedef struct l2a_reward_model l2a_reward_model;
 typedef struct l2a_controller l2a_controller;
 
 /* ---- error codes --------------------------------------------------------------------- */
@@ -308,6 +309,47 @@ int l2a_score_trajectory(l2a_ctx* ctx, const float* obs0, const float* traj, con
 int l2a_plan_rs_program(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, double discount,
                         const l2a_reward_program* program, int cand_offset, float* returns_out,
                         unsigned long long* best_key, float* traj_out, void* stream);
+
+/* ---- plans with a learned reward model --------------------------------------------------------
+ * For envs with no closed-form reward at all (`use_reward_model=True`, reference policies/mpc_controller.py:121-123): the
+ * reward of a transition is an MLP of (obs, act, next_obs), evaluated on the matrix cores (csrc/l2a_score_mlp.hip).  Per
+ * row, all in fp32:
+ *   x = [ (obs - mean_obs) * inv_obs | (act - mean_act) * inv_act | ((next_obs - obs) - mean_delta) * inv_delta ],
+ *       inv = fp32(1 / (std + 1e-10)); obs_dim + act_dim + obs_dim features
+ *   z = MLP(x): n_hidden = 1 .. 3 hidden layers with `hidden_act` (L2A_ACT_*), a linear scalar output layer
+ *   r = z * fp32(std_r + 1e-10) + fp32(mean_r); r = NaN when any of the row's obs / act / next_obs values is not finite
+ * and over a trajectory R = R + fp32(disc) * r with disc = discount ** t carried in float64, as l2a_score_trajectory.
+ * A row's reward bits depend on that row's inputs only - not on m, n, cand_offset, the shard or the launch geometry.
+ *
+ * l2a_reward_model_check: host only, needs no GPU.  L2A_EINVAL - with a message through l2a_last_error(NULL) - unless
+ * 1 <= obs_dim <= 64, 1 <= act_dim <= 16, 1 <= n_hidden <= 3, every hidden width a multiple of 64 up to 512 and
+ * hidden_act one of L2A_ACT_*.  l2a_reward_model_create calls it first; a new model has identity statistics.
+ * l2a_reward_model_set_weights: fp32 DEVICE arrays { hidden_0/kernel [2 obs_dim + act_dim, h0], hidden_0/bias [h0], ...,
+ * output/kernel [hL, 1], output/bias [1] }, kernels row-major [in, out] as l2a_model_set_weights; re-packed on `stream`.
+ * l2a_reward_model_set_norm: float64 HOST vectors (mean_r / std_r: one value each); all eight NULL = identity.
+ * l2a_reward_model_predict: obs [rows, obs_dim], act [rows, act_dim], next_obs [rows, obs_dim] -> rewards_out [rows]
+ * (device fp32) - the same kernel as a one-step trajectory with per-row observations.
+ * l2a_score_trajectory_model: arguments and outputs as l2a_score_trajectory (keys, ties, NaN, best_key zeroed on `stream`).
+ * l2a_plan_rs_reward_model: the carry chain of l2a_plan_rs_program - h one-step launches of the rollout kernels through
+ * traj_out (or the model's own buffer) - followed by l2a_score_trajectory_model.  `rm` and `model` must live on the same
+ * context and agree on obs_dim and act_dim (L2A_EINVAL).  A flagged tile-split launch anywhere in the chain flags the
+ * call (l2a_launch_status), as for l2a_plan_rs_program.                                                              */
+int l2a_reward_model_check(int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act);
+int l2a_reward_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act,
+                            l2a_reward_model** out);
+void l2a_reward_model_destroy(l2a_reward_model* rm);
+int l2a_reward_model_set_weights(l2a_reward_model* rm, const void* const* device_ptrs, void* stream);
+int l2a_reward_model_set_norm(l2a_reward_model* rm, const double* mean_obs, const double* std_obs, const double* mean_act,
+                              const double* std_act, const double* mean_delta, const double* std_delta, const double* mean_r,
+                              const double* std_r, void* stream);
+int l2a_reward_model_predict(l2a_reward_model* rm, const float* obs, const float* act, const float* next_obs, int rows,
+                             float* rewards_out, void* stream);
+int l2a_score_trajectory_model(l2a_reward_model* rm, const float* obs0, const float* traj, const float* actions, int m, int n,
+                               int h, double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
+                               void* stream);
+int l2a_plan_rs_reward_model(l2a_model* model, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
+                             int h, double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
+                             float* traj_out, void* stream);
 
 /* One-step batched prediction: MLPDynamicsModel.predict / MetaMLPDynamicsModel.predict
  * (mlp_dynamics.py:204-222, meta_mlp_dynamics.py:276-294).

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("L2A_LIB_PATH") or os.path.join(_HERE, "libl2a_hip.so"
 
 # include/l2a.h
 L2A_OK = 0
+L2A_EINVAL = -1
 L2A_ESTATE = -4
 L2A_ESPLIT = -5
 L2A_STEP_MISS = 1
@@ -32,7 +33,9 @@ EXPORTED_SYMBOLS = (
     "l2a_launch_status", "l2a_set_debug_buffer", "l2a_set_spin_limit", "l2a_inject_status",
     "l2a_model_create", "l2a_model_destroy", "l2a_model_set_weights", "l2a_model_set_weights_strided",
     "l2a_model_set_norm", "l2a_model_adapt_sgd", "l2a_model_adapt_sgd_host", "l2a_model_adapt_sgd_raw", "l2a_model_get_weights",
-    "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_reward_program_check", "l2a_score_trajectory", "l2a_plan_rs_program", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
+    "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_reward_program_check", "l2a_score_trajectory", "l2a_plan_rs_program",
+    "l2a_reward_model_check", "l2a_reward_model_create", "l2a_reward_model_destroy", "l2a_reward_model_set_weights", "l2a_reward_model_set_norm",
+    "l2a_reward_model_predict", "l2a_score_trajectory_model", "l2a_plan_rs_reward_model", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
     "l2a_packed_layer_floats", "l2a_pack_layer_host", "l2a_micro_layout_floats", "l2a_micro_pack_layer_host",
     "l2a_comm_unique_id", "l2a_comm_init", "l2a_comm_destroy", "l2a_allreduce_best", "l2a_plan_payload",
     "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick", "l2a_cem_refit_sample", "l2a_cem_refit_sample_fused",
@@ -69,6 +72,16 @@ def plan_geometry(obs_dim, act_dim, hidden, n_sets, mode, m, n, h, split=-1, fan
     return dict(kernel=("valu", "mfma16", "micro")[v[0]], nt=v[1], split=v[2], split_from=v[3], fan=bool(v[4]), workgroups=v[5],
                 lds_bytes=v[6], sets_per_batch=v[7], micro_tiles=v[8], placement_units=v[9], front_workgroups=v[10],
                 whole_instance=bool(v[11]))
+
+
+def reward_model_check(obs_dim, act_dim, hidden, hidden_act):
+    """``l2a_reward_model_check`` (host only, no GPU): ``None`` when the matrix-core reward scorer takes this network, else the
+    library's reason.  ``hidden_act``: a nonlinearity name (``ACT_CODES``) or an integer code."""
+    lib = load()
+    hid = (ctypes.c_int * max(len(hidden), 1))(*[int(x) for x in hidden])
+    code = hidden_act if isinstance(hidden_act, int) else ACT_CODES.get(hidden_act, -1)
+    rc = lib.l2a_reward_model_check(int(obs_dim), int(act_dim), len(hidden), hid, int(code))
+    return None if rc == L2A_OK else lib.l2a_last_error(None).decode()
 
 
 _lib = None
@@ -169,6 +182,23 @@ def load():
     lib.l2a_score_trajectory.restype = i32
     lib.l2a_plan_rs_program.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), i32, vp, vp, vp, vp]
     lib.l2a_plan_rs_program.restype = i32
+    if hasattr(lib, "l2a_reward_model_create"):         # (absent from older variant libraries selected with L2A_LIB_PATH)
+        lib.l2a_reward_model_check.argtypes = [i32, i32, i32, c.POINTER(i32), i32]
+        lib.l2a_reward_model_check.restype = i32
+        lib.l2a_reward_model_create.argtypes = [vp, i32, i32, i32, c.POINTER(i32), i32, c.POINTER(vp)]
+        lib.l2a_reward_model_create.restype = i32
+        lib.l2a_reward_model_destroy.argtypes = [vp]
+        lib.l2a_reward_model_destroy.restype = None
+        lib.l2a_reward_model_set_weights.argtypes = [vp, c.POINTER(vp), vp]
+        lib.l2a_reward_model_set_weights.restype = i32
+        lib.l2a_reward_model_set_norm.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
+        lib.l2a_reward_model_set_norm.restype = i32
+        lib.l2a_reward_model_predict.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+        lib.l2a_reward_model_predict.restype = i32
+        lib.l2a_score_trajectory_model.argtypes = [vp, vp, vp, vp, i32, i32, i32, c.c_double, i32, vp, vp, vp]
+        lib.l2a_score_trajectory_model.restype = i32
+        lib.l2a_plan_rs_reward_model.argtypes = [vp, vp, vp, vp, i32, i32, i32, c.c_double, i32, vp, vp, vp, vp]
+        lib.l2a_plan_rs_reward_model.restype = i32
     lib.l2a_predict.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.l2a_predict.restype = i32
     lib.l2a_key_encode.argtypes = [f32, i32]

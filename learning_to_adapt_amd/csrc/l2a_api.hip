@@ -1350,9 +1350,35 @@ int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, cons
     return launch_rollout(md, p, stream_v);
 }
 
-// The plan step of an env with a reward program: h one-step carry launches of the rollout kernels - all-zero fused
-// reward, state_out = traj[t], the trajectory slice itself being the hand-off buffer - and one scoring launch
-// (l2a_score.hip).  Stream-ordered throughout.
+// The carry chain of the plans that are scored by a separate launch: h one-step launches of the rollout kernels - all-zero
+// fused reward, state_out = traj[t], the trajectory slice itself being the hand-off buffer.  *traj: traj_out, or the model's
+// own buffer (grown on demand, which synchronises the stream).  Stream-ordered throughout.
+static int plan_carry_chain(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                            int cand_offset, float* traj_out, void* stream_v, float** traj) {
+    l2a_ctx* ctx = md->ctx;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    const long long rows = (long long)m * n;
+    const long long need = rows + (traj_out ? 0 : (long long)h * rows * md->obs_dim);
+    if (need > md->prog_buf_floats) {
+        l2a_device_guard guard(ctx->device);
+        if (md->prog_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->prog_buf)); md->prog_buf = nullptr; md->prog_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->prog_buf), (size_t)need * sizeof(float)));
+        md->prog_buf_floats = need;
+    }
+    float* carry_returns = md->prog_buf;            // the chunk launches' required returns_out: all zero rewards, never read
+    *traj = traj_out ? traj_out : md->prog_buf + rows;
+    l2a_reward zero;
+    std::memset(&zero, 0, sizeof(zero));
+    const long long step_state = rows * md->obs_dim, step_act = rows * md->act_dim;
+    for (int t = 0; t < h; ++t) {
+        const int rc = l2a_plan_rs_chunk(md, t == 0 ? obs0 : *traj + (t - 1) * step_state, t > 0, actions + t * step_act, m, n, 1, 0,
+                                         discount, &zero, cand_offset, nullptr, carry_returns, *traj + t * step_state, nullptr, stream_v);
+        if (rc != L2A_OK) return rc;
+    }
+    return L2A_OK;
+}
+
+// The plan step of an env with a reward program: the carry chain and one scoring launch (l2a_score.hip).
 int l2a_plan_rs_program(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
                         const l2a_reward_program* program, int cand_offset, float* returns_out,
                         unsigned long long* best_key, float* traj_out, void* stream_v) {
@@ -1365,27 +1391,36 @@ int l2a_plan_rs_program(l2a_model* md, const float* obs0, const float* actions, 
     if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: m, n and h must be >= 1");
     if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: too many candidates");
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    const long long rows = (long long)m * n;
-    const long long need = rows + (traj_out ? 0 : (long long)h * rows * md->obs_dim);
-    if (need > md->prog_buf_floats) {
-        l2a_device_guard guard(ctx->device);
-        if (md->prog_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->prog_buf)); md->prog_buf = nullptr; md->prog_buf_floats = 0; }
-        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->prog_buf), (size_t)need * sizeof(float)));
-        md->prog_buf_floats = need;
-    }
-    float* carry_returns = md->prog_buf;            // the chunk launches' required returns_out: all zero rewards, never read
-    float* traj = traj_out ? traj_out : md->prog_buf + rows;
-    l2a_reward zero;
-    std::memset(&zero, 0, sizeof(zero));
-    const long long step_state = rows * md->obs_dim, step_act = rows * md->act_dim;
-    for (int t = 0; t < h; ++t) {
-        rc = l2a_plan_rs_chunk(md, t == 0 ? obs0 : traj + (t - 1) * step_state, t > 0, actions + t * step_act, m, n, 1, 0,
-                               discount, &zero, cand_offset, nullptr, carry_returns, traj + t * step_state, nullptr, stream_v);
-        if (rc != L2A_OK) return rc;
-    }
+    float* traj = nullptr;
+    rc = plan_carry_chain(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
     return l2a_score_trajectory(ctx, obs0, traj, actions, m, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset,
                                 returns_out, best_key, stream_v);
+}
+
+// The plan step with a learned reward model: the carry chain and the matrix-core scoring launch (l2a_score_mlp.hip).
+int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n, int h,
+                             double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
+                             float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    if (!rm) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: null reward model");
+    l2a_ctx* rm_ctx = nullptr;
+    int rm_obs = 0, rm_act = 0;
+    l2a_reward_model_facts(rm, &rm_ctx, &rm_obs, &rm_act);
+    if (rm_ctx != ctx) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: the reward model lives on another context");
+    if (rm_obs != md->obs_dim || rm_act != md->act_dim)
+        return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: the reward model is for obs_dim " + std::to_string(rm_obs) + " / act_dim " +
+                    std::to_string(rm_act) + ", the dynamics model for " + std::to_string(md->obs_dim) + " / " + std::to_string(md->act_dim));
+    if (!obs0 || !actions) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: null obs0/actions");
+    if (!best_key && !returns_out) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: nothing to write (best_key and returns_out are null)");
+    if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: m, n and h must be >= 1");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: too many candidates");
+    float* traj = nullptr;
+    const int rc = plan_carry_chain(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
+    return l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, returns_out, best_key, stream_v);
 }
 
 int l2a_predict(l2a_model* md, const float* obs, const float* act, int rows, int n_blocks,

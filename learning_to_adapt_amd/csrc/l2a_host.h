@@ -133,6 +133,7 @@ extern "C" L2A_HIDDEN int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, 
                                                 const float* c0, const float* h0, float* c_next, float* h_next, int m, void* stream);
 extern "C" L2A_HIDDEN void l2a_model_facts(const l2a_model* md, l2a_ctx** ctx, int* obs_dim, int* act_dim);
 extern "C" L2A_HIDDEN void l2a_lstm_facts(const l2a_lstm* md, l2a_ctx** ctx, int* obs_dim, int* act_dim, int* units);
+extern "C" L2A_HIDDEN void l2a_reward_model_facts(const l2a_reward_model* rm, l2a_ctx** ctx, int* obs_dim, int* act_dim);
 inline double l2a_now_us() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);

@@ -1,0 +1,501 @@
+// l2a_score_mlp.hip - learned reward models (include/l2a.h: l2a_reward_model): the host-only eligibility check, the model
+// object, and the matrix-core kernel that scores trajectories with it (l2a_score_trajectory_model,
+// l2a_plan_rs_reward_model) or evaluates it row by row (l2a_reward_model_predict).
+//
+// Semantics.  Per (step, candidate) row, all fp32:
+//   x = [ (obs - mu_obs) * inv_obs | (act - mu_act) * inv_act | ((next - obs) - mu_delta) * inv_delta ],  inv = fp32(1 / (sd + 1e-10))
+//   z = MLP(x): n_hidden = 1 .. 3 hidden layers (widths multiples of 64 up to 512, one of the five L2A_ACT_*), linear scalar output
+//   r = z * fp32(sd_r + 1e-10) + fp32(mu_r);  r = NaN when any of the row's obs / act / next values is not finite
+//   R = R + fp32(disc) * r, disc carried in float64 (disc *= discount), t = 0 .. h - 1 in order - as l2a_score_traj_k.
+// This unit is compiled with contraction off: no multiply-add outside the MFMAs is fused.
+//
+// Kernel.  D = W^T-tile x activations on v_mfma_f32_16x16x4_f32 with the fragment scheme of the rollout kernels (l2a_kernels.h:
+// the packed A fragments, the D fragment of one layer = the B fragment of the next).  A workgroup (4 waves) owns CT tiles of 16
+// candidates for the whole horizon and takes S steps of them per pass: RT = CT * S row tiles of 16 rows.  The pass's activations
+// live in ONE LDS image [row tile][k-group][lane] of f32x4, overwritten in place layer by layer: wave w computes unit tiles
+// [w * TPW, (w + 1) * TPW) of a layer (TPW = width / 64) for all RT row tiles with TPW x RT accumulators in registers, so each
+// A fragment (one 16-byte load per lane from L2, prefetched one k-group ahead) feeds 16 * RT rows and is fetched by exactly one
+// wave of the workgroup.  RT is 8 up to width 256 and 4 above (accumulators: 128 registers; LDS image: 128 KiB) - more rows per
+// fragment do not fit a CU: the image alone is rows x width x 4 bytes.
+//
+// A row's reward bits depend on the row's inputs only: every output element is ONE accumulator chain over k in the order
+// k-group 0, 1, .. and inside a group MFMA 0 .. 3, i.e. (l2a_kernels.h) features 16g + 4kk + ii for ii = 0 .. 3 (outer), kk = 0 .. 3
+// (inside the instruction) - whichever row tile, workgroup geometry (RT, CT, S), shard or cand_offset the row falls into.  K is
+// padded with zeros to a multiple of 16.  The scalar output layer is the same chain on a unit tile whose rows 1 .. 15 are zero.
+// No float atomics.
+#pragma clang fp contract(off)
+
+#include "l2a_host.h"
+#include "l2a_kernels.h"
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#define L2A_RM_THREADS 256
+#define L2A_RM_MAX_HIDDEN 3
+#define L2A_RM_MAX_ROWS 128         // 16 * RT, RT <= 8
+#define L2A_RM_MAX_ACC 32           // TPW * RT accumulators of four registers per wave
+
+struct L2ARMParams {
+    const float* wblk;              // the model's device block
+    long long pk[L2A_RM_MAX_HIDDEN + 1];    // packed kernels (floats from wblk); [n_hidden] = the output layer
+    long long bias[L2A_RM_MAX_HIDDEN + 1];  // biases
+    long long nm;                   // [mu KG0*16][inv KG0*16] in feature order
+    int tpw[L2A_RM_MAX_HIDDEN];     // hidden width / 64
+    int n_hidden, obs_dim, act_dim, d_in, KG0, kgs;     // kgs: k-groups between the row tiles of the LDS image
+    int act;
+    float sr, mur;                  // fp32(sd_r + 1e-10), fp32(mu_r)
+    const float* obs0;              // [m, obs_dim], or [rows, obs_dim] when obs_per_row
+    const float* traj;              // [h, rows, obs_dim]
+    const float* actions;           // [h, rows, act_dim]
+    float* returns_out;             // [rows] or null
+    unsigned long long* best_key;   // [m] or null
+    double discount;
+    int rows, n, h, obs_per_row, cand_offset;
+    int CT, S;                      // candidate tiles per workgroup, steps per pass; CT * S = RT
+};
+
+__global__ void l2a_rm_pack_k(const float* __restrict__ w, int k_in, int n_out, int KG, long long total, float* __restrict__ out) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    int k, u;
+    l2a_pack_decode(idx, KG, &k, &u);
+    out[idx] = (k < k_in && u < n_out) ? w[(long long)k * n_out + u] : 0.0f;
+}
+
+// One hidden layer for the pass's RT row tiles, in place: this wave's TPW unit tiles.  `live`: bit rt = row tile rt holds rows.
+// The epilogue applies max(x, floor) - relu (0) or nothing (-inf; the max propagates NaN, l2a_max_nan) - and the other
+// activations follow in a pass of their own over the image (l2a_score_mlp_k): inlined into every instance here their code
+// cost registers (spills at RT = 4) and a minute of compile time.
+template <int TPW, int RT>
+__device__ __forceinline__ void l2a_rm_layer(const f32x4* __restrict__ wp, const float* __restrict__ bias, int KGin, int kgs,
+                                             f32x4* act, float floor, unsigned live, int wave, int lane) {
+    if constexpr (TPW * RT <= L2A_RM_MAX_ACC) {
+        f32x4 acc[TPW][RT];
+#pragma unroll
+        for (int tp = 0; tp < TPW; ++tp)
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) acc[tp][rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const int c0 = wave * TPW;
+        const f32x4* wl = wp + (long long)c0 * KGin * 64 + lane;
+        f32x4 a[TPW], an[TPW];
+#pragma unroll
+        for (int tp = 0; tp < TPW; ++tp) a[tp] = wl[(long long)tp * KGin * 64];
+#pragma unroll 1
+        for (int g = 0; g < KGin; ++g) {
+            const int gn = (g + 1 < KGin) ? g + 1 : g;
+#pragma unroll
+            for (int tp = 0; tp < TPW; ++tp) an[tp] = wl[((long long)tp * KGin + gn) * 64];
+            // (row tiles without rows are computed too - branch-free MFMA stream; only their stores are skipped)
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const f32x4 b = act[(rt * kgs + g) * 64 + lane];
+#pragma unroll
+                for (int tp = 0; tp < TPW; ++tp) acc[tp][rt] = L2A_MFMA(a[tp].x, b.x, acc[tp][rt]);
+#pragma unroll
+                for (int tp = 0; tp < TPW; ++tp) acc[tp][rt] = L2A_MFMA(a[tp].y, b.y, acc[tp][rt]);
+#pragma unroll
+                for (int tp = 0; tp < TPW; ++tp) acc[tp][rt] = L2A_MFMA(a[tp].z, b.z, acc[tp][rt]);
+#pragma unroll
+                for (int tp = 0; tp < TPW; ++tp) acc[tp][rt] = L2A_MFMA(a[tp].w, b.w, acc[tp][rt]);
+            }
+#pragma unroll
+            for (int tp = 0; tp < TPW; ++tp) a[tp] = an[tp];
+        }
+        __syncthreads();        // every wave has read the layer's input: the image may be overwritten
+#pragma unroll
+        for (int tp = 0; tp < TPW; ++tp) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + 16 * (c0 + tp) + 4 * (lane >> 4));
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+                if ((live >> rt) & 1u) {
+                    f32x4 v = acc[tp][rt] + bv;
+                    v.x = l2a_max_nan(v.x, floor); v.y = l2a_max_nan(v.y, floor);
+                    v.z = l2a_max_nan(v.z, floor); v.w = l2a_max_nan(v.w, floor);
+                    act[(rt * kgs + c0 + tp) * 64 + lane] = v;
+                }
+        }
+        __syncthreads();
+    }
+}
+
+template <int RT>
+__device__ __forceinline__ void l2a_rm_layer_any(int tpw, const f32x4* wp, const float* bias, int KGin, int kgs, f32x4* act,
+                                                 float floor, unsigned live, int wave, int lane) {
+    switch (tpw) {
+        case 1: l2a_rm_layer<1, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        case 2: l2a_rm_layer<2, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        case 3: l2a_rm_layer<3, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        case 4: l2a_rm_layer<4, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        case 5: l2a_rm_layer<5, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        case 6: l2a_rm_layer<6, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        case 7: l2a_rm_layer<7, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+        default: l2a_rm_layer<8, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
+    }
+}
+
+// One workgroup = 16 * CT consecutive candidates (rows r of [0, m * n)) over the whole horizon, S steps per pass.
+// Row tile rt = ct * S + s of a pass holds candidates r0 + 16 ct + 0 .. 15 at step t0 + s.
+template <int RT>
+__global__ __launch_bounds__(L2A_RM_THREADS) void l2a_score_mlp_k(const L2ARMParams p) {
+    extern __shared__ f32x4 act[];                      // [RT][kgs][64]
+    __shared__ float sz[L2A_RM_MAX_ROWS];               // the pass's network outputs
+    __shared__ int sbad[L2A_RM_MAX_ROWS];               // row holds a non-finite input
+    __shared__ unsigned long long skey[L2A_RM_MAX_ROWS];
+    __shared__ int senv[L2A_RM_MAX_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int CT = p.CT, S = p.S;
+    const int r0 = (int)blockIdx.x * 16 * CT;
+    const int nr = min(16 * CT, p.rows - r0);           // candidates of this workgroup
+    const float* __restrict__ mu = p.wblk + p.nm;
+    const float* __restrict__ inv = mu + 16 * p.KG0;
+    const int kpad = 16 * p.KG0;
+    float* actf = reinterpret_cast<float*>(act);
+
+    if (tid < L2A_RM_MAX_ROWS) sbad[tid] = 0;
+    __syncthreads();
+    float R = 0.0f;
+    double disc = 1.0;
+    for (int t0 = 0; t0 < p.h; t0 += S) {
+        unsigned live = 0;
+        for (int rt = 0; rt < RT; ++rt)
+            if (16 * (rt / S) < nr && t0 + rt % S < p.h) live |= 1u << rt;
+        // ---- features of the pass into the image (zero rows and zero padding where there is nothing) ----
+        for (int e = tid; e < 16 * RT * kpad; e += L2A_RM_THREADS) {
+            const int i = e / kpad, k = e - i * kpad;
+            const int rt = i >> 4, j = i & 15;
+            const int ci = 16 * (rt / S) + j, t = t0 + rt % S;
+            float x = 0.0f;
+            if (ci < nr && t < p.h && k < p.d_in) {
+                const size_t r = (size_t)(r0 + ci);
+                const float* o = p.obs_per_row ? p.obs0 + r * p.obs_dim
+                                 : (t == 0)    ? p.obs0 + (r / (size_t)p.n) * p.obs_dim
+                                               : p.traj + ((size_t)(t - 1) * p.rows + r) * p.obs_dim;
+                const size_t q = (size_t)t * p.rows + r;
+                float v;
+                bool fin;
+                if (k < p.obs_dim) {
+                    v = o[k];
+                    fin = isfinite(v);
+                } else if (k < p.obs_dim + p.act_dim) {
+                    v = p.actions[q * p.act_dim + (k - p.obs_dim)];
+                    fin = isfinite(v);
+                } else {
+                    const int d = k - p.obs_dim - p.act_dim;
+                    const float nx = p.traj[q * p.obs_dim + d];
+                    v = nx - o[d];
+                    fin = isfinite(nx);
+                }
+                if (!fin) sbad[i] = 1;
+                x = (v - mu[k]) * inv[k];
+            }
+            actf[(((rt * p.kgs + (k >> 4)) * 64) + ((k >> 2) & 3) * 16 + j) * 4 + (k & 3)] = x;
+        }
+        __syncthreads();
+        // ---- hidden layers, in place ----
+        int KGin = p.KG0;
+        const float floor = (p.act == L2A_ACT_RELU) ? 0.0f : -__builtin_inff();
+        for (int l = 0; l < p.n_hidden; ++l) {
+            l2a_rm_layer_any<RT>(p.tpw[l], reinterpret_cast<const f32x4*>(p.wblk + p.pk[l]), p.wblk + p.bias[l], KGin, p.kgs, act,
+                                 floor, live, wave, lane);
+            KGin = 4 * p.tpw[l];
+            if (p.act != L2A_ACT_RELU && p.act != L2A_ACT_IDENTITY) {       // tanh / sigmoid / swish: elementwise over the live tiles
+                for (int e = tid; e < RT * KGin * 64; e += L2A_RM_THREADS) {
+                    const int rt = e / (KGin * 64);
+                    if ((live >> rt) & 1u) {
+                        f32x4* q = act + (rt * p.kgs) * 64 + (e - rt * KGin * 64);
+                        f32x4 v = *q;
+                        v.x = l2a_act1(v.x, p.act); v.y = l2a_act1(v.y, p.act); v.z = l2a_act1(v.z, p.act); v.w = l2a_act1(v.w, p.act);
+                        *q = v;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // ---- the scalar output layer: row tiles dealt to the waves; unit 0 = register 0 of lanes 0 .. 15 ----
+        {
+            const f32x4* wo = reinterpret_cast<const f32x4*>(p.wblk + p.pk[p.n_hidden]) + lane;
+            const float bo = p.wblk[p.bias[p.n_hidden]];
+#pragma unroll
+            for (int q = 0; q < (RT + 3) / 4; ++q) {
+                const int rt = wave + 4 * q;
+                if (rt < RT && ((live >> rt) & 1u)) {
+                    f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                    for (int g = 0; g < KGin; ++g) {
+                        const f32x4 a = wo[g * 64];
+                        const f32x4 b = act[(rt * p.kgs + g) * 64 + lane];
+                        acc = L2A_MFMA(a.x, b.x, acc);
+                        acc = L2A_MFMA(a.y, b.y, acc);
+                        acc = L2A_MFMA(a.z, b.z, acc);
+                        acc = L2A_MFMA(a.w, b.w, acc);
+                    }
+                    if (lane < 16) sz[rt * 16 + lane] = acc.x + bo;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- the pass's steps of this thread's candidate, in order ----
+        if (tid < nr) {
+            const int ct = tid >> 4, j = tid & 15;
+            for (int s = 0; s < S && t0 + s < p.h; ++s) {
+                const int i = (ct * S + s) * 16 + j;
+                float r = sz[i] * p.sr + p.mur;
+                if (sbad[i]) { r = __builtin_nanf(""); sbad[i] = 0; }
+                R = R + (float)disc * r;
+                disc *= p.discount;
+            }
+        }
+        __syncthreads();        // the next pass overwrites the image, sz and sbad
+    }
+
+    if (tid < nr) {
+        const int row = r0 + tid, env = row / p.n;
+        if (p.returns_out) p.returns_out[row] = R;
+        skey[tid] = l2a_key_pack(R, p.cand_offset + (row - env * p.n));
+        senv[tid] = env;
+    }
+    __syncthreads();
+    // one atomic per (workgroup, env touched): the first row of every env's run in this block reduces the run
+    if (p.best_key && tid < nr && (tid == 0 || senv[tid - 1] != senv[tid])) {
+        unsigned long long best = skey[tid];
+        for (int i = tid + 1; i < nr && senv[i] == senv[tid]; ++i) best = (skey[i] > best) ? skey[i] : best;
+        atomicMax(p.best_key + senv[tid], best);
+    }
+}
+
+struct l2a_reward_model {
+    l2a_ctx* ctx = nullptr;
+    int obs_dim = 0, act_dim = 0, d_in = 0, KG0 = 0, kgs = 0;
+    int n_hidden = 0, hidden[L2A_RM_MAX_HIDDEN] = {0}, act = L2A_ACT_RELU;
+    float* wblk = nullptr;
+    long long blk_floats = 0;
+    long long pk[L2A_RM_MAX_HIDDEN + 1] = {0}, bias[L2A_RM_MAX_HIDDEN + 1] = {0}, nm = 0;
+    float sr = 1.0f, mur = 0.0f;
+    bool weights_set = false;
+    std::vector<float> norm_stage;              // host staging, kept alive for the async H2D
+};
+
+namespace {
+
+// Launch geometry: RT row tiles per pass (accumulator and LDS budget), of them S steps x CT candidate tiles.  Any choice gives
+// the same bits; this one minimises (rounds of workgroups) x (passes) x (pass cost ~ RT + 2).
+void choose_geometry(const l2a_reward_model* rm, long long rows, int h, int* rt_out, int* ct_out, int* s_out) {
+    int tpw_max = 1;
+    for (int l = 0; l < rm->n_hidden; ++l) tpw_max = rm->hidden[l] / 64 > tpw_max ? rm->hidden[l] / 64 : tpw_max;
+    const int cus = rm->ctx->num_cu > 0 ? rm->ctx->num_cu : 256;
+    long long best_cost = -1;
+    for (int rt = 8; rt >= 1; rt >>= 1) {
+        if (rt * tpw_max > L2A_RM_MAX_ACC) continue;
+        if ((long long)rt * rm->kgs * 1024 + 4096 > rm->ctx->lds_per_block) continue;
+        for (int s = rt; s >= 1; s >>= 1) {
+            if (s > 1 && s / 2 >= h) continue;          // steps per pass beyond the horizon are empty tiles
+            const int ct = rt / s;
+            const long long wgs = (rows + 16 * ct - 1) / (16 * ct);
+            const long long cost = ((wgs + cus - 1) / cus) * ((h + s - 1) / s) * (rt + 2);
+            if (best_cost < 0 || cost < best_cost) { best_cost = cost; *rt_out = rt; *ct_out = ct; *s_out = s; }
+        }
+    }
+}
+
+// The function attribute is per (device, instance), not per model: it is raised ONCE to all the LDS a workgroup may take, so
+// that models of different widths do not lower it under each other.
+template <int RT>
+int launch_rt(l2a_reward_model* rm, const L2ARMParams& p, unsigned blocks, hipStream_t stream) {
+    static bool allowed[64] = {false};
+    const size_t bytes = (size_t)RT * rm->kgs * 1024;
+    const int dev = rm->ctx->device;
+    if (bytes > 48 * 1024 && !(dev >= 0 && dev < 64 && allowed[dev])) {
+        L2A_HIP(rm->ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_score_mlp_k<RT>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, rm->ctx->lds_per_block - 4096));
+        if (dev >= 0 && dev < 64) allowed[dev] = true;
+    }
+    hipLaunchKernelGGL(l2a_score_mlp_k<RT>, dim3(blocks), dim3(L2A_RM_THREADS), bytes, stream, p);
+    L2A_HIP(rm->ctx, hipGetLastError());
+    return L2A_OK;
+}
+
+int launch(l2a_reward_model* rm, L2ARMParams& p, hipStream_t stream) {
+    p.wblk = rm->wblk;
+    for (int l = 0; l <= rm->n_hidden; ++l) { p.pk[l] = rm->pk[l]; p.bias[l] = rm->bias[l]; }
+    p.nm = rm->nm;
+    for (int l = 0; l < L2A_RM_MAX_HIDDEN; ++l) p.tpw[l] = l < rm->n_hidden ? rm->hidden[l] / 64 : 0;
+    p.n_hidden = rm->n_hidden; p.obs_dim = rm->obs_dim; p.act_dim = rm->act_dim; p.d_in = rm->d_in; p.KG0 = rm->KG0; p.kgs = rm->kgs;
+    p.act = rm->act; p.sr = rm->sr; p.mur = rm->mur;
+    int rt = 1, ct = 1, s = 1;
+    choose_geometry(rm, p.rows, p.h, &rt, &ct, &s);
+    p.CT = ct; p.S = s;
+    const unsigned blocks = (unsigned)(((long long)p.rows + 16 * ct - 1) / (16 * ct));
+    switch (rt) {
+        case 8: return launch_rt<8>(rm, p, blocks, stream);
+        case 4: return launch_rt<4>(rm, p, blocks, stream);
+        case 2: return launch_rt<2>(rm, p, blocks, stream);
+        default: return launch_rt<1>(rm, p, blocks, stream);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int l2a_reward_model_check(int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act) {
+    const std::string who = "reward model: ";
+    if (obs_dim < 1 || obs_dim > 16 * L2A_OTMAX)
+        return l2a_fail(nullptr, L2A_EINVAL, who + "obs_dim " + std::to_string(obs_dim) + " (1 .. " + std::to_string(16 * L2A_OTMAX) + ")");
+    if (act_dim < 1 || act_dim > 16)
+        return l2a_fail(nullptr, L2A_EINVAL, who + "act_dim " + std::to_string(act_dim) + " (1 .. 16)");
+    if (n_hidden < 1 || n_hidden > L2A_RM_MAX_HIDDEN)
+        return l2a_fail(nullptr, L2A_EINVAL, who + std::to_string(n_hidden) + " hidden layers (1 .. " + std::to_string(L2A_RM_MAX_HIDDEN) + ")");
+    if (!hidden) return l2a_fail(nullptr, L2A_EINVAL, who + "null hidden sizes");
+    for (int l = 0; l < n_hidden; ++l)
+        if (hidden[l] < 64 || hidden[l] > 512 || hidden[l] % 64 != 0)
+            return l2a_fail(nullptr, L2A_EINVAL, who + "hidden width " + std::to_string(hidden[l]) + " (a multiple of 64 up to 512)");
+    if (hidden_act < L2A_ACT_IDENTITY || hidden_act > L2A_ACT_SWISH)
+        return l2a_fail(nullptr, L2A_EINVAL, who + "unknown activation " + std::to_string(hidden_act));
+    return L2A_OK;
+}
+
+int l2a_reward_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act,
+                            l2a_reward_model** out) {
+    if (!ctx || !out) return L2A_EINVAL;
+    const int rc = l2a_reward_model_check(obs_dim, act_dim, n_hidden, hidden, hidden_act);
+    if (rc != L2A_OK) return l2a_fail(ctx, rc, l2a_last_error(nullptr));
+    l2a_reward_model* rm = new l2a_reward_model();
+    rm->ctx = ctx;
+    rm->obs_dim = obs_dim; rm->act_dim = act_dim; rm->d_in = 2 * obs_dim + act_dim; rm->KG0 = l2a_ceil_div(rm->d_in, 16);
+    rm->n_hidden = n_hidden; rm->act = hidden_act;
+    rm->kgs = rm->KG0;
+    long long off = 0;
+    int kg = rm->KG0;
+    for (int l = 0; l <= n_hidden; ++l) {
+        const int n_out = l < n_hidden ? hidden[l] : 1;
+        if (l < n_hidden) { rm->hidden[l] = hidden[l]; rm->kgs = hidden[l] / 16 > rm->kgs ? hidden[l] / 16 : rm->kgs; }
+        rm->pk[l] = off;
+        off += (long long)l2a_ceil_div(n_out, 16) * kg * 256;
+        rm->bias[l] = off;
+        off += (n_out + 63) / 64 * 64;
+        kg = n_out / 16;
+    }
+    rm->nm = off;
+    off += 32 * rm->KG0;
+    rm->blk_floats = off;
+    l2a_device_guard guard(ctx->device);
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&rm->wblk), (size_t)off * sizeof(float));
+    if (e != hipSuccess) {
+        delete rm;
+        return l2a_fail(ctx, L2A_EHIP, std::string("l2a_reward_model_create: hipMalloc: ") + hipGetErrorString(e));
+    }
+    // identity statistics until l2a_reward_model_set_norm is called (on the null stream, drained here)
+    const int rc_n = l2a_reward_model_set_norm(rm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc_n == L2A_OK && hipStreamSynchronize(nullptr) == hipSuccess) { *out = rm; return L2A_OK; }
+    l2a_reward_model_destroy(rm);
+    return rc_n != L2A_OK ? rc_n : l2a_fail(ctx, L2A_EHIP, "l2a_reward_model_create: hipStreamSynchronize failed");
+}
+
+void l2a_reward_model_destroy(l2a_reward_model* rm) {
+    if (!rm) return;
+    l2a_device_guard guard(rm->ctx->device);
+    if (rm->wblk) (void)hipFree(rm->wblk);
+    delete rm;
+}
+
+int l2a_reward_model_set_weights(l2a_reward_model* rm, const void* const* device_ptrs, void* stream_v) {
+    if (!rm) return L2A_EINVAL;
+    l2a_ctx* ctx = rm->ctx;
+    if (!device_ptrs) return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_set_weights: null pointer table");
+    for (int i = 0; i < 2 * (rm->n_hidden + 1); ++i)
+        if (!device_ptrs[i]) return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_set_weights: null parameter " + std::to_string(i));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    int k_in = rm->d_in, kg = rm->KG0;
+    for (int l = 0; l <= rm->n_hidden; ++l) {
+        const int n_out = l < rm->n_hidden ? rm->hidden[l] : 1;
+        const long long total = (long long)l2a_ceil_div(n_out, 16) * kg * 256;
+        hipLaunchKernelGGL(l2a_rm_pack_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                           static_cast<const float*>(device_ptrs[2 * l]), k_in, n_out, kg, total, rm->wblk + rm->pk[l]);
+        L2A_HIP(ctx, hipGetLastError());
+        L2A_HIP(ctx, hipMemcpyAsync(rm->wblk + rm->bias[l], device_ptrs[2 * l + 1], sizeof(float) * (size_t)n_out,
+                                    hipMemcpyDeviceToDevice, stream));
+        k_in = n_out;
+        kg = n_out / 16;
+    }
+    rm->weights_set = true;
+    return L2A_OK;
+}
+
+int l2a_reward_model_set_norm(l2a_reward_model* rm, const double* mean_obs, const double* std_obs, const double* mean_act,
+                              const double* std_act, const double* mean_delta, const double* std_delta, const double* mean_r,
+                              const double* std_r, void* stream_v) {
+    if (!rm) return L2A_EINVAL;
+    l2a_ctx* ctx = rm->ctx;
+    const int n_null = !mean_obs + !std_obs + !mean_act + !std_act + !mean_delta + !std_delta + !mean_r + !std_r;
+    if (n_null != 0 && n_null != 8)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_set_norm: pass all eight statistics, or none for identity");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    // a previous async copy from the staging buffer must have drained before it is overwritten
+    if (!rm->norm_stage.empty()) L2A_HIP(ctx, hipStreamSynchronize(stream));
+    rm->norm_stage.assign((size_t)32 * rm->KG0, 0.0f);
+    float* mu = rm->norm_stage.data();
+    float* inv = mu + 16 * rm->KG0;
+    const double eps = 1e-10;
+    for (int k = 0; k < rm->d_in; ++k) {
+        if (n_null) { mu[k] = 0.0f; inv[k] = 1.0f; continue; }
+        const int oa = rm->obs_dim + rm->act_dim;
+        const double m_ = k < rm->obs_dim ? mean_obs[k] : k < oa ? mean_act[k - rm->obs_dim] : mean_delta[k - oa];
+        const double s_ = k < rm->obs_dim ? std_obs[k] : k < oa ? std_act[k - rm->obs_dim] : std_delta[k - oa];
+        mu[k] = (float)m_;
+        inv[k] = (float)(1.0 / (s_ + eps));
+    }
+    rm->mur = n_null ? 0.0f : (float)*mean_r;
+    rm->sr = n_null ? 1.0f : (float)(*std_r + eps);
+    L2A_HIP(ctx, hipMemcpyAsync(rm->wblk + rm->nm, mu, rm->norm_stage.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    return L2A_OK;
+}
+
+int l2a_reward_model_predict(l2a_reward_model* rm, const float* obs, const float* act, const float* next_obs, int rows,
+                             float* rewards_out, void* stream_v) {
+    if (!rm) return L2A_EINVAL;
+    l2a_ctx* ctx = rm->ctx;
+    if (!obs || !act || !next_obs || !rewards_out) return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_predict: null pointer");
+    if (rows < 1 || rows > 0x3fffffff) return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_predict: rows must be 1 .. 2^30 - 1");
+    if (!rm->weights_set) return l2a_fail(ctx, L2A_ESTATE, "the reward model's weights were never set");
+    l2a_device_guard guard(ctx->device);
+    L2ARMParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.obs0 = obs; p.traj = next_obs; p.actions = act; p.returns_out = rewards_out; p.best_key = nullptr;
+    p.discount = 1.0; p.rows = rows; p.n = rows; p.h = 1; p.obs_per_row = 1; p.cand_offset = 0;
+    return launch(rm, p, reinterpret_cast<hipStream_t>(stream_v));
+}
+
+int l2a_score_trajectory_model(l2a_reward_model* rm, const float* obs0, const float* traj, const float* actions, int m, int n,
+                               int h, double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
+                               void* stream_v) {
+    if (!rm) return L2A_EINVAL;
+    l2a_ctx* ctx = rm->ctx;
+    if (!obs0 || !traj || !actions) return l2a_fail(ctx, L2A_EINVAL, "l2a_score_trajectory_model: null obs0/traj/actions");
+    if (!best_key && !returns_out)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_score_trajectory_model: nothing to write (best_key and returns_out are null)");
+    if (m < 1 || n < 1 || h < 1) return l2a_fail(ctx, L2A_EINVAL, "l2a_score_trajectory_model: m, n and h must be >= 1");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_score_trajectory_model: too many candidates");
+    if (!rm->weights_set) return l2a_fail(ctx, L2A_ESTATE, "the reward model's weights were never set");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    if (best_key) L2A_HIP(ctx, hipMemsetAsync(best_key, 0, sizeof(unsigned long long) * (size_t)m, stream));
+    L2ARMParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.obs0 = obs0; p.traj = traj; p.actions = actions; p.returns_out = returns_out; p.best_key = best_key;
+    p.discount = discount; p.rows = m * n; p.n = n; p.h = h; p.obs_per_row = 0; p.cand_offset = cand_offset;
+    return launch(rm, p, stream);
+}
+
+void l2a_reward_model_facts(const l2a_reward_model* rm, l2a_ctx** ctx, int* obs_dim, int* act_dim) {
+    if (ctx) *ctx = rm->ctx;
+    if (obs_dim) *obs_dim = rm->obs_dim;
+    if (act_dim) *act_dim = rm->act_dim;
+}
+
+}  // extern "C"

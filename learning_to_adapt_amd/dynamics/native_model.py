@@ -53,6 +53,7 @@ class NativeModel(object):
         self.handle = handle
         self._keep = {}     # source tensors kept alive until the stream has consumed them
         self.program_plans = 0      # calls of plan_rs_program (diagnostics: which plan path a controller took)
+        self.reward_model_plans = 0     # calls of plan_rs_reward_model
 
     def close(self):
         if getattr(self, "handle", None):
@@ -241,6 +242,27 @@ class NativeModel(object):
                                           _ptr(traj_out), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_plan_rs_program")
 
+    def plan_rs_reward_model(self, obs0, actions, m, n, h, discount, reward_model, cand_offset=0, returns_out=None,
+                             best_key=None, traj_out=None):
+        """Plan step with a learned reward (``l2a_plan_rs_reward_model``): the carry chain of ``plan_rs_program``, then the
+        matrix-core scorer of ``reward_model`` (a ``NativeRewardModel``).  Arguments as ``plan_rs_program``."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if traj_out is not None:
+            assert traj_out.is_cuda and traj_out.dtype == torch.float32 and traj_out.is_contiguous()
+            assert traj_out.numel() == h * m * n * self.obs_dim
+        assert isinstance(reward_model, NativeRewardModel)
+        self.reward_model_plans += 1
+        rc = self.lib.l2a_plan_rs_reward_model(self.handle, reward_model.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h),
+                                               float(discount), int(cand_offset), _ptr(returns_out), _ptr(best_key),
+                                               _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_plan_rs_reward_model")
+
     def plan_rs_sync(self, obs_host, actions, m, n, h, discount, reward, cand_offset=0, returns_out=None):
         """Blocking plan step (``l2a_plan_rs_sync``): ``obs_host`` is a HOST array ``[m, obs_dim]``; returns the
         arg-max keys as a NumPy uint64 array ``[m]``, or ``None`` when the launch was flagged invalid (tile-split
@@ -293,3 +315,104 @@ class NativeModel(object):
                                   int(n_blocks), _ptr(out), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_predict")
         return out
+
+
+class NativeRewardModel(object):
+    """Python handle on an ``l2a_reward_model``: a reward MLP over ``[obs | act | next_obs - obs]`` that the planner scores
+    trajectories with on the matrix cores (``csrc/l2a_score_mlp.hip``).  Raises ``L2AError`` on any failure."""
+
+    def __init__(self, obs_dim, act_dim, hidden_sizes, hidden_act, device=None):
+        if not torch.cuda.is_available():
+            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the reward scorer is HIP-only (there is no CPU fallback)")
+        if device is None:
+            device = torch.cuda.current_device()
+        self.ctx = _lib.Context.get(device)
+        self.lib = self.ctx.lib
+        self.device = torch.device("cuda", device)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
+        if hidden_act not in _lib.ACT_CODES:
+            raise _lib.L2AError("nonlinearity %r is not supported by the HIP kernels" % (hidden_act,))
+        hid = (ctypes.c_int * len(self.hidden_sizes))(*self.hidden_sizes)
+        handle = ctypes.c_void_p()
+        rc = self.lib.l2a_reward_model_create(self.ctx.handle, self.obs_dim, self.act_dim, len(self.hidden_sizes), hid,
+                                              _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
+        self.ctx.check(rc, "l2a_reward_model_create")
+        self.handle = handle
+        self._keep = {}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.l2a_reward_model_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, params):
+        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]``; the first ``in`` is ``2 * obs_dim + act_dim``, the last
+        ``out`` is 1."""
+        dev = []
+        for p in params:
+            t = torch.as_tensor(p) if not torch.is_tensor(p) else p
+            dev.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        sizes = (2 * self.obs_dim + self.act_dim,) + self.hidden_sizes + (1,)
+        assert len(dev) == 2 * (len(sizes) - 1), "expected %d parameter arrays" % (2 * (len(sizes) - 1))
+        for li in range(len(sizes) - 1):
+            assert tuple(dev[2 * li].shape) == (sizes[li], sizes[li + 1]), \
+                "kernel %d has shape %s, expected %s" % (li, tuple(dev[2 * li].shape), (sizes[li], sizes[li + 1]))
+            assert tuple(dev[2 * li + 1].shape) == (sizes[li + 1],)
+        ptrs = (ctypes.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
+        rc = self.lib.l2a_reward_model_set_weights(self.handle, ptrs, _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_reward_model_set_weights")
+        self._keep["w"] = dev
+
+    def set_norm(self, norm):
+        """``norm``: dict ``'obs' / 'act' / 'delta' / 'reward' -> (mean, std)`` (reward: scalars), or ``None`` for identity."""
+        if norm is None:
+            null = ctypes.POINTER(ctypes.c_double)()
+            rc = self.lib.l2a_reward_model_set_norm(self.handle, null, null, null, null, null, null, null, null,
+                                                    _stream_ptr(self.device))
+        else:
+            keep, args = [], []
+            for key in ("obs", "act", "delta", "reward"):
+                for j in (0, 1):
+                    arr, p = _dvec(np.reshape(norm[key][j], -1))
+                    expect = {"act": self.act_dim, "reward": 1}.get(key, self.obs_dim)
+                    assert arr.shape == (expect,), "normalization[%r] has shape %s" % (key, arr.shape)
+                    keep.append(arr)
+                    args.append(p)
+            rc = self.lib.l2a_reward_model_set_norm(self.handle, *args, _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_reward_model_set_norm")
+
+    def predict(self, obs, act, next_obs, out=None):
+        """fp32 CUDA ``[rows, obs_dim]``, ``[rows, act_dim]``, ``[rows, obs_dim]`` -> fp32 CUDA ``[rows]``."""
+        for t in (obs, act, next_obs):
+            assert t.is_cuda and t.dtype == torch.float32
+        rows = int(obs.shape[0])
+        assert tuple(obs.shape) == (rows, self.obs_dim) == tuple(next_obs.shape) and tuple(act.shape) == (rows, self.act_dim)
+        if out is None:
+            out = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        rc = self.lib.l2a_reward_model_predict(self.handle, _ptr(obs.contiguous()), _ptr(act.contiguous()),
+                                               _ptr(next_obs.contiguous()), rows, _ptr(out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_reward_model_predict")
+        return out
+
+    def score_trajectory(self, obs0, traj, actions, m, n, h, discount, cand_offset=0, returns_out=None, best_key=None):
+        """The scorer alone (``l2a_score_trajectory_model``) on trajectories that are already on the device: ``obs0``
+        ``[m, obs_dim]``, ``traj`` ``[h, m * n, obs_dim]``, ``actions`` ``[h, m * n, act_dim]`` fp32 CUDA tensors."""
+        for t in (obs0, traj, actions):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and traj.numel() == h * m * n * self.obs_dim
+        assert actions.numel() == h * m * n * self.act_dim
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        rc = self.lib.l2a_score_trajectory_model(self.handle, _ptr(obs0), _ptr(traj), _ptr(actions), int(m), int(n), int(h),
+                                                 float(discount), int(cand_offset), _ptr(returns_out), _ptr(best_key),
+                                                 _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_score_trajectory_model")

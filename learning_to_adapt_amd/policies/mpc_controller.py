@@ -243,14 +243,33 @@ class MPCController(Policy, Serializable):
         self.dynamics_model.planner_model().plan_payload(best, m, self._rank_digest(), payload)
         return payload
 
+    _takes_reward_models = True     # (RNNMPCController: False - the recurrent plans take neither programs nor reward models)
+
     def _fusable(self):
-        return (self._reward_spec is not None) and hasattr(self.dynamics_model, "planner_model")
+        return ((self._reward_spec is not None or self._native_reward_model() is not None)
+                and hasattr(self.dynamics_model, "planner_model"))
+
+    def _native_reward_model(self):
+        """``use_reward_model=True`` with a reward model the library scores on the GPU: one that offers
+        ``planner_reward_model()`` and passes ``l2a_reward_model_check`` (``MLPRewardModel``).  ``None`` for every other
+        object with a ``predict``: those keep the reference's loop (``_get_rs_action_unfused``).  The check is host only and
+        made once."""
+        if not (self.use_reward_model and self._takes_reward_models):
+            return None
+        ok = self.__dict__.get("_reward_model_ok")
+        if ok is None or ok[0] is not self.reward_model:
+            rm = self.reward_model
+            good = rm is not None and hasattr(rm, "planner_reward_model") and \
+                (not hasattr(rm, "native_eligible") or rm.native_eligible() is None)
+            ok = self._reward_model_ok = (rm, bool(good))
+        return self.reward_model if ok[1] else None
 
     def _program(self):
-        """The env's reward is a ``RewardProgram``: the plan runs through ``l2a_plan_rs_program`` (``_rollout``), and every
-        path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking launch, the horizon-chunked
-        pipelines, the C controllers - declines."""
-        return isinstance(self._reward_spec, RewardProgram)
+        """The plan is scored by a launch of its own behind the rollout's carry chain - the env's reward is a
+        ``RewardProgram`` (``l2a_plan_rs_program``) or a native reward model stands in for it (``l2a_plan_rs_reward_model``) -
+        through ``_rollout``, and every path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking
+        launch, the horizon-chunked pipelines, the C controllers - declines."""
+        return isinstance(self._reward_spec, RewardProgram) or self._native_reward_model() is not None
 
     def _buf(self, key, shape, dtype, device):
         t = self._bufs.get(key)
@@ -371,6 +390,11 @@ class MPCController(Policy, Serializable):
         obs0 = obs_dev if obs_dev is not None else self._upload_obs(observations)
         best = self._buf("best", (m,), torch.int64, dev)
         rets = self._buf("rets", (m, n_local), torch.float32, dev) if want_returns else None
+        rm = self._native_reward_model()
+        if rm is not None:
+            native.plan_rs_reward_model(obs0, actions_local, m, n_local, self.horizon, self.discount, rm.planner_reward_model(),
+                                        cand_offset=cand_offset, returns_out=rets, best_key=best)
+            return best, rets
         plan = native.plan_rs_program if self._program() else native.plan_rs
         plan(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
              cand_offset=cand_offset, returns_out=rets, best_key=best)
@@ -1170,7 +1194,8 @@ class MPCController(Policy, Serializable):
 
     def get_cem_action(self, observations):
         if not self._fusable():
-            raise _lib.L2AError("CEM planning needs a fusable closed-form reward (env.reward_spec: a RewardSpec or a RewardProgram)")
+            raise _lib.L2AError("CEM planning needs a fusable closed-form reward (env.reward_spec: a RewardSpec or a RewardProgram) "
+                                "or, with use_reward_model, a reward model the library scores (MLPRewardModel)")
         if self.native_cem_step:
             out = self._native_cem_step(observations)
             if out is not None:

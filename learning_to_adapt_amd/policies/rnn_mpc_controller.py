@@ -27,6 +27,7 @@ class RNNMPCController(MPCController):
     _hid_stale = None       # which copy is out of date: None | "host" | "dev"
     _hid_next = None        # (c, h) already advanced with the chosen actions by the blocking plan launch
     _hid_flip = 0
+    _takes_reward_models = False    # the recurrent plans score with the fused l2a_reward only: a reward model keeps its old path
 
     def __init__(
             self,
