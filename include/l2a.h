@@ -607,6 +607,43 @@ int l2a_lstm_advance(l2a_lstm* model, const float* obs, const float* act, const 
 /* 1 when (obs_dim, act_dim, units) is eligible for the MFMA LSTM kernel, else 0.                 */
 int l2a_lstm_mfma_eligible(int obs_dim, int act_dim, int units);
 
+/* ---- recurrent plans with a reward program or a learned reward model ---------------------------
+ * The recurrent counterpart of l2a_plan_rs_program / l2a_plan_rs_reward_model: the model's predicted trajectory goes
+ * to HBM and the scorers of csrc/l2a_score.hip / l2a_score_mlp.hip - unchanged - run behind it.  All stream-ordered; no
+ * host synchronisation unless a buffer of the model's own grows.
+ *
+ * l2a_lstm_rollout_traj: the model's rollout alone.  obs0 [m, obs_dim], c0 / h0 [m, state width] (one row per env, as
+ * l2a_lstm_plan_rs), actions [h, m*n, act_dim] -> traj_out device fp32 [h, m*n, obs_dim], traj_out[t] = the predicted
+ * observation after horizon step t.  No rewards.  Two paths, the same bits on both:
+ *   single launch  one LSTM layer of 256 / 512 units, for the plans l2a_lstm_plan_rs rolls on micro tiles (at most three
+ *                  micro tiles per CU, and wanted under l2a_set_micro: 0 never, 2 whenever eligible): the trajectory-writing
+ *                  instance of the micro-tile kernel, c / h never leave the CU.
+ *   carry chain    everything else (128 units, GRU / BasicRNN / stacks, the VALU kernels, larger plans): h one-step
+ *                  l2a_lstm_plan_rs_chunk launches with an all-zero reward, state_out = traj_out[t]; c / h ping-pong between
+ *                  two buffer pairs of the model's own ([m*n, state width] each, grown on demand, which synchronises `stream`).
+ * cand_offset is validated as everywhere and changes nothing in the trajectory.  The launch status word keeps its meaning: a
+ * flagged unit-tile-split launch anywhere in the chain flags the call (l2a_launch_status).
+ *
+ * l2a_lstm_plan_rs_program: the rollout above, then l2a_score_trajectory.  l2a_lstm_plan_rs_reward_model: the rollout, then
+ * l2a_score_trajectory_model; `rm` and `model` must live on the same context and agree on obs_dim / act_dim (L2A_EINVAL).
+ * returns_out [m, n] or NULL, best_key [m] or NULL (not both), keys as l2a_lstm_plan_rs packs them.  traj_out: device fp32
+ * [h, m*n, obs_dim], or NULL: the model keeps a buffer of its own (grown on demand; freed with the model).
+ *
+ * l2a_lstm_traj_geometry: host only, needs no GPU - which path l2a_lstm_rollout_traj takes for one LSTM layer of `units`
+ * under micro policy `micro_policy` (0 | 1 | 2) on `num_cu` CUs (<= 0: 256) with the automatic kernel choice; the decision
+ * function is the launcher's own.  out[8]: { 0 single launch (1) or chain (0), 1 launches of the rollout, 2 workgroups of a
+ * launch, 3 workgroups per env (single launch), 4 micro tiles of the largest workgroup (99: no workgroup geometry),
+ * 5 workgroups of that size per env, 6 .. 7 zero }.                                                                   */
+int l2a_lstm_rollout_traj(l2a_lstm* model, const float* obs0, const float* c0, const float* h0, const float* actions,
+                          int m, int n, int h, int cand_offset, float* traj_out, void* stream);
+int l2a_lstm_plan_rs_program(l2a_lstm* model, const float* obs0, const float* c0, const float* h0, const float* actions,
+                             int m, int n, int h, double discount, const l2a_reward_program* program, int cand_offset,
+                             float* returns_out, unsigned long long* best_key, float* traj_out, void* stream);
+int l2a_lstm_plan_rs_reward_model(l2a_lstm* model, l2a_reward_model* rm, const float* obs0, const float* c0, const float* h0,
+                                  const float* actions, int m, int n, int h, double discount, int cand_offset,
+                                  float* returns_out, unsigned long long* best_key, float* traj_out, void* stream);
+int l2a_lstm_traj_geometry(int obs_dim, int act_dim, int units, int m, int n, int h, int micro_policy, int num_cu, int* out);
+
 /* ---- the controller step as one call ----------------------------------------------------------
  * `MPCController.get_actions(observations)` in random-shooting mode (policies/mpc_controller.py:59-69,108-129) and
  * `RNNMPCController.get_actions` (policies/rnn_mpc_controller.py:57-65,112-134), as their caller sees them: float64

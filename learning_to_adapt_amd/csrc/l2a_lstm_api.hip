@@ -45,6 +45,10 @@ struct l2a_lstm {
     long long lmk[L2A_RNN_MAX_LAYERS][2] = {{0}};
     bool gmicro4_ok = false;                      // ... with workgroups of four micro tiles (plans beyond three per CU)
     float* adv_buf = nullptr;                     // l2a_lstm_plan_rs_sync: [64, act_dim] chosen actions + [64, obs_dim] next obs
+    float* traj_buf = nullptr;                    // l2a_lstm_plan_rs_program / _reward_model: [returns of the carry launches (rows) | trajectory (h x rows x obs_dim)]
+    long long traj_buf_floats = 0;
+    float* hid_buf = nullptr;                     // the carry chain's c / h: two pairs [c | h] of [rows, state width], used in turn
+    long long hid_buf_floats = 0;
 };
 
 // First action of every env's winning candidate: out[i] = actions[step 0][i * n + (index(best_key[i]) - cand_offset)]
@@ -111,6 +115,40 @@ long long generic_mfma_smem(const l2a_lstm* md) {
 }
 bool generic_uses_mfma(const l2a_lstm* md) {
     return md->generic && md->ctx->kernel_kind != L2A_KERNEL_VALU && generic_mfma_smem(md) <= md->ctx->lds_per_block;
+}
+
+// Micro tiles for the tuned LSTM kernel (l2a_micro.h): every env's ceil(n / 4) candidate tiles of four dealt to W workgroups of
+// at most three - one workgroup per CU, none idle, no exchange.  The ONE decision function of the fused plan (launch() below),
+// the trajectory rollout (rollout_traj) and l2a_lstm_traj_geometry; pure host arithmetic.
+struct lstm_micro_geom { int W, hi, mc_r; };
+bool lstm_micro_wanted(bool micro_ok, int micro_policy, int num_cu, int m, int n, lstm_micro_geom* g) {
+    const int cus_m = num_cu > 0 ? num_cu : 256;
+    const long long tiles16 = (long long)m * l2a_ceil_div(n, 16);
+    const int quads = l2a_ceil_div(n, 4);
+    int W = cus_m / m;
+    if (W > quads) W = quads;
+    const int hi = W > 0 ? l2a_ceil_div(quads, W) : 99;
+    // ... and the fewest workgroups that keep the largest one at `hi` micro tiles (the chip is power limited under this
+    // kernel, see launch_rollout in l2a_api.hip)
+    if (hi >= 1 && hi <= 3) W = l2a_ceil_div(quads, hi);
+    // automatic (profiles/r04_ab_micro.jsonl): the plans the 16-candidate geometries cannot fill - more than CUs / 2
+    // tiles (no unit-tile split) and fewer than CUs (the ReBAL default: 0.91 of the 16-candidate launch; 512 units: 0.85)
+    // - and plans of at most one micro tile per CU (0.87 - 0.95 of the unit-tile split); in between the unit-tile
+    // split wins (1.04 - 1.16).
+    const bool unfilled = 2 * tiles16 > cus_m && tiles16 < cus_m;
+    const bool wanted = micro_policy == 2 || (micro_policy == 1 && (unfilled || hi == 1));
+    g->W = W;
+    g->hi = hi;
+    g->mc_r = quads - W * (hi - 1);          // workgroups that take `hi` micro tiles
+    return micro_ok && hi <= 3 && wanted;
+}
+// ... and of the trajectory rollout: the single launch where the fused plan would take micro tiles, on the matrix-core kernels,
+// with a step's slices of the trajectory and of the actions inside one buffer descriptor each (the kernel's range check)
+bool lstm_traj_single(bool micro_ok, bool kind_mfma, int micro_policy, int num_cu, int obs_dim, int act_dim, int m, int n,
+                      lstm_micro_geom* g) {
+    const bool wanted = lstm_micro_wanted(micro_ok, micro_policy, num_cu, m, n, g);
+    const long long rows = (long long)m * n;
+    return wanted && kind_mfma && rows * obs_dim * 4 < 0x7ffffff0LL && rows * act_dim * 4 < 0x7ffffff0LL;
 }
 
 int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = true) {
@@ -192,33 +230,17 @@ int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = tr
         const int UT = L2A_NW * md->UTW, U = md->units;
         p.tiles_per_env = l2a_ceil_div(p.n, 16 * nt);
         {
-            // Micro tiles (l2a_micro.h): every env's ceil(n / 4) candidate tiles of four dealt to W workgroups of at most
-            // three - one workgroup per CU, none idle, no exchange.  Plans only (no per-row states, no state written out:
+            // Micro tiles (lstm_micro_wanted).  Plans only (no per-row states, no state written out:
             // those launches are one step long or chunk continuations and keep the 16-candidate kernel - same bits).
-            const int cus_m = ctx->num_cu > 0 ? ctx->num_cu : 256;
-            const long long tiles16 = (long long)p.m * p.tiles_per_env;
-            const int quads = l2a_ceil_div(p.n, 4);
-            int W = cus_m / p.m;
-            if (W > quads) W = quads;
-            const int hi = W > 0 ? l2a_ceil_div(quads, W) : 99;
-            // ... and the fewest workgroups that keep the largest one at `hi` micro tiles (the chip is power limited under this
-            // kernel, see launch_rollout in l2a_api.hip)
-            if (hi >= 1 && hi <= 3) W = l2a_ceil_div(quads, hi);
-            const bool eligible = md->micro_ok && !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && hi <= 3 &&
-                                  (p.returns_out || p.best_key);
-            // automatic (profiles/r04_ab_micro.jsonl): the plans the 16-candidate geometries cannot fill - more than CUs / 2
-            // tiles (no unit-tile split) and fewer than CUs (the ReBAL default: 0.91 of the 16-candidate launch; 512 units: 0.85)
-            // - and plans of at most one micro tile per CU (0.87 - 0.95 of the unit-tile split); in between the unit-tile
-            // split wins (1.04 - 1.16).
-            const bool unfilled = 2 * tiles16 > cus_m && tiles16 < cus_m;
-            const bool wanted = ctx->micro_policy == 2 || (ctx->micro_policy == 1 && (unfilled || hi == 1));
-            if (eligible && wanted) {
-                p.mc_w = W;
-                p.mc_hi = hi;
-                p.mc_r = quads - W * (hi - 1);          // workgroups that take `hi` micro tiles
+            lstm_micro_geom g;
+            const bool eligible = !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && (p.returns_out || p.best_key);
+            if (lstm_micro_wanted(md->micro_ok, ctx->micro_policy, ctx->num_cu, p.m, p.n, &g) && eligible) {
+                p.mc_w = g.W;
+                p.mc_hi = g.hi;
+                p.mc_r = g.mc_r;
                 int smem_m = l2a_lstm_micro_smem(U, md->KG0);
                 if (smem_m < 84 * 1024) smem_m = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
-                const int rc = l2a_launch_lstm_micro(U, &p, (unsigned)(p.m * W), smem_m, stream);
+                const int rc = l2a_launch_lstm_micro(U, &p, (unsigned)(p.m * g.W), smem_m, stream);
                 if (rc != 0) return l2a_fail(ctx, L2A_EHIP, std::string("micro-tile LSTM kernel launch: ") +
                                                             (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
                 L2A_HIP(ctx, hipGetLastError());
@@ -294,9 +316,163 @@ int launch_advance(l2a_lstm* md, const float* obs, const float* act, const unsig
     return L2A_OK;
 }
 
+// One of the model's own buffers, at least `need` floats (growing synchronises the stream: the old one may be in use).
+int grow(l2a_ctx* ctx, float** buf, long long* have, long long need, hipStream_t stream) {
+    if (need <= *have) return L2A_OK;
+    l2a_device_guard guard(ctx->device);
+    if (*buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(*buf)); *buf = nullptr; *have = 0; }
+    L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(buf), (size_t)need * sizeof(float)));
+    *have = need;
+    return L2A_OK;
+}
+
+// The predicted trajectory [h, m n, obs_dim] of a plan -> traj (arguments validated by the callers).  Single launch of the
+// trajectory-writing micro-tile instance where lstm_traj_single says so, else the carry chain: h one-step launches of the
+// rollout kernels - all-zero fused reward, state_out = traj[t], the trajectory slice itself being the state hand-off, c / h
+// through the model's two buffer pairs in turn.  Stream-ordered; the same bits on both paths.
+int rollout_traj(l2a_lstm* md, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n, int h,
+                 int cand_offset, float* traj, void* stream_v) {
+    l2a_ctx* ctx = md->ctx;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    if (!md->weights_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM weights were never set");
+    if (!md->norm_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM normalisation was never set");
+    int kind = ctx->kernel_kind;
+    if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
+    lstm_micro_geom g;
+    if (lstm_traj_single(!md->generic && md->micro_ok, !md->generic && kind == L2A_KERNEL_MFMA && md->mfma_ok, ctx->micro_policy,
+                         ctx->num_cu, md->obs_dim, md->act_dim, m, n, &g)) {
+        l2a_device_guard guard(ctx->device);
+        L2ALstmParams p;
+        fill(md, p);
+        p.obs0 = obs0; p.c0 = c0; p.h0 = h0; p.actions = actions;
+        p.state_out = traj;                             // (this instance: the whole trajectory)
+        p.m = m; p.n = n; p.h = h; p.cand_offset = cand_offset; p.discount = 1.0;
+        p.tiles_per_env = l2a_ceil_div(n, 16);
+        p.dbg = ctx->dbg;
+        p.mc_w = g.W; p.mc_hi = g.hi; p.mc_r = g.mc_r;
+        int smem_m = l2a_lstm_micro_smem(md->units, md->KG0);
+        if (smem_m < 84 * 1024) smem_m = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
+        const int rc = l2a_launch_lstm_micro_traj(md->units, &p, (unsigned)(m * g.W), smem_m, stream);
+        if (rc != 0) return l2a_fail(ctx, L2A_EHIP, std::string("trajectory micro-tile LSTM kernel launch: ") +
+                                                    (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
+        L2A_HIP(ctx, hipGetLastError());
+        return L2A_OK;
+    }
+    const long long rows = (long long)m * n;
+    const long long hid = rows * md->units;             // (stacks: units = sum of the layers')
+    int rc = grow(ctx, &md->hid_buf, &md->hid_buf_floats, 4 * hid, stream);
+    if (rc == L2A_OK) rc = grow(ctx, &md->traj_buf, &md->traj_buf_floats, rows, stream);   // (the plan entries ask for more first)
+    if (rc != L2A_OK) return rc;
+    float* carry_returns = md->traj_buf;                // the chunk launches' required returns_out: all zero rewards, never read
+    l2a_reward zero;
+    std::memset(&zero, 0, sizeof(zero));
+    const long long step_state = rows * md->obs_dim, step_act = rows * md->act_dim;
+    for (int t = 0; t < h; ++t) {
+        const float* c_in = t == 0 ? c0 : md->hid_buf + ((t - 1) & 1) * 2 * hid;
+        const float* h_in = t == 0 ? h0 : md->hid_buf + ((t - 1) & 1) * 2 * hid + hid;
+        float* c_nx = md->hid_buf + (t & 1) * 2 * hid;
+        rc = l2a_lstm_plan_rs_chunk(md, t == 0 ? obs0 : traj + (t - 1) * step_state, c_in, h_in, t > 0, actions + t * step_act, m, n, 1,
+                                    0, 1.0, &zero, cand_offset, nullptr, carry_returns, traj + t * step_state, c_nx, c_nx + hid,
+                                    nullptr, stream_v);
+        if (rc != L2A_OK) return rc;
+    }
+    return L2A_OK;
+}
+
+// argument checks shared by the three entries; *traj: traj_out, or the model's own buffer behind the carry returns
+int traj_args(l2a_lstm* md, const char* who, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n,
+              int h, int cand_offset, bool need_out, bool have_out) {
+    l2a_ctx* ctx = md->ctx;
+    const std::string w(who);
+    if (!obs0 || !c0 || !h0 || !actions) return l2a_fail(ctx, L2A_EINVAL, w + ": null obs0/c0/h0/actions");
+    if (need_out && !have_out) return l2a_fail(ctx, L2A_EINVAL, w + ": nothing to write");
+    if (m < 1 || n < 1 || h < 1) return l2a_fail(ctx, L2A_EINVAL, w + ": m, n and h must be >= 1");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return l2a_fail(ctx, L2A_EINVAL, w + ": too many candidates");
+    return L2A_OK;
+}
+
+// the rollout of a plan entry -> *traj (traj_out, or the model's own buffer)
+int plan_traj(l2a_lstm* md, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n, int h,
+              int cand_offset, float* traj_out, void* stream_v, float** traj) {
+    const long long rows = (long long)m * n;
+    if (!traj_out) {
+        const int rc = grow(md->ctx, &md->traj_buf, &md->traj_buf_floats, rows + (long long)h * rows * md->obs_dim,
+                            reinterpret_cast<hipStream_t>(stream_v));
+        if (rc != L2A_OK) return rc;
+    }
+    *traj = traj_out ? traj_out : md->traj_buf + rows;
+    return rollout_traj(md, obs0, c0, h0, actions, m, n, h, cand_offset, *traj, stream_v);
+}
+
 }  // namespace
 
 extern "C" {
+
+int l2a_lstm_traj_geometry(int obs_dim, int act_dim, int units, int m, int n, int h, int micro_policy, int num_cu, int* out) {
+    if (!out || obs_dim < 1 || act_dim < 1 || units < 1 || units > 1024 || m < 1 || n < 1 || h < 1 || micro_policy < 0 || micro_policy > 2)
+        return L2A_EINVAL;
+    if ((long long)m * n > 0x3fffffffLL) return L2A_EINVAL;
+    const bool mfma_ok = lstm_mfma_eligible(obs_dim, act_dim, units);
+    lstm_micro_geom g;
+    const bool single = lstm_traj_single(mfma_ok && (units == 256 || units == 512), mfma_ok, micro_policy, num_cu, obs_dim, act_dim, m, n, &g);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = single ? 1 : 0;
+    out[1] = single ? 1 : h;
+    out[2] = single ? m * g.W : m * l2a_ceil_div(n, 16);        // (chain: before any unit-tile split of the one-step launches)
+    out[3] = single ? g.W : 0;
+    out[4] = g.hi;
+    out[5] = single ? g.mc_r : 0;
+    return L2A_OK;
+}
+
+int l2a_lstm_rollout_traj(l2a_lstm* md, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n,
+                          int h, int cand_offset, float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    const int rc = traj_args(md, "l2a_lstm_rollout_traj", obs0, c0, h0, actions, m, n, h, cand_offset, true, traj_out != nullptr);
+    if (rc != L2A_OK) return rc;
+    return rollout_traj(md, obs0, c0, h0, actions, m, n, h, cand_offset, traj_out, stream_v);
+}
+
+// The recurrent plan step of an env with a reward program: the rollout and one scoring launch (l2a_score.hip).
+int l2a_lstm_plan_rs_program(l2a_lstm* md, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n,
+                             int h, double discount, const l2a_reward_program* program, int cand_offset, float* returns_out,
+                             unsigned long long* best_key, float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    int rc = l2a_reward_program_check(program, md->obs_dim, md->act_dim);
+    if (rc != L2A_OK) return l2a_fail(ctx, rc, l2a_last_error(nullptr));
+    rc = traj_args(md, "l2a_lstm_plan_rs_program", obs0, c0, h0, actions, m, n, h, cand_offset, true, best_key || returns_out);
+    if (rc != L2A_OK) return rc;
+    float* traj = nullptr;
+    rc = plan_traj(md, obs0, c0, h0, actions, m, n, h, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
+    return l2a_score_trajectory(ctx, obs0, traj, actions, m, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset,
+                                returns_out, best_key, stream_v);
+}
+
+// ... with a learned reward model: the rollout and the matrix-core scoring launch (l2a_score_mlp.hip).
+int l2a_lstm_plan_rs_reward_model(l2a_lstm* md, l2a_reward_model* rm, const float* obs0, const float* c0, const float* h0,
+                                  const float* actions, int m, int n, int h, double discount, int cand_offset, float* returns_out,
+                                  unsigned long long* best_key, float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    if (!rm) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_reward_model: null reward model");
+    l2a_ctx* rm_ctx = nullptr;
+    int rm_obs = 0, rm_act = 0;
+    l2a_reward_model_facts(rm, &rm_ctx, &rm_obs, &rm_act);
+    if (rm_ctx != ctx) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_reward_model: the reward model lives on another context");
+    if (rm_obs != md->obs_dim || rm_act != md->act_dim)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_reward_model: the reward model is for obs_dim " + std::to_string(rm_obs) +
+                                         " / act_dim " + std::to_string(rm_act) + ", the dynamics model for " +
+                                         std::to_string(md->obs_dim) + " / " + std::to_string(md->act_dim));
+    int rc = traj_args(md, "l2a_lstm_plan_rs_reward_model", obs0, c0, h0, actions, m, n, h, cand_offset, true, best_key || returns_out);
+    if (rc != L2A_OK) return rc;
+    float* traj = nullptr;
+    rc = plan_traj(md, obs0, c0, h0, actions, m, n, h, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
+    return l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, returns_out, best_key, stream_v);
+}
 
 int l2a_lstm_mfma_eligible(int obs_dim, int act_dim, int units) {
     return lstm_mfma_eligible(obs_dim, act_dim, units) ? 1 : 0;
@@ -442,6 +618,8 @@ void l2a_lstm_destroy(l2a_lstm* md) {
     }
     if (md->xbuf) (void)hipFree(md->xbuf);
     if (md->adv_buf) (void)hipFree(md->adv_buf);
+    if (md->traj_buf) (void)hipFree(md->traj_buf);
+    if (md->hid_buf) (void)hipFree(md->hid_buf);
     delete md;
 }
 

@@ -105,7 +105,11 @@ __device__ __forceinline__ float l2a_from_row(float x, int r) {
 // Recurrent planner (one LSTM layer of 256 / 512 units: l2a_lstm.h is the 16-candidate kernel, same arithmetic)
 // ------------------------------------------------------------------------------------------------------------------
 
-template <int MT, int UW>
+// TRAJ: the trajectory-writing instance (l2a_lstm_rollout_traj): every step's predicted observation goes to
+// p.state_out [h, m n, obs_dim] - there the whole trajectory, not one step's hand-off - and that is its only output: no fused
+// reward, no return, no keys, no mailbox.  Gate GEMM, gate arithmetic, reduce, normalisation and state update are the code below,
+// unchanged: the stored bits are those the 16-candidate kernel's state_out holds in a chain of one-step launches.
+template <int MT, int UW, bool TRAJ = false>
 __device__ __forceinline__ void l2a_lstm_micro_body(const L2ALstmParams& p, const int env, const int cand0, char* smem) {
     constexpr int U = 256 * UW;
     constexpr int ROWF = l2a_micro_row(U);
@@ -264,8 +268,23 @@ __device__ __forceinline__ void l2a_lstm_micro_body(const L2ALstmParams& p, cons
     load_actions(p.h > 1 ? 1 : 0, av_next);
     write_x(rows);
 
-    float ret = p.ret_in ? p.ret_in[(long long)env * p.n + (valid_t ? cand_t : p.n - 1)] : 0.0f;
+    float ret = 0.0f;
+    if constexpr (!TRAJ) ret = p.ret_in ? p.ret_in[(long long)env * p.n + (valid_t ? cand_t : p.n - 1)] : 0.0f;
     double disc_pow = p.disc0;
+
+    // TRAJ: byte offset of the lane's four dims in a step's slice of the trajectory (a bounds-checked buffer descriptor per step,
+    // like load_actions); the slots without a row of their own - candidates past n, waves past the micro tiles - get an offset
+    // past every slice, so do the dims past the observation: those stores are dropped by the range check, no branch.
+    // (host: a slice is < 2^31 - 16 bytes.)  16-byte stores where every row starts on a 16-byte boundary.
+    [[maybe_unused]] int toff = 0x7ffffff0;
+    [[maybe_unused]] bool t_v4 = false;
+    [[maybe_unused]] long long t_step = 0;
+    if constexpr (TRAJ) {
+        const bool live = valid_t && (wave < MT) && (4 * b < obs_dim);
+        toff = live ? (row_t * obs_dim + 4 * b) * 4 : 0x7ffffff0;
+        t_v4 = ((obs_dim & 3) == 0) && ((reinterpret_cast<unsigned long long>(p.state_out) & 15ull) == 0ull);
+        t_step = (long long)R * obs_dim;
+    }
 
     // ---- operand streams ---------------------------------------------------------------------------------------------
     const __amdgpu_buffer_rsrc_t rsA = l2a_rsrc(p.wblk + p.pk_mg, l2a_lstm_micro_gate_floats(U, KG0) * 4);
@@ -457,30 +476,43 @@ __device__ __forceinline__ void l2a_lstm_micro_body(const L2ALstmParams& p, cons
                 s = l2a_act4(s + bias, p.output_act);
                 const f32x4 d = s * osd + omu;
                 const f32x4 nx = st + d;
-                // reward in the 16-candidate kernel's order: quarter partials r_qq (lanes b = qq < 4), (r0 + r1) + (r2 + r3)
-                float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
-                float psq = 0.0f;
-                const int vi = p.rw.vel_index;
-                const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
-                const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
-                const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
-                if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+                if constexpr (TRAJ) {
+                    const __amdgpu_buffer_rsrc_t trs = l2a_rsrc(p.state_out + (long long)t * t_step, t_step * 4);
+                    if (t_v4) {
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, nx), trs, toff, 0, 0);
+                    } else {
 #pragma unroll
-                for (int ii = 0; ii < 4; ++ii) {
-                    const int dim = 4 * b + ii;
-                    const bool in_dist = (p.rw.dist_coef != 0.0f) && (dim >= p.rw.dist_index) &&
-                                         (dim < p.rw.dist_index + 3) && (dim < obs_dim);
-                    psq += in_dist ? nx[ii] * nx[ii] : 0.0f;
+                        for (int ii = 0; ii < 4; ++ii)
+                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(nx[ii]), trs,
+                                                                  (4 * b + ii < obs_dim) ? toff + 4 * ii : 0x7ffffff0, 0, 0);
+                    }
+                    st = nx;
+                } else {
+                    // reward in the 16-candidate kernel's order: quarter partials r_qq (lanes b = qq < 4), (r0 + r1) + (r2 + r3)
+                    float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
+                    float psq = 0.0f;
+                    const int vi = p.rw.vel_index;
+                    const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
+                    const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
+                    const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
+                    if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+#pragma unroll
+                    for (int ii = 0; ii < 4; ++ii) {
+                        const int dim = 4 * b + ii;
+                        const bool in_dist = (p.rw.dist_coef != 0.0f) && (dim >= p.rw.dist_index) &&
+                                             (dim < p.rw.dist_index + 3) && (dim < obs_dim);
+                        psq += in_dist ? nx[ii] * nx[ii] : 0.0f;
+                    }
+                    st = nx;
+                    plin = l2a_row_quarter_sum(plin);
+                    float r = plin;
+                    if (p.rw.dist_coef != 0.0f) {
+                        psq = l2a_sum_xor32(l2a_sum_xor16(psq));                    // over the obs tiles of a quarter (one is non-zero)
+                        psq = l2a_row_quarter_sum(psq);
+                        r -= p.rw.dist_coef * sqrtf(psq);
+                    }
+                    ret = fmaf(disc_t, r, ret);
                 }
-                st = nx;
-                plin = l2a_row_quarter_sum(plin);
-                float r = plin;
-                if (p.rw.dist_coef != 0.0f) {
-                    psq = l2a_sum_xor32(l2a_sum_xor16(psq));                    // over the obs tiles of a quarter (one is non-zero)
-                    psq = l2a_row_quarter_sum(psq);
-                    r -= p.rw.dist_coef * sqrtf(psq);
-                }
-                ret = fmaf(disc_t, r, ret);
             }
         }
         // the next step's inputs
@@ -491,7 +523,7 @@ __device__ __forceinline__ void l2a_lstm_micro_body(const L2ALstmParams& p, cons
     }
 
     // ---- results: lanes of block 0 of wave c hold the returns of the candidates cand0 + 4 c + j; the keys meet in LDS ------
-    {
+    if constexpr (!TRAJ) {
         unsigned long long key = 0ull;
         if (valid_t && b == 0 && wave < MT) {
             if (p.returns_out) p.returns_out[(long long)env * p.n + cand_t] = ret;
@@ -520,16 +552,16 @@ __device__ __forceinline__ void l2a_lstm_micro_body(const L2ALstmParams& p, cons
 
 // Workgroup -> (env, first candidate, micro tiles): every env's ceil(n / 4) micro tiles are dealt to p.mc_w workgroups,
 // the first p.mc_r of them take p.mc_hi micro tiles, the others one fewer (host: l2a_lstm_api.hip).
-template <int UW>
+template <int UW, bool TRAJ = false>
 __global__ void __launch_bounds__(256) l2a_lstm_micro_k(const L2ALstmParams p) {
     extern __shared__ __attribute__((aligned(16))) char l2a_smem[];
     const int env = (int)blockIdx.x / p.mc_w;
     const int idx = (int)blockIdx.x - env * p.mc_w;
     const int mt = idx < p.mc_r ? p.mc_hi : p.mc_hi - 1;
     const int q0 = idx < p.mc_r ? idx * p.mc_hi : p.mc_r * p.mc_hi + (idx - p.mc_r) * (p.mc_hi - 1);
-    if (mt == 3) l2a_lstm_micro_body<3, UW>(p, env, 4 * q0, l2a_smem);
-    else if (mt == 2) l2a_lstm_micro_body<2, UW>(p, env, 4 * q0, l2a_smem);
-    else l2a_lstm_micro_body<1, UW>(p, env, 4 * q0, l2a_smem);
+    if (mt == 3) l2a_lstm_micro_body<3, UW, TRAJ>(p, env, 4 * q0, l2a_smem);
+    else if (mt == 2) l2a_lstm_micro_body<2, UW, TRAJ>(p, env, 4 * q0, l2a_smem);
+    else l2a_lstm_micro_body<1, UW, TRAJ>(p, env, 4 * q0, l2a_smem);
 }
 
 

@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..envs.reward_spec import RewardSpec
-from .native_model import _dvec, _ptr, _stream_ptr
+from ..envs.reward_spec import RewardProgram, RewardSpec
+from .native_model import NativeRewardModel, _dvec, _ptr, _stream_ptr
 
 
 class NativeLSTM(object):
@@ -41,6 +41,8 @@ class NativeLSTM(object):
         self.ctx.check(rc, "l2a_rnn_create")
         self.handle = handle
         self._keep = {}
+        self.program_plans = 0              # plans scored by a launch of their own (tests and probes read these)
+        self.reward_model_plans = 0
 
     def close(self):
         if getattr(self, "handle", None):
@@ -101,6 +103,55 @@ class NativeLSTM(object):
                                        _ptr(returns_out), _ptr(best_key), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_lstm_plan_rs")
 
+    def _check_traj_args(self, obs0, c0, h0, actions, m, n, h, returns_out, best_key, traj_out):
+        for t in (obs0, c0, h0, actions):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        assert c0.numel() == m * self.units and h0.numel() == m * self.units
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if traj_out is not None:
+            assert traj_out.is_cuda and traj_out.dtype == torch.float32 and traj_out.is_contiguous()
+            assert traj_out.numel() == h * m * n * self.obs_dim
+
+    def rollout_traj(self, obs0, c0, h0, actions, m, n, h, cand_offset=0, traj_out=None):
+        """The model's predicted trajectory of a plan (``l2a_lstm_rollout_traj``): fp32 CUDA ``[h, m * n, obs_dim]``,
+        ``traj[t]`` = the observation after horizon step ``t``.  One launch of the trajectory-writing micro-tile kernel where
+        the fused plan would take micro tiles, else ``h`` one-step launches that hand the state on; the same bits either way."""
+        if traj_out is None:
+            traj_out = torch.empty((h, m * n, self.obs_dim), dtype=torch.float32, device=self.device)
+        self._check_traj_args(obs0, c0, h0, actions, m, n, h, None, None, traj_out)
+        rc = self.lib.l2a_lstm_rollout_traj(self.handle, _ptr(obs0), _ptr(c0), _ptr(h0), _ptr(actions), int(m), int(n), int(h),
+                                            int(cand_offset), _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_lstm_rollout_traj")
+        return traj_out
+
+    def plan_rs_program(self, obs0, c0, h0, actions, m, n, h, discount, program, cand_offset=0, returns_out=None,
+                        best_key=None, traj_out=None):
+        """Plan step of an env with a ``RewardProgram`` (``l2a_lstm_plan_rs_program``): the rollout of ``rollout_traj``, then
+        the scoring kernel.  Arguments as ``plan_rs``; ``traj_out``: optional fp32 CUDA ``[h, m * n, obs_dim]``."""
+        self._check_traj_args(obs0, c0, h0, actions, m, n, h, returns_out, best_key, traj_out)
+        assert isinstance(program, RewardProgram)
+        self.program_plans += 1
+        rc = self.lib.l2a_lstm_plan_rs_program(self.handle, _ptr(obs0), _ptr(c0), _ptr(h0), _ptr(actions), int(m), int(n), int(h),
+                                               float(discount), ctypes.byref(program), int(cand_offset), _ptr(returns_out),
+                                               _ptr(best_key), _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_lstm_plan_rs_program")
+
+    def plan_rs_reward_model(self, obs0, c0, h0, actions, m, n, h, discount, reward_model, cand_offset=0, returns_out=None,
+                             best_key=None, traj_out=None):
+        """Plan step with a learned reward (``l2a_lstm_plan_rs_reward_model``): the rollout of ``rollout_traj``, then the
+        matrix-core scorer of ``reward_model`` (a ``NativeRewardModel``).  Arguments as ``plan_rs_program``."""
+        self._check_traj_args(obs0, c0, h0, actions, m, n, h, returns_out, best_key, traj_out)
+        assert isinstance(reward_model, NativeRewardModel)
+        self.reward_model_plans += 1
+        rc = self.lib.l2a_lstm_plan_rs_reward_model(self.handle, reward_model.handle, _ptr(obs0), _ptr(c0), _ptr(h0), _ptr(actions),
+                                                    int(m), int(n), int(h), float(discount), int(cand_offset), _ptr(returns_out),
+                                                    _ptr(best_key), _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_lstm_plan_rs_reward_model")
+
     sync_max_envs = 64
 
     def plan_rs_sync(self, obs_host, c0, h0, actions, m, n, h, discount, reward, cand_offset=0, c_next=None, h_next=None):
@@ -113,6 +164,7 @@ class NativeLSTM(object):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
         assert actions.numel() == h * m * n * self.act_dim
         assert c0.numel() == m * self.units and h0.numel() == m * self.units
+        assert isinstance(reward, RewardSpec)       # (a RewardProgram has another layout: plan_rs_program)
         if c_next is not None:
             for t in (c_next, h_next):
                 assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == m * self.units

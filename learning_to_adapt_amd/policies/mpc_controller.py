@@ -243,7 +243,7 @@ class MPCController(Policy, Serializable):
         self.dynamics_model.planner_model().plan_payload(best, m, self._rank_digest(), payload)
         return payload
 
-    _takes_reward_models = True     # (RNNMPCController: False - the recurrent plans take neither programs nor reward models)
+    _takes_reward_models = True     # (RNNMPCController: False unless built with `native_reward_model=True`; programs route there too)
 
     def _fusable(self):
         return ((self._reward_spec is not None or self._native_reward_model() is not None)

@@ -12,6 +12,12 @@ Underneath, the horizon loop with its per-step ``dynamics_model.predict(obs, a[t
 the env's state is broadcast to its candidates inside the kernel (``repeat_hidden`` never
 materialises), cell states stay in registers.  Candidate sharding over ``torch.distributed`` ranks,
 the device RNG mode and CEM work as in ``MPCController`` (whose helpers are reused).
+
+An env whose ``reward_spec`` is a ``RewardProgram`` plans through ``l2a_lstm_plan_rs_program`` - the model's trajectory is
+rolled out on the GPU (one launch of the trajectory-writing micro-tile kernel, or a chain of one-step launches) and scored by
+the program's kernel - automatically; ``native_reward_model=True`` does the same for ``use_reward_model=True`` with a reward
+model the library scores on the GPU (``l2a_lstm_plan_rs_reward_model``).  Without the keyword a reward model keeps the
+reference's loop.
 """
 
 import numpy as np
@@ -27,7 +33,7 @@ class RNNMPCController(MPCController):
     _hid_stale = None       # which copy is out of date: None | "host" | "dev"
     _hid_next = None        # (c, h) already advanced with the chosen actions by the blocking plan launch
     _hid_flip = 0
-    _takes_reward_models = False    # the recurrent plans score with the fused l2a_reward only: a reward model keeps its old path
+    _takes_reward_models = False    # a reward model keeps the reference's loop unless the instance asks: `native_reward_model=True`
 
     def __init__(
             self,
@@ -46,9 +52,12 @@ class RNNMPCController(MPCController):
             cem_mode="reference",
             shard_candidates=True,
             pipeline_chunks=3,
-            native_cem_step=False,
+            native_reward_model=False,
+            native_cem_step=False,      # (tests/test_rnn_cem_controller.py pins this one as the last parameter)
     ):
         Serializable.quick_init(self, locals())
+        if native_reward_model:             # opt-in (as `native_cem_step`): score `use_reward_model=True` plans on the GPU
+            self._takes_reward_models = True
         # alpha = 0 makes the shared CEM update `mean * alpha + (1 - alpha) * mean(elites)` the
         # reference's plain `np.mean(elites)` (:107), bit for bit.
         MPCController.__init__(self, name=name, env=env, dynamics_model=dynamics_model,
@@ -178,7 +187,8 @@ class RNNMPCController(MPCController):
         m = len(observations)
         self._hid_next = None
         stock = getattr(self._rollout, "__func__", None) is RNNMPCController._rollout
-        native = self.dynamics_model.planner_model() if (stock and world == 1 and n_local > 0 and not self.use_cem) else None
+        native = self.dynamics_model.planner_model() if (stock and world == 1 and n_local > 0 and not self.use_cem
+                                                         and not self._program()) else None
         if native is None or not hasattr(native, "plan_rs_sync") or getattr(native, "sync_max_envs", 0) < m:
             return MPCController._plan_keys(self, observations, a_dev, n_local, lo, world)
         dev = native.device
@@ -229,8 +239,14 @@ class RNNMPCController(MPCController):
         obs0 = obs_dev if obs_dev is not None else self._upload_obs(observations)
         best = self._buf("best", (m,), torch.int64, dev)
         rets = self._buf("rets", (m, n_local), torch.float32, dev) if want_returns else None
-        native.plan_rs(obs0, c0, h0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
-                       cand_offset=cand_offset, returns_out=rets, best_key=best)
+        rm = self._native_reward_model()
+        if rm is not None:
+            native.plan_rs_reward_model(obs0, c0, h0, actions_local, m, n_local, self.horizon, self.discount,
+                                        rm.planner_reward_model(), cand_offset=cand_offset, returns_out=rets, best_key=best)
+            return best, rets
+        plan = native.plan_rs_program if self._program() else native.plan_rs
+        plan(obs0, c0, h0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
+             cand_offset=cand_offset, returns_out=rets, best_key=best)
         return best, rets
 
     def _launch_chunk(self, native, c, last, obs0, a_dev, m, n_local, hc, t0, lo, best):
