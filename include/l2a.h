@@ -333,8 +333,15 @@ int l2a_plan_rs_program(l2a_model* model, const float* obs0, const float* action
  * l2a_plan_rs_reward_model: the carry chain of l2a_plan_rs_program - h one-step launches of the rollout kernels through
  * traj_out (or the model's own buffer) - followed by l2a_score_trajectory_model.  `rm` and `model` must live on the same
  * context and agree on obs_dim and act_dim (L2A_EINVAL).  A flagged tile-split launch anywhere in the chain flags the
- * call (l2a_launch_status), as for l2a_plan_rs_program.                                                              */
+ * call (l2a_launch_status), as for l2a_plan_rs_program.
+ * l2a_reward_model_geometry: host only, needs no GPU - the scorer's launcher decision (its own function, on plain integers)
+ * for `rows` = m * n candidates over `h` steps on a device of `num_cu` CUs (<= 0: 256) and `lds_per_block` bytes of LDS per
+ * workgroup.  out[8] = { RT row tiles per pass, CT candidate tiles per workgroup, S steps per pass (CT * S = RT),
+ * workgroups = ceil(rows / (16 CT)), passes = ceil(h / S), dynamic LDS bytes, 0, 0 }.  L2A_EINVAL for a NULL out, rows < 1,
+ * h < 1, a model l2a_reward_model_check refuses, or an LDS size that no geometry fits.  Any geometry gives the same bits. */
 int l2a_reward_model_check(int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act);
+int l2a_reward_model_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, long long rows, int h, int num_cu,
+                              int lds_per_block, int* out);
 int l2a_reward_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act,
                             l2a_reward_model** out);
 void l2a_reward_model_destroy(l2a_reward_model* rm);

@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = (
     "l2a_model_create", "l2a_model_destroy", "l2a_model_set_weights", "l2a_model_set_weights_strided",
     "l2a_model_set_norm", "l2a_model_adapt_sgd", "l2a_model_adapt_sgd_host", "l2a_model_adapt_sgd_raw", "l2a_model_get_weights",
     "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_reward_program_check", "l2a_score_trajectory", "l2a_plan_rs_program",
-    "l2a_reward_model_check", "l2a_reward_model_create", "l2a_reward_model_destroy", "l2a_reward_model_set_weights", "l2a_reward_model_set_norm",
+    "l2a_reward_model_check", "l2a_reward_model_geometry", "l2a_reward_model_create", "l2a_reward_model_destroy", "l2a_reward_model_set_weights", "l2a_reward_model_set_norm",
     "l2a_reward_model_predict", "l2a_score_trajectory_model", "l2a_plan_rs_reward_model", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
     "l2a_packed_layer_floats", "l2a_pack_layer_host", "l2a_micro_layout_floats", "l2a_micro_pack_layer_host",
     "l2a_comm_unique_id", "l2a_comm_init", "l2a_comm_destroy", "l2a_allreduce_best", "l2a_plan_payload",
@@ -97,6 +97,20 @@ def reward_model_check(obs_dim, act_dim, hidden, hidden_act):
     code = hidden_act if isinstance(hidden_act, int) else ACT_CODES.get(hidden_act, -1)
     rc = lib.l2a_reward_model_check(int(obs_dim), int(act_dim), len(hidden), hid, int(code))
     return None if rc == L2A_OK else lib.l2a_last_error(None).decode()
+
+
+def reward_model_geometry(obs_dim, act_dim, hidden, rows, h, cus=0, lds_per_block=160 * 1024):
+    """The launch geometry of the reward-model scorer (``l2a_reward_model_geometry``: the launcher's own decision function, no
+    GPU needed) for ``rows`` candidates over ``h`` steps on ``cus`` CUs (0: 256) with ``lds_per_block`` bytes of LDS.  Returns a
+    dict: RT (row tiles per pass), CT (candidate tiles per workgroup), S (steps per pass), workgroups, passes, lds_bytes."""
+    lib = load()
+    hid = (ctypes.c_int * max(len(hidden), 1))(*[int(x) for x in hidden])
+    out = (ctypes.c_int * 8)()
+    rc = lib.l2a_reward_model_geometry(int(obs_dim), int(act_dim), len(hidden), hid, int(rows), int(h), int(cus), int(lds_per_block), out)
+    if rc != L2A_OK:
+        raise L2AError("l2a_reward_model_geometry failed (%d): %s" % (rc, lib.l2a_last_error(None).decode()))
+    v = list(out)
+    return dict(RT=v[0], CT=v[1], S=v[2], workgroups=v[3], passes=v[4], lds_bytes=v[5])
 
 
 _lib = None
@@ -200,6 +214,9 @@ def load():
     if hasattr(lib, "l2a_reward_model_create"):         # (absent from older variant libraries selected with L2A_LIB_PATH)
         lib.l2a_reward_model_check.argtypes = [i32, i32, i32, c.POINTER(i32), i32]
         lib.l2a_reward_model_check.restype = i32
+        if hasattr(lib, "l2a_reward_model_geometry"):
+            lib.l2a_reward_model_geometry.argtypes = [i32, i32, i32, c.POINTER(i32), c.c_longlong, i32, i32, i32, c.POINTER(i32)]
+            lib.l2a_reward_model_geometry.restype = i32
         lib.l2a_reward_model_create.argtypes = [vp, i32, i32, i32, c.POINTER(i32), i32, c.POINTER(vp)]
         lib.l2a_reward_model_create.restype = i32
         lib.l2a_reward_model_destroy.argtypes = [vp]

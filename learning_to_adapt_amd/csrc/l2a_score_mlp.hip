@@ -281,15 +281,24 @@ struct l2a_reward_model {
 namespace {
 
 // Launch geometry: RT row tiles per pass (accumulator and LDS budget), of them S steps x CT candidate tiles.  Any choice gives
-// the same bits; this one minimises (rounds of workgroups) x (passes) x (pass cost ~ RT + 2).
-void choose_geometry(const l2a_reward_model* rm, long long rows, int h, int* rt_out, int* ct_out, int* s_out) {
+// the same bits; this one minimises (rounds of workgroups) x (passes) x (pass cost ~ RT + 2).  Plain integers, no context and
+// no HIP call: launch() and l2a_reward_model_geometry share it.  False (outputs untouched) when no RT fits the LDS.
+int rm_kgs(int n_hidden, const int* hidden, int obs_dim, int act_dim) {
+    int kgs = l2a_ceil_div(2 * obs_dim + act_dim, 16);
+    for (int l = 0; l < n_hidden; ++l) kgs = hidden[l] / 16 > kgs ? hidden[l] / 16 : kgs;
+    return kgs;
+}
+
+bool choose_geometry(int n_hidden, const int* hidden, int obs_dim, int act_dim, long long rows, int h, int num_cu,
+                     int lds_per_block, int* rt_out, int* ct_out, int* s_out) {
     int tpw_max = 1;
-    for (int l = 0; l < rm->n_hidden; ++l) tpw_max = rm->hidden[l] / 64 > tpw_max ? rm->hidden[l] / 64 : tpw_max;
-    const int cus = rm->ctx->num_cu > 0 ? rm->ctx->num_cu : 256;
+    for (int l = 0; l < n_hidden; ++l) tpw_max = hidden[l] / 64 > tpw_max ? hidden[l] / 64 : tpw_max;
+    const int kgs = rm_kgs(n_hidden, hidden, obs_dim, act_dim);
+    const int cus = num_cu > 0 ? num_cu : 256;
     long long best_cost = -1;
     for (int rt = 8; rt >= 1; rt >>= 1) {
         if (rt * tpw_max > L2A_RM_MAX_ACC) continue;
-        if ((long long)rt * rm->kgs * 1024 + 4096 > rm->ctx->lds_per_block) continue;
+        if ((long long)rt * kgs * 1024 + 4096 > lds_per_block) continue;
         for (int s = rt; s >= 1; s >>= 1) {
             if (s > 1 && s / 2 >= h) continue;          // steps per pass beyond the horizon are empty tiles
             const int ct = rt / s;
@@ -298,6 +307,7 @@ void choose_geometry(const l2a_reward_model* rm, long long rows, int h, int* rt_
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; *rt_out = rt; *ct_out = ct; *s_out = s; }
         }
     }
+    return best_cost >= 0;
 }
 
 // The function attribute is per (device, instance), not per model: it is raised ONCE to all the LDS a workgroup may take, so
@@ -325,7 +335,8 @@ int launch(l2a_reward_model* rm, L2ARMParams& p, hipStream_t stream) {
     p.n_hidden = rm->n_hidden; p.obs_dim = rm->obs_dim; p.act_dim = rm->act_dim; p.d_in = rm->d_in; p.KG0 = rm->KG0; p.kgs = rm->kgs;
     p.act = rm->act; p.sr = rm->sr; p.mur = rm->mur;
     int rt = 1, ct = 1, s = 1;
-    choose_geometry(rm, p.rows, p.h, &rt, &ct, &s);
+    (void)choose_geometry(rm->n_hidden, rm->hidden, rm->obs_dim, rm->act_dim, p.rows, p.h, rm->ctx->num_cu, rm->ctx->lds_per_block,
+                          &rt, &ct, &s);
     p.CT = ct; p.S = s;
     const unsigned blocks = (unsigned)(((long long)p.rows + 16 * ct - 1) / (16 * ct));
     switch (rt) {
@@ -357,6 +368,24 @@ int l2a_reward_model_check(int obs_dim, int act_dim, int n_hidden, const int* hi
     return L2A_OK;
 }
 
+int l2a_reward_model_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, long long rows, int h, int num_cu,
+                              int lds_per_block, int* out) {
+    if (!out || rows < 1 || h < 1) return L2A_EINVAL;
+    const int rc = l2a_reward_model_check(obs_dim, act_dim, n_hidden, hidden, L2A_ACT_RELU);
+    if (rc != L2A_OK) return rc;
+    int rt = 1, ct = 1, s = 1;
+    if (!choose_geometry(n_hidden, hidden, obs_dim, act_dim, rows, h, num_cu, lds_per_block, &rt, &ct, &s))
+        return l2a_fail(nullptr, L2A_EINVAL, "reward model: no launch geometry fits " + std::to_string(lds_per_block) + " bytes of LDS");
+    const long long wgs = (rows + 16 * ct - 1) / (16 * ct);
+    if (wgs > 0x7fffffffLL) return l2a_fail(nullptr, L2A_EINVAL, "reward model: too many rows");
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = rt; out[1] = ct; out[2] = s;
+    out[3] = (int)wgs;
+    out[4] = (h + s - 1) / s;
+    out[5] = rt * rm_kgs(n_hidden, hidden, obs_dim, act_dim) * 1024;
+    return L2A_OK;
+}
+
 int l2a_reward_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act,
                             l2a_reward_model** out) {
     if (!ctx || !out) return L2A_EINVAL;
@@ -366,12 +395,12 @@ int l2a_reward_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden
     rm->ctx = ctx;
     rm->obs_dim = obs_dim; rm->act_dim = act_dim; rm->d_in = 2 * obs_dim + act_dim; rm->KG0 = l2a_ceil_div(rm->d_in, 16);
     rm->n_hidden = n_hidden; rm->act = hidden_act;
-    rm->kgs = rm->KG0;
+    rm->kgs = rm_kgs(n_hidden, hidden, obs_dim, act_dim);
     long long off = 0;
     int kg = rm->KG0;
     for (int l = 0; l <= n_hidden; ++l) {
         const int n_out = l < n_hidden ? hidden[l] : 1;
-        if (l < n_hidden) { rm->hidden[l] = hidden[l]; rm->kgs = hidden[l] / 16 > rm->kgs ? hidden[l] / 16 : rm->kgs; }
+        if (l < n_hidden) rm->hidden[l] = hidden[l];
         rm->pk[l] = off;
         off += (long long)l2a_ceil_div(n_out, 16) * kg * 256;
         rm->bias[l] = off;

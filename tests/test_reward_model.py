@@ -1,4 +1,5 @@
-"""Learned reward models without a GPU: the library's host-only eligibility check, the ABI, the float64 restatement of
+"""Learned reward models without a GPU: the library's host-only eligibility check, the ABI, the scorer's launch geometry
+(``l2a_reward_model_geometry`` over the table of tests/reward_model_geometries.py), the float64 restatement of
 the model's semantics against a ``torch`` module, ``MLPRewardModel.fit``, and the controller's routing with the native
 calls stubbed."""
 
@@ -12,6 +13,7 @@ import torch
 import cases
 import oracle_backend
 import reward_model_cases as rmc
+import reward_model_geometries as rmg
 from learning_to_adapt_amd import _lib
 from learning_to_adapt_amd.dynamics import MLPRewardModel
 from learning_to_adapt_amd.envs import SyntheticEnv
@@ -74,6 +76,107 @@ def test_new_symbols_are_exported():
     for name in NEW_SYMBOLS:
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name), name
     assert not hasattr(lib, "l2a_reward_model_facts")       # internal to the library
+
+
+# ------------------------------------------------------------------------------------------
+# 1b. the scorer's launch geometry (l2a_reward_model_geometry: the launcher's own function, no GPU)
+# ------------------------------------------------------------------------------------------
+def _geo(obs, act, hidden, rows, h, cus, lds=rmg.LDS):
+    g = _lib.reward_model_geometry(obs, act, hidden, rows, h, cus=cus, lds_per_block=lds)
+    return (g["RT"], g["CT"], g["S"]), g
+
+
+@pytest.mark.parametrize("cus", rmg.CUS)
+@pytest.mark.parametrize("row", rmg.ROWS, ids=lambda r: r.id)
+def test_every_table_row_takes_its_geometry(row, cus):
+    n = rmg.plan_n(row, cus)
+    rows = row.m * n
+    assert rows >= row.a * 16 * cus + row.b and (row.m == 1 or n % 16) and rows < row.a * 16 * cus + row.b + 2 * row.m
+    geo, g = _geo(row.obs, row.act, row.hidden, rows, row.h, cus)
+    assert geo == row.expect
+    RT, CT, S = geo
+    assert g["workgroups"] == -(-rows // (16 * CT)) and g["passes"] == -(-row.h // S)
+    kgs = max([-(-(2 * row.obs + row.act) // 16)] + [w // 16 for w in row.hidden])
+    assert g["lds_bytes"] == RT * kgs * 1024
+    # what the row is there for: a ragged candidate tile in the last workgroup, and empty ones behind it at CT >= 2
+    if row.m == 1:
+        last = rows - (g["workgroups"] - 1) * 16 * CT
+        assert last % 16 == 5 and (CT == 1 or last < 16 * (CT - 1))
+
+
+def test_the_table_covers_every_geometry_width_and_activation():
+    assert sorted(rmg.GEOMETRIES) == sorted({(rt, rt // s, s) for rt in (1, 2, 4, 8) for s in (1, 2, 4, 8) if rt % s == 0})
+    assert len(rmg.GEOMETRIES) == 10 and {r.expect for r in rmg.ROWS} == set(rmg.GEOMETRIES)
+    assert len({r.id for r in rmg.ROWS}) == len(rmg.ROWS)
+    widths = {w for r in rmg.ROWS for w in r.hidden}
+    assert {64, 128, 192, 256, 320, 384, 448, 512} <= widths
+    assert {(3, 1), (17, 5), (20, 6), (41, 8), (64, 16)} <= {(r.obs, r.act) for r in rmg.ROWS}
+    assert {(64, 512), (512, 64), (128, 448, 64)} <= {r.hidden for r in rmg.ROWS}
+    assert any(-(-(2 * r.obs + r.act) // 16) > max(r.hidden) // 16 for r in rmg.ROWS)         # kgs = KG0
+    acts = {"identity", "relu", "tanh", "sigmoid", "swish"}
+    assert {r.activation for r in rmg.ROWS if r.h > r.expect[2]} == acts                         # on a multi-pass row
+    assert {r.activation for r in rmg.ROWS if r.expect[1] > 1} == acts                           # on a CT > 1 row
+    assert {r.expect[1] for r in rmg.ROWS if r.m == 3 and r.expect[1] > 1} == {2, 4, 8}         # env boundaries in a workgroup
+    for r in rmg.ROWS:
+        assert r.a == 0 or len(r.hidden) <= 2                                                   # large-row cases stay shallow
+    twin = rmg.by_id(rmg.PREDICT[0])
+    assert twin.expect == (8, 8, 1) and twin.m == 1 and twin.h == 1
+    assert any(r.expect == (8, 8, 1) and r.m == 3 and r.h == 1 and r.id not in rmg.PREDICT for r in rmg.ROWS)
+
+
+WIDTH_CLASSES = [(20, 6, (64 * t,)) for t in range(1, 9)] + [(64, 16, (64,)), (20, 6, (64, 512)), (41, 8, (128, 448, 64)),
+                                                               (3, 1, (256, 256))]
+
+
+@pytest.mark.parametrize("obs,act,hidden", WIDTH_CLASSES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_geometry_properties_over_a_sweep(obs, act, hidden):
+    tpw = max(hidden) // 64
+    kgs = max([-(-(2 * obs + act) // 16)] + [w // 16 for w in hidden])
+    rows_sweep = sorted(set(list(range(1, 70001, 997)) + [16 * k * cus + d for cus in rmg.CUS for k in range(1, 9)
+                                                          for d in (-1, 0, 1, 37) if 0 < 16 * k * cus + d <= 70000] + [70000]))
+    seen = set()
+    for cus in rmg.CUS:
+        for rows in rows_sweep:
+            for h in range(1, 34):
+                (RT, CT, S), g = _geo(obs, act, hidden, rows, h, cus)
+                assert CT * S == RT and RT in (1, 2, 4, 8)
+                assert RT * tpw <= 32
+                assert RT * kgs * 1024 + 4096 <= rmg.LDS
+                assert S == 1 or S // 2 < h
+                assert g["workgroups"] == -(-rows // (16 * CT)) and g["passes"] == -(-h // S)
+                seen.add((RT, CT, S))
+    assert seen <= set(rmg.GEOMETRIES) and max(g[0] for g in seen) == max(rt for rt in (1, 2, 4, 8) if rt * tpw <= 32)
+
+
+def test_the_geometries_design_quotes():
+    """DESIGN section 4.9, a (256, 256) net on 256 CUs: config 2 runs 125 workgroups x 4 passes of 8 steps, the config-1 shape
+    32 workgroups x 3 passes of 4 steps."""
+    geo, g = _geo(20, 6, (256, 256), 2000, 30, 256)
+    assert geo == (8, 1, 8) and g["workgroups"] == 125 and g["passes"] == 4 and g["lds_bytes"] == 128 * 1024
+    geo, g = _geo(20, 6, (256, 256), 500, 10, 256)
+    assert geo == (4, 1, 4) and g["workgroups"] == 32 and g["passes"] == 3
+    assert _geo(20, 6, (256, 256), 500, 10, 0) == (geo, g)                  # num_cu <= 0 means 256
+    assert _geo(20, 6, (256, 256), 500, 10, -3) == (geo, g)
+
+
+def test_geometry_rejects():
+    lib = _lib.load()
+    out = (ctypes.c_int * 8)()
+    hid = (ctypes.c_int * 2)(256, 256)
+    call = lambda **kw: lib.l2a_reward_model_geometry(*[kw.get(k, d) for k, d in (                      # noqa: E731
+        ("obs", 20), ("act", 6), ("n_hidden", 2), ("hidden", hid), ("rows", 500), ("h", 10), ("cus", 256), ("lds", rmg.LDS), ("out", out))])
+    assert call() == _lib.L2A_OK and list(out)[:5] == [4, 1, 4, 32, 3] and list(out)[6:] == [0, 0]
+    assert call(out=None) == _lib.L2A_EINVAL
+    assert call(rows=0) == _lib.L2A_EINVAL and call(rows=-5) == _lib.L2A_EINVAL
+    assert call(h=0) == _lib.L2A_EINVAL
+    assert call(hidden=None) == _lib.L2A_EINVAL
+    for kw, word in ((dict(obs=65), "obs_dim 65"), (dict(act=17), "act_dim 17"), (dict(n_hidden=0), "0 hidden layers"),
+                     (dict(n_hidden=4), "4 hidden layers"), (dict(hidden=(ctypes.c_int * 2)(256, 96)), "width 96")):
+        assert call(**kw) == _lib.L2A_EINVAL and word in lib.l2a_last_error(None).decode()
+    assert call(lds=8 * 1024) == _lib.L2A_EINVAL            # not even RT = 1 fits
+    with pytest.raises(_lib.L2AError, match="width 96"):
+        _lib.reward_model_geometry(20, 6, (96,), 100, 3)
+    assert "l2a_reward_model_geometry" in _lib.EXPORTED_SYMBOLS
 
 
 # ------------------------------------------------------------------------------------------
