@@ -35,8 +35,8 @@ int l2a_fail(const l2a_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
-struct l2a_model {
-    l2a_ctx* ctx = nullptr;
+// What the launch logic needs to know of a model's shape (model_shape fills it; set_stride: l2a_model_create) - no storage.
+struct l2a_mlp_shape {
     int obs_dim = 0, act_dim = 0, in_dim = 0;
     int n_hidden = 0;
     int hidden[L2A_MAX_LAYERS] = {0};
@@ -44,19 +44,21 @@ struct l2a_model {
     int n_sets = 1, mode = L2A_MODE_SINGLE;
     bool mfma_ok = false;
     int H = 0, TPW = 0, KG0 = 0, OT = 0, hmax = 0;
-    float* wblk = nullptr;
     long long set_stride = 0;
+    bool micro_ok = false;                        // the micro-tile kernel of l2a_micro.h has an instance (hidden width 256 / 512)
+    int m_o4 = 0;                                 // ... and sums dims 16 .. 19 per quarter of the hidden units, like the 16-candidate O4 instance
+};
+
+struct l2a_model : l2a_mlp_shape {
+    l2a_ctx* ctx = nullptr;
+    float* wblk = nullptr;
     long long raw_w[L2A_MAX_LAYERS] = {0};
     long long raw_b[L2A_MAX_LAYERS] = {0};
     long long pk_w0 = 0, pk_wmid = 0, pk_wmid_stride = 0, pk_wout = 0, pk_bout = 0, nm_off = 0;
-    bool micro_ok = false;                        // the micro-tile kernel of l2a_micro.h has an instance (hidden width 256 / 512)
-    int m_o4 = 0;                                 // ... and sums dims 16 .. 19 per quarter of the hidden units, like the 16-candidate O4 instance
-    long long pk_m = 0;                           // its copy of a set's weights (wave-stream order, l2a_micro_pack.h)
+    long long pk_m = 0;                           // the micro-tile kernel's copy of a set's weights (wave-stream order, l2a_micro_pack.h)
     std::vector<char> weights_set, norm_set;
     std::vector<std::vector<float>> norm_stage;   // host staging, kept alive for async H2D
-    unsigned long long* xbuf = nullptr;           // member-split exchange granules
-    long long xbuf_granules = 0;
-    unsigned int launch_nonce = 0;
+    l2a_xbuf xb;                                  // member-split exchange granules
     float* adapt_scratch = nullptr;               // l2a_model_adapt_sgd: layer inputs and dZ of every task
     long long adapt_scratch_floats = 0;
     float* prog_buf = nullptr;                    // l2a_plan_rs_program: [returns of the carry launches (rows) | trajectory (h x rows x obs_dim)]
@@ -103,67 +105,118 @@ int allow_big_lds(const l2a_ctx* ctx, K kernel, int bytes) {
     return L2A_OK;
 }
 
+// ---- the launch plan of a rollout: decided once by plan_rollout (pure host arithmetic: no HIP call, no environment, nothing
+//      written but the plan), then executed by launch_rollout or reported by l2a_plan_geometry ------------------------------
+
+// What the decision depends on beside the model and the request: the context's policies and device facts, and the two
+// developer switches of the environment (read once, here).
+struct l2a_rollout_policy {
+    int kernel_kind, split_policy, fan_policy, double_policy, micro_policy, batch_sets, xcd_align;
+    int num_cu, lds_per_block;
+    int force_nt;           // L2A_FORCE_NT=1 | 2: developer A/B of the NT choice (tools/ab_nt.py); 0 = choose_nt decides
+    bool dbg_front;         // L2A_DBG_FRONT=1: of two launches the double tiles in front write the phase stamps (launch_rollout)
+};
+
+l2a_rollout_policy rollout_policy(const l2a_ctx* ctx) {
+    static const int force_nt = [] { const char* e = std::getenv("L2A_FORCE_NT"); return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }();
+    static const bool dbg_front = [] { const char* e = std::getenv("L2A_DBG_FRONT"); return e && e[0] == '1'; }();
+    return {ctx->kernel_kind, ctx->split_policy, ctx->fan_policy, ctx->double_policy, ctx->micro_policy, ctx->batch_sets,
+            ctx->xcd_align, ctx->num_cu > 0 ? ctx->num_cu : 256, ctx->lds_per_block, force_nt, dbg_front};
+}
+
+struct l2a_rollout_request {
+    int mode, m, n, h;
+    bool obs_per_row, state_out, results;   // per-row start states | a state is written out | returns or keys are wanted
+};
+
+enum { L2A_FAMILY_VALU = 0, L2A_FAMILY_MFMA16 = 1, L2A_FAMILY_MICRO = 2 };     // (the numbers l2a_plan_geometry reports)
+
+// One kernel launch: the instance, its grid and LDS, and every geometry field of L2AKParams (fields a family does not read are 0).
+struct l2a_rollout_launch {
+    int family;
+    int nt, geo, gact;      // instance: candidate tiles per workgroup (16-candidate MFMA only), l2a_launch_mfma's geo, generic activations
+    unsigned grid;
+    int smem;
+    int c_lo, c_hi, sa_elems, tiles_per_env, cst_set, n_cst, lb, cst_off;
+    int split, split_from;
+    int pl_units, pl_f, pl_r, pl_w;
+    int mc_w, mc_hi, mc_r;
+    long long m_bytes;
+};
+
+struct l2a_rollout_plan {
+    int n_launch;                   // 1, or 2: the double tiles in front, then the rest
+    l2a_rollout_launch launch[2];
+    int done_total;                 // what the mailbox counts over both launches (0 = the one launch's own)
+    long long xbuf_bytes;           // exchange buffer the (last) launch needs; 0 = none
+};
+
 // Which tile-split flavour a model / policy allows: 2 = groups + shared middle (or only) set, 1 = whole
 // sets, 0 = none.
-int split_mode_for(const l2a_model* md, int e_loop) {
-    const int policy = md->ctx->split_policy;
+int split_mode_for(const l2a_mlp_shape& md, int policy, int e_loop) {
     if (policy == 0) return 0;
-    if ((e_loop & 1) && md->n_hidden >= 2 && policy == 1) return 2;
+    if ((e_loop & 1) && md.n_hidden >= 2 && policy == 1) return 2;
     return (e_loop >= 2) ? 1 : 0;
 }
 
 // Launch geometry of the MFMA kernel for (m, n): NT candidate tiles per workgroup.  Costs in units of
 // "one workgroup running one tile for the whole horizon": NT = 2 costs 1.9, a shared tail round ~0.8.
-int choose_nt(const l2a_model* md, int m, int n, int e_loop, int sa_bytes_nt2, int other_bytes_nt2) {
-    const int cus = md->ctx->num_cu > 0 ? md->ctx->num_cu : 256;
-    if (2 * sa_bytes_nt2 + other_bytes_nt2 > md->ctx->lds_per_block) return 1;
+int choose_nt(const l2a_mlp_shape& md, const l2a_rollout_policy& pol, int m, int n, int e_loop, int sa_bytes_nt2, int other_bytes_nt2) {
+    const int cus = pol.num_cu;
+    if (2 * sa_bytes_nt2 + other_bytes_nt2 > pol.lds_per_block) return 1;
     // Two candidate tiles per workgroup pay only where their instance keeps its registers: at hidden width 512 every NT = 2
     // instance spilled (55 - 388 VGPRs to scratch) and lost to NT = 1 on every multi-round plan measured - Ant 2 x 512,
     // n = 8000: 2.51 against 2.13 ms, config 4's 16 000 candidates: 3.53 against 3.50 ms per 10 steps (profiles/r04_ab_nt.jsonl)
     // - and so do the 49 - 64-dimensional observations at width 256.  Those shapes run NT = 1 (whole rounds + a shared tail);
     // the (2, 8) instances are no longer built.
-    if (md->TPW >= 8 || md->OT >= 4) return 1;      // (no NT = 2 instance exists for OT >= 4: l2a_mfma_inst.hip)
-    static const int force_nt = [] { const char* e = std::getenv("L2A_FORCE_NT"); return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }();
-    if (force_nt) return force_nt;      // developer A/B (tools/ab_nt.py)
+    if (md.TPW >= 8 || md.OT >= 4) return 1;      // (no NT = 2 instance exists for OT >= 4: l2a_mfma_inst.hip)
+    if (pol.force_nt) return pol.force_nt;
     const long long wg1 = (long long)m * ceil_div(n, 16);
     const long long wg2 = (long long)m * ceil_div(n, 32);
     const long long t = wg1 % cus;
     double cost1 = (double)((wg1 + cus - 1) / cus);
-    if (wg1 > cus && t != 0 && 2 * t <= cus && split_mode_for(md, e_loop) != 0) cost1 = (double)(wg1 / cus) + 0.8;
+    if (wg1 > cus && t != 0 && 2 * t <= cus && split_mode_for(md, pol.split_policy, e_loop) != 0) cost1 = (double)(wg1 / cus) + 0.8;
     const double cost2 = (double)((wg2 + cus - 1) / cus) * 1.9;
     return (cost2 < cost1) ? 2 : 1;
 }
 
-int sa_elems_for(const l2a_model* md, int nt) {
-    const int ht = md->H / 16;
+int sa_elems_for(const l2a_mlp_shape& md, int nt) {
+    const int ht = md.H / 16;
     const int a = nt * ht;
-    const int b = L2A_NW * nt * md->OT;         // output-layer partials (one per wave)
+    const int b = L2A_NW * nt * md.OT;         // output-layer partials (one per wave)
     return (a > b ? a : b) * 64;
 }
 
-int launch_rollout(l2a_model* md, L2AKParams& p, void* stream_v) {
-    l2a_ctx* ctx = md->ctx;
-    l2a_device_guard guard(ctx->device);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    const int sets_needed = ctx->dry ? 0 : (p.mode == L2A_MODE_PER_BLOCK) ? (p.m < md->n_sets ? p.m : md->n_sets) : md->n_sets;
-    for (int e = 0; e < sets_needed; ++e) {
-        if (!md->weights_set[e]) return fail(ctx, L2A_ESTATE, "weight set " + std::to_string(e) + " was never set");
-        if (!md->norm_set[e]) return fail(ctx, L2A_ESTATE, "normalisation of set " + std::to_string(e) + " was never set");
+// The plan of one rollout request, or an error code with its message.
+int plan_rollout(const l2a_mlp_shape& md, const l2a_rollout_policy& pol, const l2a_rollout_request& rq, l2a_rollout_plan* plan,
+                 std::string* err) {
+    auto bad = [err](int code, const std::string& msg) { *err = msg; return code; };
+    *plan = l2a_rollout_plan();
+    plan->n_launch = 1;
+    if (rq.mode == L2A_MODE_PER_BLOCK && rq.m > md.n_sets)
+        return bad(L2A_EINVAL, "per-block mode needs one weight set per env/block");
+    int kind = pol.kernel_kind;
+    if (kind == L2A_KERNEL_AUTO) kind = md.mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
+    if (kind == L2A_KERNEL_MFMA && !md.mfma_ok)
+        return bad(L2A_EINVAL, "model shape is not eligible for the MFMA kernel "
+                               "(needs equal hidden widths of 128/256/512, obs_dim<=64, act_dim<=16)");
+    if (kind != L2A_KERNEL_MFMA) {
+        l2a_rollout_launch& d = plan->launch[0];
+        d.family = L2A_FAMILY_VALU;
+        d.c_hi = rq.n;
+        d.tiles_per_env = ceil_div(rq.n, L2A_VT);
+        d.smem = (md.in_dim + 2 * md.hmax + 3 * md.obs_dim + md.act_dim + 1) * L2A_VT * 4;
+        if (d.smem > pol.lds_per_block)
+            return bad(L2A_EINVAL, "LDS budget exceeded by the VALU kernel (" + std::to_string(d.smem) + " B)");
+        d.grid = (unsigned)(rq.m * d.tiles_per_env);
+        return L2A_OK;
     }
-    if (p.mode == L2A_MODE_PER_BLOCK && p.m > md->n_sets)
-        return fail(ctx, L2A_EINVAL, "per-block mode needs one weight set per env/block");
-    p.c_lo = 0; p.c_hi = p.n; p.done_total = 0;     // one launch covers the plan unless the MFMA branch below cuts it in two
-
-    int kind = ctx->kernel_kind;
-    if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
-    if (kind == L2A_KERNEL_MFMA && !md->mfma_ok)
-        return fail(ctx, L2A_EINVAL, "model shape is not eligible for the MFMA kernel "
-                                     "(needs equal hidden widths of 128/256/512, obs_dim<=64, act_dim<=16)");
 
     // ---- matrix-core kernels: where the plan is cut, and which geometry each part takes -----------------------------------
-    const int e_loop0 = (p.mode == L2A_MODE_MEAN) ? md->n_sets : 1;
-    const int cus0 = ctx->num_cu > 0 ? ctx->num_cu : 256;
-    const int cst_set = 32 * md->KG0 + 48 * md->OT + md->n_hidden * md->H;
+    const int e_loop = (rq.mode == L2A_MODE_MEAN) ? md.n_sets : 1;
+    const int cus = pol.num_cu;
+    const int cst_set = 32 * md.KG0 + 48 * md.OT + md.n_hidden * md.H;
+    const bool gact = !(fast_act(md.hidden_act) && fast_act(md.output_act));
     // LDS plan of a launch whose busiest workgroup runs `nseq` sets in sequence: sets per batch, start of the constants,
     // bytes (l2a_mfma.h: activation regions | chunk partials of a batch (lb > 1) | constants | exchange staging).
     // lb = sets per batch: with two hidden layers, layer 0 of up to lb sets runs back to back, then their hidden
@@ -171,14 +224,14 @@ int launch_rollout(l2a_model* md, L2AKParams& p, void* stream_v) {
     // (<= 4, <= the longest set sequence of a workgroup) that fits the CU's LDS; 1 = one set at a time.
     auto lds_plan = [&](int nt_, int nseq, int x_bytes, int* lb_out, int* cst_off_out) {
         const int sa = sa_elems_for(md, nt_);
-        const int ps_bytes = L2A_NW * nt_ * md->OT * 64 * 16;       // the waves' output-layer partials of one set
+        const int ps_bytes = L2A_NW * nt_ * md.OT * 64 * 16;       // the waves' output-layer partials of one set
         const int cst_bytes_all = nseq * cst_set * 4;
         int lb_ = 1, part_bytes = 0;
-        if (md->n_hidden == 2 && ctx->batch_sets != 1) {
-            const int cap = ctx->batch_sets > 0 ? ctx->batch_sets : 4;
+        if (md.n_hidden == 2 && pol.batch_sets != 1) {
+            const int cap = pol.batch_sets > 0 ? pol.batch_sets : 4;
             for (int lb = (nseq < cap ? nseq : cap); lb >= 2; --lb) {
                 const int pbytes = lb * ps_bytes;
-                if (lb * sa * 16 + pbytes + cst_bytes_all + x_bytes <= ctx->lds_per_block) {
+                if (lb * sa * 16 + pbytes + cst_bytes_all + x_bytes <= pol.lds_per_block) {
                     lb_ = lb;
                     part_bytes = pbytes;
                     break;
@@ -198,251 +251,212 @@ int launch_rollout(l2a_model* md, L2AKParams& p, void* stream_v) {
     // Per tile a double round costs ~0.93 of a single one (profiles/r06_ab_double.jsonl).  Same arithmetic per candidate:
     // bit-identical results.
     int front_k = 0;                    // double tiles per env of the front launch
-    if (kind == L2A_KERNEL_MFMA) {
-        const long long tiles1 = (long long)p.m * ceil_div(p.n, 16);
-        int lb2 = 1, off2 = 0;
-        if (ctx->double_policy != 0 && md->TPW == 8 && md->OT <= 3 && tiles1 >= 2LL * cus0 &&
-            lds_plan(2, e_loop0, 0, &lb2, &off2) <= ctx->lds_per_block) {
-            const long long D = tiles1 / (2LL * cus0);
-            const long long R = tiles1 - 2LL * cus0 * D;
-            if (R == 0 || 2 * R > 3LL * cus0) front_k = ceil_div(p.n, 32);       // everything on double tiles
-            else front_k = (int)((cus0 * D) / p.m);
-            if (32LL * front_k >= p.n) front_k = ceil_div(p.n, 32);
+    l2a_rollout_launch front = l2a_rollout_launch();
+    const long long tiles1 = (long long)rq.m * ceil_div(rq.n, 16);
+    if (pol.double_policy != 0 && md.TPW == 8 && md.OT <= 3 && tiles1 >= 2LL * cus) {
+        front.smem = lds_plan(2, e_loop, 0, &front.lb, &front.cst_off);
+        if (front.smem <= pol.lds_per_block) {
+            const long long D = tiles1 / (2LL * cus);
+            const long long R = tiles1 - 2LL * cus * D;
+            if (R == 0 || 2 * R > 3LL * cus) front_k = ceil_div(rq.n, 32);       // everything on double tiles
+            else front_k = (int)((cus * D) / rq.m);
+            if (32LL * front_k >= rq.n) front_k = ceil_div(rq.n, 32);
         }
     }
-    const int n_front = (32LL * front_k >= p.n) ? (front_k ? p.n : 0) : 32 * front_k;
-    const int n_rest = p.n - n_front;
+    const int n_front = (32LL * front_k >= rq.n) ? (front_k ? rq.n : 0) : 32 * front_k;
+    const int n_rest = rq.n - n_front;
+    if (front_k) {
+        front.family = L2A_FAMILY_MFMA16;
+        front.nt = 2; front.geo = 2; front.gact = gact ? 1 : 0;
+        front.grid = (unsigned)((long long)rq.m * front_k);
+        front.c_lo = 0; front.c_hi = n_front;
+        front.sa_elems = sa_elems_for(md, 2);
+        front.tiles_per_env = front_k;
+        front.cst_set = cst_set;
+        front.n_cst = e_loop;
+        front.split_from = -1;
+        plan->launch[0] = front;
+        if (n_rest == 0) {
+            plan->done_total = (int)front.grid;
+            return L2A_OK;
+        }
+        plan->n_launch = 2;
+    }
+    l2a_rollout_launch& d = plan->launch[plan->n_launch - 1];
+    d.c_lo = n_front; d.c_hi = rq.n;
 
-    // Micro tiles (l2a_micro.h) for the plan - or for the rest behind a double round: every env's ceil(n / 4) candidate tiles of
-    // four dealt to W workgroups of at most three - one workgroup per CU, none idle, no exchange between workgroups.  Plans only
-    // (no per-row start states, no state written out: those launches are one step long or chunk continuations and keep the
-    // 16-candidate kernel - same bits).
-    bool micro = false;
-    int mc_W = 0, mc_hi = 0, mc_quads = 0, smem_m = 0;
-    long long mc_span = 0;
-    if (kind == L2A_KERNEL_MFMA && n_rest > 0 && md->micro_ok && ctx->micro_policy != 0) {
-        const long long tiles16 = (long long)p.m * ceil_div(n_rest, 16);
-        const int quads = ceil_div(n_rest, 4);
-        int W = cus0 / p.m;
-        if (W > quads) W = quads;
-        const int hi = W > 0 ? ceil_div(quads, W) : 99;
-        // ... and the FEWEST workgroups that keep the largest one at `hi` micro tiles: under this kernel the chip is power limited
-        // (2.1 GHz with 255 busy CUs against 2.37 with 125: tools/timeline_micro.py), and a workgroup of fewer micro tiles streams
-        // the same weights for less work - 2 500 candidates on 5 x 42 workgroups of 12 instead of 5 x 51 of 12 and 8: c3b 0.325 ->
-        // 0.304 ms, the ReBAL default 0.195 -> 0.183 ms (profiles/r04_ab_micro.jsonl)
-        if (hi >= 1 && hi <= 3) W = ceil_div(quads, hi);
-        const int smem_need = l2a_mlp_micro_smem(md->H, md->KG0, md->n_hidden, e_loop0);
-        const long long span = (long long)((p.mode == L2A_MODE_PER_BLOCK ? p.m : e_loop0) - 1) * md->set_stride * 4 +
-                               l2a_mlp_micro_floats(md->H, md->KG0, md->n_hidden) * 4;
-        const bool eligible = !p.obs_per_row && !p.state_out && hi <= 3 && (p.returns_out || p.best_key) &&
-                              smem_need <= ctx->lds_per_block && span < (1LL << 31);
+    // Micro tiles (l2a_micro.h) for the plan - or for the rest behind a double round: l2a_deal_micro, at most three per workgroup
+    // - one workgroup per CU, none idle, no exchange between workgroups.  Plans only (no per-row start states, no state written
+    // out: those launches are one step long or chunk continuations and keep the 16-candidate kernel - same bits).
+    if (md.micro_ok && pol.micro_policy != 0) {
+        const long long tiles16 = (long long)rq.m * ceil_div(n_rest, 16);
+        const l2a_micro_deal deal = l2a_deal_micro(cus, rq.m, n_rest, 3);
+        const int smem_need = l2a_mlp_micro_smem(md.H, md.KG0, md.n_hidden, e_loop);
+        const long long span = (long long)((rq.mode == L2A_MODE_PER_BLOCK ? rq.m : e_loop) - 1) * md.set_stride * 4 +
+                               l2a_mlp_micro_floats(md.H, md.KG0, md.n_hidden) * 4;
+        const bool eligible = !rq.obs_per_row && !rq.state_out && deal.hi <= 3 && rq.results &&
+                              smem_need <= pol.lds_per_block && span < (1LL << 31);
         // automatic (profiles/r04_ab_micro.jsonl, hidden width 512): the plans the 16-candidate geometries cannot fill - more
         // than CUs / 2 tiles (no tile split) and fewer than CUs: 0.80 - 0.90 of the 16-candidate launch (per-block 3 x 512 /
         // 2 x 512, mean E = 5, single) - and plans of at most CUs / 2 tiles that run ONE set per candidate (single model,
         // per-block), whose tile split is bound by its per-step exchange: 0.77 - 0.91 (config 3's rest behind its double round,
         // 5 x 23 tiles: 0.312 -> 0.266 ms, profiles/r06_ab_rest.jsonl).  Small ENSEMBLE plans stay with the tile
         // split (every workgroup would stream all E sets: 1.2x), and so does hidden width 256 (one 64-unit tile per wave: 1.12x).
-        const bool unfilled = 2 * tiles16 > cus0 && tiles16 < cus0;
-        const bool small_one_set = e_loop0 == 1 && 2 * tiles16 <= cus0;
-        const bool wanted = ctx->micro_policy == 2 || (ctx->micro_policy == 1 && md->H == 512 && (unfilled || small_one_set));
+        const bool unfilled = 2 * tiles16 > cus && tiles16 < cus;
+        const bool small_one_set = e_loop == 1 && 2 * tiles16 <= cus;
+        const bool wanted = pol.micro_policy == 2 || (pol.micro_policy == 1 && md.H == 512 && (unfilled || small_one_set));
         if (eligible && wanted) {
-            micro = true;
-            mc_W = W; mc_hi = hi; mc_quads = quads; mc_span = span;
-            smem_m = smem_need;
-            if (smem_m < 84 * 1024) smem_m = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
-        }
-    }
-    const int cst_bytes = e_loop0 * cst_set * 4;
-    int nt = (kind == L2A_KERNEL_MFMA && n_rest > 0 && !micro)
-                 ? choose_nt(md, p.m, n_rest, e_loop0, sa_elems_for(md, 2) * 16, cst_bytes + 4 * md->OT * 64 * 16) : 1;
-    bool front_has_dbg = false;
-    int front_wg = 0;
-    if (front_k) {
-        L2AKParams pa = p;
-        pa.c_lo = 0; pa.c_hi = n_front;
-        pa.sa_elems = sa_elems_for(md, 2);
-        pa.tiles_per_env = front_k;
-        pa.cst_set = cst_set;
-        pa.split = 0; pa.split_from = -1; pa.pl_units = 0;
-        pa.n_cst = e_loop0;
-        // (phase stamps, tools/timeline.py: one launch writes them - the rest by default, the double tiles with L2A_DBG_FRONT=1)
-        static const bool dbg_front = [] { const char* e = std::getenv("L2A_DBG_FRONT"); return e && e[0] == '1'; }();
-        pa.dbg = (n_rest == 0 || dbg_front) ? ctx->dbg : nullptr;
-        front_has_dbg = pa.dbg != nullptr;
-        const int smem_a = lds_plan(2, e_loop0, 0, &pa.lb, &pa.cst_off);
-        const long long wg_a = (long long)p.m * front_k;
-        // what the mailbox counts: one per workgroup that owns a tile's (or micro-tile group's) key, over both launches
-        const long long rest_units = n_rest == 0 ? 0 : micro ? (long long)p.m * mc_W : (long long)p.m * ceil_div(n_rest, 16 * nt);
-        pa.done_total = (int)(wg_a + rest_units);
-        p.done_total = pa.done_total;
-        if (ctx->dry) {
-            if (n_rest == 0) {
-                const int g[12] = {1, 2, 0, -1, 0, (int)wg_a, smem_a, pa.lb, 0, 0, 0, 1};
-                std::memcpy(ctx->dry, g, sizeof(g));
-                return L2A_OK;
-            }
-        } else {
-            const bool gact_a = !(fast_act(md->hidden_act) && fast_act(md->output_act));
-            const int rc_a = l2a_launch_mfma(2, md->TPW, md->OT, md->KG0, gact_a ? 1 : 0, 2, &pa, (unsigned)wg_a, smem_a, stream);
-            if (rc_a == -100) return fail(ctx, L2A_EINVAL, "no whole-tile MFMA kernel instance for this (obs_dim, act_dim, hidden)");
-            if (rc_a != 0) return fail(ctx, L2A_EHIP, std::string("MFMA kernel launch (double rounds): ") + hipGetErrorString((hipError_t)rc_a));
-            L2A_HIP(ctx, hipGetLastError());
-            if (n_rest == 0) return L2A_OK;
-        }
-        p.c_lo = n_front;
-        front_wg = (int)wg_a;
-    }
-    if (micro) {
-        p.mc_w = mc_W;
-        p.mc_hi = mc_hi;
-        p.mc_r = mc_quads - mc_W * (mc_hi - 1);          // workgroups that take `hi` micro tiles
-        p.m_bytes = mc_span;
-        p.dbg = front_has_dbg ? nullptr : ctx->dbg;
-        const bool gact_m = !(fast_act(md->hidden_act) && fast_act(md->output_act)) || md->n_hidden == 1;
-        if (ctx->dry) {     // [kind, nt, split, split_from, fan, workgroups, lds bytes, sets per batch, micro tiles of the largest workgroup, placement units, double-tile workgroups in front, 0]
-            const int g[12] = {2, 0, 0, -1, 0, p.m * mc_W, smem_m, 1, mc_hi, 0, front_wg, 0};
-            std::memcpy(ctx->dry, g, sizeof(g));
+            d.family = L2A_FAMILY_MICRO;
+            d.gact = (gact || md.n_hidden == 1) ? 1 : 0;
+            d.grid = (unsigned)(rq.m * deal.W);
+            d.smem = smem_need < 84 * 1024 ? 84 * 1024 : smem_need;     // more than half a CU's LDS: one workgroup per CU
+            d.mc_w = deal.W; d.mc_hi = deal.hi; d.mc_r = deal.mc_r;
+            d.m_bytes = span;
+            if (front_k) plan->done_total = (int)(front.grid + d.grid);
             return L2A_OK;
         }
-        const int rc = l2a_launch_mlp_micro(md->H, gact_m ? 1 : 0, &p, (unsigned)(p.m * mc_W), smem_m, stream);
-        if (rc != 0) return fail(ctx, L2A_EHIP, std::string("micro-tile MLP kernel launch: ") +
-                                                    (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
-        L2A_HIP(ctx, hipGetLastError());
-        return L2A_OK;
     }
-    if (kind == L2A_KERNEL_MFMA) {
-        // Member fan (l2a_mfma.h): E workgroups per tile, one set each - small mean-ensemble plans, e.g. one rank's shard of
-        // config 5 (n = 500: 32 tiles -> 160 workgroups of one set instead of 64 of 2.5 sets).  With two candidate tiles per
-        // workgroup (width 512, up to 48 observation dims) it reaches twice as far: one of FOUR ranks' shard of config 5
-        // (n = 1000: 32 double tiles x 5) - each weight fragment feeds two tiles and the step's fixed costs are paid once for both.
-        int fan_nt = 0;
-        if (!front_k && ctx->split_policy != 0 && ctx->fan_policy != 0 && p.h < 4096 && p.mode == L2A_MODE_MEAN && e_loop0 >= 3 && e_loop0 <= 8) {
-            if ((long long)p.m * ceil_div(p.n, 16) * e_loop0 <= cus0) fan_nt = 1;
-            else if (md->TPW == 8 && md->OT <= 3 && (long long)p.m * ceil_div(p.n, 32) * e_loop0 <= cus0 &&
-                     2 * sa_elems_for(md, 2) * 16 + (32 * md->KG0 + 48 * md->OT + md->n_hidden * md->H) * 4 + e_loop0 * 2 * md->OT * 64 * 16 <= ctx->lds_per_block)
-                fan_nt = 2;
-        }
-        if (fan_nt) nt = fan_nt;
-        p.sa_elems = sa_elems_for(md, nt);
-        p.tiles_per_env = ceil_div(n_rest, 16 * nt);
-        const int e_loop = (p.mode == L2A_MODE_MEAN) ? md->n_sets : 1;
-        p.cst_set = cst_set;
-        // Member split: two workgroups per candidate tile (group A | group B of the ensemble) when
-        // that still fits one workgroup per CU - e.g. config 2: 125 tiles -> 250 workgroups.
-        const long long pairs = (long long)p.m * p.tiles_per_env;
-        const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
-        // 1 = group A | group B; 2 = additionally the middle set of an odd ensemble (or the single
-        // set of a lone model) is shared: each workgroup runs the last hidden layer and the output
-        // layer for one half of its hidden tiles (needs >= 2 hidden layers).
-        p.split = 0;
-        p.split_from = -1;
-        long long split_pairs = 0;          // tiles shared by two workgroups
-        auto split_mode = [&]() { return split_mode_for(md, e_loop); };
-        const bool fan = fan_nt != 0;
-        if (fan) {
-            p.split = 3;
-            split_pairs = pairs;
-        } else if (ctx->split_policy != 0 && nt == 1 && p.h < 4096) {
-            if (2 * pairs <= cus) {
-                p.split = split_mode();
-                split_pairs = p.split ? pairs : 0;
-            } else if (pairs > cus && pairs % cus != 0 && 2 * (pairs % cus) <= cus && split_mode() != 0) {
-                // Tail split: a multi-round plan whose last round would fill less than half of the chip -
-                // the left-over tiles are shared by two workgroups each (dispatched last, see l2a_mfma.h).
-                p.split = split_mode();
-                split_pairs = pairs % cus;
-                p.split_from = (int)(pairs - split_pairs);
-            }
-        }
-        if (p.split && !ctx->dry) {
-            // in 8-byte units: per shared tile 2 workgroups x 2 step parities x 2 regions (fan: E workgroups x 2 parities)
-            const long long need = split_pairs * (fan ? e_loop : 4) * 2 * (long long)(nt * md->OT * 2 * 64 * 16) / 8;
-            if (need > md->xbuf_granules) {
-                if (md->xbuf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->xbuf)); md->xbuf = nullptr; }
-                L2A_HIP(ctx, l2a_xbuf_alloc(reinterpret_cast<void**>(&md->xbuf), (size_t)need * 8));
-                L2A_HIP(ctx, hipMemsetAsync(md->xbuf, 0, (size_t)need * 8, stream));   // ordered before the launch
-                md->xbuf_granules = need;
-                md->launch_nonce = 0;
-            }
-            md->launch_nonce += 1;
-            if (md->launch_nonce >= (1u << 20)) {     // tag space exhausted: wipe stale tags, restart
-                L2A_HIP(ctx, hipMemsetAsync(md->xbuf, 0, (size_t)md->xbuf_granules * 8, stream));
-                md->launch_nonce = 1;
-            }
-            p.xtag = md->launch_nonce << 12;
-            p.xbuf = md->xbuf;
-            p.status = ctx->status_dev;
-            p.spin_limit = ctx->spin_limit;
-        }
-        p.dbg = front_has_dbg ? nullptr : ctx->dbg;
-        const bool uniform_split = p.split && p.split_from < 0;
-        const int e_half = (e_loop + 1) / 2;
-        const int nseq = fan ? 1 : uniform_split ? e_half : e_loop;  // sets the busiest workgroup runs in sequence
-        const int x_bytes = (fan ? e_loop : 2) * nt * md->OT * 64 * 16;   // exchange staging: the partner's two regions / every member's term
-        p.n_cst = nseq;
-        const int smem = lds_plan(nt, nseq, x_bytes, &p.lb, &p.cst_off);
-        if (smem > ctx->lds_per_block)
-            return fail(ctx, L2A_EINVAL, "LDS budget exceeded (" + std::to_string(smem) + " B)");
-        long long n_wg = fan ? pairs * e_loop : pairs + (p.split ? split_pairs : 0);
-        p.pl_units = 0;
-        if (ctx->xcd_align && p.split_from < 0 && n_wg <= cus) {
-            // one unit of weight-sharing workgroups per XCD (see the kernel's geometry): the two groups of a split
-            // ensemble, the environments of a per-block plan (both workgroups of a split tile stream the same set)
-            int units = 0;
-            long long w = 0;
-            if (p.mode == L2A_MODE_PER_BLOCK) { units = p.m; w = (long long)p.tiles_per_env * (p.split ? 2 : 1); }
-            else if (fan) { units = e_loop; w = pairs; }      // every member's workgroups on their own XCD(s)
-            else if (p.split && e_loop > 1) { units = 2; w = pairs; }
-            if (units >= 2 && units <= 8) {
-                const int f = 8 / units;
-                const long long slots = (w + f - 1) / f;       // per XCD, of the units with f XCDs
-                if (8 * slots <= cus) {
-                    p.pl_units = units; p.pl_f = f; p.pl_r = 8 - units * f; p.pl_w = (int)w;
-                    n_wg = 8 * slots;
-                }
-            }
-        }
-        const dim3 grid((unsigned)n_wg), block(64 * L2A_NW);
-        const bool gact = !(fast_act(md->hidden_act) && fast_act(md->output_act));
-        if (ctx->dry) {
-            const bool whole1_dry = !fan && ctx->double_policy != 0 && e_loop == 1 && nt == 1 && md->TPW == 8 && md->OT <= 3 &&
-                                    p.split == 0 && p.split_from < 0;
-            const int g[12] = {1, nt, p.split, p.split_from, fan ? 1 : 0, (int)n_wg, smem, p.lb, 0, p.pl_units, front_wg, whole1_dry ? 1 : 0};
-            std::memcpy(ctx->dry, g, sizeof(g));
-            return L2A_OK;
-        }
-        // Whole tiles of ONE set per candidate (single model, per-block sets) at width 512 also run on the whole-tiles-only
-        // instances (332 - 368 VGPRs instead of 442 - 496: -3 .. -4 % per round, profiles/r06_ab_whole1.jsonl); ensembles keep the
-        // general instances (config 5's iteration, five sets in batches of three: +3.4 % on the whole-tiles-only one)
-        const bool whole1 = !fan && ctx->double_policy != 0 && e_loop == 1 && nt == 1 && md->TPW == 8 && md->OT <= 3 &&
-                            p.split == 0 && p.split_from < 0;
-        const int geo = fan ? 1 : whole1 ? 2 : 0;
-        int rc = l2a_launch_mfma(nt, md->TPW, md->OT, md->KG0, gact ? 1 : 0, geo, &p, grid.x, smem, stream);
-        if (rc == -100) return fail(ctx, L2A_EINVAL, "no MFMA kernel instance for this (obs_dim, act_dim, hidden)");
-        if (rc != 0) return fail(ctx, L2A_EHIP, std::string("MFMA kernel launch: ") + hipGetErrorString((hipError_t)rc));
-        rc = L2A_OK;
-        if (rc != L2A_OK) return rc;
-    } else {
-        p.tiles_per_env = ceil_div(p.n, L2A_VT);
-        const int smem = (md->in_dim + 2 * md->hmax + 3 * md->obs_dim + md->act_dim + 1) * L2A_VT * 4;
-        if (smem > ctx->lds_per_block)
-            return fail(ctx, L2A_EINVAL, "LDS budget exceeded by the VALU kernel (" + std::to_string(smem) + " B)");
-        if (ctx->dry) {
-            const int g[12] = {0, 0, 0, -1, 0, p.m * p.tiles_per_env, smem, 1, 0, 0, 0, 0};
-            std::memcpy(ctx->dry, g, sizeof(g));
-            return L2A_OK;
-        }
-        int rc = allow_big_lds(ctx, l2a_rollout_valu_k, smem);
-        if (rc != L2A_OK) return rc;
-        const dim3 grid((unsigned)(p.m * p.tiles_per_env)), block(256);
-        hipLaunchKernelGGL(l2a_rollout_valu_k, grid, block, smem, stream, p);
+
+    d.family = L2A_FAMILY_MFMA16;
+    d.gact = gact ? 1 : 0;
+    int nt = choose_nt(md, pol, rq.m, n_rest, e_loop, sa_elems_for(md, 2) * 16, e_loop * cst_set * 4 + 4 * md.OT * 64 * 16);
+    // Member fan (l2a_mfma.h): E workgroups per tile, one set each - small mean-ensemble plans, e.g. one rank's shard of
+    // config 5 (n = 500: 32 tiles -> 160 workgroups of one set instead of 64 of 2.5 sets).  With two candidate tiles per
+    // workgroup (width 512, up to 48 observation dims) it reaches twice as far: one of FOUR ranks' shard of config 5
+    // (n = 1000: 32 double tiles x 5) - each weight fragment feeds two tiles and the step's fixed costs are paid once for both.
+    int fan_nt = 0;
+    if (!front_k && pol.split_policy != 0 && pol.fan_policy != 0 && rq.h < 4096 && rq.mode == L2A_MODE_MEAN && e_loop >= 3 && e_loop <= 8) {
+        if ((long long)rq.m * ceil_div(rq.n, 16) * e_loop <= cus) fan_nt = 1;
+        else if (md.TPW == 8 && md.OT <= 3 && (long long)rq.m * ceil_div(rq.n, 32) * e_loop <= cus &&
+                 2 * sa_elems_for(md, 2) * 16 + cst_set * 4 + e_loop * 2 * md.OT * 64 * 16 <= pol.lds_per_block)
+            fan_nt = 2;
     }
-    L2A_HIP(ctx, hipGetLastError());
+    const bool fan = fan_nt != 0;
+    if (fan) nt = fan_nt;
+    d.nt = nt;
+    d.sa_elems = sa_elems_for(md, nt);
+    d.tiles_per_env = ceil_div(n_rest, 16 * nt);
+    d.cst_set = cst_set;
+    // Member split: two workgroups per candidate tile (group A | group B of the ensemble) when
+    // that still fits one workgroup per CU - e.g. config 2: 125 tiles -> 250 workgroups.
+    const long long pairs = (long long)rq.m * d.tiles_per_env;
+    // 1 = group A | group B; 2 = additionally the middle set of an odd ensemble (or the single
+    // set of a lone model) is shared: each workgroup runs the last hidden layer and the output
+    // layer for one half of its hidden tiles (needs >= 2 hidden layers).
+    d.split_from = -1;
+    long long split_pairs = 0;          // tiles shared by two workgroups
+    const int split_mode = split_mode_for(md, pol.split_policy, e_loop);
+    if (fan) {
+        d.split = 3;
+        split_pairs = pairs;
+    } else if (pol.split_policy != 0 && nt == 1 && rq.h < 4096) {
+        if (2 * pairs <= cus) {
+            d.split = split_mode;
+            split_pairs = d.split ? pairs : 0;
+        } else if (pairs > cus && pairs % cus != 0 && 2 * (pairs % cus) <= cus && split_mode != 0) {
+            // Tail split: a multi-round plan whose last round would fill less than half of the chip -
+            // the left-over tiles are shared by two workgroups each (dispatched last, see l2a_mfma.h).
+            d.split = split_mode;
+            split_pairs = pairs % cus;
+            d.split_from = (int)(pairs - split_pairs);
+        }
+    }
+    // per shared tile 2 workgroups x 2 step parities x 2 regions (fan: E workgroups x 2 parities)
+    if (d.split) plan->xbuf_bytes = split_pairs * (fan ? e_loop : 4) * 2 * (long long)(nt * md.OT * 2 * 64 * 16);
+    const bool uniform_split = d.split && d.split_from < 0;
+    const int nseq = fan ? 1 : uniform_split ? (e_loop + 1) / 2 : e_loop;   // sets the busiest workgroup runs in sequence
+    const int x_bytes = (fan ? e_loop : 2) * nt * md.OT * 64 * 16;   // exchange staging: the partner's two regions / every member's term
+    d.n_cst = nseq;
+    d.smem = lds_plan(nt, nseq, x_bytes, &d.lb, &d.cst_off);
+    if (d.smem > pol.lds_per_block)
+        return bad(L2A_EINVAL, "LDS budget exceeded (" + std::to_string(d.smem) + " B)");
+    long long n_wg = fan ? pairs * e_loop : pairs + (d.split ? split_pairs : 0);
+    if (pol.xcd_align && d.split_from < 0 && n_wg <= cus) {
+        // one unit of weight-sharing workgroups per XCD (see the kernel's geometry): the two groups of a split
+        // ensemble, the environments of a per-block plan (both workgroups of a split tile stream the same set)
+        int units = 0;
+        long long w = 0;
+        if (rq.mode == L2A_MODE_PER_BLOCK) { units = rq.m; w = (long long)d.tiles_per_env * (d.split ? 2 : 1); }
+        else if (fan) { units = e_loop; w = pairs; }      // every member's workgroups on their own XCD(s)
+        else if (d.split && e_loop > 1) { units = 2; w = pairs; }
+        if (units >= 2 && units <= 8) {
+            const int f = 8 / units;
+            const long long slots = (w + f - 1) / f;       // per XCD, of the units with f XCDs
+            if (8 * slots <= cus) {
+                d.pl_units = units; d.pl_f = f; d.pl_r = 8 - units * f; d.pl_w = (int)w;
+                n_wg = 8 * slots;
+            }
+        }
+    }
+    d.grid = (unsigned)n_wg;
+    // Whole tiles of ONE set per candidate (single model, per-block sets) at width 512 also run on the whole-tiles-only
+    // instances (332 - 368 VGPRs instead of 442 - 496: -3 .. -4 % per round, profiles/r06_ab_whole1.jsonl); ensembles keep the
+    // general instances (config 5's iteration, five sets in batches of three: +3.4 % on the whole-tiles-only one)
+    const bool whole1 = !fan && pol.double_policy != 0 && e_loop == 1 && nt == 1 && md.TPW == 8 && md.OT <= 3 &&
+                        d.split == 0 && d.split_from < 0;
+    d.geo = fan ? 1 : whole1 ? 2 : 0;
+    // what the mailbox counts: one per workgroup that owns a tile's (or micro-tile group's) key, over both launches
+    if (front_k) plan->done_total = (int)(front.grid + pairs);
     return L2A_OK;
 }
 
-// What the launch logic needs to know of a model's shape (no storage): shared by l2a_model_create and l2a_plan_geometry.
-void model_shape(l2a_model* md, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act, int output_act,
+// Executes the plan of `p`'s request: fills the geometry fields of `p` and launches on `stream_v`.
+int launch_rollout(l2a_model* md, L2AKParams& p, void* stream_v) {
+    l2a_ctx* ctx = md->ctx;
+    l2a_device_guard guard(ctx->device);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    const int sets_needed = (p.mode == L2A_MODE_PER_BLOCK) ? (p.m < md->n_sets ? p.m : md->n_sets) : md->n_sets;
+    for (int e = 0; e < sets_needed; ++e) {
+        if (!md->weights_set[e]) return fail(ctx, L2A_ESTATE, "weight set " + std::to_string(e) + " was never set");
+        if (!md->norm_set[e]) return fail(ctx, L2A_ESTATE, "normalisation of set " + std::to_string(e) + " was never set");
+    }
+    const l2a_rollout_policy pol = rollout_policy(ctx);
+    l2a_rollout_plan plan;
+    std::string err;
+    const int prc = plan_rollout(*md, pol, {p.mode, p.m, p.n, p.h, p.obs_per_row != 0, p.state_out != nullptr,
+                                            p.returns_out || p.best_key}, &plan, &err);
+    if (prc != L2A_OK) return fail(ctx, prc, err);
+    p.done_total = plan.done_total;
+    for (int i = 0; i < plan.n_launch; ++i) {
+        const l2a_rollout_launch& d = plan.launch[i];
+        if (d.split) {      // (the last launch only: the exchange buffer is reserved behind the double tiles)
+            const int rc = l2a_xbuf_reserve(ctx, &md->xb, plan.xbuf_bytes, stream, &p.xtag);
+            if (rc != L2A_OK) return rc;
+            p.xbuf = md->xb.buf;
+            p.status = ctx->status_dev;
+            p.spin_limit = ctx->spin_limit;
+        }
+        p.c_lo = d.c_lo; p.c_hi = d.c_hi;
+        p.sa_elems = d.sa_elems; p.tiles_per_env = d.tiles_per_env;
+        p.cst_set = d.cst_set; p.n_cst = d.n_cst; p.lb = d.lb; p.cst_off = d.cst_off;
+        p.split = d.split; p.split_from = d.split_from;
+        p.pl_units = d.pl_units; p.pl_f = d.pl_f; p.pl_r = d.pl_r; p.pl_w = d.pl_w;
+        p.mc_w = d.mc_w; p.mc_hi = d.mc_hi; p.mc_r = d.mc_r; p.m_bytes = d.m_bytes;
+        // (phase stamps, tools/timeline.py: one launch writes them - the rest by default, the double tiles with L2A_DBG_FRONT=1)
+        p.dbg = (plan.n_launch == 1 || (i == 0) == pol.dbg_front) ? ctx->dbg : nullptr;
+        if (d.family == L2A_FAMILY_MFMA16) {
+            const bool dbl = d.geo == 2 && d.nt == 2;       // the double tiles
+            const int rc = l2a_launch_mfma(d.nt, md->TPW, md->OT, md->KG0, d.gact, d.geo, &p, d.grid, d.smem, stream);
+            if (rc == -100) return fail(ctx, L2A_EINVAL, dbl ? "no whole-tile MFMA kernel instance for this (obs_dim, act_dim, hidden)"
+                                                             : "no MFMA kernel instance for this (obs_dim, act_dim, hidden)");
+            if (rc != 0) return fail(ctx, L2A_EHIP, std::string(dbl ? "MFMA kernel launch (double rounds): " : "MFMA kernel launch: ") +
+                                                        hipGetErrorString((hipError_t)rc));
+        } else if (d.family == L2A_FAMILY_MICRO) {
+            const int rc = l2a_launch_mlp_micro(md->H, d.gact, &p, d.grid, d.smem, stream);
+            if (rc != 0) return fail(ctx, L2A_EHIP, std::string("micro-tile MLP kernel launch: ") +
+                                                        (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
+        } else {
+            const int rc = allow_big_lds(ctx, l2a_rollout_valu_k, d.smem);
+            if (rc != L2A_OK) return rc;
+            hipLaunchKernelGGL(l2a_rollout_valu_k, dim3(d.grid), dim3(256), d.smem, stream, p);
+        }
+        L2A_HIP(ctx, hipGetLastError());
+    }
+    return L2A_OK;
+}
+
+// Shared by l2a_model_create and l2a_plan_geometry.
+void model_shape(l2a_mlp_shape* md, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act, int output_act,
                  int n_sets, int mode) {
     md->obs_dim = obs_dim; md->act_dim = act_dim; md->in_dim = obs_dim + act_dim;
     md->n_hidden = n_hidden;
@@ -556,7 +570,7 @@ int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden,
                       const int* policy, int* out) {
     if (!hidden || !out || obs_dim < 1 || act_dim < 1 || n_hidden < 1 || n_hidden > L2A_MAX_LAYERS - 1 || n_sets < 1 || m < 1 || n < 1 || h < 1)
         return L2A_EINVAL;
-    l2a_ctx ctx;                                    // never touches a device: the launcher stops before its first HIP call
+    l2a_ctx ctx;                                    // (its default policies; never touches a device)
     ctx.num_cu = 256;
     ctx.lds_per_block = 160 * 1024;
     if (policy) {
@@ -566,20 +580,18 @@ int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden,
         if (policy[3] > 0) ctx.num_cu = policy[3];
         if (policy[4] >= 0) ctx.double_policy = policy[4];
     }
-    l2a_model md;
-    md.ctx = &ctx;
+    l2a_mlp_shape md;
     model_shape(&md, obs_dim, act_dim, n_hidden, hidden, L2A_ACT_RELU, L2A_ACT_IDENTITY, n_sets, mode);
-    L2AKParams p;
-    fill_model_params(&md, p);
-    p.m = m; p.n = n; p.h = h; p.discount = 1.0; p.disc0 = 1.0;
-    unsigned long long dummy = 0;
-    p.best_key = &dummy;                            // "a plan": returns or keys are wanted (never dereferenced here)
-    int g[12] = {0};
-    ctx.dry = g;
-    const int rc = launch_rollout(&md, p, nullptr);
-    ctx.dry = nullptr;
+    l2a_rollout_plan plan;
+    std::string err;
+    const int rc = plan_rollout(md, rollout_policy(&ctx), {mode, m, n, h, false, false, true}, &plan, &err);   // "a plan": returns or keys are wanted
     if (rc != L2A_OK) return rc;
-    for (int i = 0; i < 12; ++i) out[i] = g[i];
+    // the plan's last launch, and the workgroups of the double tiles in front of it if there are any
+    const l2a_rollout_launch& d = plan.launch[plan.n_launch - 1];
+    const bool mfma16 = d.family == L2A_FAMILY_MFMA16;
+    const int g[12] = {d.family, d.nt, d.split, mfma16 ? d.split_from : -1, d.geo == 1, (int)d.grid, d.smem, mfma16 ? d.lb : 1,
+                       d.mc_hi, d.pl_units, plan.n_launch == 2 ? (int)plan.launch[0].grid : 0, d.geo == 2};
+    std::memcpy(out, g, sizeof(g));
     return L2A_OK;
 }
 
@@ -783,7 +795,7 @@ void l2a_model_destroy(l2a_model* md) {
         (void)hipDeviceSynchronize();
         (void)hipFree(md->wblk);
     }
-    if (md->xbuf) (void)hipFree(md->xbuf);
+    if (md->xb.buf) (void)hipFree(md->xb.buf);
     if (md->adapt_scratch) (void)hipFree(md->adapt_scratch);
     if (md->prog_buf) (void)hipFree(md->prog_buf);
     for (auto& sl : md->aslot) {
@@ -1108,6 +1120,18 @@ int l2a_model_set_norm(l2a_model* md, int e, const double* mean_obs, const doubl
     return L2A_OK;
 }
 
+// The candidate-count and reward-index checks of the plan entry points.
+static int check_candidates_and_reward(const l2a_model* md, const char* who, int m, int n, int cand_offset, const l2a_reward* reward) {
+    const l2a_ctx* ctx = md->ctx;
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, std::string(who) + ": too many candidates");
+    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
+        return fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
+    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
+        return fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    return L2A_OK;
+}
+
 int l2a_plan_rs(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h,
                 double discount, const l2a_reward* reward, int cand_offset, float* returns_out,
                 unsigned long long* best_key, void* stream_v) {
@@ -1116,12 +1140,8 @@ int l2a_plan_rs(l2a_model* md, const float* obs0, const float* actions, int m, i
     if (!obs0 || !actions || !reward) return fail(ctx, L2A_EINVAL, "l2a_plan_rs: null obs0/actions/reward");
     if (!best_key && !returns_out) return fail(ctx, L2A_EINVAL, "l2a_plan_rs: nothing to write (best_key and returns_out are null)");
     if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, "l2a_plan_rs: m, n and h must be >= 1");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return fail(ctx, L2A_EINVAL, "l2a_plan_rs: too many candidates");
-    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
-        return fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
-    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
-        return fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    const int arc = check_candidates_and_reward(md, "l2a_plan_rs", m, n, cand_offset, reward);
+    if (arc != L2A_OK) return arc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
     if (best_key) L2A_HIP(ctx, hipMemsetAsync(best_key, 0, sizeof(unsigned long long) * (size_t)m, stream));
@@ -1266,19 +1286,15 @@ int l2a_plan_rs_sync_hook(l2a_model* md, const float* obs_host, const float* act
     if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_sync: m, n and h must be >= 1");
     if (m > L2A_MAIL_KEYS || (long long)m * md->obs_dim > L2A_MAIL_OBS)
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_sync: at most 64 envs / 4096 observation floats (use l2a_plan_rs)");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return fail(ctx, L2A_EINVAL, "l2a_plan_rs_sync: too many candidates");
-    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
-        return fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
-    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
-        return fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    int rc = check_candidates_and_reward(md, "l2a_plan_rs_sync", m, n, cand_offset, reward);
+    if (rc != L2A_OK) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
     int kind = ctx->kernel_kind;
     if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
     const bool publish = (kind == L2A_KERNEL_MFMA);        // the VALU kernel has no mailbox epilogue
     l2a_mail_ticket tk;
-    int rc = l2a_mail_begin(ctx, m, obs_host, (long long)m * md->obs_dim, stream, &tk);
+    rc = l2a_mail_begin(ctx, m, obs_host, (long long)m * md->obs_dim, stream, &tk);
     if (rc != L2A_OK) return rc;
     tk.shape = (unsigned long long)(size_t)md ^ ((unsigned long long)m << 48) ^ ((unsigned long long)n << 24) ^ (unsigned long long)h;
     L2AKParams p;
@@ -1329,12 +1345,8 @@ int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, cons
     if (m < 1 || n < 1 || h_chunk < 1 || t0 < 0) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_chunk: bad m / n / h_chunk / t0");
     if (t0 > 0 && (!returns_in || !state_per_row))
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_chunk: a continuation needs returns_in and per-row states");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return fail(ctx, L2A_EINVAL, "l2a_plan_rs_chunk: too many candidates");
-    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
-        return fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
-    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
-        return fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    const int arc = check_candidates_and_reward(md, "l2a_plan_rs_chunk", m, n, cand_offset, reward);
+    if (arc != L2A_OK) return arc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
     if (best_key) L2A_HIP(ctx, hipMemsetAsync(best_key, 0, sizeof(unsigned long long) * (size_t)m, stream));

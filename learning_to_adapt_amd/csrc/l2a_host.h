@@ -30,7 +30,6 @@ struct l2a_ctx {
     unsigned int* status_host = nullptr;  // pinned, device-visible launch status word
     unsigned int* status_dev = nullptr;
     unsigned long long* dbg = nullptr;    // optional timeline buffer (l2a_set_debug_buffer)
-    int* dry = nullptr;                   // l2a_plan_geometry: the launcher records its decisions here and launches nothing
     unsigned int spin_limit = 1u << 18;   // exchange polls per workgroup and launch before it gives up (~0.5 s)
     // result mailbox of l2a_plan_rs_sync (allocated on first use)
     struct l2a_mail* mail_host = nullptr; // host-mapped
@@ -78,6 +77,54 @@ inline hipError_t l2a_xbuf_alloc(void** ptr, size_t bytes) {
     }
     if (mode == 0) return hipMalloc(ptr, bytes);
     return hipExtMallocWithFlags(ptr, bytes, mode == 1 ? hipDeviceMallocFinegrained : hipDeviceMallocUncached);
+}
+
+// A model's exchange buffer and the nonce its launches tag their granules with.
+struct l2a_xbuf {
+    unsigned long long* buf = nullptr;
+    long long bytes = 0;
+    unsigned int nonce = 0;
+};
+// Before a launch that exchanges through `need` bytes: grows the buffer (synchronises `stream`: the old one may be in use; the
+// new one is zeroed on the stream, ordered before the launch) and draws the launch's tag base -> *xtag.
+inline int l2a_xbuf_reserve(const l2a_ctx* ctx, l2a_xbuf* x, long long need, hipStream_t stream, unsigned int* xtag) {
+    if (need > x->bytes) {
+        if (x->buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(x->buf)); x->buf = nullptr; }
+        L2A_HIP(ctx, l2a_xbuf_alloc(reinterpret_cast<void**>(&x->buf), (size_t)need));
+        L2A_HIP(ctx, hipMemsetAsync(x->buf, 0, (size_t)need, stream));
+        x->bytes = need;
+        x->nonce = 0;
+    }
+    x->nonce += 1;
+    if (x->nonce >= (1u << 20)) {     // tag space exhausted: wipe stale tags, restart
+        L2A_HIP(ctx, hipMemsetAsync(x->buf, 0, (size_t)x->bytes, stream));
+        x->nonce = 1;
+    }
+    *xtag = x->nonce << 12;
+    return L2A_OK;
+}
+
+// The micro-tile deal of the three launchers (l2a_micro.h, l2a_rnn_micro.h): every env's ceil(n / 4) candidate tiles of four
+// dealt to W <= CUs / m workgroups, the largest of which takes `hi` micro tiles and mc_r of which take that many - and the
+// FEWEST workgroups that keep the largest one at `hi`: under these kernels the chip is power limited (2.1 GHz with 255 busy CUs
+// against 2.37 with 125: tools/timeline_micro.py), and a workgroup of fewer micro tiles streams the same weights for less work -
+// 2 500 candidates on 5 x 42 workgroups of 12 instead of 5 x 51 of 12 and 8: c3b 0.325 -> 0.304 ms, the ReBAL default 0.195 ->
+// 0.183 ms (profiles/r04_ab_micro.jsonl).  A plan of more than `max_hi` per workgroup is left as dealt (hi > max_hi: not for
+// these kernels) unless `rounds`: then its workgroups take max_hi each, in as many rounds as that takes.
+struct l2a_micro_deal { int W, hi, mc_r; };
+inline l2a_micro_deal l2a_deal_micro(int cus, int m, int n, int max_hi, bool rounds = false) {
+    const int quads = l2a_ceil_div(n, 4);
+    int W = cus / m;
+    if (W > quads) W = quads;
+    int hi = W > 0 ? l2a_ceil_div(quads, W) : 99;
+    if (hi > max_hi && rounds) hi = max_hi;
+    if (hi <= max_hi) {
+        W = l2a_ceil_div(quads, hi);
+        // (a `hi` forced down is not the natural ceil(quads / W) of the W it yields - quads = 5: W = 2 would leave 5 - 2 * 3 = -1
+        // workgroups of four: take the natural one, so that 1 <= mc_r <= W always holds; a natural `hi` is left as it is)
+        hi = l2a_ceil_div(quads, W);
+    }
+    return {W, hi, quads - W * (hi - 1)};
 }
 
 // ---- blocking launches through the result mailbox (l2a_plan_rs_sync, l2a_lstm_plan_rs_sync; defined in l2a_api.hip) ----

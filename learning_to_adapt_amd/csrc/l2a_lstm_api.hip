@@ -32,9 +32,7 @@ struct l2a_lstm {
     long long raw_wk = 0, raw_bk = 0, raw_wo = 0, raw_bo = 0, pk_wg = 0, pk_wout = 0, pk_bout = 0, nm_off = 0;
     bool weights_set = false, norm_set = false;
     std::vector<float> norm_stage;
-    unsigned long long* xbuf = nullptr;           // unit-tile split exchange granules
-    long long xbuf_bytes = 0;
-    unsigned int launch_nonce = 0;
+    l2a_xbuf xb;                                  // unit-tile split exchange granules
     // generic stacks (l2a_rnn_create): any cell type / several layers -> l2a_rnn_valu_k; `units` = sum(lunits)
     bool generic = false;
     int n_layers = 1, cell_type = L2A_CELL_LSTM;
@@ -117,35 +115,26 @@ bool generic_uses_mfma(const l2a_lstm* md) {
     return md->generic && md->ctx->kernel_kind != L2A_KERNEL_VALU && generic_mfma_smem(md) <= md->ctx->lds_per_block;
 }
 
-// Micro tiles for the tuned LSTM kernel (l2a_micro.h): every env's ceil(n / 4) candidate tiles of four dealt to W workgroups of
-// at most three - one workgroup per CU, none idle, no exchange.  The ONE decision function of the fused plan (launch() below),
-// the trajectory rollout (rollout_traj) and l2a_lstm_traj_geometry; pure host arithmetic.
-struct lstm_micro_geom { int W, hi, mc_r; };
-bool lstm_micro_wanted(bool micro_ok, int micro_policy, int num_cu, int m, int n, lstm_micro_geom* g) {
+// Micro tiles for the tuned LSTM kernel (l2a_micro.h): l2a_deal_micro, at most three per workgroup - one workgroup per CU, none
+// idle, no exchange.  The ONE decision function of the fused plan (launch() below), the trajectory rollout (rollout_traj) and
+// l2a_lstm_traj_geometry; pure host arithmetic.
+bool lstm_micro_wanted(bool micro_ok, int micro_policy, int num_cu, int m, int n, l2a_micro_deal* g) {
     const int cus_m = num_cu > 0 ? num_cu : 256;
     const long long tiles16 = (long long)m * l2a_ceil_div(n, 16);
-    const int quads = l2a_ceil_div(n, 4);
-    int W = cus_m / m;
-    if (W > quads) W = quads;
-    const int hi = W > 0 ? l2a_ceil_div(quads, W) : 99;
-    // ... and the fewest workgroups that keep the largest one at `hi` micro tiles (the chip is power limited under this
-    // kernel, see launch_rollout in l2a_api.hip)
-    if (hi >= 1 && hi <= 3) W = l2a_ceil_div(quads, hi);
+    *g = l2a_deal_micro(cus_m, m, n, 3);
+    const int hi = g->hi;
     // automatic (profiles/r04_ab_micro.jsonl): the plans the 16-candidate geometries cannot fill - more than CUs / 2
     // tiles (no unit-tile split) and fewer than CUs (the ReBAL default: 0.91 of the 16-candidate launch; 512 units: 0.85)
     // - and plans of at most one micro tile per CU (0.87 - 0.95 of the unit-tile split); in between the unit-tile
     // split wins (1.04 - 1.16).
     const bool unfilled = 2 * tiles16 > cus_m && tiles16 < cus_m;
     const bool wanted = micro_policy == 2 || (micro_policy == 1 && (unfilled || hi == 1));
-    g->W = W;
-    g->hi = hi;
-    g->mc_r = quads - W * (hi - 1);          // workgroups that take `hi` micro tiles
     return micro_ok && hi <= 3 && wanted;
 }
 // ... and of the trajectory rollout: the single launch where the fused plan would take micro tiles, on the matrix-core kernels,
 // with a step's slices of the trajectory and of the actions inside one buffer descriptor each (the kernel's range check)
 bool lstm_traj_single(bool micro_ok, bool kind_mfma, int micro_policy, int num_cu, int obs_dim, int act_dim, int m, int n,
-                      lstm_micro_geom* g) {
+                      l2a_micro_deal* g) {
     const bool wanted = lstm_micro_wanted(micro_ok, micro_policy, num_cu, m, n, g);
     const long long rows = (long long)m * n;
     return wanted && kind_mfma && rows * obs_dim * 4 < 0x7ffffff0LL && rows * act_dim * 4 < 0x7ffffff0LL;
@@ -169,27 +158,18 @@ int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = tr
             // unit-tile split, so every plan that leaves CUs idle under 16-candidate tiles - and every plan of at most three micro
             // tiles per CU - takes them (policy 1); policy 0 keeps the 16-candidate kernel, 2 forces micro tiles where eligible.
             const int cus_m = ctx->num_cu > 0 ? ctx->num_cu : 256;
-            const int quads = l2a_ceil_div(p.n, 4);
-            int W = cus_m / p.m;
-            if (W > quads) W = quads;
-            int hi = W > 0 ? l2a_ceil_div(quads, W) : 99;
+            l2a_micro_deal g = l2a_deal_micro(cus_m, p.m, p.n, 3);
             // Larger plans: workgroups of FOUR micro tiles, ceil(quads / 4) per env, as many rounds as that takes (the instances
             // with LDS rows for sixteen candidates: 256-unit layers, where the stack still fits)
             int mtm = 3;
-            if (hi > 3 && md->gmicro4_ok) { hi = 4; mtm = 4; }
-            if (hi >= 1 && hi <= 4) {
-                W = l2a_ceil_div(quads, hi);
-                // `hi` forced down to four is not the natural ceil(quads / W) of the W it yields (quads = 5: W = 2 would leave
-                // 5 - 2 * 3 = -1 workgroups of four): take the natural one, so that 1 <= mc_r <= W always holds
-                hi = l2a_ceil_div(quads, W);
-            }
-            const int mc_r = quads - W * (hi - 1);
-            const bool eligible = !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && hi <= mtm && (p.returns_out || p.best_key) &&
-                                  W >= 1 && mc_r >= 1 && mc_r <= W;
+            if (g.hi > 3 && md->gmicro4_ok) { g = l2a_deal_micro(cus_m, p.m, p.n, 4, true); mtm = 4; }
+            const int W = g.W;
+            const bool eligible = !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && g.hi <= mtm && (p.returns_out || p.best_key) &&
+                                  W >= 1 && g.mc_r >= 1 && g.mc_r <= W;
             if (eligible && ctx->micro_policy != 0) {
                 p.mc_w = W;
-                p.mc_hi = hi;
-                p.mc_r = quads - W * (hi - 1);
+                p.mc_hi = g.hi;
+                p.mc_r = g.mc_r;
                 int smem_g = (int)l2a_rnn_micro_smem(md->cell_type, md->n_layers, md->lunits[0], md->KG0, mtm);
                 if (smem_g < 84 * 1024) smem_g = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
                 const int rc = l2a_launch_rnn_micro(md->lunits[0], md->cell_type, mtm, &p, (unsigned)(p.m * W), smem_g, stream);
@@ -232,7 +212,7 @@ int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = tr
         {
             // Micro tiles (lstm_micro_wanted).  Plans only (no per-row states, no state written out:
             // those launches are one step long or chunk continuations and keep the 16-candidate kernel - same bits).
-            lstm_micro_geom g;
+            l2a_micro_deal g;
             const bool eligible = !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && (p.returns_out || p.best_key);
             if (lstm_micro_wanted(md->micro_ok, ctx->micro_policy, ctx->num_cu, p.m, p.n, &g) && eligible) {
                 p.mc_w = g.W;
@@ -257,21 +237,9 @@ int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = tr
         // be resident: they swap their halves of h once per step).  Same bits as the unsplit launch.
         p.split = (allow_split && ctx->split_policy != 0 && 2 * tiles <= cus && p.h < 4096) ? 1 : 0;
         if (p.split) {
-            const long long need = tiles * 4 * (long long)(UT / 2 + md->OT) * 2048;
-            if (need > md->xbuf_bytes) {
-                if (md->xbuf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->xbuf)); md->xbuf = nullptr; }
-                L2A_HIP(ctx, l2a_xbuf_alloc(reinterpret_cast<void**>(&md->xbuf), (size_t)need));
-                L2A_HIP(ctx, hipMemsetAsync(md->xbuf, 0, (size_t)need, stream));
-                md->xbuf_bytes = need;
-                md->launch_nonce = 0;
-            }
-            md->launch_nonce += 1;
-            if (md->launch_nonce >= (1u << 20)) {     // tag space exhausted: wipe stale tags, restart
-                L2A_HIP(ctx, hipMemsetAsync(md->xbuf, 0, (size_t)md->xbuf_bytes, stream));
-                md->launch_nonce = 1;
-            }
-            p.xtag = md->launch_nonce << 12;
-            p.xbuf = md->xbuf;
+            const int xrc = l2a_xbuf_reserve(ctx, &md->xb, tiles * 4 * (long long)(UT / 2 + md->OT) * 2048, stream, &p.xtag);
+            if (xrc != L2A_OK) return xrc;
+            p.xbuf = md->xb.buf;
             p.status = ctx->status_dev;
             p.spin_limit = ctx->spin_limit;
         }
@@ -338,7 +306,7 @@ int rollout_traj(l2a_lstm* md, const float* obs0, const float* c0, const float* 
     if (!md->norm_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM normalisation was never set");
     int kind = ctx->kernel_kind;
     if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
-    lstm_micro_geom g;
+    l2a_micro_deal g;
     if (lstm_traj_single(!md->generic && md->micro_ok, !md->generic && kind == L2A_KERNEL_MFMA && md->mfma_ok, ctx->micro_policy,
                          ctx->num_cu, md->obs_dim, md->act_dim, m, n, &g)) {
         l2a_device_guard guard(ctx->device);
@@ -414,7 +382,7 @@ int l2a_lstm_traj_geometry(int obs_dim, int act_dim, int units, int m, int n, in
         return L2A_EINVAL;
     if ((long long)m * n > 0x3fffffffLL) return L2A_EINVAL;
     const bool mfma_ok = lstm_mfma_eligible(obs_dim, act_dim, units);
-    lstm_micro_geom g;
+    l2a_micro_deal g;
     const bool single = lstm_traj_single(mfma_ok && (units == 256 || units == 512), mfma_ok, micro_policy, num_cu, obs_dim, act_dim, m, n, &g);
     for (int i = 0; i < 8; ++i) out[i] = 0;
     out[0] = single ? 1 : 0;
@@ -616,7 +584,7 @@ void l2a_lstm_destroy(l2a_lstm* md) {
         (void)hipDeviceSynchronize();
         (void)hipFree(md->wblk);
     }
-    if (md->xbuf) (void)hipFree(md->xbuf);
+    if (md->xb.buf) (void)hipFree(md->xb.buf);
     if (md->adv_buf) (void)hipFree(md->adv_buf);
     if (md->traj_buf) (void)hipFree(md->traj_buf);
     if (md->hid_buf) (void)hipFree(md->hid_buf);

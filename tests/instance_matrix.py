@@ -62,7 +62,7 @@ UNREACHABLE = OrderedDict()
 for _ot, _kg0 in ((4, 4), (4, 5)):
     for _gact, _n1 in ((False, False), (True, False), (True, True)):
         UNREACHABLE[Instance("mlp", "whole_1_8", _ot, _kg0, "", _gact, _n1)] = \
-            "l2a_api.hip:406,415 - the whole-tiles route of one tile per workgroup requires OT <= 3"
+            "l2a_api.hip:395 - the whole-tiles route of one tile per workgroup requires OT <= 3"
 for _unit in MFMA_UNITS:
     UNREACHABLE[Instance("mlp", _unit, 3, 4, "k0l1", True, False)] = \
         "l2a_mfma_inst.hip:52 - K0L = 1 is chosen for the fast activations only (no line of l2a_api.hip: the unit's own switch)"

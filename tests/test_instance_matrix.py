@@ -1,6 +1,6 @@
 """The instance matrix (tests/instance_matrix.py) against the launcher's own routing code, without a GPU.
 
-(a) every MLP row, under its policy, is routed (`l2a_plan_geometry`: launch_rollout stopped before its first HIP call) to the
+(a) every MLP row, under its policy, is routed (`l2a_plan_geometry`: the plan `plan_rollout` decides and launch_rollout executes) to the
     unit its instance lives in, and the unit's switch (restated in `instance_matrix.dispatched_instance`) picks that instance;
 (b) the rows cover the literal enumeration of instances minus the explicit UNREACHABLE list - removing a row, or changing a
     policy so that it routes elsewhere, fails here;
@@ -67,7 +67,7 @@ def test_carry_launches_route_to_the_rows_instance(row):
     """Chunk A is a launch of h = 1, chunk B one of h = 2, and the predict (every row has m = 1: n rows in one block) is
     h = 1 again (l2a_api.hip: l2a_predict), all with micro = 0: the launcher must pick the geometry of the row's own plan - and
     with it, by (a), the row's instance.  (A launch with per-row states or a state output never takes the micro tiles whatever the
-    policy says: l2a_api.hip:235.)"""
+    policy says: l2a_api.hip:297.)"""
     assert row.m == 1
     for h in (1, 2):
         g = _geometry(row, h=h, micro=0)
@@ -115,9 +115,9 @@ def test_lstm_rows_meet_the_launcher_conditions():
             assert row.policy["micro"] == 0
             assert row.policy["split"] == (1 if row.instance.variant == "split" else 0)
             assert 2 * tiles <= 256 and row.h < 4096
-            # The carry launches take the same branch: the unit-tile split of :236 reads only the tile count, the split policy
+            # The carry launches take the same branch: the unit-tile split of :238 reads only the tile count, the split policy
             # and h < 4096 (chunks of h = 1 and 2 over the same m, n; l2a_lstm_predict is m = 1, n = rows, h = 1 with the default
-            # `allow_split`), and :207 keeps every launch with per-row states or a state output off the micro tiles.
+            # `allow_split`), and :216 keeps every launch with per-row states or a state output off the micro tiles.
             assert row.m == 1           # so a predict of m * n rows is the plan's own tile count
 
 

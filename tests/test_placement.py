@@ -1,4 +1,4 @@
-"""The XCD placement of single-round launches (csrc/l2a_mfma.h geometry, csrc/l2a_api.hip launch_rollout): a Python mirror of
+"""The XCD placement of single-round launches (csrc/l2a_mfma.h geometry, csrc/l2a_api.hip plan_rollout): a Python mirror of
 the index arithmetic - every logical workgroup must be run by exactly one hardware workgroup, the spare ones must all
 return, and a unit's workgroups must sit on that unit's XCDs only (hardware workgroup i runs on XCD i % 8)."""
 
@@ -6,7 +6,7 @@ import pytest
 
 
 def _host(units, w, cus=256):
-    """launch_rollout: (pl_units, pl_f, pl_r, pl_w, grid) or None when the contiguous remap stays."""
+    """plan_rollout: (pl_units, pl_f, pl_r, pl_w, grid) or None when the contiguous remap stays."""
     if not 2 <= units <= 8:
         return None
     f = 8 // units

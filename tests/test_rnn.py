@@ -798,7 +798,7 @@ ADVANCE_GUARD = 16          # rows of sentinel on each side of c_out / h_out
 
 def _advance_model(obs_dim, act_dim, units, activation, seed):
     """One LSTM layer on which `l2a_lstm_advance` runs `l2a_lstm_advance_k`, with `advance_kernel_ok`'s conditions
-    (l2a_lstm_api.hip:274) asserted: not a generic model, units a multiple of 16, not the VALU kernel, the LDS rows fit.
+    (l2a_lstm_api.hip:264) asserted: not a generic model, units a multiple of 16, not the VALU kernel, the LDS rows fit.
     `NativeLSTM` (l2a_rnn_create) makes a width outside the tuned kernel's {128, 256, 512} a GENERIC model, whose state step
     is one step of the rollout kernel; `l2a_lstm_create` keeps it the plain one-layer model that takes the small-rows kernel."""
     import ctypes
@@ -908,7 +908,7 @@ def test_advance_cases_cover_every_value_twice_and_all_run():
                          (3, ("tanh", "relu"))):
         seen = [c[axis] for c in ADVANCE_CASES]
         assert set(seen) == set(values) and all(seen.count(v) >= 2 for v in values), (axis, seen)
-    for rows, units, (obs_dim, act_dim), _ in ADVANCE_CASES:        # advance_kernel_ok's arithmetic (l2a_lstm_api.hip:274)
+    for rows, units, (obs_dim, act_dim), _ in ADVANCE_CASES:        # advance_kernel_ok's arithmetic (l2a_lstm_api.hip:264)
         assert units % 16 == 0 and units >= 16 and (obs_dim + act_dim + units) * 8 * 4 + 4 * 64 * 8 * 4 <= 64 * 1024
     ks = {obs_dim + act_dim + units for _, units, (obs_dim, act_dim), _ in ADVANCE_CASES}
     assert any(k % 4 for k in ks) and any(k % 4 == 0 and k % 8 for k in ks) and any(k % 8 == 0 for k in ks)

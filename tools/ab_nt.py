@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """NT = 1 against NT = 2 (two candidate tiles per workgroup) on multi-round plans, shape by shape - run once per value of
-L2A_FORCE_NT (the library reads it at the first launch): feeds the NT choice of launch_rollout (csrc/l2a_api.hip), in particular
+L2A_FORCE_NT (the library reads it once, when it first builds a launch policy: rollout_policy): feeds the NT choice of plan_rollout
+(choose_nt, csrc/l2a_api.hip), in particular
 for the instances whose NT = 2 form spills registers (wide observations at hidden width 512)."""
 import json
 import os
