@@ -295,7 +295,8 @@ int l2a_plan_rs_chunk(l2a_model* model, const float* state, int state_per_row, c
  * indices are cand_offset + r % n).  A workgroup's 64 rows of a step must fit the LDS:
  * 256 * (2 * (obs_dim | 1) + (act_dim | 1)) bytes <= 63 KiB, e.g. obs_dim <= 117 at act_dim 16.
  *
- * l2a_plan_rs_program: the plan step for an env with a reward program - `h` one-step launches of the rollout kernels
+ * l2a_plan_rs_program: the plan step for an env with a reward program - the rollout of l2a_rollout_traj (below: ONE launch
+ * of the trajectory-writing micro-tile kernel for the plans that fit one, the same bits) or else `h` one-step launches of the rollout kernels
  * with the state carried from launch to launch (l2a_plan_rs_chunk's hand-off: traj[t] is launch t's state_out and launch
  * t + 1's state), then ONE scoring launch; all on `stream`, no host synchronisation inside.  The price of generality is
  * h launches per plan instead of one and a trajectory that passes through HBM; the rollout kernels themselves are
@@ -330,8 +331,8 @@ int l2a_plan_rs_program(l2a_model* model, const float* obs0, const float* action
  * l2a_reward_model_predict: obs [rows, obs_dim], act [rows, act_dim], next_obs [rows, obs_dim] -> rewards_out [rows]
  * (device fp32) - the same kernel as a one-step trajectory with per-row observations.
  * l2a_score_trajectory_model: arguments and outputs as l2a_score_trajectory (keys, ties, NaN, best_key zeroed on `stream`).
- * l2a_plan_rs_reward_model: the carry chain of l2a_plan_rs_program - h one-step launches of the rollout kernels through
- * traj_out (or the model's own buffer) - followed by l2a_score_trajectory_model.  `rm` and `model` must live on the same
+ * l2a_plan_rs_reward_model: the rollout of l2a_plan_rs_program - the single launch of l2a_rollout_traj, or h one-step launches of
+ * the rollout kernels through traj_out (or the model's own buffer) - followed by l2a_score_trajectory_model.  `rm` and `model` must live on the same
  * context and agree on obs_dim and act_dim (L2A_EINVAL).  A flagged tile-split launch anywhere in the chain flags the
  * call (l2a_launch_status), as for l2a_plan_rs_program.
  * l2a_reward_model_geometry: host only, needs no GPU - the scorer's launcher decision (its own function, on plain integers)
@@ -357,6 +358,33 @@ int l2a_score_trajectory_model(l2a_reward_model* rm, const float* obs0, const fl
 int l2a_plan_rs_reward_model(l2a_model* model, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
                              int h, double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
                              float* traj_out, void* stream);
+
+/* ---- the MLP planner's trajectory rollout -------------------------------------------------------
+ * What l2a_plan_rs_program and l2a_plan_rs_reward_model put in front of their scoring launch, and the MLP counterpart of
+ * l2a_lstm_rollout_traj.  Stream-ordered; no host synchronisation unless the model's own buffer grows.
+ *
+ * l2a_rollout_traj: the model's rollout alone.  obs0 [m, obs_dim] (one row per env, as l2a_plan_rs), actions
+ * [h, m*n, act_dim] -> traj_out device fp32 [h, m*n, obs_dim], traj_out[t] = the predicted observation after horizon step t;
+ * traj_out NULL: the model's own buffer (grown on demand; freed with the model).  No rewards.  Two paths, the same bits on both:
+ *   single launch  hidden width 256 / 512 on the matrix-core kernels, when the whole plan is one micro-tile launch (at most
+ *                  three micro tiles per CU), its LDS fits, the streamed weight sets span < 2^31 bytes and a step's slice of the
+ *                  trajectory and of the actions is < 2^31 - 16 bytes - and wanted under l2a_set_micro (0 never, 2 whenever
+ *                  eligible, 1 the measured classes: DESIGN 4.8): the trajectory-writing instance of the micro-tile kernel,
+ *                  the state never leaves the CU between steps.
+ *   carry chain    everything else: h one-step l2a_plan_rs_chunk launches with an all-zero reward, state_out = traj_out[t].
+ * cand_offset is validated as everywhere and changes nothing in the trajectory.  The launch status word keeps its meaning: a
+ * flagged tile-split launch anywhere in the chain flags the call (l2a_launch_status); the single launch has no exchange.
+ *
+ * l2a_mlp_traj_geometry: host only, needs no GPU - which path l2a_rollout_traj takes for `n_hidden` layers of `hidden` units,
+ * `n_sets` weight sets in `mode` (L2A_MODE_*), under micro policy `micro_policy` (0 | 1 | 2) on `num_cu` CUs (<= 0: 256) with
+ * the automatic kernel choice and 160 KiB of LDS; the decision function is the launcher's own.  out[8]: { 0 single launch (1) or
+ * chain (0), 1 launches of the rollout, 2 workgroups of a launch, 3 workgroups per env (single launch), 4 micro tiles of the
+ * largest workgroup (99: no workgroup geometry), 5 workgroups of that size per env, 6 .. 7 zero }.  L2A_EINVAL for a NULL out,
+ * sizes < 1, an unknown mode or policy, more than 2^30 - 1 candidates, per-block mode with m > n_sets.                     */
+int l2a_rollout_traj(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, int cand_offset,
+                     float* traj_out, void* stream);
+int l2a_mlp_traj_geometry(int obs_dim, int act_dim, int n_hidden, int hidden, int mode, int n_sets, int m, int n, int h,
+                          int micro_policy, int num_cu, int* out);
 
 /* One-step batched prediction: MLPDynamicsModel.predict / MetaMLPDynamicsModel.predict
  * (mlp_dynamics.py:204-222, meta_mlp_dynamics.py:276-294).

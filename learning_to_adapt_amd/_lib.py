@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry",
+    "l2a_rollout_traj", "l2a_mlp_traj_geometry",
     "l2a_controller_create", "l2a_controller_create_sharded", "l2a_controller_create_sharded_device", "l2a_lstm_controller_create", "l2a_controller_create_device", "l2a_lstm_controller_create_device",
     "l2a_lstm_controller_create_sharded", "l2a_lstm_controller_create_sharded_device",
     "l2a_controller_destroy", "l2a_controller_step", "l2a_controller_begin", "l2a_lstm_controller_begin", "l2a_controller_finish",
@@ -66,6 +67,22 @@ def lstm_traj_geometry(obs_dim, act_dim, units, m, n, h, micro=1, cus=0):
     rc = lib.l2a_lstm_traj_geometry(int(obs_dim), int(act_dim), int(units), int(m), int(n), int(h), int(micro), int(cus), out)
     if rc != L2A_OK:
         raise L2AError("l2a_lstm_traj_geometry failed (%d)" % rc)
+    v = list(out)
+    return dict(single=bool(v[0]), launches=v[1], workgroups=v[2], workgroups_per_env=v[3], micro_tiles=v[4], full_workgroups=v[5])
+
+
+def mlp_traj_geometry(obs_dim, act_dim, n_hidden, hidden, mode, n_sets, m, n, h, micro=1, cus=0):
+    """Which path ``l2a_rollout_traj`` takes for ``n_hidden`` layers of ``hidden`` units with ``n_sets`` weight sets in ``mode``
+    ('single' | 'per_block' | 'mean') (``l2a_mlp_traj_geometry``: the launcher's own decision function, no GPU needed) under micro
+    policy ``micro`` on ``cus`` CUs (0: 256).  Returns a dict: single (one launch of the trajectory-writing micro-tile instance) or
+    the carry chain, launches, workgroups, workgroups_per_env, micro_tiles (of the largest workgroup; 99: none fits),
+    full_workgroups (per env, of that size)."""
+    lib = load()
+    out = (ctypes.c_int * 8)()
+    rc = lib.l2a_mlp_traj_geometry(int(obs_dim), int(act_dim), int(n_hidden), int(hidden), MODE_CODES[mode], int(n_sets), int(m), int(n),
+                                   int(h), int(micro), int(cus), out)
+    if rc != L2A_OK:
+        raise L2AError("l2a_mlp_traj_geometry failed (%d)" % rc)
     v = list(out)
     return dict(single=bool(v[0]), launches=v[1], workgroups=v[2], workgroups_per_env=v[3], micro_tiles=v[4], full_workgroups=v[5])
 
@@ -309,6 +326,11 @@ def load():
         lib.l2a_lstm_plan_rs_reward_model.restype = i32
         lib.l2a_lstm_traj_geometry.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, c.POINTER(i32)]
         lib.l2a_lstm_traj_geometry.restype = i32
+    if hasattr(lib, "l2a_rollout_traj"):                # (absent from older variant libraries selected with L2A_LIB_PATH)
+        lib.l2a_rollout_traj.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        lib.l2a_rollout_traj.restype = i32
+        lib.l2a_mlp_traj_geometry.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, c.POINTER(i32)]
+        lib.l2a_mlp_traj_geometry.restype = i32
     if os.environ.get("L2A_LIB_PATH") and not hasattr(lib, "l2a_controller_step"):
         pass                                               # developer A/B against a library of an earlier round
     else:

@@ -400,6 +400,61 @@ int plan_rollout(const l2a_mlp_shape& md, const l2a_rollout_policy& pol, const l
     return L2A_OK;
 }
 
+// ---- the trajectory rollout of the plans a separate launch scores (l2a_rollout_traj, l2a_plan_rs_program, l2a_plan_rs_reward_model):
+//      ONE launch of the trajectory-writing micro-tile instance (l2a_mlp_micro_k<UW, GACT, true>), or the carry chain of h one-step
+//      launches.  The ONE decision function of the launcher (rollout_traj_launch) and of l2a_mlp_traj_geometry; pure host
+//      arithmetic beside plan_rollout, which it neither calls nor changes -------------------------------------------------------
+struct l2a_traj_plan {
+    bool single;            // one launch of the micro-tile instance; else the chain (every field below is then informational)
+    l2a_micro_deal deal;    // workgroups per env, micro tiles of the largest, how many of that size
+    int gact, smem;
+    long long m_bytes;      // the weight span of the launch's buffer descriptor
+};
+
+l2a_traj_plan plan_traj_rollout(const l2a_mlp_shape& md, const l2a_rollout_policy& pol, int mode, int m, int n) {
+    l2a_traj_plan tp = l2a_traj_plan();
+    tp.deal = {0, 99, 0};
+    int kind = pol.kernel_kind;
+    if (kind == L2A_KERNEL_AUTO) kind = md.mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
+    if (kind != L2A_KERNEL_MFMA || !md.mfma_ok || !md.micro_ok) return tp;
+    if (mode == L2A_MODE_PER_BLOCK && m > md.n_sets) return tp;          // (the chain reports the error)
+    const int e_loop = (mode == L2A_MODE_MEAN) ? md.n_sets : 1;
+    const int cus = pol.num_cu;
+    tp.deal = l2a_deal_micro(cus, m, n, 3);
+    const int smem_need = l2a_mlp_micro_smem(md.H, md.KG0, md.n_hidden, e_loop);
+    const long long span = (long long)((mode == L2A_MODE_PER_BLOCK ? m : e_loop) - 1) * md.set_stride * 4 +
+                           l2a_mlp_micro_floats(md.H, md.KG0, md.n_hidden) * 4;
+    const long long rows = (long long)m * n;
+    // Eligible: the whole plan is ONE micro-tile launch (at most three micro tiles per workgroup, one workgroup per CU: no double
+    // round in front, no second launch), its LDS fits, the weights of every set it streams lie inside one buffer descriptor, and
+    // so does a step's slice of the trajectory - and of the actions - with the 16 bytes of a lane's widest access to spare:
+    // the kernel's stores and loads are range-checked against exactly these slices.
+    const bool eligible = tp.deal.hi <= 3 && smem_need <= pol.lds_per_block && span < (1LL << 31) &&
+                          rows * md.obs_dim * 4 < 0x7ffffff0LL && rows * md.act_dim * 4 < 0x7ffffff0LL;
+    // automatic: the fused path's rule (plan_rollout: width 512, and either more than CUs / 2 16-candidate tiles or one set per
+    // candidate) asks whether ONE micro-tile launch beats ONE 16-candidate launch.  Here the competitor is h one-step launches,
+    // each of which pays its launch, its constants, its start state through HBM and the fill of its operand ring, so the rule is
+    // wider: every class of eligible plan (width x one set | ensemble x at most | more than CUs / 2 tiles) whose single launch
+    // measured faster than the chain of the commit before it by more than the run-to-run spread of the two measurements
+    // (tools/probe_mlp_traj.py -> profiles/mlp_traj.jsonl, h = 10, l2a_plan_rs_program end to end):
+    //   one set per candidate (single model, per-block sets), both widths, any size: 0.51 - 0.80 of that chain
+    //     (config-1 shape 0.60, GrBAL default 0.78, 2 x 256 0.51, 5 adapted 3 x 256 0.66, n = 100 0.59, n = 3000 on three micro
+    //     tiles per CU 0.80; spread <= 0.014);
+    //   mean ensembles of more than CUs / 2 tiles, both widths: 0.77 - 0.90 (E = 5; width 512: n = 2100 0.77, n = 3000 0.89;
+    //     width 256: 0.88, 0.90; spread <= 0.005);
+    //   mean ensembles of at most CUs / 2 tiles keep the chain: every workgroup of four to twelve candidates streams all E sets,
+    //     which the chain's tile split and member fan spread over the chip - 2.0 - 2.1 of the chain at width 512, 1.23 at 256.
+    // The fused rule's classes are all among these, so no plan rolls on micro tiles fused and on the chain here.
+    const long long tiles16 = (long long)m * ceil_div(n, 16);
+    const bool measured = e_loop == 1 || 2 * tiles16 > cus;
+    const bool wanted = pol.micro_policy == 2 || (pol.micro_policy == 1 && measured);
+    tp.single = eligible && wanted;
+    tp.gact = (!(fast_act(md.hidden_act) && fast_act(md.output_act)) || md.n_hidden == 1) ? 1 : 0;
+    tp.smem = smem_need < 84 * 1024 ? 84 * 1024 : smem_need;             // more than half a CU's LDS: one workgroup per CU
+    tp.m_bytes = span;
+    return tp;
+}
+
 // Executes the plan of `p`'s request: fills the geometry fields of `p` and launches on `stream_v`.
 int launch_rollout(l2a_model* md, L2AKParams& p, void* stream_v) {
     l2a_ctx* ctx = md->ctx;
@@ -475,6 +530,32 @@ void model_shape(l2a_mlp_shape* md, int obs_dim, int act_dim, int n_hidden, cons
     md->micro_ok = md->mfma_ok && (md->H == 256 || md->H == 512);
     // the quarter sums of the O4 instance (l2a_mfma_inst.hip picks it for exactly these shapes)
     md->m_o4 = (md->micro_ok && md->OT == 2 && md->KG0 == 2 && n_hidden > 1 && obs_dim - 16 <= 4) ? 1 : 0;
+}
+
+// Lays out one weight-set block (offsets in floats, every region 64-B aligned) -> the block's size, a set's stride in the model's
+// storage.  `dst`: the model whose offsets are filled in, or null (l2a_mlp_traj_geometry: the stride alone).
+long long layout_weight_set(const l2a_mlp_shape& md, l2a_model* dst) {
+    l2a_model scratch;
+    l2a_model* o = dst ? dst : &scratch;
+    long long off = 0;
+    auto take = [&off](long long n) { long long at = off; off += (n + 15) / 16 * 16; return at; };
+    int k_in = md.in_dim;
+    for (int l = 0; l <= md.n_hidden; ++l) {
+        const int n_out = (l < md.n_hidden) ? md.hidden[l] : md.obs_dim;
+        o->raw_w[l] = take((long long)k_in * n_out);
+        o->raw_b[l] = take(n_out);
+        k_in = n_out;
+    }
+    if (md.mfma_ok) {
+        o->pk_w0 = take(packed_floats(md.in_dim, md.H));
+        o->pk_wmid_stride = packed_floats(md.H, md.H);
+        o->pk_wmid = take(o->pk_wmid_stride * (md.n_hidden - 1));
+        o->pk_wout = take(packed_floats(md.H, md.obs_dim));
+        if (md.micro_ok) o->pk_m = take(l2a_mlp_micro_floats(md.H, md.KG0, md.n_hidden));
+    }
+    o->pk_bout = take(16 * md.OT);
+    o->nm_off = take(32 * md.KG0 + 32 * md.OT);
+    return off;
 }
 
 void fill_model_params(const l2a_model* md, L2AKParams& p) {
@@ -592,6 +673,34 @@ int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden,
     const int g[12] = {d.family, d.nt, d.split, mfma16 ? d.split_from : -1, d.geo == 1, (int)d.grid, d.smem, mfma16 ? d.lb : 1,
                        d.mc_hi, d.pl_units, plan.n_launch == 2 ? (int)plan.launch[0].grid : 0, d.geo == 2};
     std::memcpy(out, g, sizeof(g));
+    return L2A_OK;
+}
+
+int l2a_mlp_traj_geometry(int obs_dim, int act_dim, int n_hidden, int hidden, int mode, int n_sets, int m, int n, int h,
+                          int micro_policy, int num_cu, int* out) {
+    if (!out || obs_dim < 1 || act_dim < 1 || n_hidden < 1 || n_hidden > L2A_MAX_LAYERS - 1 || hidden < 1 || n_sets < 1 ||
+        m < 1 || n < 1 || h < 1 || micro_policy < 0 || micro_policy > 2)
+        return L2A_EINVAL;
+    if (mode != L2A_MODE_SINGLE && mode != L2A_MODE_PER_BLOCK && mode != L2A_MODE_MEAN) return L2A_EINVAL;
+    if ((long long)m * n > 0x3fffffffLL || (mode == L2A_MODE_PER_BLOCK && m > n_sets)) return L2A_EINVAL;
+    l2a_ctx ctx;                                    // (its default policies; never touches a device)
+    ctx.num_cu = num_cu > 0 ? num_cu : 256;
+    ctx.lds_per_block = 160 * 1024;
+    ctx.micro_policy = micro_policy;
+    int widths[L2A_MAX_LAYERS];
+    for (int i = 0; i < L2A_MAX_LAYERS; ++i) widths[i] = hidden;
+    l2a_mlp_shape md;
+    model_shape(&md, obs_dim, act_dim, n_hidden, widths, L2A_ACT_RELU, L2A_ACT_IDENTITY, n_sets, mode);
+    // (the stride of a set in the model's weight block: what l2a_model_create lays out)
+    md.set_stride = layout_weight_set(md, nullptr);
+    const l2a_traj_plan tp = plan_traj_rollout(md, rollout_policy(&ctx), mode, m, n);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = tp.single ? 1 : 0;
+    out[1] = tp.single ? 1 : h;
+    out[2] = tp.single ? m * tp.deal.W : m * ceil_div(n, 16);    // (chain: before any tile split of the one-step launches)
+    out[3] = tp.single ? tp.deal.W : 0;
+    out[4] = tp.deal.hi;
+    out[5] = tp.single ? tp.deal.mc_r : 0;
     return L2A_OK;
 }
 
@@ -752,25 +861,7 @@ int l2a_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden, const
     md->ctx = ctx;
     model_shape(md, obs_dim, act_dim, n_hidden, hidden, hidden_act, output_act, n_sets, mode);
 
-    // ---- lay out one weight-set block (offsets in floats, every region 64-B aligned) ------
-    long long off = 0;
-    auto take = [&off](long long n) { long long o = off; off += (n + 15) / 16 * 16; return o; };
-    int k_in = md->in_dim;
-    for (int l = 0; l <= n_hidden; ++l) {
-        const int n_out = (l < n_hidden) ? hidden[l] : obs_dim;
-        md->raw_w[l] = take((long long)k_in * n_out);
-        md->raw_b[l] = take(n_out);
-        k_in = n_out;
-    }
-    if (md->mfma_ok) {
-        md->pk_w0 = take(packed_floats(md->in_dim, md->H));
-        md->pk_wmid_stride = packed_floats(md->H, md->H);
-        md->pk_wmid = take(md->pk_wmid_stride * (n_hidden - 1));
-        md->pk_wout = take(packed_floats(md->H, obs_dim));
-        if (md->micro_ok) md->pk_m = take(l2a_mlp_micro_floats(md->H, md->KG0, n_hidden));
-    }
-    md->pk_bout = take(16 * md->OT);
-    md->nm_off = take(32 * md->KG0 + 32 * md->OT);
+    const long long off = layout_weight_set(*md, md);
     md->set_stride = off;
 
     hipError_t e = hipSetDevice(ctx->device);
@@ -1390,7 +1481,59 @@ static int plan_carry_chain(l2a_model* md, const float* obs0, const float* actio
     return L2A_OK;
 }
 
-// The plan step of an env with a reward program: the carry chain and one scoring launch (l2a_score.hip).
+// The predicted trajectory [h, m n, obs_dim] of a plan -> *traj (traj_out, or the model's own buffer behind the carry returns;
+// arguments validated by the callers).  One launch of the trajectory-writing micro-tile instance where plan_traj_rollout says so,
+// else plan_carry_chain.  Stream-ordered; the same bits on both paths.
+static int rollout_traj_launch(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                               int cand_offset, float* traj_out, void* stream_v, float** traj) {
+    l2a_ctx* ctx = md->ctx;
+    const l2a_traj_plan tp = plan_traj_rollout(*md, rollout_policy(ctx), md->mode, m, n);
+    if (!tp.single) return plan_carry_chain(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, traj);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    const int sets_needed = (md->mode == L2A_MODE_PER_BLOCK) ? (m < md->n_sets ? m : md->n_sets) : md->n_sets;
+    for (int e = 0; e < sets_needed; ++e) {
+        if (!md->weights_set[e]) return fail(ctx, L2A_ESTATE, "weight set " + std::to_string(e) + " was never set");
+        if (!md->norm_set[e]) return fail(ctx, L2A_ESTATE, "normalisation of set " + std::to_string(e) + " was never set");
+    }
+    const long long rows = (long long)m * n;
+    const long long need = rows + (traj_out ? 0 : (long long)h * rows * md->obs_dim);       // (the chain's layout: either path may follow)
+    if (!traj_out && need > md->prog_buf_floats) {
+        if (md->prog_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->prog_buf)); md->prog_buf = nullptr; md->prog_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->prog_buf), (size_t)need * sizeof(float)));
+        md->prog_buf_floats = need;
+    }
+    *traj = traj_out ? traj_out : md->prog_buf + rows;
+    L2AKParams p;
+    fill_model_params(md, p);
+    p.obs0 = obs0; p.obs_per_row = 0; p.actions = actions;
+    p.state_out = *traj;                                // (this instance: the whole trajectory)
+    p.disc0 = 1.0; p.discount = 1.0;
+    p.m = m; p.n = n; p.h = h; p.cand_offset = cand_offset;
+    p.c_lo = 0; p.c_hi = n;
+    p.mc_w = tp.deal.W; p.mc_hi = tp.deal.hi; p.mc_r = tp.deal.mc_r; p.m_bytes = tp.m_bytes;
+    p.dbg = ctx->dbg;
+    const int rc = l2a_launch_mlp_micro_traj(md->H, tp.gact, &p, (unsigned)(m * tp.deal.W), tp.smem, stream);
+    if (rc != 0) return fail(ctx, L2A_EHIP, std::string("trajectory micro-tile MLP kernel launch: ") +
+                                                (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
+}
+
+// The model's rollout alone: what the two plan entries below put in front of their scoring launch.
+int l2a_rollout_traj(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, int cand_offset, float* traj_out,
+                     void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    if (!obs0 || !actions) return fail(ctx, L2A_EINVAL, "l2a_rollout_traj: null obs0/actions");
+    if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, "l2a_rollout_traj: m, n and h must be >= 1");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, "l2a_rollout_traj: too many candidates");
+    float* traj = nullptr;
+    return rollout_traj_launch(md, obs0, actions, m, n, h, 1.0, cand_offset, traj_out, stream_v, &traj);
+}
+
+// The plan step of an env with a reward program: the rollout and one scoring launch (l2a_score.hip).
 int l2a_plan_rs_program(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
                         const l2a_reward_program* program, int cand_offset, float* returns_out,
                         unsigned long long* best_key, float* traj_out, void* stream_v) {
@@ -1404,13 +1547,13 @@ int l2a_plan_rs_program(l2a_model* md, const float* obs0, const float* actions, 
     if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: too many candidates");
     float* traj = nullptr;
-    rc = plan_carry_chain(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    rc = rollout_traj_launch(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
     if (rc != L2A_OK) return rc;
     return l2a_score_trajectory(ctx, obs0, traj, actions, m, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset,
                                 returns_out, best_key, stream_v);
 }
 
-// The plan step with a learned reward model: the carry chain and the matrix-core scoring launch (l2a_score_mlp.hip).
+// The plan step with a learned reward model: the rollout and the matrix-core scoring launch (l2a_score_mlp.hip).
 int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n, int h,
                              double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
                              float* traj_out, void* stream_v) {
@@ -1430,7 +1573,7 @@ int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* o
     if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: too many candidates");
     float* traj = nullptr;
-    const int rc = plan_carry_chain(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    const int rc = rollout_traj_launch(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
     if (rc != L2A_OK) return rc;
     return l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, returns_out, best_key, stream_v);
 }

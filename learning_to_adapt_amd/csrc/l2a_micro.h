@@ -580,7 +580,12 @@ __global__ void __launch_bounds__(256) l2a_lstm_micro_k(const L2ALstmParams p) {
 // so the operand ring (three records requested ahead) runs through every phase boundary and into the next set with a
 // record counter and nothing else.
 // ------------------------------------------------------------------------------------------------------------------
-template <int MT, int UW, bool GACT>
+//
+// TRAJ: the trajectory-writing instance (l2a_rollout_traj; l2a_mlp_micro_traj_inst.hip), as in l2a_lstm_micro_body: every step's
+// predicted observation goes to p.state_out [h, m n, obs_dim] - there the whole trajectory, not one step's hand-off - and that is
+// its only output: no fused reward, no return, no keys, no mailbox.  Layers, reduce, ensemble mean and state update are the code
+// below, unchanged: the stored bits are those the 16-candidate kernel's state_out holds in a chain of one-step launches.
+template <int MT, int UW, bool GACT, bool TRAJ = false>
 __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const int env, const int cand0, char* smem) {
     constexpr int H = 256 * UW;
     constexpr int ROWF = l2a_micro_row(H);
@@ -675,7 +680,7 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
     // Branch-free: the row offsets of a lane's values are loop invariants, a slot that holds no feature of this lane goes to
     // the row's padding (floats 96 .. 103, never read); a set's constants come as 16-byte reads, all issued before the arithmetic.
     f32x4 av[2];
-    float asq;
+    [[maybe_unused]] float asq = 0.0f;
     int xo_s[4], xo_a[2][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -690,7 +695,7 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
             xo_a[s2][ii] = (b < 4 && k >= obs_dim && k < obs_dim + act_dim) ? l2a_chain_k(k) : 96 + (lane & 7);
         }
     auto write_x = [&]() {
-        {
+        if constexpr (!TRAJ) {
             float s = 0.0f;
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii) {
@@ -725,10 +730,25 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
     load_actions(p.h > 1 ? 1 : 0, av_next);
     write_x();
 
-    float ret = p.ret_in ? p.ret_in[(long long)env * p.n + (valid ? cand : p.c_hi - 1)] : 0.0f;
-    double disc_pow = p.disc0;
+    [[maybe_unused]] float ret = 0.0f;
+    if constexpr (!TRAJ) ret = p.ret_in ? p.ret_in[(long long)env * p.n + (valid ? cand : p.c_hi - 1)] : 0.0f;
+    [[maybe_unused]] double disc_pow = p.disc0;
     const float e_count = (float)e_loop;
     const float e_inv = 1.0f / e_count;
+
+    // TRAJ: byte offset of the lane's four dims in a step's slice of the trajectory (a bounds-checked buffer descriptor per step,
+    // like load_actions); the slots without a row of their own - candidates past the plan, waves past the micro tiles - get an
+    // offset past every slice, so do the dims past the observation: those stores are dropped by the range check, no branch.
+    // (host: a slice is < 2^31 - 16 bytes.)  16-byte stores where every row starts on a 16-byte boundary.
+    [[maybe_unused]] int toff = 0x7ffffff0;
+    [[maybe_unused]] bool t_v4 = false;
+    [[maybe_unused]] long long t_step = 0;
+    if constexpr (TRAJ) {
+        const bool live = valid && (wave < MT) && (4 * b < obs_dim);
+        toff = live ? (row * obs_dim + 4 * b) * 4 : 0x7ffffff0;
+        t_v4 = ((obs_dim & 3) == 0) && ((reinterpret_cast<unsigned long long>(p.state_out) & 15ull) == 0ull);
+        t_step = (long long)R * obs_dim;
+    }
 
     // ---- operand stream ----------------------------------------------------------------------------------------------
     const __amdgpu_buffer_rsrc_t rsA = l2a_rsrc(p.wblk + p.pk_m, p.m_bytes);
@@ -895,8 +915,11 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
         L2A_MTS(11)
 
         // ---- group A + group B, ensemble mean, reward, state update (this wave's micro tile) ----------------------------------
-        const float disc_t = (float)disc_pow;
-        disc_pow *= p.discount;
+        [[maybe_unused]] float disc_t = 0.0f;
+        if constexpr (!TRAJ) {
+            disc_t = (float)disc_pow;
+            disc_pow *= p.discount;
+        }
         {
             f32x4 d = dsum + dgrp;
             if (e_loop > 1) {
@@ -912,30 +935,43 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii)      // padding lanes stay exact zeros, also for a diverged candidate (l2a_mfma.h)
                 if (4 * b + ii >= obs_dim) nx[ii] = 0.0f;
-            // reward in the 16-candidate kernel's order: quarter partials r_qq (lanes b = qq < 4), (r0 + r1) + (r2 + r3)
-            float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
-            float psq = 0.0f;
-            const int vi = p.rw.vel_index;
-            const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
-            const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
-            const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
-            if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+            if constexpr (TRAJ) {
+                const __amdgpu_buffer_rsrc_t trs = l2a_rsrc(p.state_out + (long long)t * t_step, t_step * 4);
+                if (t_v4) {
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, nx), trs, toff, 0, 0);
+                } else {
 #pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                const int dim = 4 * b + ii;
-                const bool in_dist = (p.rw.dist_coef != 0.0f) && (dim >= p.rw.dist_index) &&
-                                     (dim < p.rw.dist_index + 3) && (dim < obs_dim);
-                psq += in_dist ? nx[ii] * nx[ii] : 0.0f;
+                    for (int ii = 0; ii < 4; ++ii)
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(nx[ii]), trs,
+                                                              (4 * b + ii < obs_dim) ? toff + 4 * ii : 0x7ffffff0, 0, 0);
+                }
+                st = nx;
+            } else {
+                // reward in the 16-candidate kernel's order: quarter partials r_qq (lanes b = qq < 4), (r0 + r1) + (r2 + r3)
+                float plin = ((qq == 0) ? p.rw.alive : 0.0f) - (p.rw.ctrl_coef != 0.0f ? p.rw.ctrl_coef * asq : 0.0f);
+                float psq = 0.0f;
+                const int vi = p.rw.vel_index;
+                const float dsel = (vi & 2) ? ((vi & 1) ? d[3] : d[2]) : ((vi & 1) ? d[1] : d[0]);
+                const float ssel = (vi & 2) ? ((vi & 1) ? st[3] : st[2]) : ((vi & 1) ? st[1] : st[0]);
+                const float dvel = l2a_from_row(dsel + (ssel - ssel), vi >> 4);         // block (vi >> 2) & 3 of row 0 <- the lane that holds dim vel_index
+                if (p.rw.w_vel != 0.0f && qq == ((vi >> 2) & 3)) plin += p.rw.w_vel * dvel * p.rw.inv_dt;
+#pragma unroll
+                for (int ii = 0; ii < 4; ++ii) {
+                    const int dim = 4 * b + ii;
+                    const bool in_dist = (p.rw.dist_coef != 0.0f) && (dim >= p.rw.dist_index) &&
+                                         (dim < p.rw.dist_index + 3) && (dim < obs_dim);
+                    psq += in_dist ? nx[ii] * nx[ii] : 0.0f;
+                }
+                st = nx;
+                plin = l2a_row_quarter_sum(plin);
+                float r = plin;
+                if (p.rw.dist_coef != 0.0f) {
+                    psq = l2a_sum_xor32(l2a_sum_xor16(psq));                    // over the obs tiles of a quarter (one is non-zero)
+                    psq = l2a_row_quarter_sum(psq);
+                    r -= p.rw.dist_coef * sqrtf(psq);
+                }
+                ret = fmaf(disc_t, r, ret);
             }
-            st = nx;
-            plin = l2a_row_quarter_sum(plin);
-            float r = plin;
-            if (p.rw.dist_coef != 0.0f) {
-                psq = l2a_sum_xor32(l2a_sum_xor16(psq));                    // over the obs tiles of a quarter (one is non-zero)
-                psq = l2a_row_quarter_sum(psq);
-                r -= p.rw.dist_coef * sqrtf(psq);
-            }
-            ret = fmaf(disc_t, r, ret);
         }
         // the next step's inputs
         L2A_MTS(12)
@@ -945,7 +981,7 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
     }
 
     // ---- results: lanes of block 0 of wave c hold the returns of the candidates cand0 + 4 c + j; the keys meet in LDS ------
-    {
+    if constexpr (!TRAJ) {
         unsigned long long key = 0ull;
         if (valid && b == 0 && wave < MT) {
             if (p.returns_out) p.returns_out[(long long)env * p.n + cand] = ret;
@@ -974,7 +1010,7 @@ __device__ __forceinline__ void l2a_mlp_micro_body(const L2AKParams& p, const in
 
 // Workgroup -> (env, first candidate, micro tiles) as in l2a_lstm_micro_k; logical ids are contiguous per XCD
 // (l2a_logical_wg), so that the workgroups of one env - one weight set in per-block mode - share an XCD's L2.
-template <int UW, bool GACT>
+template <int UW, bool GACT, bool TRAJ = false>
 __global__ void __launch_bounds__(256) l2a_mlp_micro_k(const L2AKParams p) {
     extern __shared__ __attribute__((aligned(16))) char l2a_smem[];
     const int bid = l2a_logical_wg((int)blockIdx.x, (int)gridDim.x);
@@ -986,9 +1022,9 @@ __global__ void __launch_bounds__(256) l2a_mlp_micro_k(const L2AKParams p) {
     unsigned long long wg_r0_;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wg_r0_) : : "memory");
 #endif
-    if (mt == 3) l2a_mlp_micro_body<3, UW, GACT>(p, env, p.c_lo + 4 * q0, l2a_smem);
-    else if (mt == 2) l2a_mlp_micro_body<2, UW, GACT>(p, env, p.c_lo + 4 * q0, l2a_smem);
-    else l2a_mlp_micro_body<1, UW, GACT>(p, env, p.c_lo + 4 * q0, l2a_smem);
+    if (mt == 3) l2a_mlp_micro_body<3, UW, GACT, TRAJ>(p, env, p.c_lo + 4 * q0, l2a_smem);
+    else if (mt == 2) l2a_mlp_micro_body<2, UW, GACT, TRAJ>(p, env, p.c_lo + 4 * q0, l2a_smem);
+    else l2a_mlp_micro_body<1, UW, GACT, TRAJ>(p, env, p.c_lo + 4 * q0, l2a_smem);
 #ifdef L2A_TIMELINE
     if (p.dbg && threadIdx.x == 0) {        // per-workgroup record behind the phase stamps: lifetime (100 MHz real time), XCD, size
         unsigned long long wg_r1_;

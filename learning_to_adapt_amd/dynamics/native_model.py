@@ -220,11 +220,27 @@ class NativeModel(object):
                                   _ptr(returns_out), _ptr(best_key), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_plan_rs")
 
+    def rollout_traj(self, obs0, actions, m, n, h, cand_offset=0, traj_out=None):
+        """The model's predicted trajectory of a plan (``l2a_rollout_traj``): fp32 CUDA ``[h, m * n, obs_dim]``, ``traj[t]`` = the
+        observation after horizon step ``t``.  One launch of the trajectory-writing micro-tile kernel where the plan fits one
+        (``_lib.mlp_traj_geometry``), else ``h`` one-step launches that hand the state on; the same bits either way."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        if traj_out is None:
+            traj_out = torch.empty((h, m * n, self.obs_dim), dtype=torch.float32, device=self.device)
+        assert traj_out.is_cuda and traj_out.dtype == torch.float32 and traj_out.is_contiguous()
+        assert traj_out.numel() == h * m * n * self.obs_dim
+        rc = self.lib.l2a_rollout_traj(self.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h), int(cand_offset),
+                                       _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_rollout_traj")
+        return traj_out
+
     def plan_rs_program(self, obs0, actions, m, n, h, discount, program, cand_offset=0, returns_out=None, best_key=None,
                         traj_out=None):
-        """Plan step of an env with a ``RewardProgram`` (``l2a_plan_rs_program``): ``h`` one-step rollout launches that hand
-        the state on through the trajectory buffer, then the scoring kernel.  Arguments as ``plan_rs``; ``traj_out``:
-        optional fp32 CUDA ``[h, m * n, obs_dim]`` that receives every candidate's states."""
+        """Plan step of an env with a ``RewardProgram`` (``l2a_plan_rs_program``): the rollout of ``rollout_traj``, then the
+        scoring kernel.  Arguments as ``plan_rs``; ``traj_out``: optional fp32 CUDA ``[h, m * n, obs_dim]`` that receives every
+        candidate's states."""
         assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
         assert obs0.is_contiguous() and actions.is_contiguous()
         assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
@@ -244,7 +260,7 @@ class NativeModel(object):
 
     def plan_rs_reward_model(self, obs0, actions, m, n, h, discount, reward_model, cand_offset=0, returns_out=None,
                              best_key=None, traj_out=None):
-        """Plan step with a learned reward (``l2a_plan_rs_reward_model``): the carry chain of ``plan_rs_program``, then the
+        """Plan step with a learned reward (``l2a_plan_rs_reward_model``): the rollout of ``rollout_traj``, then the
         matrix-core scorer of ``reward_model`` (a ``NativeRewardModel``).  Arguments as ``plan_rs_program``."""
         assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
         assert obs0.is_contiguous() and actions.is_contiguous()

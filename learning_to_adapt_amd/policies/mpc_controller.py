@@ -265,7 +265,7 @@ class MPCController(Policy, Serializable):
         return self.reward_model if ok[1] else None
 
     def _program(self):
-        """The plan is scored by a launch of its own behind the rollout's carry chain - the env's reward is a
+        """The plan is scored by a launch of its own behind the trajectory rollout (``l2a_rollout_traj``) - the env's reward is a
         ``RewardProgram`` (``l2a_plan_rs_program``) or a native reward model stands in for it (``l2a_plan_rs_reward_model``) -
         through ``_rollout``, and every path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking
         launch, the horizon-chunked pipelines, the C controllers - declines."""
