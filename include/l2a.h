@@ -885,6 +885,24 @@ int l2a_controller_stats(l2a_controller* controller, double* out, int cap);
  * on the geometry (bit-identical); this is how tests/test_host_logic.py pins the routing table without a GPU.          */
 int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, int n_sets, int mode, int m, int n, int h,
                       const int* policy, int* out);
+/* The same for the recurrent launcher: which launch the library picks for a request of m envs x n candidates x h steps on the
+ * model l2a_rnn_create builds from (obs_dim, act_dim, n_layers, units[], cell_type) - n_layers == 0: the model of
+ * l2a_lstm_create with units[0] units - as the launcher's own plan function decides it, without a HIP call.
+ * request: bit 0 per-row start states, bit 1 a state is written out (state_out / c_out / h_out), bit 2 NO results wanted
+ * (neither returns nor keys), bit 3 the unit-tile split is NOT allowed (the state advance behind a blocking plan), bit 4 the
+ * trajectory rollout (l2a_lstm_rollout_traj: its single launch, or one of the h one-step launches of its carry chain; the other
+ * bits are then ignored).  0 = a plan as l2a_lstm_plan_rs launches it.
+ * policy: NULL or {kernel kind (L2A_KERNEL_*), split, micro, compute units, LDS bytes per workgroup} (negative / 0 = the default:
+ * auto, 1, 1, 256, 160 KiB).
+ * out[12] = {kernel family (0 LSTM VALU, 1 LSTM matrix core on 16-candidate tiles, 2 LSTM micro tiles, 3 LSTM micro tiles writing
+ * the trajectory, 4 generic VALU, 5 generic matrix core, 6 generic micro tiles), micro tiles a workgroup of the instance holds (3
+ * or 4; 0: a 16-candidate kernel), unit-tile split (0 / 1), workgroups, LDS bytes per workgroup, 16-candidate tiles per env,
+ * micro tiles: workgroups per env, micro tiles of the largest one, workgroups of that size per env (0 elsewhere), bytes of the
+ * split's exchange buffer, 1 when a blocking plan on this shape and policy publishes its keys through the mailbox (else: copy and
+ * synchronise), 0}.  Returns the launch's own error code (L2A_EINVAL: a kernel asked for that the shape is not eligible for, LDS
+ * budget exceeded) with out untouched.  Results do not depend on the geometry (bit-identical).                          */
+int l2a_lstm_plan_geometry(int obs_dim, int act_dim, int n_layers, const int* units, int cell_type, int m, int n, int h, int request,
+                           const int* policy, int* out);
 /* 1 when (obs_dim, act_dim, hidden[]) is eligible for the MFMA kernel, else 0.
  * Eligible shapes whose kernel instance keeps part of its working set in scratch memory (spilled VGPRs; correct, slower per
  * MFMA than their neighbours - tools/isa_notes.sh, profiles/r05_scratch_table.txt; none is a BASELINE.json shape):

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick", "l2a_cem_refit_sample", "l2a_cem_refit_sample_fused",
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
-    "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry",
+    "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry", "l2a_lstm_plan_geometry",
     "l2a_rollout_traj", "l2a_mlp_traj_geometry",
     "l2a_controller_create", "l2a_controller_create_sharded", "l2a_controller_create_sharded_device", "l2a_lstm_controller_create", "l2a_controller_create_device", "l2a_lstm_controller_create_device",
     "l2a_lstm_controller_create_sharded", "l2a_lstm_controller_create_sharded_device",
@@ -104,6 +104,29 @@ def plan_geometry(obs_dim, act_dim, hidden, n_sets, mode, m, n, h, split=-1, fan
     return dict(kernel=("valu", "mfma16", "micro")[v[0]], nt=v[1], split=v[2], split_from=v[3], fan=bool(v[4]), workgroups=v[5],
                 lds_bytes=v[6], sets_per_batch=v[7], micro_tiles=v[8], placement_units=v[9], front_workgroups=v[10],
                 whole_instance=bool(v[11]))
+
+
+LSTM_FAMILIES = ("lstm_valu", "lstm_mfma16", "lstm_micro", "lstm_micro_traj", "generic_valu", "generic_mfma16", "generic_micro")
+LSTM_REQUEST_BITS = {"per_row": 1, "state_out": 2, "no_results": 4, "no_split": 8, "traj": 16}
+
+
+def lstm_plan_geometry(obs_dim, act_dim, units, cell, m, n, h, request=(), kernel="auto", split=-1, micro=-1, cus=0, lds=0):
+    """The launch the recurrent launcher would pick (``l2a_lstm_plan_geometry``: its own plan function, no GPU needed) for the
+    model ``l2a_rnn_create`` builds from ``units`` (a list: one entry per layer; an int: the model of ``l2a_lstm_create``).
+    ``request``: names of ``LSTM_REQUEST_BITS``.  Returns a dict: family (``LSTM_FAMILIES``), mtm, split, workgroups, lds_bytes,
+    tiles_per_env, mc_w, mc_hi, mc_r, exchange_bytes, publish."""
+    lib = load()
+    layers = [int(units)] if isinstance(units, int) else [int(x) for x in units]
+    arr = (ctypes.c_int * len(layers))(*layers)
+    pol = (ctypes.c_int * 5)(KERNEL_CODES[kernel], int(split), int(micro), int(cus), int(lds))
+    out = (ctypes.c_int * 12)()
+    rc = lib.l2a_lstm_plan_geometry(int(obs_dim), int(act_dim), 0 if isinstance(units, int) else len(layers), arr, CELL_CODES[cell],
+                                    int(m), int(n), int(h), sum(LSTM_REQUEST_BITS[r] for r in request), pol, out)
+    if rc != L2A_OK:
+        raise L2AError("l2a_lstm_plan_geometry failed (%d)" % rc)
+    v = list(out)
+    return dict(family=LSTM_FAMILIES[v[0]], mtm=v[1], split=v[2], workgroups=v[3], lds_bytes=v[4], tiles_per_env=v[5], mc_w=v[6],
+                mc_hi=v[7], mc_r=v[8], exchange_bytes=v[9], publish=bool(v[10]))
 
 
 def reward_model_check(obs_dim, act_dim, hidden, hidden_act):
@@ -326,6 +349,9 @@ def load():
         lib.l2a_lstm_plan_rs_reward_model.restype = i32
         lib.l2a_lstm_traj_geometry.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, c.POINTER(i32)]
         lib.l2a_lstm_traj_geometry.restype = i32
+    if hasattr(lib, "l2a_lstm_plan_geometry"):          # (absent from older variant libraries selected with L2A_LIB_PATH)
+        lib.l2a_lstm_plan_geometry.argtypes = [i32, i32, i32, c.POINTER(i32), i32, i32, i32, i32, i32, c.POINTER(i32), c.POINTER(i32)]
+        lib.l2a_lstm_plan_geometry.restype = i32
     if hasattr(lib, "l2a_rollout_traj"):                # (absent from older variant libraries selected with L2A_LIB_PATH)
         lib.l2a_rollout_traj.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
         lib.l2a_rollout_traj.restype = i32

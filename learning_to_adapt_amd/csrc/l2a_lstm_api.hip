@@ -19,29 +19,34 @@
 #include <string>
 #include <vector>
 
-struct l2a_lstm {
-    l2a_ctx* ctx = nullptr;
+// What the launcher's decisions read of a model: dimensions, layers and which kernels have an instance for them.  Computed by
+// rnn_shape for both create functions and for l2a_lstm_plan_geometry.
+struct l2a_rnn_shape {
     int obs_dim = 0, act_dim = 0, in_dim = 0, units = 0;
-    int cell_act = L2A_ACT_TANH, output_act = L2A_ACT_IDENTITY;
+    int KG0 = 0, OT = 0, UTW = 0;
     bool mfma_ok = false;
     bool micro_ok = false;                        // the micro-tile kernel of l2a_micro.h has an instance (256 / 512 units)
-    long long pk_mg = 0, pk_mo = 0;               // its copies of the gate matrix / output layer
-    int UTW = 0, KG0 = 0, OT = 0;
+    // generic stacks (l2a_rnn_create): any cell type / several layers -> l2a_rnn_valu_k; `units` = sum(lunits)
+    bool generic = false;
+    int n_layers = 1, cell_type = L2A_CELL_LSTM;
+    int lunits[L2A_RNN_MAX_LAYERS] = {0};
+    bool gmicro_ok = false;                       // the micro-tile kernel of l2a_rnn_micro.h has one (every layer 256 or every layer 512 units wide)
+    bool gmicro4_ok = false;                      // ... with workgroups of four micro tiles (plans beyond three per CU)
+};
+
+struct l2a_lstm : l2a_rnn_shape {
+    l2a_ctx* ctx = nullptr;
+    int cell_act = L2A_ACT_TANH, output_act = L2A_ACT_IDENTITY;
+    long long pk_mg = 0, pk_mo = 0;               // the micro-tile kernel's copies of the gate matrix / output layer
     float* wblk = nullptr;
     long long total = 0;
     long long raw_wk = 0, raw_bk = 0, raw_wo = 0, raw_bo = 0, pk_wg = 0, pk_wout = 0, pk_bout = 0, nm_off = 0;
     bool weights_set = false, norm_set = false;
     std::vector<float> norm_stage;
     l2a_xbuf xb;                                  // unit-tile split exchange granules
-    // generic stacks (l2a_rnn_create): any cell type / several layers -> l2a_rnn_valu_k; `units` = sum(lunits)
-    bool generic = false;
-    int n_layers = 1, cell_type = L2A_CELL_LSTM;
-    int lunits[L2A_RNN_MAX_LAYERS] = {0};
-    long long lw[L2A_RNN_MAX_LAYERS][2] = {{0}}, lb[L2A_RNN_MAX_LAYERS][2] = {{0}};
+    long long lw[L2A_RNN_MAX_LAYERS][2] = {{0}}, lb[L2A_RNN_MAX_LAYERS][2] = {{0}};     // generic stacks: the layers' kernels / biases
     long long lpk[L2A_RNN_MAX_LAYERS][2] = {{0}};  // the kernels again in MFMA fragment order (l2a_rnn_mfma.h); pk_wout alike
-    bool gmicro_ok = false;                       // ... and in the micro-tile kernel's (l2a_rnn_micro.h: every layer 256 or every layer 512 units wide)
-    long long lmk[L2A_RNN_MAX_LAYERS][2] = {{0}};
-    bool gmicro4_ok = false;                      // ... with workgroups of four micro tiles (plans beyond three per CU)
+    long long lmk[L2A_RNN_MAX_LAYERS][2] = {{0}};  // ... and in the micro-tile kernel's (l2a_rnn_micro.h)
     float* adv_buf = nullptr;                     // l2a_lstm_plan_rs_sync: [64, act_dim] chosen actions + [64, obs_dim] next obs
     float* traj_buf = nullptr;                    // l2a_lstm_plan_rs_program / _reward_model: [returns of the carry launches (rows) | trajectory (h x rows x obs_dim)]
     long long traj_buf_floats = 0;
@@ -105,21 +110,94 @@ void fill(const l2a_lstm* md, L2ALstmParams& p) {
     p.disc0 = 1.0;
 }
 
-// generic models (stacks / GRU / BasicRNN / odd LSTM widths): does the launch take the matrix-core kernel of l2a_rnn_mfma.h?
-// (unless the caller asked for the VALU one, or its padded LDS rows do not fit: the VALU kernel's dense rows may still)
-long long generic_mfma_smem(const l2a_lstm* md) {
-    const int gates = md->cell_type == L2A_CELL_LSTM ? 4 : (md->cell_type == L2A_CELL_GRU ? 3 : 1);
-    return 4 * l2a_rnn_mfma_lds_floats(md->in_dim, md->obs_dim, md->n_layers, md->lunits, gates);
+// LDS of a 16-candidate tile's rows: the generic matrix-core kernel's padded ones, and the dense ones of the two VALU kernels
+long long generic_mfma_smem(const l2a_rnn_shape& s) {
+    const int gates = s.cell_type == L2A_CELL_LSTM ? 4 : (s.cell_type == L2A_CELL_GRU ? 3 : 1);
+    return 4 * l2a_rnn_mfma_lds_floats(s.in_dim, s.obs_dim, s.n_layers, s.lunits, gates);
 }
-bool generic_uses_mfma(const l2a_lstm* md) {
-    return md->generic && md->ctx->kernel_kind != L2A_KERNEL_VALU && generic_mfma_smem(md) <= md->ctx->lds_per_block;
+long long valu_smem(const l2a_rnn_shape& s) { return (long long)(s.in_dim + 3 * s.units + 2 * s.obs_dim + 1) * L2A_LVT * 4; }
+
+// The shape of a model: `n_layers` layers of `units[]` cells - or, n_layers == 0, the model of l2a_lstm_create: one LSTM layer of
+// units[0] on the LSTM kernels whatever its width.  Pure; `force_generic`: the developer switch L2A_FORCE_GENERIC.
+l2a_rnn_shape rnn_shape(int obs_dim, int act_dim, int n_layers, const int* units, int cell_type, int lds_per_block, bool force_generic) {
+    l2a_rnn_shape s;
+    s.obs_dim = obs_dim; s.act_dim = act_dim; s.in_dim = obs_dim + act_dim;
+    s.KG0 = l2a_ceil_div(s.in_dim, 16);
+    s.OT = l2a_ceil_div(obs_dim, 16);
+    // the run_rebal.py configuration, at the widths its tuned kernel is instantiated for: the model of l2a_lstm_create;
+    // one LSTM layer of any other width takes the generic matrix-core kernel like the stacks below
+    // (L2A_FORCE_GENERIC: developer switch - A/B of the generic kernels against the tuned one on its own shape)
+    if (n_layers == 0 || (n_layers == 1 && cell_type == L2A_CELL_LSTM && lstm_mfma_eligible(obs_dim, act_dim, units[0]) && !force_generic)) {
+        s.units = s.lunits[0] = units[0];
+        s.mfma_ok = lstm_mfma_eligible(obs_dim, act_dim, units[0]);
+        s.UTW = s.mfma_ok ? units[0] / (16 * L2A_NW) : 0;
+        s.micro_ok = s.mfma_ok && (units[0] == 256 || units[0] == 512);
+        return s;
+    }
+    s.generic = true;
+    s.n_layers = n_layers; s.cell_type = cell_type;
+    for (int l = 0; l < n_layers; ++l) { s.lunits[l] = units[l]; s.units += units[l]; }
+    // micro tiles (l2a_rnn_micro.h): every layer 256 (or every layer 512) units wide, the input shapes of the tuned LSTM kernel,
+    // LDS for the whole stack (256 units: up to three layers; 512: one GRU or BasicRNN layer)
+    s.gmicro_ok = lstm_mfma_eligible(obs_dim, act_dim, 256) && (units[0] == 256 || (units[0] == 512 && cell_type != L2A_CELL_LSTM));
+    for (int l = 0; l < n_layers; ++l) s.gmicro_ok = s.gmicro_ok && units[l] == units[0];
+    s.gmicro_ok = s.gmicro_ok && l2a_rnn_micro_smem(cell_type, n_layers, units[0], s.KG0, 3) <= lds_per_block;
+    // (and only where a 16-candidate kernel fits too - the matrix-core one or, for three-layer stacks, the VALU one: one-step
+    // launches - predict, chunk continuations - stay with those)
+    s.gmicro_ok = s.gmicro_ok && (generic_mfma_smem(s) <= lds_per_block || valu_smem(s) <= lds_per_block);
+    s.gmicro4_ok = s.gmicro_ok && units[0] == 256 && l2a_rnn_micro_smem(cell_type, n_layers, 256, s.KG0, 4) <= lds_per_block;
+    return s;
+}
+bool force_generic() {
+    static const bool on = std::getenv("L2A_FORCE_GENERIC") != nullptr;
+    return on;
+}
+
+// ---- the launch plan of a recurrent rollout: decided once by plan_rnn_launch (pure host arithmetic: no HIP call, no environment,
+//      nothing written but the plan), then executed by launch() / rollout_traj() or reported by l2a_lstm_plan_geometry and
+//      l2a_lstm_traj_geometry ------------------------------------------------------------------------------------------------------
+
+// What the decision depends on beside the model and the request: the context's policies and device facts.
+struct l2a_rnn_policy { int kernel_kind, split_policy, micro_policy, num_cu, lds_per_block; };
+l2a_rnn_policy rnn_policy(const l2a_ctx* ctx) {
+    return {ctx->kernel_kind, ctx->split_policy, ctx->micro_policy, ctx->num_cu > 0 ? ctx->num_cu : 256, ctx->lds_per_block};
+}
+
+struct l2a_rnn_request {
+    int m, n, h;
+    bool per_row, state_out, results;   // per-row start states | a state is written out (state_out, c_out or h_out) | returns or keys are wanted
+    bool allow_split;                   // the unit-tile split may be taken
+    bool traj;                          // the trajectory rollout (rollout_traj): its single launch, or one step of its carry chain
+};
+
+enum { L2A_RNN_LSTM_VALU = 0, L2A_RNN_LSTM_MFMA16 = 1, L2A_RNN_LSTM_MICRO = 2, L2A_RNN_LSTM_MICRO_TRAJ = 3,
+       L2A_RNN_GENERIC_VALU = 4, L2A_RNN_GENERIC_MFMA16 = 5, L2A_RNN_GENERIC_MICRO = 6 };   // (the numbers l2a_lstm_plan_geometry reports)
+
+// One kernel launch: the family, its grid and LDS, and every geometry field of L2ALstmParams (fields a family does not read are 0).
+struct l2a_rnn_launch {
+    int family;
+    int mtm;                // micro tiles the instance's workgroups hold (3; generic stacks: 3 or 4), 0: a 16-candidate kernel
+    unsigned grid;
+    long long smem;
+    long long xbuf_bytes;   // exchange buffer of the unit-tile split; 0 = none
+    int tiles_per_env, mc_w, mc_hi, mc_r, split;
+};
+
+// Does a launch on 16-candidate tiles take a matrix-core kernel?  Generic models (stacks / GRU / BasicRNN / odd LSTM widths): the
+// kernel of l2a_rnn_mfma.h unless the caller asked for the VALU one, or its padded LDS rows do not fit (the VALU kernel's dense
+// rows may still); one LSTM layer: the tuned kernel where the shape has an instance, or where the caller asked for it (the plan
+// then fails).  Also WHETHER A BLOCKING PLAN PUBLISHES through the mailbox (l2a_lstm_plan_rs_sync_hook): only the matrix-core
+// kernels have the mailbox epilogue.  That is not "the plan's family is not a VALU one": a stack whose matrix-core rows do not
+// fit while gmicro_ok holds through the VALU kernel's rows (three 256-unit LSTM layers) launches micro tiles and does not publish.
+bool rnn_uses_mfma(const l2a_rnn_shape& md, const l2a_rnn_policy& pol) {
+    if (md.generic)
+        return pol.kernel_kind != L2A_KERNEL_VALU && generic_mfma_smem(md) <= pol.lds_per_block;
+    return pol.kernel_kind == L2A_KERNEL_AUTO ? md.mfma_ok : pol.kernel_kind == L2A_KERNEL_MFMA;
 }
 
 // Micro tiles for the tuned LSTM kernel (l2a_micro.h): l2a_deal_micro, at most three per workgroup - one workgroup per CU, none
-// idle, no exchange.  The ONE decision function of the fused plan (launch() below), the trajectory rollout (rollout_traj) and
-// l2a_lstm_traj_geometry; pure host arithmetic.
-bool lstm_micro_wanted(bool micro_ok, int micro_policy, int num_cu, int m, int n, l2a_micro_deal* g) {
-    const int cus_m = num_cu > 0 ? num_cu : 256;
+// idle, no exchange.
+bool lstm_micro_wanted(bool micro_ok, int micro_policy, int cus_m, int m, int n, l2a_micro_deal* g) {
     const long long tiles16 = (long long)m * l2a_ceil_div(n, 16);
     *g = l2a_deal_micro(cus_m, m, n, 3);
     const int hi = g->hi;
@@ -131,133 +209,157 @@ bool lstm_micro_wanted(bool micro_ok, int micro_policy, int num_cu, int m, int n
     const bool wanted = micro_policy == 2 || (micro_policy == 1 && (unfilled || hi == 1));
     return micro_ok && hi <= 3 && wanted;
 }
-// ... and of the trajectory rollout: the single launch where the fused plan would take micro tiles, on the matrix-core kernels,
-// with a step's slices of the trajectory and of the actions inside one buffer descriptor each (the kernel's range check)
-bool lstm_traj_single(bool micro_ok, bool kind_mfma, int micro_policy, int num_cu, int obs_dim, int act_dim, int m, int n,
-                      l2a_micro_deal* g) {
-    const bool wanted = lstm_micro_wanted(micro_ok, micro_policy, num_cu, m, n, g);
-    const long long rows = (long long)m * n;
-    return wanted && kind_mfma && rows * obs_dim * 4 < 0x7ffffff0LL && rows * act_dim * 4 < 0x7ffffff0LL;
-}
 
-int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = true) {
-    l2a_ctx* ctx = md->ctx;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    l2a_device_guard guard(ctx->device);
-    if (!md->weights_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM weights were never set");
-    if (!md->norm_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM normalisation was never set");
-    p.dbg = ctx->dbg;
-    if (md->generic) {
-        // stacks / GRU / BasicRNN: the matrix-core kernel of l2a_rnn_mfma.h unless the caller asked for the VALU one (or
-        // its padded LDS rows do not fit: the VALU kernel's dense rows may still)
-        p.tiles_per_env = l2a_ceil_div(p.n, L2A_LVT);
-        const long long smem_m = generic_mfma_smem(md);
-        const int smem_v = (md->in_dim + 3 * md->units + 2 * md->obs_dim + 1) * L2A_LVT * 4;
-        if (ctx->kernel_kind != L2A_KERNEL_VALU && md->gmicro_ok) {
-            // Micro tiles (l2a_rnn_micro.h; geometry and conditions: the tuned LSTM kernel's branch below).  These models have no
-            // unit-tile split, so every plan that leaves CUs idle under 16-candidate tiles - and every plan of at most three micro
-            // tiles per CU - takes them (policy 1); policy 0 keeps the 16-candidate kernel, 2 forces micro tiles where eligible.
-            const int cus_m = ctx->num_cu > 0 ? ctx->num_cu : 256;
-            l2a_micro_deal g = l2a_deal_micro(cus_m, p.m, p.n, 3);
+// The launch of one request, or an error code with its message.
+int plan_rnn_launch(const l2a_rnn_shape& md, const l2a_rnn_policy& pol, l2a_rnn_request rq, l2a_rnn_launch* d, std::string* err) {
+    auto bad = [err](int code, const std::string& msg) { *err = msg; return code; };
+    *d = l2a_rnn_launch();
+    const int cus = pol.num_cu;
+    const bool mfma = rnn_uses_mfma(md, pol);
+    auto micro_tiles = [&](int family, int mtm, const l2a_micro_deal& g, long long smem) {
+        d->family = family; d->mtm = mtm;
+        d->mc_w = g.W; d->mc_hi = g.hi; d->mc_r = g.mc_r;
+        d->grid = (unsigned)(rq.m * g.W);
+        d->smem = smem < 84 * 1024 ? 84 * 1024 : smem;      // more than half a CU's LDS: one workgroup per CU
+        return L2A_OK;
+    };
+    d->tiles_per_env = l2a_ceil_div(rq.n, 16);              // (16 = L2A_LVT: every 16-candidate kernel's tile)
+    l2a_micro_deal g = {0, 99, 0};
+    const bool lstm_micro = !md.generic && mfma && md.mfma_ok && lstm_micro_wanted(md.micro_ok, pol.micro_policy, cus, rq.m, rq.n, &g);
+    if (rq.traj) {
+        // The trajectory rollout: the single launch where the fused plan would take micro tiles, on the matrix-core kernels, with
+        // a step's slices of the trajectory and of the actions inside one buffer descriptor each (the kernel's range check) ...
+        const long long rows = (long long)rq.m * rq.n;
+        if (lstm_micro && rows * md.obs_dim * 4 < 0x7ffffff0LL && rows * md.act_dim * 4 < 0x7ffffff0LL)
+            return micro_tiles(L2A_RNN_LSTM_MICRO_TRAJ, 3, g, l2a_lstm_micro_smem(md.units, md.KG0));
+        // ... else the carry chain: this is one of its h one-step launches, each writing its state out
+        rq = {rq.m, rq.n, 1, false, true, true, true, false};
+    }
+    // Micro tiles are for plans only (no per-row states, no state written out: those launches are one step long or chunk
+    // continuations and keep the 16-candidate kernel - same bits).
+    const bool plan_only = !rq.per_row && !rq.state_out && rq.results;
+    if (md.generic) {
+        if (pol.kernel_kind != L2A_KERNEL_VALU && md.gmicro_ok && pol.micro_policy != 0) {
+            // Micro tiles (l2a_rnn_micro.h; geometry: the tuned LSTM kernel's).  These models have no unit-tile split, so every
+            // plan that leaves CUs idle under 16-candidate tiles - and every plan of at most three micro tiles per CU - takes
+            // them (policy 1); policy 0 keeps the 16-candidate kernel, 2 forces micro tiles where eligible.
+            g = l2a_deal_micro(cus, rq.m, rq.n, 3);
             // Larger plans: workgroups of FOUR micro tiles, ceil(quads / 4) per env, as many rounds as that takes (the instances
             // with LDS rows for sixteen candidates: 256-unit layers, where the stack still fits)
             int mtm = 3;
-            if (g.hi > 3 && md->gmicro4_ok) { g = l2a_deal_micro(cus_m, p.m, p.n, 4, true); mtm = 4; }
-            const int W = g.W;
-            const bool eligible = !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && g.hi <= mtm && (p.returns_out || p.best_key) &&
-                                  W >= 1 && g.mc_r >= 1 && g.mc_r <= W;
-            if (eligible && ctx->micro_policy != 0) {
-                p.mc_w = W;
-                p.mc_hi = g.hi;
-                p.mc_r = g.mc_r;
-                int smem_g = (int)l2a_rnn_micro_smem(md->cell_type, md->n_layers, md->lunits[0], md->KG0, mtm);
-                if (smem_g < 84 * 1024) smem_g = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
-                const int rc = l2a_launch_rnn_micro(md->lunits[0], md->cell_type, mtm, &p, (unsigned)(p.m * W), smem_g, stream);
-                if (rc != 0) return l2a_fail(ctx, L2A_EHIP, std::string("micro-tile recurrent kernel launch: ") +
-                                                            (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
-                L2A_HIP(ctx, hipGetLastError());
-                return L2A_OK;
-            }
+            if (g.hi > 3 && md.gmicro4_ok) { g = l2a_deal_micro(cus, rq.m, rq.n, 4, true); mtm = 4; }
+            if (plan_only && g.hi <= mtm && g.W >= 1 && g.mc_r >= 1 && g.mc_r <= g.W)
+                return micro_tiles(L2A_RNN_GENERIC_MICRO, mtm, g, l2a_rnn_micro_smem(md.cell_type, md.n_layers, md.lunits[0], md.KG0, mtm));
         }
-        bool mfma = ctx->kernel_kind != L2A_KERNEL_VALU;
-        if (mfma && smem_m > ctx->lds_per_block) {
-            if (ctx->kernel_kind == L2A_KERNEL_MFMA)
-                return l2a_fail(ctx, L2A_EINVAL, "LDS budget exceeded by the matrix-core recurrent kernel (" + std::to_string(smem_m) + " B)");
-            mfma = false;
-        }
-        if (!mfma && smem_v > ctx->lds_per_block)
-            return l2a_fail(ctx, L2A_EINVAL, "LDS budget exceeded by the generic recurrent kernel (" + std::to_string(smem_v) +
-                                             " B): the layers' units may sum to about 800 at most");
-        if (mfma) {
-            L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_rnn_mfma_k),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_m));
-            hipLaunchKernelGGL(l2a_rnn_mfma_k, dim3((unsigned)(p.m * p.tiles_per_env)), dim3(256), (size_t)smem_m, stream, p);
-        } else {
-            L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_rnn_valu_k),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem_v));
-            hipLaunchKernelGGL(l2a_rnn_valu_k, dim3((unsigned)(p.m * p.tiles_per_env)), dim3(256), smem_v, stream, p);
-        }
-        L2A_HIP(ctx, hipGetLastError());
+        const long long smem_m = generic_mfma_smem(md), smem_v = valu_smem(md);
+        if (!mfma && pol.kernel_kind == L2A_KERNEL_MFMA)
+            return bad(L2A_EINVAL, "LDS budget exceeded by the matrix-core recurrent kernel (" + std::to_string(smem_m) + " B)");
+        if (!mfma && smem_v > pol.lds_per_block)
+            return bad(L2A_EINVAL, "LDS budget exceeded by the generic recurrent kernel (" + std::to_string(smem_v) +
+                                   " B): the layers' units may sum to about 800 at most");
+        d->family = mfma ? L2A_RNN_GENERIC_MFMA16 : L2A_RNN_GENERIC_VALU;
+        d->smem = mfma ? smem_m : smem_v;
+        d->grid = (unsigned)(rq.m * d->tiles_per_env);
         return L2A_OK;
     }
-    int kind = ctx->kernel_kind;
-    if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
-    if (kind == L2A_KERNEL_MFMA && !md->mfma_ok)
-        return l2a_fail(ctx, L2A_EINVAL, "LSTM shape is not eligible for the MFMA kernel "
-                                         "(needs a single LSTM layer, units in {128, 256, 512}, obs_dim <= 64, act_dim <= 16)");
-    if (kind == L2A_KERNEL_MFMA) {
-        const int nt = 1;
-        const int UT = L2A_NW * md->UTW, U = md->units;
-        p.tiles_per_env = l2a_ceil_div(p.n, 16 * nt);
-        {
-            // Micro tiles (lstm_micro_wanted).  Plans only (no per-row states, no state written out:
-            // those launches are one step long or chunk continuations and keep the 16-candidate kernel - same bits).
-            l2a_micro_deal g;
-            const bool eligible = !p.obs_per_row && !p.state_out && !p.c_out && !p.h_out && (p.returns_out || p.best_key);
-            if (lstm_micro_wanted(md->micro_ok, ctx->micro_policy, ctx->num_cu, p.m, p.n, &g) && eligible) {
-                p.mc_w = g.W;
-                p.mc_hi = g.hi;
-                p.mc_r = g.mc_r;
-                int smem_m = l2a_lstm_micro_smem(U, md->KG0);
-                if (smem_m < 84 * 1024) smem_m = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
-                const int rc = l2a_launch_lstm_micro(U, &p, (unsigned)(p.m * g.W), smem_m, stream);
-                if (rc != 0) return l2a_fail(ctx, L2A_EHIP, std::string("micro-tile LSTM kernel launch: ") +
-                                                            (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
-                L2A_HIP(ctx, hipGetLastError());
-                return L2A_OK;
-            }
-        }
-        const int smem = 2 * nt * UT * 64 * 16 + 2 * (L2A_NW * nt * md->OT * 64) * 16 +
-                         (32 * md->KG0 + 48 * md->OT + 4 * U) * 4;
-        if (smem > ctx->lds_per_block)
-            return l2a_fail(ctx, L2A_EINVAL, "LDS budget exceeded (" + std::to_string(smem) + " B)");
-        const long long tiles = (long long)p.m * p.tiles_per_env;
-        const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
-        // Unit-tile split: two workgroups per candidate tile when that still fits one workgroup per CU (both must
-        // be resident: they swap their halves of h once per step).  Same bits as the unsplit launch.
-        p.split = (allow_split && ctx->split_policy != 0 && 2 * tiles <= cus && p.h < 4096) ? 1 : 0;
-        if (p.split) {
-            const int xrc = l2a_xbuf_reserve(ctx, &md->xb, tiles * 4 * (long long)(UT / 2 + md->OT) * 2048, stream, &p.xtag);
-            if (xrc != L2A_OK) return xrc;
-            p.xbuf = md->xb.buf;
-            p.status = ctx->status_dev;
-            p.spin_limit = ctx->spin_limit;
-        }
-        const unsigned grid = (unsigned)(tiles * (p.split ? 2 : 1));
-        const int rc = l2a_launch_lstm(md->UTW, nt, md->OT, md->KG0, &p, grid, smem, stream);
+    if (mfma && !md.mfma_ok)
+        return bad(L2A_EINVAL, "LSTM shape is not eligible for the MFMA kernel "
+                               "(needs a single LSTM layer, units in {128, 256, 512}, obs_dim <= 64, act_dim <= 16)");
+    if (!mfma) {
+        d->family = L2A_RNN_LSTM_VALU;
+        d->smem = valu_smem(md);
+        if (d->smem > pol.lds_per_block)
+            return bad(L2A_EINVAL, "LDS budget exceeded by the VALU LSTM kernel (" + std::to_string(d->smem) + " B)");
+        d->grid = (unsigned)(rq.m * d->tiles_per_env);
+        return L2A_OK;
+    }
+    if (lstm_micro && plan_only) return micro_tiles(L2A_RNN_LSTM_MICRO, 3, g, l2a_lstm_micro_smem(md.units, md.KG0));
+    d->family = L2A_RNN_LSTM_MFMA16;
+    const int UT = L2A_NW * md.UTW, U = md.units;
+    d->smem = 2 * UT * 64 * 16 + 2 * (L2A_NW * md.OT * 64) * 16 + (32 * md.KG0 + 48 * md.OT + 4 * U) * 4;
+    if (d->smem > pol.lds_per_block) return bad(L2A_EINVAL, "LDS budget exceeded (" + std::to_string(d->smem) + " B)");
+    const long long tiles = (long long)rq.m * d->tiles_per_env;
+    // Unit-tile split: two workgroups per candidate tile when that still fits one workgroup per CU (both must
+    // be resident: they swap their halves of h once per step).  Same bits as the unsplit launch.
+    d->split = (rq.allow_split && pol.split_policy != 0 && 2 * tiles <= cus && rq.h < 4096) ? 1 : 0;
+    if (d->split) d->xbuf_bytes = tiles * 4 * (long long)(UT / 2 + md.OT) * 2048;
+    d->grid = (unsigned)(tiles * (d->split ? 2 : 1));
+    return L2A_OK;
+}
+
+// Launches `d` for the request in `p`: copies the geometry fields and dispatches on the family.
+int execute_rnn_launch(l2a_lstm* md, L2ALstmParams& p, const l2a_rnn_launch& d, hipStream_t stream) {
+    l2a_ctx* ctx = md->ctx;
+    if (d.xbuf_bytes) {
+        const int xrc = l2a_xbuf_reserve(ctx, &md->xb, d.xbuf_bytes, stream, &p.xtag);
+        if (xrc != L2A_OK) return xrc;
+        p.xbuf = md->xb.buf;
+        p.status = ctx->status_dev;
+        p.spin_limit = ctx->spin_limit;
+    }
+    p.dbg = ctx->dbg;
+    p.tiles_per_env = d.tiles_per_env; p.split = d.split;
+    p.mc_w = d.mc_w; p.mc_hi = d.mc_hi; p.mc_r = d.mc_r;
+    const int smem = (int)d.smem;
+    auto micro_rc = [ctx](int rc, const char* what) {
+        return l2a_fail(ctx, L2A_EHIP, std::string(what) + (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
+    };
+    switch (d.family) {
+    case L2A_RNN_GENERIC_MICRO: {
+        const int rc = l2a_launch_rnn_micro(md->lunits[0], md->cell_type, d.mtm, &p, d.grid, smem, stream);
+        if (rc != 0) return micro_rc(rc, "micro-tile recurrent kernel launch: ");
+        break;
+    }
+    case L2A_RNN_LSTM_MICRO: {
+        const int rc = l2a_launch_lstm_micro(md->units, &p, d.grid, smem, stream);
+        if (rc != 0) return micro_rc(rc, "micro-tile LSTM kernel launch: ");
+        break;
+    }
+    case L2A_RNN_LSTM_MICRO_TRAJ: {
+        const int rc = l2a_launch_lstm_micro_traj(md->units, &p, d.grid, smem, stream);
+        if (rc != 0) return micro_rc(rc, "trajectory micro-tile LSTM kernel launch: ");
+        break;
+    }
+    case L2A_RNN_LSTM_MFMA16: {
+        const int rc = l2a_launch_lstm(md->UTW, 1, md->OT, md->KG0, &p, d.grid, smem, stream);
         if (rc == -100) return l2a_fail(ctx, L2A_EINVAL, "no MFMA LSTM kernel instance for this (obs_dim, act_dim, units)");
         if (rc != 0) return l2a_fail(ctx, L2A_EHIP, std::string("MFMA LSTM kernel launch: ") + hipGetErrorString((hipError_t)rc));
-    } else {
-        p.tiles_per_env = l2a_ceil_div(p.n, L2A_LVT);
-        const int smem = (md->in_dim + 3 * md->units + 2 * md->obs_dim + 1) * L2A_LVT * 4;
-        if (smem > ctx->lds_per_block)
-            return l2a_fail(ctx, L2A_EINVAL, "LDS budget exceeded by the VALU LSTM kernel (" + std::to_string(smem) + " B)");
-        L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_lstm_valu_k),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        hipLaunchKernelGGL(l2a_lstm_valu_k, dim3((unsigned)(p.m * p.tiles_per_env)), dim3(256), smem, stream, p);
+        break;
+    }
+    case L2A_RNN_GENERIC_MFMA16:
+        L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_rnn_mfma_k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        hipLaunchKernelGGL(l2a_rnn_mfma_k, dim3(d.grid), dim3(256), (size_t)smem, stream, p);
+        break;
+    case L2A_RNN_GENERIC_VALU:
+        L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_rnn_valu_k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        hipLaunchKernelGGL(l2a_rnn_valu_k, dim3(d.grid), dim3(256), smem, stream, p);
+        break;
+    default:
+        L2A_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_lstm_valu_k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        hipLaunchKernelGGL(l2a_lstm_valu_k, dim3(d.grid), dim3(256), smem, stream, p);
     }
     L2A_HIP(ctx, hipGetLastError());
     return L2A_OK;
+}
+
+// The plan of a request on a model that is ready to launch.
+int plan_launch(const l2a_lstm* md, const l2a_rnn_request& rq, l2a_rnn_launch* d) {
+    const l2a_ctx* ctx = md->ctx;
+    if (!md->weights_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM weights were never set");
+    if (!md->norm_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM normalisation was never set");
+    std::string err;
+    const int prc = plan_rnn_launch(*md, rnn_policy(ctx), rq, d, &err);
+    return prc == L2A_OK ? L2A_OK : l2a_fail(ctx, prc, err);
+}
+
+// Plans the request in `p` and launches it on `stream_v`.
+int launch(l2a_lstm* md, L2ALstmParams& p, void* stream_v, bool allow_split = true) {
+    l2a_device_guard guard(md->ctx->device);
+    l2a_rnn_launch d;
+    const int prc = plan_launch(md, {p.m, p.n, p.h, p.obs_per_row != 0, p.state_out || p.c_out || p.h_out,
+                                     p.returns_out || p.best_key, allow_split, false}, &d);
+    if (prc != L2A_OK) return prc;
+    return execute_rnn_launch(md, p, d, reinterpret_cast<hipStream_t>(stream_v));
 }
 
 // The controller's own state step on the small-rows kernel (single LSTM layer, units a multiple of 16): see l2a_lstm_advance_k.
@@ -295,40 +397,28 @@ int grow(l2a_ctx* ctx, float** buf, long long* have, long long need, hipStream_t
 }
 
 // The predicted trajectory [h, m n, obs_dim] of a plan -> traj (arguments validated by the callers).  Single launch of the
-// trajectory-writing micro-tile instance where lstm_traj_single says so, else the carry chain: h one-step launches of the
+// trajectory-writing micro-tile instance where plan_rnn_launch says so, else the carry chain: h one-step launches of the
 // rollout kernels - all-zero fused reward, state_out = traj[t], the trajectory slice itself being the state hand-off, c / h
 // through the model's two buffer pairs in turn.  Stream-ordered; the same bits on both paths.
 int rollout_traj(l2a_lstm* md, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n, int h,
                  int cand_offset, float* traj, void* stream_v) {
     l2a_ctx* ctx = md->ctx;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    if (!md->weights_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM weights were never set");
-    if (!md->norm_set) return l2a_fail(ctx, L2A_ESTATE, "LSTM normalisation was never set");
-    int kind = ctx->kernel_kind;
-    if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
-    l2a_micro_deal g;
-    if (lstm_traj_single(!md->generic && md->micro_ok, !md->generic && kind == L2A_KERNEL_MFMA && md->mfma_ok, ctx->micro_policy,
-                         ctx->num_cu, md->obs_dim, md->act_dim, m, n, &g)) {
+    l2a_rnn_launch d;
+    int rc = plan_launch(md, {m, n, h, false, true, true, true, true}, &d);
+    if (rc != L2A_OK) return rc;
+    if (d.family == L2A_RNN_LSTM_MICRO_TRAJ) {
         l2a_device_guard guard(ctx->device);
         L2ALstmParams p;
         fill(md, p);
         p.obs0 = obs0; p.c0 = c0; p.h0 = h0; p.actions = actions;
         p.state_out = traj;                             // (this instance: the whole trajectory)
         p.m = m; p.n = n; p.h = h; p.cand_offset = cand_offset; p.discount = 1.0;
-        p.tiles_per_env = l2a_ceil_div(n, 16);
-        p.dbg = ctx->dbg;
-        p.mc_w = g.W; p.mc_hi = g.hi; p.mc_r = g.mc_r;
-        int smem_m = l2a_lstm_micro_smem(md->units, md->KG0);
-        if (smem_m < 84 * 1024) smem_m = 84 * 1024;     // more than half a CU's LDS: one workgroup per CU
-        const int rc = l2a_launch_lstm_micro_traj(md->units, &p, (unsigned)(m * g.W), smem_m, stream);
-        if (rc != 0) return l2a_fail(ctx, L2A_EHIP, std::string("trajectory micro-tile LSTM kernel launch: ") +
-                                                    (rc > 0 ? hipGetErrorString((hipError_t)rc) : "no instance"));
-        L2A_HIP(ctx, hipGetLastError());
-        return L2A_OK;
+        return execute_rnn_launch(md, p, d, stream);
     }
     const long long rows = (long long)m * n;
     const long long hid = rows * md->units;             // (stacks: units = sum of the layers')
-    int rc = grow(ctx, &md->hid_buf, &md->hid_buf_floats, 4 * hid, stream);
+    rc = grow(ctx, &md->hid_buf, &md->hid_buf_floats, 4 * hid, stream);
     if (rc == L2A_OK) rc = grow(ctx, &md->traj_buf, &md->traj_buf_floats, rows, stream);   // (the plan entries ask for more first)
     if (rc != L2A_OK) return rc;
     float* carry_returns = md->traj_buf;                // the chunk launches' required returns_out: all zero rewards, never read
@@ -347,6 +437,37 @@ int rollout_traj(l2a_lstm* md, const float* obs0, const float* c0, const float* 
     return L2A_OK;
 }
 
+// The candidate-count and reward-index checks of the plan entry points (`reward` null: a plan without a fused reward).
+int check_candidates_and_reward(const l2a_lstm* md, const std::string& who, int m, int n, int cand_offset, const l2a_reward* reward) {
+    const l2a_ctx* ctx = md->ctx;
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return l2a_fail(ctx, L2A_EINVAL, who + ": too many candidates");
+    if (reward && reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
+        return l2a_fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
+    if (reward && reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
+        return l2a_fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    return L2A_OK;
+}
+
+// The model's buffer of a state advance on the rollout kernels: [64, act_dim] chosen actions + [64, obs_dim] next obs.
+int ensure_adv_buf(l2a_lstm* md) {
+    if (!md->adv_buf)
+        L2A_HIP(md->ctx, hipMalloc(reinterpret_cast<void**>(&md->adv_buf), sizeof(float) * L2A_MAIL_KEYS * (md->act_dim + md->obs_dim)));
+    return L2A_OK;
+}
+
+// One step of the rollout kernel for `rows` independent rows, each with its own state (the launch of l2a_lstm_predict, and of
+// the state advance of generic cells / stacks: the predicted observation then goes to the back of adv_buf and is dropped).
+void one_step(const l2a_lstm* md, L2ALstmParams& q, const float* obs, const float* act, const float* c, const float* h, int rows,
+              float* next_obs, float* c_out, float* h_out) {
+    fill(md, q);
+    q.obs0 = obs; q.c0 = c; q.h0 = h; q.actions = act;
+    q.state_out = next_obs ? next_obs : md->adv_buf + (size_t)L2A_MAIL_KEYS * md->act_dim;
+    q.c_out = c_out; q.h_out = h_out;
+    q.obs_per_row = 1; q.hid_per_row = 1;
+    q.m = 1; q.n = rows; q.h = 1; q.discount = 1.0;
+}
+
 // argument checks shared by the three entries; *traj: traj_out, or the model's own buffer behind the carry returns
 int traj_args(l2a_lstm* md, const char* who, const float* obs0, const float* c0, const float* h0, const float* actions, int m, int n,
               int h, int cand_offset, bool need_out, bool have_out) {
@@ -355,9 +476,7 @@ int traj_args(l2a_lstm* md, const char* who, const float* obs0, const float* c0,
     if (!obs0 || !c0 || !h0 || !actions) return l2a_fail(ctx, L2A_EINVAL, w + ": null obs0/c0/h0/actions");
     if (need_out && !have_out) return l2a_fail(ctx, L2A_EINVAL, w + ": nothing to write");
     if (m < 1 || n < 1 || h < 1) return l2a_fail(ctx, L2A_EINVAL, w + ": m, n and h must be >= 1");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return l2a_fail(ctx, L2A_EINVAL, w + ": too many candidates");
-    return L2A_OK;
+    return check_candidates_and_reward(md, w, m, n, cand_offset, nullptr);
 }
 
 // the rollout of a plan entry -> *traj (traj_out, or the model's own buffer)
@@ -381,16 +500,48 @@ int l2a_lstm_traj_geometry(int obs_dim, int act_dim, int units, int m, int n, in
     if (!out || obs_dim < 1 || act_dim < 1 || units < 1 || units > 1024 || m < 1 || n < 1 || h < 1 || micro_policy < 0 || micro_policy > 2)
         return L2A_EINVAL;
     if ((long long)m * n > 0x3fffffffLL) return L2A_EINVAL;
-    const bool mfma_ok = lstm_mfma_eligible(obs_dim, act_dim, units);
-    l2a_micro_deal g;
-    const bool single = lstm_traj_single(mfma_ok && (units == 256 || units == 512), mfma_ok, micro_policy, num_cu, obs_dim, act_dim, m, n, &g);
+    const int cus = num_cu > 0 ? num_cu : 256, lds = 160 * 1024;
+    l2a_rnn_launch d;
+    std::string err;
+    const int rc = plan_rnn_launch(rnn_shape(obs_dim, act_dim, 0, &units, L2A_CELL_LSTM, lds, false),
+                                   {L2A_KERNEL_AUTO, 1, micro_policy, cus, lds}, {m, n, h, false, true, true, true, true}, &d, &err);
+    const bool single = rc == L2A_OK && d.family == L2A_RNN_LSTM_MICRO_TRAJ;    // (a chain whose launches would fail is a chain here)
     for (int i = 0; i < 8; ++i) out[i] = 0;
     out[0] = single ? 1 : 0;
     out[1] = single ? 1 : h;
-    out[2] = single ? m * g.W : m * l2a_ceil_div(n, 16);        // (chain: before any unit-tile split of the one-step launches)
-    out[3] = single ? g.W : 0;
-    out[4] = g.hi;
-    out[5] = single ? g.mc_r : 0;
+    out[2] = single ? (int)d.grid : m * l2a_ceil_div(n, 16);    // (chain: before any unit-tile split of the one-step launches)
+    out[3] = single ? d.mc_w : 0;
+    out[4] = single ? d.mc_hi : l2a_deal_micro(cus, m, n, 3).hi;
+    out[5] = single ? d.mc_r : 0;
+    return L2A_OK;
+}
+
+int l2a_lstm_plan_geometry(int obs_dim, int act_dim, int n_layers, const int* units, int cell_type, int m, int n, int h, int request,
+                           const int* policy, int* out) {
+    if (!units || !out || obs_dim < 1 || act_dim < 1 || n_layers < 0 || n_layers > L2A_RNN_MAX_LAYERS || m < 1 || n < 1 || h < 1 ||
+        request < 0 || request > 31 || (long long)m * n > 0x3fffffffLL)
+        return L2A_EINVAL;
+    if (cell_type != L2A_CELL_LSTM && cell_type != L2A_CELL_GRU && cell_type != L2A_CELL_RNN) return L2A_EINVAL;
+    for (int l = 0; l < (n_layers ? n_layers : 1); ++l)
+        if (units[l] < 1 || units[l] > 1024) return L2A_EINVAL;
+    if (policy && policy[0] > L2A_KERNEL_VALU) return L2A_EINVAL;
+    l2a_rnn_policy pol = {L2A_KERNEL_AUTO, 1, 1, 256, 160 * 1024};
+    if (policy) {
+        if (policy[0] > 0) pol.kernel_kind = policy[0];
+        if (policy[1] >= 0) pol.split_policy = policy[1];
+        if (policy[2] >= 0) pol.micro_policy = policy[2];
+        if (policy[3] > 0) pol.num_cu = policy[3];
+        if (policy[4] > 0) pol.lds_per_block = policy[4];
+    }
+    const l2a_rnn_shape md = rnn_shape(obs_dim, act_dim, n_layers, units, cell_type, pol.lds_per_block, force_generic());
+    l2a_rnn_launch d;
+    std::string err;
+    const int rc = plan_rnn_launch(md, pol, {m, n, h, (request & 1) != 0, (request & 2) != 0, (request & 4) == 0, (request & 8) == 0,
+                                             (request & 16) != 0}, &d, &err);
+    if (rc != L2A_OK) return rc;
+    const int g[12] = {d.family, d.mtm, d.split, (int)d.grid, (int)d.smem, d.tiles_per_env, d.mc_w, d.mc_hi, d.mc_r, (int)d.xbuf_bytes,
+                       rnn_uses_mfma(md, pol) ? 1 : 0, 0};
+    std::memcpy(out, g, sizeof(g));
     return L2A_OK;
 }
 
@@ -446,6 +597,27 @@ int l2a_lstm_mfma_eligible(int obs_dim, int act_dim, int units) {
     return lstm_mfma_eligible(obs_dim, act_dim, units) ? 1 : 0;
 }
 
+// A new model of `shape`, and the tail of both create functions: the weight block of md->total floats, zeroed.
+static l2a_lstm* new_model(l2a_ctx* ctx, const l2a_rnn_shape& shape, int cell_act, int output_act) {
+    l2a_lstm* md = new l2a_lstm();
+    static_cast<l2a_rnn_shape&>(*md) = shape;
+    md->ctx = ctx;
+    md->cell_act = cell_act; md->output_act = output_act;
+    return md;
+}
+static int alloc_model(l2a_ctx* ctx, l2a_lstm* md, const char* what, l2a_lstm** out) {
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&md->wblk), (size_t)md->total * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(md->wblk, 0, (size_t)md->total * sizeof(float));
+    if (e != hipSuccess) {
+        std::string msg = std::string("allocating ") + what + " model storage: " + hipGetErrorString(e);
+        delete md;
+        return l2a_fail(ctx, L2A_EHIP, msg);
+    }
+    *out = md;
+    return L2A_OK;
+}
+
 int l2a_lstm_create(l2a_ctx* ctx, int obs_dim, int act_dim, int units, int cell_act, int output_act,
                     l2a_lstm** out) {
     if (!ctx) return L2A_EINVAL;
@@ -455,14 +627,7 @@ int l2a_lstm_create(l2a_ctx* ctx, int obs_dim, int act_dim, int units, int cell_
     if (units < 1 || units > 1024) return l2a_fail(ctx, L2A_EINVAL, "units must be in [1, 1024]");
     if (cell_act < 0 || cell_act > L2A_ACT_SWISH || output_act < 0 || output_act > L2A_ACT_SWISH)
         return l2a_fail(ctx, L2A_EINVAL, "unsupported nonlinearity");
-    l2a_lstm* md = new l2a_lstm();
-    md->ctx = ctx;
-    md->obs_dim = obs_dim; md->act_dim = act_dim; md->in_dim = obs_dim + act_dim; md->units = units;
-    md->cell_act = cell_act; md->output_act = output_act;
-    md->KG0 = l2a_ceil_div(md->in_dim, 16);
-    md->OT = l2a_ceil_div(obs_dim, 16);
-    md->mfma_ok = lstm_mfma_eligible(obs_dim, act_dim, units);
-    md->UTW = md->mfma_ok ? units / (16 * L2A_NW) : 0;
+    l2a_lstm* md = new_model(ctx, rnn_shape(obs_dim, act_dim, 0, &units, L2A_CELL_LSTM, ctx->lds_per_block, false), cell_act, output_act);
     long long off = 0;
     auto take = [&off](long long n) { long long o = off; off += (n + 15) / 16 * 16; return o; };
     md->raw_wk = take((long long)(md->in_dim + units) * 4 * units);
@@ -473,7 +638,6 @@ int l2a_lstm_create(l2a_ctx* ctx, int obs_dim, int act_dim, int units, int cell_
         const int UT = units / 16;
         md->pk_wg = take(4LL * UT * (md->KG0 + UT) * 256);
         md->pk_wout = take((long long)md->OT * UT * 256);
-        md->micro_ok = (units == 256 || units == 512);
         if (md->micro_ok) {
             md->pk_mg = take(l2a_lstm_micro_gate_floats(units, md->KG0));
             md->pk_mo = take((long long)(units / 4) * 256);
@@ -482,16 +646,7 @@ int l2a_lstm_create(l2a_ctx* ctx, int obs_dim, int act_dim, int units, int cell_
     md->pk_bout = take(16 * md->OT);
     md->nm_off = take(32 * md->KG0 + 32 * md->OT);
     md->total = off;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&md->wblk), (size_t)off * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(md->wblk, 0, (size_t)off * sizeof(float));
-    if (e != hipSuccess) {
-        std::string msg = std::string("allocating LSTM model storage: ") + hipGetErrorString(e);
-        delete md;
-        return l2a_fail(ctx, L2A_EHIP, msg);
-    }
-    *out = md;
-    return L2A_OK;
+    return alloc_model(ctx, md, "LSTM", out);
 }
 
 int l2a_rnn_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_layers, const int* units, int cell_type,
@@ -503,47 +658,19 @@ int l2a_rnn_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_layers, const i
         return l2a_fail(ctx, L2A_EINVAL, "l2a_rnn_create: 1 to " + std::to_string(L2A_RNN_MAX_LAYERS) + " layers");
     if (cell_type != L2A_CELL_LSTM && cell_type != L2A_CELL_GRU && cell_type != L2A_CELL_RNN)
         return l2a_fail(ctx, L2A_EINVAL, "l2a_rnn_create: unknown cell type");
-    // the run_rebal.py configuration, at the widths its tuned kernel is instantiated for: the model of l2a_lstm_create;
-    // one LSTM layer of any other width takes the generic matrix-core kernel like the stacks below
-    // (L2A_FORCE_GENERIC: developer switch - A/B of the generic kernels against the tuned one on its own shape)
-    if (n_layers == 1 && cell_type == L2A_CELL_LSTM && lstm_mfma_eligible(obs_dim, act_dim, units[0]) && !getenv("L2A_FORCE_GENERIC"))
-        return l2a_lstm_create(ctx, obs_dim, act_dim, units[0], cell_act, output_act, out);
     if (obs_dim < 1 || act_dim < 1) return l2a_fail(ctx, L2A_EINVAL, "obs_dim and act_dim must be >= 1");
     if (cell_act < 0 || cell_act > L2A_ACT_SWISH || output_act < 0 || output_act > L2A_ACT_SWISH)
         return l2a_fail(ctx, L2A_EINVAL, "unsupported nonlinearity");
-    int width = 0;
-    for (int l = 0; l < n_layers; ++l) {
+    for (int l = 0; l < n_layers; ++l)
         if (units[l] < 1 || units[l] > 1024) return l2a_fail(ctx, L2A_EINVAL, "units must be in [1, 1024]");
-        width += units[l];
-    }
-    l2a_lstm* md = new l2a_lstm();
-    md->ctx = ctx;
-    md->generic = true;
-    md->n_layers = n_layers; md->cell_type = cell_type;
-    md->obs_dim = obs_dim; md->act_dim = act_dim; md->in_dim = obs_dim + act_dim; md->units = width;
-    md->cell_act = cell_act; md->output_act = output_act;
-    md->KG0 = l2a_ceil_div(md->in_dim, 16);
-    md->OT = l2a_ceil_div(obs_dim, 16);
+    const l2a_rnn_shape shape = rnn_shape(obs_dim, act_dim, n_layers, units, cell_type, ctx->lds_per_block, force_generic());
+    if (!shape.generic) return l2a_lstm_create(ctx, obs_dim, act_dim, units[0], cell_act, output_act, out);
+    l2a_lstm* md = new_model(ctx, shape, cell_act, output_act);
     long long off = 0;
     auto take = [&off](long long n) { long long o = off; off += (n + 15) / 16 * 16; return o; };
-    // micro tiles (l2a_rnn_micro.h): every layer 256 (or every layer 512) units wide, the input shapes of the tuned LSTM kernel,
-    // LDS for the whole stack (256 units: up to three layers; 512: one GRU or BasicRNN layer)
-    md->gmicro_ok = lstm_mfma_eligible(obs_dim, act_dim, 256) && (units[0] == 256 || (units[0] == 512 && cell_type != L2A_CELL_LSTM));
-    for (int l = 0; l < n_layers; ++l) md->gmicro_ok = md->gmicro_ok && units[l] == units[0];
-    md->gmicro_ok = md->gmicro_ok && l2a_rnn_micro_smem(cell_type, n_layers, units[0], md->KG0, 3) <= ctx->lds_per_block;
-    // (and only where a 16-candidate kernel fits too - the matrix-core one or, for three-layer stacks, the VALU one: one-step
-    // launches - predict, chunk continuations - stay with those)
-    if (md->gmicro_ok) {
-        const int gates = cell_type == L2A_CELL_LSTM ? 4 : (cell_type == L2A_CELL_GRU ? 3 : 1);
-        const long long smem_v = (long long)(md->in_dim + 3 * width + 2 * obs_dim + 1) * L2A_LVT * 4;
-        md->gmicro_ok = 4 * l2a_rnn_mfma_lds_floats(md->in_dim, obs_dim, n_layers, units, gates) <= ctx->lds_per_block ||
-                        smem_v <= ctx->lds_per_block;
-    }
-    md->gmicro4_ok = md->gmicro_ok && units[0] == 256 && l2a_rnn_micro_smem(cell_type, n_layers, 256, md->KG0, 4) <= ctx->lds_per_block;
     int kin = md->in_dim;
     for (int l = 0; l < n_layers; ++l) {
         const int U = units[l];
-        md->lunits[l] = U;
         const int cols0 = (cell_type == L2A_CELL_LSTM) ? 4 * U : (cell_type == L2A_CELL_GRU ? 2 * U : U);
         md->lw[l][0] = take((long long)(kin + U) * cols0);
         md->lb[l][0] = take(cols0);
@@ -566,16 +693,7 @@ int l2a_rnn_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_layers, const i
     md->pk_bout = take(16 * md->OT);
     md->nm_off = take(32 * md->KG0 + 32 * md->OT);
     md->total = off;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&md->wblk), (size_t)off * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(md->wblk, 0, (size_t)off * sizeof(float));
-    if (e != hipSuccess) {
-        std::string msg = std::string("allocating recurrent model storage: ") + hipGetErrorString(e);
-        delete md;
-        return l2a_fail(ctx, L2A_EHIP, msg);
-    }
-    *out = md;
-    return L2A_OK;
+    return alloc_model(ctx, md, "recurrent", out);
 }
 
 void l2a_lstm_destroy(l2a_lstm* md) {
@@ -732,12 +850,8 @@ int l2a_lstm_plan_rs(l2a_lstm* md, const float* obs0, const float* c0, const flo
         return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs: null obs0/c0/h0/actions/reward");
     if (!best_key && !returns_out) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs: nothing to write");
     if (m < 1 || n < 1 || h < 1) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs: m, n and h must be >= 1");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs: too many candidates");
-    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
-        return l2a_fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
-    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
-        return l2a_fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    const int arc = check_candidates_and_reward(md, "l2a_lstm_plan_rs", m, n, cand_offset, reward);
+    if (arc != L2A_OK) return arc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
     if (best_key) L2A_HIP(ctx, hipMemsetAsync(best_key, 0, sizeof(unsigned long long) * (size_t)m, stream));
@@ -773,22 +887,14 @@ int l2a_lstm_plan_rs_sync_hook(l2a_lstm* md, const float* obs_host, const float*
     if (c_next && (c_next == c0 || h_next == h0))
         return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_sync: the next state must not alias the current one");
     if (m < 1 || n < 1 || h < 1) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_sync: m, n and h must be >= 1");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_sync: too many candidates");
-    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
-        return l2a_fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
-    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
-        return l2a_fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    int rc = check_candidates_and_reward(md, "l2a_lstm_plan_rs_sync", m, n, cand_offset, reward);
+    if (rc != L2A_OK) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
-    int kind = ctx->kernel_kind;
-    if (kind == L2A_KERNEL_AUTO) kind = md->mfma_ok ? L2A_KERNEL_MFMA : L2A_KERNEL_VALU;
-    // only the matrix-core kernels have the mailbox epilogue
-    const bool publish = md->generic ? generic_uses_mfma(md) : (kind == L2A_KERNEL_MFMA);
-    if (c_next && !md->adv_buf)
-        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->adv_buf), sizeof(float) * L2A_MAIL_KEYS * (md->act_dim + md->obs_dim)));
+    const bool publish = rnn_uses_mfma(*md, rnn_policy(ctx));       // only the matrix-core kernels have the mailbox epilogue
+    if (c_next && (rc = ensure_adv_buf(md)) != L2A_OK) return rc;
     l2a_mail_ticket tk;
-    int rc = l2a_mail_begin(ctx, m, obs_host, (long long)m * md->obs_dim, stream, &tk);
+    rc = l2a_mail_begin(ctx, m, obs_host, (long long)m * md->obs_dim, stream, &tk);
     if (rc != L2A_OK) return rc;
     tk.shape = (unsigned long long)(size_t)md ^ ((unsigned long long)m << 48) ^ ((unsigned long long)n << 24) ^ (unsigned long long)h;
     L2ALstmParams p;
@@ -812,16 +918,10 @@ int l2a_lstm_plan_rs_sync_hook(l2a_lstm* md, const float* obs_host, const float*
         rc = launch_advance(md, tk.obs_dev, nullptr, tk.keys_dev, actions, n, cand_offset, c0, h0, c_next, h_next, m, stream);
     } else if (rc == L2A_OK && c_next) {
         // generic cells / stacks: a gather launch and a one-step launch of the rollout kernel
-        float* act_sel = md->adv_buf;
-        float* obs_next = md->adv_buf + (size_t)L2A_MAIL_KEYS * md->act_dim;
         hipLaunchKernelGGL(l2a_gather_best_k, dim3((unsigned)m), dim3(64), 0, stream, tk.keys_dev, actions, m, n, cand_offset,
-                           md->act_dim, act_sel);
+                           md->act_dim, md->adv_buf);
         L2ALstmParams q;
-        fill(md, q);
-        q.obs0 = tk.obs_dev; q.c0 = c0; q.h0 = h0; q.actions = act_sel;
-        q.state_out = obs_next; q.c_out = c_next; q.h_out = h_next;
-        q.obs_per_row = 1; q.hid_per_row = 1;
-        q.m = 1; q.n = m; q.h = 1; q.discount = 1.0;
+        one_step(md, q, tk.obs_dev, md->adv_buf, c0, h0, m, nullptr, c_next, h_next);
         // NEVER tile-split: l2a_mail_end reads the status word as soon as the PLAN has published, while this launch may
         // still run - an exchange timeout in it would be noticed one call late and the state it wrote adopted
         rc = launch(md, q, stream_v, false);
@@ -853,8 +953,8 @@ int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, const unsigned long lo
     l2a_device_guard guard(ctx->device);
     // one LSTM layer, actions in a table: the advance kernel gathers through the keys itself (as behind the unsharded plan)
     if (table && advance_kernel_ok(md)) return launch_advance(md, obs, nullptr, keys, table, n, 0, c0, h0, c_next, h_next, m, stream);
-    if (!md->adv_buf)
-        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->adv_buf), sizeof(float) * L2A_MAIL_KEYS * (md->act_dim + md->obs_dim)));
+    const int brc = ensure_adv_buf(md);
+    if (brc != L2A_OK) return brc;
     float* act_sel = md->adv_buf;
     if (table)
         hipLaunchKernelGGL(l2a_gather_best_k, dim3((unsigned)m), dim3(64), 0, stream, keys, table, m, n, 0, md->act_dim, act_sel);
@@ -866,11 +966,7 @@ int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, const unsigned long lo
     // generic cells / stacks: one step of the rollout kernel on the gathered actions - never tile-split (see the comment in
     // l2a_lstm_plan_rs_sync_hook: a flag raised here would be noticed one step late)
     L2ALstmParams q;
-    fill(md, q);
-    q.obs0 = obs; q.c0 = c0; q.h0 = h0; q.actions = act_sel;
-    q.state_out = md->adv_buf + (size_t)L2A_MAIL_KEYS * md->act_dim; q.c_out = c_next; q.h_out = h_next;
-    q.obs_per_row = 1; q.hid_per_row = 1;
-    q.m = 1; q.n = m; q.h = 1; q.discount = 1.0;
+    one_step(md, q, obs, act_sel, c0, h0, m, nullptr, c_next, h_next);
     return launch(md, q, stream_v, false);
 }
 
@@ -889,12 +985,8 @@ int l2a_lstm_plan_rs_chunk(l2a_lstm* md, const float* state, const float* c, con
         return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_chunk: a continuation needs returns_in and per-row states");
     if ((!state_out) != (!c_out) || (!state_out) != (!h_out))
         return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_chunk: pass state_out, c_out and h_out together");
-    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
-        return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_plan_rs_chunk: too many candidates");
-    if (reward->w_vel != 0.0f && (reward->vel_index < 0 || reward->vel_index >= md->obs_dim))
-        return l2a_fail(ctx, L2A_EINVAL, "reward.vel_index out of range");
-    if (reward->dist_coef != 0.0f && (reward->dist_index < 0 || reward->dist_index >= md->obs_dim))
-        return l2a_fail(ctx, L2A_EINVAL, "reward.dist_index out of range");
+    const int arc = check_candidates_and_reward(md, "l2a_lstm_plan_rs_chunk", m, n, cand_offset, reward);
+    if (arc != L2A_OK) return arc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
     if (best_key) L2A_HIP(ctx, hipMemsetAsync(best_key, 0, sizeof(unsigned long long) * (size_t)m, stream));
@@ -924,14 +1016,10 @@ int l2a_lstm_advance(l2a_lstm* md, const float* obs, const float* act, const flo
     if (advance_kernel_ok(md)) return launch_advance(md, obs, act, nullptr, nullptr, 0, 0, c, h, c_out, h_out, rows, stream);
     // generic cells / stacks (and the VALU kernel when asked for): one step of the rollout kernel, the predicted observation dropped
     if ((long long)rows > L2A_MAIL_KEYS) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_advance: at most 64 rows (use l2a_lstm_predict)");
-    if (!md->adv_buf)
-        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->adv_buf), sizeof(float) * L2A_MAIL_KEYS * (md->act_dim + md->obs_dim)));
+    const int brc = ensure_adv_buf(md);
+    if (brc != L2A_OK) return brc;
     L2ALstmParams p;
-    fill(md, p);
-    p.obs0 = obs; p.c0 = c; p.h0 = h; p.actions = act;
-    p.state_out = md->adv_buf + (size_t)L2A_MAIL_KEYS * md->act_dim; p.c_out = c_out; p.h_out = h_out;
-    p.obs_per_row = 1; p.hid_per_row = 1;
-    p.m = 1; p.n = rows; p.h = 1; p.discount = 1.0;
+    one_step(md, p, obs, act, c, h, rows, nullptr, c_out, h_out);
     return launch(md, p, stream_v, false);
 }
 
@@ -943,11 +1031,7 @@ int l2a_lstm_predict(l2a_lstm* md, const float* obs, const float* act, const flo
         return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_predict: null pointer");
     if (rows < 1) return l2a_fail(ctx, L2A_EINVAL, "l2a_lstm_predict: rows must be >= 1");
     L2ALstmParams p;
-    fill(md, p);
-    p.obs0 = obs; p.c0 = c; p.h0 = h; p.actions = act;
-    p.state_out = next_obs_out; p.c_out = c_out; p.h_out = h_out;
-    p.obs_per_row = 1; p.hid_per_row = 1;
-    p.m = 1; p.n = rows; p.h = 1; p.discount = 1.0;
+    one_step(md, p, obs, act, c, h, rows, next_obs_out, c_out, h_out);
     return launch(md, p, stream_v);
 }
 

@@ -13,8 +13,8 @@ compute units).  Per row:
 
 Rows that differ in policy alone share their model, inputs and oracle trace (`_mlp_case`, `_lstm_case`: read-only).
 
-The CARRY of every row that has one (the micro-tile kernels are never launched with one: l2a_api.hip:297,
-l2a_lstm_api.hip:167,216) - what a launch hands to the next one: `state_out` (LSTM: `c_out`, `h_out`) written, per-row
+The CARRY of every row that has one (the micro-tile kernels are never launched with one: `plan_rollout` in l2a_api.hip and
+`plan_rnn_launch` in l2a_lstm_api.hip keep every launch with per-row states or a state output off them) - what a launch hands to the next one: `state_out` (LSTM: `c_out`, `h_out`) written, per-row
 observations / hidden states, `returns_in` and the discount power read.  In the same test, while the row's case is warm, under
 the row's policy with micro = 0 and again under BASELINE:
 
@@ -28,12 +28,12 @@ the row's policy with micro = 0 and again under BASELINE:
 `test_generic_recurrent_branches_match_oracle`: the same four launches on the generic recurrent kernels (matrix-core and VALU),
 one row of `instance_matrix.GENERIC_ROWS` per run-time branch of l2a_rnn_mfma.h, against `OracleRNNStackDynamics` in float64.
 
-LSTM: the launcher has no dry run, so the routing of those rows rests on its conditions as read from l2a_lstm_api.hip (and
-restated arithmetically in test_instance_matrix.py): with micro policy 0 the micro-tile branch is skipped (:131, `wanted`); the
-unit-tile split is taken iff the split policy is non-zero and 2 x tiles <= CUs and h < 4096 (:238) - n = 37, m = 1 is three
-tiles; with micro policy 2 a plan of at most three micro tiles per workgroup on 256 / 512 units takes the micro-tile kernel
-(:132, :216; the generic stacks' branch at :150 is not involved: a single LSTM layer is not `generic`).  SPLIT on and SPLIT off
-must agree bit for bit.
+LSTM: test_instance_matrix.py asks the launcher's plan function (`plan_rnn_launch`, through `l2a_lstm_plan_geometry`) that every
+row reaches its instance, and restates its conditions arithmetically: with micro policy 0 no plan takes micro tiles
+(`lstm_micro_wanted`); the unit-tile split is taken iff the split policy is non-zero and 2 x tiles <= CUs and h < 4096 - n = 37,
+m = 1 is three tiles; with micro policy 2 a plan of at most three micro tiles per workgroup on 256 / 512 units takes the micro-tile
+kernel (the generic stacks' branch is not involved: `rnn_shape` makes a single eligible LSTM layer the tuned model, not a
+`generic` one).  SPLIT on and SPLIT off must agree bit for bit.
 """
 
 import functools
@@ -102,7 +102,7 @@ def _frozen(a):
 
 
 def has_carry(row):
-    """The micro-tile kernels are never given a carry launch (l2a_api.hip:297, l2a_lstm_api.hip:167,216)."""
+    """The micro-tile kernels are never given a carry launch (`plan_rollout`, `plan_rnn_launch`: plans only)."""
     return row.instance.family in ("mlp", "lstm")
 
 

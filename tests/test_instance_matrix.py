@@ -102,8 +102,21 @@ def test_unreachable_list_matches_the_launcher_and_the_sources():
 
 
 def test_lstm_rows_meet_the_launcher_conditions():
-    """The LSTM launcher has no dry run; the conditions its routing relies on (l2a_lstm_api.hip) are arithmetic on the row."""
+    """Every LSTM row reaches its instance - the family, and split on or off, at 256 CUs - by the launcher's own plan
+    (`plan_rnn_launch`, asked through `lstm_plan_geometry`); the conditions that plan relies on, restated as arithmetic on the row."""
     for row in im.LSTM_ROWS:
+        g = _lib.lstm_plan_geometry(row.obs_dim, row.act_dim, [row.hidden], "lstm", row.m, row.n, row.h, split=row.policy["split"],
+                                    micro=row.policy["micro"], cus=256)
+        if row.instance.family == "lstm_micro":
+            assert (g["family"], g["split"], g["mtm"]) == ("lstm_micro", 0, 3), row.id
+        else:
+            assert (g["family"], g["split"]) == ("lstm_mfma16", 1 if row.instance.variant == "split" else 0), row.id
+            assert g["workgroups"] == 3 * (1 + g["split"]) and (g["exchange_bytes"] > 0) == bool(g["split"]), row.id
+            # the carry launches (chunks of h = 1 and 2 with a state output, the second with per-row states; a predict of n rows)
+            for h, request in ((1, ("state_out",)), (2, ("per_row", "state_out")), (1, ("per_row", "state_out"))):
+                c = _lib.lstm_plan_geometry(row.obs_dim, row.act_dim, [row.hidden], "lstm", row.m, row.n, h, request=request,
+                                            split=row.policy["split"], micro=0, cus=256)
+                assert (c["family"], c["split"], c["workgroups"]) == (g["family"], g["split"], g["workgroups"]), (row.id, h)
         tiles = row.m * ((row.n + 15) // 16)
         quads = (row.n + 3) // 4
         assert row.hidden in (128, 256, 512) and row.obs_dim <= 64 and row.act_dim <= 16
@@ -115,9 +128,9 @@ def test_lstm_rows_meet_the_launcher_conditions():
             assert row.policy["micro"] == 0
             assert row.policy["split"] == (1 if row.instance.variant == "split" else 0)
             assert 2 * tiles <= 256 and row.h < 4096
-            # The carry launches take the same branch: the unit-tile split of :238 reads only the tile count, the split policy
+            # The carry launches take the same branch: the unit-tile split reads only the tile count, the split policy
             # and h < 4096 (chunks of h = 1 and 2 over the same m, n; l2a_lstm_predict is m = 1, n = rows, h = 1 with the default
-            # `allow_split`), and :216 keeps every launch with per-row states or a state output off the micro tiles.
+            # `allow_split`), and `plan_only` keeps every launch with per-row states or a state output off the micro tiles.
             assert row.m == 1           # so a predict of m * n rows is the plan's own tile count
 
 

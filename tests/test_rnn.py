@@ -634,8 +634,9 @@ def test_gpu_rnn_unit_tile_split_is_bit_identical(units, m, n, h):
 def test_gpu_rnn_micro_tiles_are_bit_identical(units, m, n, h, env_name):
     """The micro-tile kernel (csrc/l2a_micro.h: candidate tiles of FOUR on the 4x4x1 MFMA, workgroups of 4 / 8 / 12
     candidates, no exchange) against the 16-candidate kernel, split and unsplit: every return and the arg-max keys bit
-    for bit, from non-zero hidden states, with a discount, ragged last tiles, more envs than a workgroup per CU allows
-    three micro tiles for (falls back), through the plain and the blocking entry point."""
+    for bit, from non-zero hidden states, with a discount, ragged last tiles, 64 envs of three micro tiles each (one per
+    workgroup on 192 CUs), through the plain and the blocking entry point.  (The geometries:
+    tests/test_lstm_plan_geometry_table.py.)"""
     from learning_to_adapt_amd import _lib
     base = {"hc": "hc_rnn_rs_u128_n40_h3"}.get(env_name, "hc_rnn_rs_u128_n40_h3")
     case = dict(cases.CASES[base], units=units, m=m, n=n, h=h)
@@ -728,6 +729,7 @@ def test_gpu_blocking_recurrent_plan_matches_the_plain_launches(cell, units, m, 
     ("gru", (256, 256), 1, 2000, 4, "hc", "tanh"), ("rnn", (256, 256, 256), 2, 37, 3, "hc", "relu"), ("lstm", (256, 256, 256), 3, 333, 3, "ant", "tanh"),
     ("gru", (256,), 64, 12, 2, "arm", "sigmoid"), ("lstm", (256, 256), 1, 5, 2, "hc", "swish"), ("gru", (256, 256, 256), 5, 250, 4, "ant", "tanh"),
     # plans beyond three micro tiles per CU: workgroups of four micro tiles, one round (875 quads on 219 workgroups) and several
+    # (pinned without a GPU in tests/test_lstm_plan_geometry_table.py)
     ("gru", (256, 256), 1, 3500, 3, "hc", "tanh"), ("lstm", (256, 256), 3, 1500, 3, "hc", "tanh"), ("rnn", (256,), 2, 3001, 2, "ant", "relu"),
     ("gru", (256,), 1, 16000, 2, "hc", "tanh")])
 def test_gpu_rnn_generic_micro_tiles_match_the_16_candidate_kernel_and_the_oracle(cell, hidden, m, n, h, env_name, act):
@@ -798,7 +800,7 @@ ADVANCE_GUARD = 16          # rows of sentinel on each side of c_out / h_out
 
 def _advance_model(obs_dim, act_dim, units, activation, seed):
     """One LSTM layer on which `l2a_lstm_advance` runs `l2a_lstm_advance_k`, with `advance_kernel_ok`'s conditions
-    (l2a_lstm_api.hip:264) asserted: not a generic model, units a multiple of 16, not the VALU kernel, the LDS rows fit.
+    (`advance_kernel_ok`, l2a_lstm_api.hip) asserted: not a generic model, units a multiple of 16, not the VALU kernel, the LDS rows fit.
     `NativeLSTM` (l2a_rnn_create) makes a width outside the tuned kernel's {128, 256, 512} a GENERIC model, whose state step
     is one step of the rollout kernel; `l2a_lstm_create` keeps it the plain one-layer model that takes the small-rows kernel."""
     import ctypes
@@ -908,7 +910,7 @@ def test_advance_cases_cover_every_value_twice_and_all_run():
                          (3, ("tanh", "relu"))):
         seen = [c[axis] for c in ADVANCE_CASES]
         assert set(seen) == set(values) and all(seen.count(v) >= 2 for v in values), (axis, seen)
-    for rows, units, (obs_dim, act_dim), _ in ADVANCE_CASES:        # advance_kernel_ok's arithmetic (l2a_lstm_api.hip:264)
+    for rows, units, (obs_dim, act_dim), _ in ADVANCE_CASES:        # advance_kernel_ok's arithmetic (l2a_lstm_api.hip)
         assert units % 16 == 0 and units >= 16 and (obs_dim + act_dim + units) * 8 * 4 + 4 * 64 * 8 * 4 <= 64 * 1024
     ks = {obs_dim + act_dim + units for _, units, (obs_dim, act_dim), _ in ADVANCE_CASES}
     assert any(k % 4 for k in ks) and any(k % 4 == 0 and k % 8 for k in ks) and any(k % 8 == 0 for k in ks)

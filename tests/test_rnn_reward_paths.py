@@ -73,7 +73,7 @@ def test_geometry_rejects(args):
 # 2. single launch or chain: the launcher's micro-tile conditions, restated
 # ------------------------------------------------------------------------------------------
 def _restated(obs_dim, act_dim, units, m, n, h, micro, cus):
-    """``launch()``'s conditions for micro tiles (csrc/l2a_lstm_api.hip), as plain arithmetic."""
+    """``plan_rnn_launch``'s conditions for micro tiles (csrc/l2a_lstm_api.hip), as plain arithmetic."""
     cus = cus if cus > 0 else 256
     eligible = units in (256, 512) and 1 <= obs_dim <= 64 and 1 <= act_dim <= 16 and obs_dim + act_dim <= 80
     quads = -(-n // 4)
