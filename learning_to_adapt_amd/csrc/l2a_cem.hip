@@ -438,11 +438,16 @@ size_t crs_lds_bytes(int n, int m, int k, int act_dim, int reference) {
     return 4 * (fixed + (bins > elite ? bins : elite));
 }
 
+// LDS the kernel holds besides its dynamic array: __syncthreads_or's workgroup-reduction scratch (64 ints, the object's
+// group_segment_fixed_size).  Without it in the budget the shapes within 256 bytes of the limit (m = 1, h = 2, act_dim = 2,
+// k = n / 10: n = 17256 .. 17286) were taken as fused and failed in hipFuncSetAttribute instead of falling back.
+#define L2A_CRS_STATIC_LDS 256
+
 // Does l2a_cem_refit_sample run this shape as one launch (else: l2a_cem_refit + l2a_cem_sample inside the call)?
 bool crs_fused(const l2a_ctx* ctx, int n, int m, int h, int act_dim, int k, int reference) {
     const long long total = (long long)n * m * h * act_dim;
-    return crs_lds_bytes(n, m, k, act_dim, reference) <= (size_t)ctx->lds_per_block && 8 * act_dim <= L2A_CRS_THREADS &&
-           total <= 0x7fffffffLL;
+    return crs_lds_bytes(n, m, k, act_dim, reference) + L2A_CRS_STATIC_LDS <= (size_t)ctx->lds_per_block &&
+           8 * act_dim <= L2A_CRS_THREADS && total <= 0x7fffffffLL;
 }
 
 // the dynamic-LDS limit l2a_cem_refit_sample_k has been raised to, per device

@@ -4,7 +4,8 @@ and the arg-max key with the returns the kernel itself wrote (bit exact).  Cover
 the hand-picked golden cases: obs/act dims that straddle 16-feature tiles, every MFMA-eligible hidden
 width and depth, odd ensembles under all tile-split policies, ragged candidate counts.  Coverage per compiled kernel
 instance (every unit x (OT, KG0) x variant, on the shapes at its bounds) lives in tests/test_gpu_instance_matrix.py; this sweep
-is the random complement to that table."""
+is the random complement to that table.  The CEM kernels' iteration boundary gets the same treatment against the float64
+restatement in tests/cem_reference.py (table: tests/test_cem_kernels_gpu.py)."""
 
 import os
 
@@ -359,3 +360,32 @@ def test_random_adaptation_shapes_match_autograd_and_their_packed_copies_match_t
         ctx.set_micro(1)
     adapted.close()
     packed.close()
+
+
+@pytest.mark.parametrize("seed", range(max(10, _EXTRA)))
+def test_random_cem_iteration_boundaries_match_the_float64_reference(seed):
+    """One CEM iteration boundary (elite rank, mean / std refit, next samples, the rollout's candidate tensor) on random shapes,
+    readings, shards, elite counts, alphas and return patterns, through `l2a_cem_refit` + `l2a_cem_sample` and through
+    `l2a_cem_refit_sample` (distinct buffers or in place), each against tests/cem_reference.py - the random complement to the
+    table in tests/test_cem_kernels_gpu.py, with its harness (sentinels, guard words) and its derived bounds."""
+    import test_cem_kernels_gpu as ck
+    rs = np.random.RandomState(7100 + seed)
+    n = int(rs.choice(ck.RANK_N))
+    m = int(rs.choice([1, 2, 3]))
+    h, ad = ck.SHAPES_D[rs.randint(len(ck.SHAPES_D))]
+    if rs.rand() < 0.3:
+        h, ad = 2, int(rs.choice([1, 6, 63, 64, 65]))
+    reference = bool(rs.randint(2))
+    ks = sorted({min(max(x, 1), n) for x in (1, 2, n // 10, n - 1, n, 7, 8, 9, 24, 25, 31, 32, 33, 40, 57, 64, 65)})
+    ks = [k for k in ks if (m if reference else 1) * k <= 8192]
+    k = int(rs.choice(ks))
+    lo, hi = ck.SHARDS[rs.randint(len(ck.SHARDS))](n)
+    alpha = float(rs.choice(ck.ALPHAS))
+    pattern = str(rs.choice(ck.PATTERNS))
+    inject = bool(rs.randint(2))
+    fused_entry = "in_place" if rs.randint(2) else "fused"
+    inp = ck.make_inputs(rs, n, m, h, ad, k, reference, alpha, lo, hi, pattern=pattern, inject=inject, seed=int(rs.randint(1 << 62)),
+                         off=int(rs.choice([0, 977, (1 << 32) - 100, (1 << 40) + 12345])))
+    worst = ck.Worst()
+    ck.run_and_check(_lib.Context.get(0), inp, worst, entries=("split", fused_entry))
+    worst.report("random boundary seed=%d %s" % (seed, ck.describe(inp, fused_entry)))
