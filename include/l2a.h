@@ -495,6 +495,42 @@ int l2a_cem_refit_sample(l2a_ctx* ctx, const float* returns, const float* a_clip
 /* 1 when l2a_cem_refit_sample runs this shape as its one launch, 0 when it runs the two calls instead (or the shape is invalid). */
 int l2a_cem_refit_sample_fused(const l2a_ctx* ctx, int n, int m, int h, int act_dim, int num_elites, int reference);
 
+/* ---- reward-weighted (MPPI) planner: the per-iteration work around the rollout, on the device ---------------------
+ * PDDM's "filtered and reward-weighted refinement" (Nagabandi et al. 2019); the reference has no such planner, the
+ * semantics are build-defined.  Per env i a persistent fp32 plan mean mu[i] of shape [h, A], A = act_dim, D = h * A, kept on
+ * the device between controller steps.  One iteration = l2a_mppi_sample, the rollout (returns [m, n]), l2a_mppi_update.
+ *
+ * l2a_mppi_sample
+ *   shift  [m] device int32: < 0 the mean starts from zeros (first step, or after a reset of env i); > 0 the plan moves on one
+ *          step, mu'_t = mu_min(t + 1, h - 1); 0 the mean is kept (iterations after the first within one controller step)
+ *   noise  z[j, i, t, k] is a standard normal for element e = (j * m + i) * D + t * A + k of the [n, m, D] draw: `z` (device
+ *          fp32) or, z = NULL, l2a_cem_sample's Philox4x32-10 + Box-Muller stream at counter offset + e under `seed`.
+ *          u = z * sigma[k]; n_t = beta * u_t + (1 - beta) * n_(t-1), n_(-1) = 0 - each operation rounded to fp32 on its own,
+ *          1 - beta formed once in fp32
+ *   out    a = clip(mu'[i, t, k] + n_t, low[k], high[k]) into a_clip [n, m, D] and, unless NULL, into seq [h, m * n, A], the
+ *          candidate tensor l2a_plan_rs reads: plan row i * n + j is sample row j * m + i (l2a_cem_sample's reference = 0);
+ *          mean_out [m, D] receives mu' (it must not be mean_in: L2A_EINVAL)
+ *   sigma / low / high [act_dim] device fp32; sigma finite and >= 0 is the caller's business (the arrays live on the device).
+ *   L2A_EINVAL (nothing written): act_dim outside 1..16, n / m / h < 1, beta outside (0, 1], aliasing means, a null pointer.
+ *
+ * l2a_mppi_update
+ *   returns [m, n] device fp32, a_clip the samples they belong to, mean = the sample call's mean_out, updated in place.
+ *   A candidate is valid when its return is neither NaN nor -inf; invalid candidates weigh 0 - a diverged rollout is not a
+ *   plan to imitate (unlike the arg-max of l2a_cem_pick, where a NaN is the maximum).  Rmax = the largest valid return.
+ *   Rmax = +inf: w = 1 for the +inf returns, else 0; otherwise w_j = expf(kappa * (R_j - Rmax)) with the difference and the
+ *   product in fp32 (a difference that overflows to -inf gives 0).  mu[i, d] = sum_j w_j a[j, i, d] / sum_j w_j over the
+ *   clipped samples; an env without a valid candidate keeps mu' untouched.  No atomics, one fixed summation order.
+ *   out    [m][act_dim + 4] floats: new mu[i, 0, :] | Rmax (NaN without a valid candidate) | index of the first maximum as
+ *          the bits of an int32 (-1) | effective sample size (sum w)^2 / sum w^2 (0) | number of valid candidates, int32 bits
+ *   L2A_EINVAL (nothing written): act_dim outside 1..16, n / m / h < 1, m > 65535, kappa not positive and finite, or n * 4 bytes
+ *   plus the kernel's own L2A_MPPI_UPDATE_STATIC_LDS bytes beyond a workgroup's LDS (l2a_device_info: lds_per_block).       */
+#define L2A_MPPI_UPDATE_STATIC_LDS 4480
+int l2a_mppi_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                    const int* shift, const float* sigma, float beta, const float* low, const float* high,
+                    int n, int m, int h, int act_dim, float* mean_out, float* a_clip, float* seq, void* stream);
+int l2a_mppi_update(l2a_ctx* ctx, const float* returns, const float* a_clip, int n, int m, int h, int act_dim, float kappa,
+                    float* mean, float* out, void* stream);
+
 /* ---- sharded plans: the one collective ------------------------------------------------------
  * Candidates are independent, so G GPUs (one process and one context each) plan disjoint shards of one candidate
  * tensor (l2a_plan_rs with cand_offset = first global index of the shard) and combine the per-shard keys with ONE

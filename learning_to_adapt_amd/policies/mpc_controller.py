@@ -29,7 +29,13 @@ random shooting on one GPU: the whole step - adopt the block drawn ahead by a C 
 C call, ``l2a_controller_step``, ``policies/native_step.py``; a step that finds no valid block falls back to the path above),
 ``native_cem_step`` (off by default: ``rng="device"`` CEM through the C controller, ``l2a_cem_controller_create_device`` -
 sharded over torch.distributed ranks: ``l2a_cem_controller_create_sharded_device``, one rank each - bit-identical to
-``get_cem_action_device``, ``policies/native_cem_step.py``; every other case keeps the Python path).
+``get_cem_action_device``, ``policies/native_cem_step.py``; every other case keeps the Python path),
+``use_mppi`` (the reward-weighted planner of PDDM, Nagabandi et al. 2019 - not in the reference: a plan mean per env persists on
+the device from one controller step to the next, is moved on one step, sampled with time-correlated noise and replaced by the
+return-weighted mean of the clipped candidates, ``get_mppi_action``; needs ``rng="device"``; ``mppi_kappa`` the weights'
+temperature ``exp(kappa (R - Rmax))``, ``mppi_sigma`` the noise scale per action dimension - ``None``: a quarter of the action
+range -, ``mppi_beta`` the noise filter ``n_t = beta u_t + (1 - beta) n_(t-1)``, ``mppi_iters`` refinements per step;
+``reset(dones)`` restarts the marked envs' plans from zero).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -71,6 +77,11 @@ class MPCController(Policy, Serializable):
             draw_ahead=True,
             native_step=True,
             native_cem_step=False,
+            use_mppi=False,
+            mppi_kappa=1.0,
+            mppi_sigma=None,
+            mppi_beta=0.6,
+            mppi_iters=1,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -92,6 +103,22 @@ class MPCController(Policy, Serializable):
         self.draw_ahead = bool(draw_ahead)
         self.native_step = bool(native_step)
         self.native_cem_step = bool(native_cem_step)
+        self.use_mppi = bool(use_mppi)
+        self.mppi_kappa = float(mppi_kappa)
+        self.mppi_sigma = mppi_sigma
+        self.mppi_beta = float(mppi_beta)
+        self.mppi_iters = int(mppi_iters)
+        if self.use_mppi:
+            if use_cem:
+                raise ValueError("use_mppi and use_cem are two planners: choose one")
+            if rng != "device":
+                raise ValueError("use_mppi draws its normals on the device: pass rng='device'")
+            if not (self.mppi_kappa > 0.0 and np.isfinite(self.mppi_kappa)):
+                raise ValueError("mppi_kappa must be positive and finite")
+            if not 0.0 < self.mppi_beta <= 1.0:
+                raise ValueError("mppi_beta must lie in (0, 1]")
+            if self.mppi_iters < 1:
+                raise ValueError("mppi_iters must be at least 1")
 
         self.unwrapped_env = innermost_env(env)
 
@@ -103,6 +130,8 @@ class MPCController(Policy, Serializable):
 
         self._reward_spec = None if use_reward_model else reward_spec_for_env(env)
         self._bufs = {}
+        if self.use_mppi:
+            self._mppi_sigma_vector()       # (a bad mppi_sigma fails here, not on the first step)
         self._ahead = None          # DrawAhead chain (parity mode), created on first use
         self._cstep = None          # NativeStep (l2a_controller): the whole parity-mode step in one C call
         self._cstep_no = None       # request key the C controller was found ineligible for
@@ -119,14 +148,18 @@ class MPCController(Policy, Serializable):
     def get_action(self, observation):
         if observation.ndim == 1:
             observation = observation[None]
-        if self.use_cem:
+        if self.use_mppi:
+            action = self.get_mppi_action(observation)
+        elif self.use_cem:
             action = self.get_cem_action(observation)
         else:
             action = self.get_rs_action(observation)
         return action, dict()
 
     def get_actions(self, observations):
-        if self.use_cem:
+        if self.use_mppi:
+            actions = self.get_mppi_action(observations)
+        elif self.use_cem:
             actions = self.get_cem_action(observations)
         else:
             actions = self.get_rs_action(observations)
@@ -172,7 +205,7 @@ class MPCController(Policy, Serializable):
         return []
 
     def reset(self, dones=None):
-        pass
+        self._mppi_reset(dones)
 
     # ------------------------------------------------------------------ sharding helpers
     def _dist(self):
@@ -1226,3 +1259,132 @@ class MPCController(Policy, Serializable):
         idx = np.argmax(returns, axis=1)
         self.last_plan = dict(best_index=idx, best_return=returns[range(m), idx], cem_trace=trace)
         return cand_a[range(m), idx]
+
+    # ------------------------------------------------------------------ MPPI (PDDM's filtered, reward-weighted refinement)
+    def _mppi_sigma_vector(self):
+        """``mppi_sigma`` as an fp32 ``[act_dim]`` array: ``None`` = a quarter of each dimension's action range, a scalar = that
+        value for every dimension, or one value per dimension; finite and non-negative."""
+        low = np.asarray(self.action_space.low, dtype=np.float64)
+        high = np.asarray(self.action_space.high, dtype=np.float64)
+        if self.mppi_sigma is None:
+            sigma = 0.25 * (high - low)
+        else:
+            sigma = np.asarray(self.mppi_sigma, dtype=np.float64)
+            if sigma.ndim == 0:
+                sigma = np.full(low.shape, float(sigma))
+        if sigma.shape != low.shape:
+            raise ValueError("mppi_sigma must be None, a scalar or one value per action dimension %s, got shape %s"
+                             % (low.shape, sigma.shape))
+        if not (np.isfinite(sigma).all() and (sigma >= 0).all()):
+            raise ValueError("mppi_sigma must be finite and non-negative")
+        return sigma.astype(np.float32)
+
+    def _mppi_reset(self, dones):
+        """``reset(dones)`` for the MPPI planner: the marked envs' next step starts from a zero mean; ``None``, or a number of envs
+        other than the plan's, starts all of them afresh.  Without ``use_mppi`` nothing happens."""
+        if not self.use_mppi:
+            return
+        fresh = self._bufs.get("mppi_fresh")
+        if dones is None or fresh is None or len(fresh) != len(dones):
+            self._bufs["mppi_fresh"] = None
+        else:
+            fresh |= np.asarray(dones, dtype=bool)
+
+    def _mppi_normal_device(self, shape, device):
+        """Hook for tests: return the iteration's standard normals ``[n, m, D]`` as a CUDA fp32 tensor to inject them; ``None``
+        (the default) lets ``l2a_mppi_sample`` draw them on the device (Philox4x32-10 + Box-Muller, CEM's stream)."""
+        return None
+
+    def get_mppi_action(self, observations, retry=False):
+        """One MPPI plan step on the GPU (``csrc/l2a_mppi.hip``; semantics in ``include/l2a.h``).  The plan mean ``[m, h * act_dim]``
+        stays on the device between controller steps.  Per iteration: ``l2a_mppi_sample`` (shift - zeros for an env that is new
+        or was reset, one step on for the first iteration of a later step, none for further iterations -, filtered noise, clip,
+        the rollout's candidate tensor), the fused rollout for the returns (``_rollout``: closed-form reward, reward program or
+        reward model alike), ``l2a_mppi_update`` (weights ``exp(kappa (R - Rmax))`` over the candidates whose return is neither NaN
+        nor ``-inf``, the weighted mean of the clipped samples).  The observations go up once, one copy brings the packed result
+        back.  The action returned is the new mean's first step.  The normals of iteration ``it`` of the s-th step are the Philox
+        stream under ``torch.initial_seed()`` at offset ``(s * mppi_iters + it) * n * m * D`` (its own counter, not CEM's)."""
+        import ctypes
+        from ..dynamics.native_model import _ptr, _stream_ptr
+        if not self._fusable():
+            raise _lib.L2AError("MPPI planning needs a fusable closed-form reward (env.reward_spec: a RewardSpec or a RewardProgram) "
+                                "or, with use_reward_model, a reward model the library scores (MLPRewardModel)")
+        if self.rng != "device":
+            raise _lib.L2AError("MPPI planning draws its normals on the device (rng='device'); NumPy normals are not supported")
+        if self.native_cem_step:
+            raise _lib.L2AError("an MPPI step as one C controller call is not built: leave native_cem_step off with use_mppi")
+        if self._dist()[1] > 1:
+            raise _lib.L2AError("MPPI planning does not shard its candidates over torch.distributed ranks: pass shard_candidates=False "
+                                "(every rank then plans on its own)")
+        n, m, h = self.n_candidates, len(observations), self.horizon
+        act_dim = self.action_space.shape[0]
+        D = h * act_dim
+        dev = self._device()
+        native = self.dynamics_model.planner_model()
+        ctx, lib = native.ctx, native.lib
+        if not hasattr(lib, "l2a_mppi_sample"):
+            raise _lib.L2AError("this libl2a_hip.so has no MPPI kernels (l2a_mppi_sample): rebuild it")
+        const = self._bufs.get("mppi_const")
+        if const is None or const[0].device != dev:
+            up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
+            const = self._bufs["mppi_const"] = (up(self.action_space.low), up(self.action_space.high), up(self._mppi_sigma_vector()))
+        low, high, sigma = const
+        # the persistent mean and two scratch means: a step reads `cur` and commits its last `mean_out` only when it succeeded,
+        # so a replay starts from the same plan
+        means = self._buf("mppi_means", (3, m, D), torch.float32, dev)
+        shifts = self._bufs.get("mppi_shifts")
+        if shifts is None or shifts.device != dev or shifts.shape[1] != m:
+            shifts = self._bufs["mppi_shifts"] = torch.as_tensor(np.array([[1] * m, [0] * m, [-1] * m], dtype=np.int32), device=dev)
+            self._bufs["mppi_fresh"], self._bufs["mppi_cur"] = None, 0
+        fresh = self._bufs.get("mppi_fresh")
+        if fresh is None:
+            first = shifts[2]                                   # every env starts from zeros
+        elif fresh.any():
+            first = torch.as_tensor(np.where(fresh, -1, 1).astype(np.int32), device=dev)
+        else:
+            first = shifts[0]
+        cur = self._bufs["mppi_cur"]
+        a_clip = self._buf("mppi_a_clip", (n, m, D), torch.float32, dev)
+        seq = self._buf("mppi_seq", (h, m * n, act_dim), torch.float32, dev)
+        width = act_dim + 4
+        packed = self._buf("mppi_packed", (m * width + m * D + m * n,), torch.float32, dev)
+        obs_dev = self._upload_obs(observations)                # once per plan step
+        # counter-based stream: (seed, iterations so far); restarts when torch's seed VALUE changes, as CEM's does
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        if self._bufs.get("mppi_seed") != seed:
+            self._bufs["mppi_seed"], self._bufs["mppi_calls"] = seed, 0
+        call0 = self._bufs["mppi_calls"]
+        src = cur
+        rets = None
+        for it in range(self.mppi_iters):
+            dst = [b for b in range(3) if b != src and b != cur][0]
+            z = self._mppi_normal_device((n, m, D), dev)
+            if z is not None:
+                z = z.to(device=dev, dtype=torch.float32).contiguous()
+            offset = (call0 + it) * n * m * D
+            ctx.check(lib.l2a_mppi_sample(ctx.handle, _ptr(z), ctypes.c_ulonglong(seed), ctypes.c_ulonglong(offset & 0xFFFFFFFFFFFFFFFF),
+                                          _ptr(means[src]), _ptr(first if it == 0 else shifts[1]), _ptr(sigma), self.mppi_beta,
+                                          _ptr(low), _ptr(high), n, m, h, act_dim, _ptr(means[dst]), _ptr(a_clip), _ptr(seq),
+                                          _stream_ptr(dev)), "l2a_mppi_sample")
+            _, rets = self._rollout(observations, seq, n, 0, want_returns=True, obs_dev=obs_dev)
+            ctx.check(lib.l2a_mppi_update(ctx.handle, _ptr(rets), _ptr(a_clip), n, m, h, act_dim, self.mppi_kappa, _ptr(means[dst]),
+                                          _ptr(packed), _stream_ptr(dev)), "l2a_mppi_update")
+            src = dst
+        packed[m * width:m * width + m * D].view(m, D).copy_(means[src])
+        packed[m * width + m * D:].view(m, n).copy_(rets)
+        host = packed.cpu().numpy()
+        if self._check_status() is False:       # a launch lost its tile-split partner: the context is unsplit now
+            if retry:
+                raise _lib.L2AError("rollout launch failed twice")
+            return self.get_mppi_action(observations, retry=True)       # same counters, same starting mean: the same step again
+        self._bufs["mppi_calls"] = call0 + self.mppi_iters
+        self._bufs["mppi_cur"] = src
+        self._bufs["mppi_fresh"] = np.zeros(m, dtype=bool)
+        head = host[:m * width].reshape(m, width)
+        self.last_plan = dict(best_index=head[:, act_dim + 1].copy().view(np.int32).astype(np.int64),
+                              best_return=head[:, act_dim].copy(),
+                              returns=host[m * width + m * D:].reshape(m, n).copy(),
+                              mppi_mean=host[m * width:m * width + m * D].reshape(m, D).copy(),
+                              mppi_ess=head[:, act_dim + 2].copy(),
+                              mppi_valid=head[:, act_dim + 3].copy().view(np.int32).astype(np.int64))
+        return head[:, :act_dim].astype(np.float64)

@@ -11,7 +11,7 @@ Underneath, the horizon loop with its per-step ``dynamics_model.predict(obs, a[t
 (``:121-131`` / ``:97-104``) is ONE launch of the fused recurrent rollout (``l2a_lstm_plan_rs``):
 the env's state is broadcast to its candidates inside the kernel (``repeat_hidden`` never
 materialises), cell states stay in registers.  Candidate sharding over ``torch.distributed`` ranks,
-the device RNG mode and CEM work as in ``MPCController`` (whose helpers are reused).
+the device RNG mode, CEM and the reward-weighted planner (``use_mppi``) work as in ``MPCController`` (whose helpers are reused).
 
 An env whose ``reward_spec`` is a ``RewardProgram`` plans through ``l2a_lstm_plan_rs_program`` - the model's trajectory is
 rolled out on the GPU (one launch of the trajectory-writing micro-tile kernel, or a chain of one-step launches) and scored by
@@ -53,6 +53,11 @@ class RNNMPCController(MPCController):
             shard_candidates=True,
             pipeline_chunks=3,
             native_reward_model=False,
+            use_mppi=False,
+            mppi_kappa=1.0,
+            mppi_sigma=None,
+            mppi_beta=0.6,
+            mppi_iters=1,
             native_cem_step=False,      # (tests/test_rnn_cem_controller.py pins this one as the last parameter)
     ):
         Serializable.quick_init(self, locals())
@@ -65,7 +70,8 @@ class RNNMPCController(MPCController):
                                n_candidates=n_candidates, horizon=horizon, num_cem_iters=num_cem_iters,
                                percent_elites=percent_elites, use_reward_model=use_reward_model, alpha=0.0,
                                rng=rng, cem_mode=cem_mode, shard_candidates=shard_candidates,
-                               pipeline_chunks=pipeline_chunks, native_cem_step=native_cem_step)
+                               pipeline_chunks=pipeline_chunks, native_cem_step=native_cem_step, use_mppi=use_mppi,
+                               mppi_kappa=mppi_kappa, mppi_sigma=mppi_sigma, mppi_beta=mppi_beta, mppi_iters=mppi_iters)
         self._hidden_state = None
 
     # ------------------------------------------------------------------ hidden state: host view + device copy
@@ -119,7 +125,9 @@ class RNNMPCController(MPCController):
     def get_actions(self, observations):
         if self._hid_host is None and self._hid_dev is None:
             self.reset(dones=[True] * len(observations))
-        if self.use_cem:
+        if self.use_mppi:
+            actions = self.get_mppi_action(observations)
+        elif self.use_cem:
             actions = self.get_cem_action(observations)
         else:
             actions = self.get_rs_action(observations)
@@ -150,6 +158,7 @@ class RNNMPCController(MPCController):
         if dones is None:
             dones = [True]
         dones = np.asarray(dones, dtype=bool)
+        self._mppi_reset(dones)                                 # (MPPI: the finished envs' plans start from zero again)
         if self._hid_host is None and self._hid_dev is None:
             self._hidden_state = self.dynamics_model.get_initial_hidden(batch_size=len(dones))
         if not dones.any():

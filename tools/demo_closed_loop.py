@@ -4,7 +4,7 @@
 act with the MPC controller) with the drop-in classes, printing the collected reward and the time per
 controller step.
 
-    python tools/demo_closed_loop.py [mb_mpc|grbal|rebal] [--steps 100] [--rng numpy|device]
+    python tools/demo_closed_loop.py [mb_mpc|grbal|rebal] [--steps 100] [--rng numpy|device] [--planner rs|mppi]
 """
 import argparse
 import os
@@ -38,7 +38,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--rng", default="numpy", choices=["numpy", "device"])
     ap.add_argument("--epochs", type=int, default=0, help="training epochs (0 = per-algorithm default)")
+    ap.add_argument("--planner", default="rs", choices=["rs", "mppi"], help="random shooting, or the reward-weighted planner "
+                    "(use_mppi: draws on the device whatever --rng says)")
     args = ap.parse_args()
+    plan = dict(rng="device", use_mppi=True) if args.planner == "mppi" else dict(rng=args.rng)
     np.random.seed(0)
     torch.manual_seed(0)
     env = SyntheticEnv("half_cheetah")
@@ -49,17 +52,17 @@ def main():
         model = RNNDynamicsModel(name="dyn_model", env=env, hidden_sizes=(256,), learning_rate=5e-3, batch_size=10,
                                  backprop_steps=25, init_seed=0)
         model.fit(obs[:, :-1], act, obs[:, 1:], epochs=args.epochs or 30, valid_split_ratio=0.1)
-        policy = RNNMPCController(name="policy", env=env, dynamics_model=model, n_candidates=500, horizon=10, rng=args.rng)
+        policy = RNNMPCController(name="policy", env=env, dynamics_model=model, n_candidates=500, horizon=10, **plan)
     elif args.algo == "grbal":                  # run_grbal.py: 3x512, adapt on the last 16 transitions
         model = MetaMLPDynamicsModel(name="dyn_model", env=env, hidden_sizes=(512, 512, 512), meta_batch_size=10,
                                      inner_learning_rate=0.001, learning_rate=1e-3, batch_size=16, init_seed=0)
         model.fit(obs[:, :-1], act, obs[:, 1:], epochs=args.epochs or 80)
-        policy = MPCController(name="policy", env=env, dynamics_model=model, n_candidates=2000, horizon=10, rng=args.rng)
+        policy = MPCController(name="policy", env=env, dynamics_model=model, n_candidates=2000, horizon=10, **plan)
     else:                                       # run_mb_mpc.py with the BASELINE.json ensemble
         model = MLPDynamicsModel(name="dyn_model", env=env, hidden_sizes=(512, 512), learning_rate=1e-3,
                                  batch_size=256, ensemble_size=5, init_seed=0)
         model.fit(obs[:, :-1].reshape(-1, od), act.reshape(-1, ad), obs[:, 1:].reshape(-1, od), epochs=args.epochs or 60)
-        policy = MPCController(name="policy", env=env, dynamics_model=model, n_candidates=2000, horizon=10, rng=args.rng)
+        policy = MPCController(name="policy", env=env, dynamics_model=model, n_candidates=2000, horizon=10, **plan)
     print("%s: model fitted in %.1f s" % (args.algo, time.time() - t0))
 
     o = env.reset()
@@ -83,8 +86,8 @@ def main():
         rs = np.random.RandomState(s)
         env.reset()
         rnd.append(sum(env.step(rs.uniform(env.action_space.low, env.action_space.high))[1] for _ in range(args.steps)))
-    print("%s (%s RNG): return over %d steps %.1f (random actions: %.1f +- %.1f), %.2f ms per controller step"
-          % (args.algo, args.rng, args.steps, total, np.mean(rnd), np.std(rnd), 1e3 * t_ctrl / args.steps))
+    print("%s (%s, %s RNG): return over %d steps %.1f (random actions: %.1f +- %.1f), %.2f ms per controller step"
+          % (args.algo, args.planner, plan["rng"], args.steps, total, np.mean(rnd), np.std(rnd), 1e3 * t_ctrl / args.steps))
 
 
 if __name__ == "__main__":
