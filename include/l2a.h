@@ -530,6 +530,15 @@ int l2a_mppi_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsig
                     int n, int m, int h, int act_dim, float* mean_out, float* a_clip, float* seq, void* stream);
 int l2a_mppi_update(l2a_ctx* ctx, const float* returns, const float* a_clip, int n, int m, int h, int act_dim, float kappa,
                     float* mean, float* out, void* stream);
+/* l2a_mppi_sample for ONE rank of a sharded plan (as l2a_cem_sample's lo / hi): the rank draws, filters and clips ALL n candidates
+ * of the same stream - a_clip [n, m, D] and mean_out are l2a_mppi_sample's bit for bit, the update runs on them unchanged - and
+ * keeps the rollout tensor of its window only: seq_local [h, m * (hi - lo), A], plan row i * (hi - lo) + (j - lo) for lo <= j < hi
+ * (the values of l2a_mppi_sample's seq rows i * n + j).  lo == hi writes no seq_local (it may be NULL then).  L2A_EINVAL (nothing
+ * written): l2a_mppi_sample's, lo < 0, hi > n, lo > hi, or a NULL seq_local with lo < hi.  The same kernel body, one more instance. */
+int l2a_mppi_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                          const int* shift, const float* sigma, float beta, const float* low, const float* high,
+                          int n, int m, int h, int act_dim, int lo, int hi, float* mean_out, float* a_clip, float* seq_local,
+                          void* stream);
 
 /* ---- sharded plans: the one collective ------------------------------------------------------
  * Candidates are independent, so G GPUs (one process and one context each) plan disjoint shards of one candidate
@@ -883,6 +892,52 @@ int l2a_lstm_cem_controller_create_sharded_device(l2a_lstm* model, int m, int n,
                                                   int reference, unsigned long long seed, int rank, int world, l2a_reduce_fn reduce,
                                                   void* reduce_arg, l2a_controller** out);
 int l2a_cem_controller_result(l2a_controller* controller, float* mean_out, float* std_out, float* returns_out);
+/* ---- the MPPI controller step as one call (device mode) ------------------------------------------------------------------
+ * `MPCController.get_mppi_action` (policies/mpc_controller.py; the planner of l2a_mppi_sample / l2a_mppi_update above): the whole
+ * plan step on the launch stream - per iteration l2a_mppi_sample, the fused rollout, l2a_mppi_update - and ONE read-back of the
+ * update's packed head, m * (act_dim + 4) floats.  The plan mean [m, D] lives in the controller (three device buffers rotate: the
+ * committed mean is never written by the step that reads it) and stays on the device, as every iteration's returns do, until
+ * l2a_mppi_controller_result asks.  Iteration 0 samples with the per-env shift vector - -1 for an env that is new or was reset
+ * (l2a_mppi_controller_reset), +1 otherwise -, later iterations with shift 0.  The normals of iteration `it` are the Philox stream
+ * (seed) at offset (iter_calls + it) * n * m * D, iter_calls = iterations finished so far since create / reseed: with the same seed
+ * a step equals get_mppi_action bit for bit (action, index, Rmax, mean, ESS, valid count, returns).
+ *   iters  refinements per step (`mppi_iters`);  kappa, beta, sigma [act_dim]: `mppi_kappa`, `mppi_beta`, the noise scale per action
+ *          dimension (host float64, rounded to fp32 as `_mppi_sigma_vector` does)
+ * Refused at create (L2A_EINVAL, nothing allocated): the argument limits of l2a_mppi_sample and l2a_mppi_update - the LDS check
+ * n * 4 + L2A_MPPI_UPDATE_STATIC_LDS <= lds_per_block among them -, m > 64 or more than 4096 observation floats, a sigma that is
+ * negative or not finite, beta outside (0, 1], kappa not positive and finite, iters < 1; sharded: l2a_cem_controller_create_sharded_device's
+ * rank / world / collective rules.
+ * Steps through l2a_controller_step / _begin / _finish / _stats / _destroy: action_out = the new mean's first step as float64,
+ * index_out / return_out = the packed row's best valid index (-1 without a valid candidate) and Rmax (NaN then).  The l2a_lstm_*
+ * step functions return L2A_EINVAL.  The step's mean, iter_calls and the cleared reset marks are committed in _finish behind the
+ * verdict only: a launch flagged invalid (a tile-split partner was lost) repeats the WHOLE step unsplit from the same mean with the
+ * same offsets (L2A_STEP_UNSPLIT, same bits; flagged again: L2A_ESPLIT), and a failed step leaves the controller where it was.
+ * The in-flight exclusion rules of the CEM step apply (the step reads and clears the context's status word).
+ * Sharded (one rank of `world`): l2a_mppi_sample_shard over the window [lo, hi) = [rank n / world, (rank + 1) n / world), the
+ * rollout of that window, and per iteration the gather of the returns exactly as sharded CEM's - l2a_cem_shard_pack, the int64 MAX
+ * all-reduce of m * n + 3 words (`reduce`, or the context's communicator), l2a_cem_shard_unpack - in front of the UNCHANGED update
+ * over all n: every rank's step equals the unsharded one bit for bit.  The read-back gains the three verdict words.  The digest
+ * carries the controller kind, seed, iter_calls, m, n, h, iters, world, the bits of kappa, beta and sigma, and the step's shift
+ * vector (ranks that reset different envs would sample from different plans): a mismatch, or a hole, is L2A_ESTATE on every rank
+ * and nothing is consumed; a flag on any rank makes all of them repeat the step unsplit, together.
+ *   l2a_mppi_controller_reset  : dones [m] (non-zero: env i's next step starts from a zero mean), NULL = every env
+ *   l2a_mppi_controller_reseed : the stream restarts at 0 under `seed`; the mean is kept (what get_mppi_action does when
+ *                                torch.initial_seed() changes)
+ *   l2a_mppi_controller_result : of the latest finished step - the mean (host fp32 [m, D]), ESS [m], valid counts [m], every
+ *                                iteration's returns [iters, m, n] (sharded: the GATHERED tables); any pointer may be NULL; mean and
+ *                                returns come back in ONE copy on the latest step's stream, waited for
+ * _reset / _reseed / _result return L2A_ESTATE while a step is in flight, _result also before the first step has finished.
+ * Not built: a recurrent model, reward programs and reward models (l2a_reward only), NumPy normals.                              */
+int l2a_mppi_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
+                                      double discount, const l2a_reward* reward, int iters, float kappa, float beta,
+                                      const double* sigma, unsigned long long seed, l2a_controller** out);
+int l2a_mppi_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
+                                              double discount, const l2a_reward* reward, int iters, float kappa, float beta,
+                                              const double* sigma, unsigned long long seed, int rank, int world,
+                                              l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out);
+int l2a_mppi_controller_reset(l2a_controller* controller, const unsigned char* dones);
+int l2a_mppi_controller_reseed(l2a_controller* controller, unsigned long long seed);
+int l2a_mppi_controller_result(l2a_controller* controller, float* mean_out, float* ess_out, int* valid_out, float* returns_out);
 void l2a_controller_destroy(l2a_controller* controller);
 int l2a_controller_step(l2a_controller* controller, const double* obs, double* action_out, long long* index_out,
                         float* return_out, void* stream);

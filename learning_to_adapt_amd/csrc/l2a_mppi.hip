@@ -1,5 +1,5 @@
 // l2a_mppi.hip - the reward-weighted ("path-integral", MPPI) planner's per-iteration work around the fused rollout, on the device
-// (include/l2a.h: l2a_mppi_sample, l2a_mppi_update).  gfx950 only, wave64.  Compiled with -ffp-contract=off: the sample arithmetic
+// (include/l2a.h: l2a_mppi_sample, l2a_mppi_sample_shard, l2a_mppi_update).  gfx950 only, wave64.  Compiled with -ffp-contract=off: the sample arithmetic
 // is restated bit for bit on the host (tests/mppi_reference.py: sample_f32), so every operation below rounds once, on its own.
 //
 // The planner (PDDM's "filtered and reward-weighted refinement", Nagabandi et al. 2019) keeps one fp32 plan mean mu [h, A] per env
@@ -12,7 +12,10 @@
 //                           u = z * sigma[k];  nz = beta * u + omb * nz;  a = mu' + nz;  c = fminf(fmaxf(a, low[k]), high[k])
 //                       (omb = 1.0f - beta, formed once on the host), and c is stored twice: a_clip [n, m, D] (sample row j * m + i)
 //                       and the rollout's candidate tensor seq [h, m * n, A] (plan row i * n + j).  The chains of candidate 0 write
-//                       the shifted mean out of place (mean_out; every thread reads mean_in only).
+//                       the shifted mean out of place (mean_out; every thread reads mean_in only).  The SHARD instance
+//                       (l2a_mppi_sample_shard: one rank of a sharded plan) draws, filters and stores a_clip for ALL n candidates
+//                       and writes only its window lo <= j < hi of the rollout tensor, as seq_local [h, m * (hi - lo), A] (plan
+//                       row i * (hi - lo) + (j - lo)): the same body, one more condition and another row index at the seq store.
 //   l2a_mppi_update_k : grid (ceil(D / 32), m), 1024 threads.  Every workgroup of env i stages the env's n returns in LDS, finds the
 //                       maximum over the VALID candidates (neither NaN nor -inf; first maximum by index), turns the returns into
 //                       weights in place (w = expf(kappa * (R - Rmax)), 0 for an invalid candidate; Rmax = +inf: 1 for the +inf
@@ -35,6 +38,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <string>
 
 namespace {
 
@@ -73,7 +77,8 @@ struct MppiSampleParams {
     int n, m, h, act_dim;
     float* mean_out;            // [m, D]
     float* a_clip;              // [n, m, D]
-    float* seq;                 // [h, m * n, act_dim] or null
+    float* seq;                 // [h, m * n, act_dim] or null; SHARD: [h, m * (hi - lo), act_dim] (null when hi == lo)
+    int lo, hi;                 // SHARD: the candidates whose rollout rows this rank keeps
 };
 
 // Workgroup = L2A_MPPI_ROWS sample rows (all their D elements), the horizon in passes of as many steps as fit the LDS tiles.  Per pass:
@@ -85,6 +90,7 @@ struct MppiSampleParams {
 #define L2A_MPPI_ROWS 4
 #define L2A_MPPI_TILE 2048      // floats: L2A_MPPI_ROWS x steps per pass x act_dim (act_dim <= 16: at least 32 steps per pass)
 
+template <bool SHARD>
 __global__ void __launch_bounds__(256) l2a_mppi_sample_k(const MppiSampleParams p) {
 #pragma clang fp contract(off)
     __shared__ float tile[L2A_MPPI_TILE];       // u = z * sigma, then the clipped sample
@@ -150,15 +156,43 @@ __global__ void __launch_bounds__(256) l2a_mppi_sample_k(const MppiSampleParams 
             const int i = (int)(g - j * p.m);
             const float v = tile[q];
             p.a_clip[g * D + t0 * A + rem] = v;
-            if (p.seq) {
-                const long long prow = (long long)i * p.n + j;      // plan row of this candidate (env-major)
+            if (p.seq && (!SHARD || (j >= p.lo && j < p.hi))) {
+                // plan row of this candidate (env-major) among the rows of one horizon step: all n candidates, SHARD: the window's
+                const long long width = SHARD ? p.hi - p.lo : p.n;
+                const long long prow = (long long)i * width + (SHARD ? j - p.lo : j);
                 const int tt = rem / A;
-                p.seq[((long long)(t0 + tt) * rows + prow) * A + (rem - tt * A)] = v;
+                p.seq[((long long)(t0 + tt) * (width * p.m) + prow) * A + (rem - tt * A)] = v;
             }
             if (j == 0) p.mean_out[(long long)i * D + t0 * A + rem] = mtile[q];
         }
         __syncthreads();
     }
+}
+
+// The two sample entry points: the argument checks (nothing is written when one fails) and the launch.
+template <bool SHARD>
+int mppi_sample_launch(l2a_ctx* ctx, const char* who, MppiSampleParams p, void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    const std::string w(who);
+    if (!p.mean_in || !p.shift || !p.sigma || !p.low || !p.high || !p.mean_out || !p.a_clip) return l2a_fail(ctx, L2A_EINVAL, w + ": null pointer");
+    if (p.n < 1 || p.m < 1 || p.h < 1 || p.act_dim < 1 || p.act_dim > 16)
+        return l2a_fail(ctx, L2A_EINVAL, w + ": bad n / m / h / act_dim (1 <= act_dim <= 16)");
+    if (!(p.beta > 0.0f) || !(p.beta <= 1.0f)) return l2a_fail(ctx, L2A_EINVAL, w + ": beta must lie in (0, 1]");
+    if (p.mean_out == p.mean_in) return l2a_fail(ctx, L2A_EINVAL, w + ": mean_out must not alias mean_in");
+    const long long total = (long long)p.n * p.m * p.h * p.act_dim;
+    if (total > 0x7fffffffLL * 256) return l2a_fail(ctx, L2A_EINVAL, w + ": too many samples");
+    if (SHARD) {
+        if (p.lo < 0 || p.hi > p.n || p.lo > p.hi) return l2a_fail(ctx, L2A_EINVAL, w + ": the window needs 0 <= lo <= hi <= n");
+        if (p.hi > p.lo && !p.seq) return l2a_fail(ctx, L2A_EINVAL, w + ": null seq_local for a window that holds candidates");
+        if (p.hi == p.lo) p.seq = nullptr;
+    }
+    p.omb = 1.0f - p.beta;
+    l2a_device_guard guard(ctx->device);
+    const long long rows = (long long)p.n * p.m;
+    hipLaunchKernelGGL(l2a_mppi_sample_k<SHARD>, dim3((unsigned)((rows + L2A_MPPI_ROWS - 1) / L2A_MPPI_ROWS)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream_v), p);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
 }
 
 // ---- the update ---------------------------------------------------------------------------------------------------------------------
@@ -282,26 +316,22 @@ extern "C" {
 int l2a_mppi_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
                     const int* shift, const float* sigma, float beta, const float* low, const float* high, int n, int m, int h,
                     int act_dim, float* mean_out, float* a_clip, float* seq, void* stream_v) {
-    if (!ctx) return L2A_EINVAL;
-    if (!mean_in || !shift || !sigma || !low || !high || !mean_out || !a_clip)
-        return l2a_fail(ctx, L2A_EINVAL, "l2a_mppi_sample: null pointer");
-    if (n < 1 || m < 1 || h < 1 || act_dim < 1 || act_dim > 16)
-        return l2a_fail(ctx, L2A_EINVAL, "l2a_mppi_sample: bad n / m / h / act_dim (1 <= act_dim <= 16)");
-    if (!(beta > 0.0f) || !(beta <= 1.0f)) return l2a_fail(ctx, L2A_EINVAL, "l2a_mppi_sample: beta must lie in (0, 1]");
-    if (mean_out == mean_in) return l2a_fail(ctx, L2A_EINVAL, "l2a_mppi_sample: mean_out must not alias mean_in");
-    const long long total = (long long)n * m * h * act_dim;
-    if (total > 0x7fffffffLL * 256) return l2a_fail(ctx, L2A_EINVAL, "l2a_mppi_sample: too many samples");
-    l2a_device_guard guard(ctx->device);
     MppiSampleParams p;
     std::memset(&p, 0, sizeof(p));
     p.z = z; p.seed = seed; p.offset = offset; p.mean_in = mean_in; p.shift = shift; p.sigma = sigma; p.low = low; p.high = high;
-    p.beta = beta; p.omb = 1.0f - beta; p.n = n; p.m = m; p.h = h; p.act_dim = act_dim;
-    p.mean_out = mean_out; p.a_clip = a_clip; p.seq = seq;
-    const long long rows = (long long)n * m;
-    hipLaunchKernelGGL(l2a_mppi_sample_k, dim3((unsigned)((rows + L2A_MPPI_ROWS - 1) / L2A_MPPI_ROWS)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream_v), p);
-    L2A_HIP(ctx, hipGetLastError());
-    return L2A_OK;
+    p.beta = beta; p.n = n; p.m = m; p.h = h; p.act_dim = act_dim; p.mean_out = mean_out; p.a_clip = a_clip; p.seq = seq;
+    return mppi_sample_launch<false>(ctx, "l2a_mppi_sample", p, stream_v);
+}
+
+int l2a_mppi_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                          const int* shift, const float* sigma, float beta, const float* low, const float* high, int n, int m, int h,
+                          int act_dim, int lo, int hi, float* mean_out, float* a_clip, float* seq_local, void* stream_v) {
+    MppiSampleParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.z = z; p.seed = seed; p.offset = offset; p.mean_in = mean_in; p.shift = shift; p.sigma = sigma; p.low = low; p.high = high;
+    p.beta = beta; p.n = n; p.m = m; p.h = h; p.act_dim = act_dim; p.mean_out = mean_out; p.a_clip = a_clip; p.seq = seq_local;
+    p.lo = lo; p.hi = hi;
+    return mppi_sample_launch<true>(ctx, "l2a_mppi_sample_shard", p, stream_v);
 }
 
 int l2a_mppi_update(l2a_ctx* ctx, const float* returns, const float* a_clip, int n, int m, int h, int act_dim, float kappa,

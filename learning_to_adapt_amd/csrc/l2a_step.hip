@@ -17,6 +17,7 @@
 // call at all (a forked child: its producer thread and its HIP state did not come along).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -102,6 +103,25 @@ struct l2a_controller {
     unsigned long long steps = 0, relaunches = 0, sync_draws = 0;
     // CEM plan (l2a_cem_controller_create_device): K iterations of rollout -> l2a_cem_refit_sample, one read-back per step
     struct cem_state* cem = nullptr;
+    // MPPI plan (l2a_mppi_controller_create_device): K iterations of l2a_mppi_sample -> rollout -> l2a_mppi_update, one read-back
+    struct mppi_state* mppi = nullptr;
+    struct plan_state* plan = nullptr;          // whichever of the two: what both kinds of plan step share
+};
+
+// What the device-mode plan steps (CEM, MPPI) share: the iterations' returns, the packed result behind ONE read-back and, for one
+// rank of a sharded plan, the words of the per-iteration gather and the verdict accumulated over them.
+struct plan_state {
+    int iters = 0, D = 0, row_floats = 0;       // a result row: the action | return | index bits | ... (CEM: A + 2, MPPI: A + 4 floats)
+    unsigned long long iter_calls = 0;          // iterations planned so far (the Philox stream's position)
+    float* seq = nullptr;                       // [h, m * (hi - lo), act_dim]
+    float* rets = nullptr;                      // [iters, m, n]: every iteration's returns of the latest step
+    float* lowhigh = nullptr;                   // [2][act_dim] fp32 bounds
+    float* packed_dev = nullptr;                // m result rows (CEM: + mean [m, D], std [m, D])
+    float* packed_host = nullptr;               // page-locked
+    size_t packed_floats = 0;                   // (sharded: + the verdict's three words)
+    float* rets_local = nullptr;                // sharded [m, hi - lo]: this rank's returns of the iteration under way
+    unsigned long long* words = nullptr;        // sharded [m * n + 3]
+    unsigned int* verdict_dev = nullptr;        // sharded [3] behind packed_dev's floats: flag | holes | digest mismatch, accumulated per step
 };
 
 // Device-mode CEM (`MPCController.get_cem_action_device`, policies/mpc_controller.py): the whole plan step on the launch stream -
@@ -111,26 +131,35 @@ struct l2a_controller {
 // l2a_cem_pick_act and, with c_next / h_next, enqueues l2a_lstm_advance on the picked actions in front of the read-back.
 // One rank of a sharded plan (l2a_cem_controller_create_sharded_device) rolls out candidates [lo, hi); every iteration's returns are
 // gathered by the int64 MAX all-reduce of m * n + 3 words (l2a_cem_shard_pack / _unpack).
-struct cem_state {
-    int iters = 0, k = 0, reference = 1, D = 0;
+struct cem_state : plan_state {
+    int k = 0, reference = 1;
     float alpha = 0.1f;
-    unsigned long long iter_calls = 0;          // CEM iterations planned so far (the Philox stream's position)
     float* mean[2] = {nullptr, nullptr};        // [m, D] ping-pong (the fused launch reads one and writes the other)
     float* std = nullptr;                       // [m, D]
     float* a_clip[2] = {nullptr, nullptr};      // [n, m, D] ping-pong
     float* a_raw = nullptr;                     // [n, m, D]
-    float* seq = nullptr;                       // [h, m * (hi - lo), act_dim]
     int* rows = nullptr;                        // [m * k]
-    float* rets = nullptr;                      // [iters, m, n]: every iteration's returns of the latest step
-    float* lowhigh = nullptr;                   // [2][act_dim] fp32 bounds
-    float* packed_dev = nullptr;                // l2a_cem_pick's buffer: m x (act_dim + 2), mean [m, D], std [m, D]
-    float* packed_host = nullptr;               // page-locked
-    size_t packed_floats = 0;                   // (sharded: + the verdict's three words)
     int cur = 0;                                // the buffers of the last iteration
     float* act_dev = nullptr;                   // recurrent: the winners' first actions [m, act_dim] (l2a_cem_pick_act -> l2a_lstm_advance)
-    float* rets_local = nullptr;                // sharded [m, hi - lo]: this rank's returns of the iteration under way
-    unsigned long long* words = nullptr;        // sharded [m * n + 3]
-    unsigned int* verdict_dev = nullptr;        // sharded [3] behind packed_dev's floats: flag | holes | digest mismatch, accumulated per step
+};
+
+// Device-mode MPPI (`MPCController.get_mppi_action`): per iteration l2a_mppi_sample (sharded: l2a_mppi_sample_shard over this rank's
+// window), the rollout (sharded: + the gather of the returns, as CEM's), l2a_mppi_update over all n; the update's packed head is
+// the step's one read-back.  Philox offsets (iter_calls + it) * n * m * D.  The plan mean persists from step to step on the device:
+// a step reads mean[cur] and writes the two others in turn, and `cur`, iter_calls and the reset marks move in `finish` only - a
+// replayed or failed step starts from the same plan.
+struct mppi_state : plan_state {
+    float kappa = 1.0f, beta = 1.0f;
+    float sigma32[16] = {0};                    // (the digest carries its bits)
+    float* sigma = nullptr;                     // [act_dim] device
+    float* mean[3] = {nullptr, nullptr, nullptr};   // [m, D] each, in one allocation in front of `rets`
+    float* a_clip = nullptr;                    // [n, m, D]
+    int* shift = nullptr;                       // device [4][m]: all +1 | all 0 | all -1 | the step's own mix
+    int* shift_host = nullptr;                  // page-locked [m]: the mix of the step in flight (it stays for a replay)
+    const int* first = nullptr;                 // iteration 0's shift vector of the step in flight
+    std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts from zeros
+    int cur = 0, last = 0;                      // the committed mean | the mean the step in flight ends on
+    float* result_host = nullptr;               // page-locked [3 m D + iters m n]: l2a_mppi_controller_result's one copy
 };
 
 extern "C" unsigned long long l2a_mt19937_state_digest(const void* addr);      // csrc/l2a_rng.c
@@ -180,7 +209,7 @@ const char* const SPLIT_OFF = "l2a_controller_step: the rollout was flagged inva
 void set_in_flight(l2a_controller* c, bool on) {
     if (c->in_flight == on) return;
     c->in_flight = on;
-    int& n = c->cem ? c->ctx->cem_steps_in_flight : c->ctx->rs_steps_in_flight;
+    int& n = c->plan ? c->ctx->cem_steps_in_flight : c->ctx->rs_steps_in_flight;        // (an MPPI step counts as a CEM step: below)
     n += on ? 1 : -1;
 }
 
@@ -256,7 +285,7 @@ void kick_arm(void* arg) {
     (void)l2a_ahead_arm(a.chain, a.np_addr);
 }
 
-// ---- create: all 12 entry points fill a step_cfg and share everything below ----------------------------------------------------------
+// ---- create: all 14 entry points fill a step_cfg and share everything below ----------------------------------------------------------
 struct step_cfg {
     const char* who;                            // the entry point (the prefix of its error texts)
     l2a_model* mlp;
@@ -280,12 +309,19 @@ struct step_cfg {
     bool cem = false;                           // a CEM plan
     int iters = 0, num_elites = 0, reference = 0;
     float alpha = 0.0f;
+    bool mppi = false;                          // an MPPI plan (`iters` as CEM's)
+    float kappa = 0.0f, beta = 0.0f;
+    const double* sigma = nullptr;              // [act_dim]
 
     step_cfg& parity(void* addr, int threads) { np_addr = addr; rng_threads = threads; return *this; }
     step_cfg& device(unsigned long long s) { device_rng = true; seed = s; return *this; }
     step_cfg& shard(int r, int w, l2a_reduce_fn fn, void* arg) { sharded = true; rank = r; world = w; reduce = fn; reduce_arg = arg; return *this; }
     step_cfg& cem_plan(int it, int elites, float a, int ref, unsigned long long s) {
         cem = true; iters = it; num_elites = elites; alpha = a; reference = ref ? 1 : 0;
+        return device(s);
+    }
+    step_cfg& mppi_plan(int it, float kap, float bet, const double* sig, unsigned long long s) {
+        mppi = true; iters = it; kappa = kap; beta = bet; sigma = sig;
         return device(s);
     }
 };
@@ -311,6 +347,21 @@ int check_shape(const step_cfg& f) {
     const int m = f.m, n = f.n, h = f.h;
     const bool bad_mnh = m < 1 || m > L2A_MAIL_KEYS || (long long)m * f.obs_dim > L2A_MAIL_OBS || n < 1 || h < 1;
     const bool bad_act = f.act_dim < 1 || f.act_dim > 16;
+    if (f.mppi) {
+        // the limits of l2a_mppi_sample and l2a_mppi_update, so that no step can fail on its arguments
+        if (bad_mnh || bad_act)
+            return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1, 1 <= act_dim <= 16");
+        if (f.iters < 1) return refuse(f, L2A_EINVAL, "needs iters >= 1");
+        if (!(f.beta > 0.0f) || !(f.beta <= 1.0f)) return refuse(f, L2A_EINVAL, "beta must lie in (0, 1]");
+        if (!(f.kappa > 0.0f) || !std::isfinite(f.kappa)) return refuse(f, L2A_EINVAL, "kappa must be positive and finite");
+        for (int k = 0; k < f.act_dim; ++k)
+            if (!std::isfinite((float)f.sigma[k]) || !(f.sigma[k] >= 0.0)) return refuse(f, L2A_EINVAL, "sigma must be finite and non-negative");
+        if ((size_t)n * sizeof(float) + L2A_MPPI_UPDATE_STATIC_LDS > (size_t)f.ctx->lds_per_block)
+            return refuse(f, L2A_EINVAL, "more candidates than an env's weights fit in LDS (l2a_mppi_update)");
+        if ((long long)n * m * h * f.act_dim > 0x7fffffffLL * 256 || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
+            return refuse(f, L2A_EINVAL, "too many samples");
+        return L2A_OK;
+    }
     if (!f.cem) {
         if (bad_mnh) return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1");
         if (bad_act) return refuse(f, L2A_EINVAL, "the host draw takes 1 <= act_dim <= 16");
@@ -390,28 +441,23 @@ void alloc_rs(l2a_controller* c, const step_cfg& f) {
     c->shard.payload_host = alloc<unsigned long long>(c, MEM_PINNED, (size_t)c->m + 3);
 }
 
-// CEM: the unsharded controller is rank 0 of a world of 1 without the collective's buffers.
-void alloc_cem(l2a_controller* c, const step_cfg& f) {
-    cem_state* q = c->cem;
+// A device-mode plan (CEM, MPPI): what both kinds allocate, `packed` floats of result behind the one read-back.  The unsharded
+// controller is rank 0 of a world of 1 without the collective's buffers.  `rets_head`: floats the caller keeps in front of the
+// returns in the same allocation (MPPI: its means, so that ONE copy brings means and returns back on request).
+void alloc_plan(l2a_controller* c, const step_cfg& f, int row_floats, size_t packed, size_t rets_head = 0) {
+    plan_state* q = c->plan;
     const int A = c->act_dim;
-    q->iters = f.iters; q->k = f.num_elites; q->reference = f.reference; q->D = c->h * A; q->alpha = f.alpha;
-    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * q->D, nmd = n * md;
+    q->iters = f.iters; q->D = c->h * A; q->row_floats = row_floats;
+    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * q->D;
     const size_t n_local = (size_t)(c->shard.hi - c->shard.lo), n_alloc = n_local > 0 ? n_local : 1;
-    q->packed_floats = m * (A + 2) + 2 * md + (f.sharded ? 3 : 0);
+    q->packed_floats = packed + (f.sharded ? 3 : 0);
     alloc_launch(c);
-    for (int s = 0; s < 2; ++s) {
-        q->mean[s] = alloc<float>(c, MEM_DEVICE, md);
-        q->a_clip[s] = alloc<float>(c, MEM_DEVICE, nmd);
-    }
-    q->std = alloc<float>(c, MEM_DEVICE, md);
-    if (q->reference) q->a_raw = alloc<float>(c, MEM_DEVICE, nmd);
     q->seq = alloc<float>(c, MEM_DEVICE, n_alloc * md);
-    q->rows = alloc<int>(c, MEM_DEVICE, m * f.num_elites);
-    q->rets = alloc<float>(c, MEM_DEVICE, (size_t)f.iters * m * n);
+    q->rets = alloc<float>(c, MEM_DEVICE, rets_head + (size_t)f.iters * m * n);
+    if (q->rets) q->rets += rets_head;
     q->lowhigh = alloc<float>(c, MEM_DEVICE, 2 * (size_t)A);
     q->packed_dev = alloc<float>(c, MEM_DEVICE, q->packed_floats);
     q->packed_host = alloc<float>(c, MEM_PINNED, q->packed_floats);
-    if (f.rnn) q->act_dev = alloc<float>(c, MEM_DEVICE, m * A);
     if (f.sharded) {
         q->rets_local = alloc<float>(c, MEM_DEVICE, m * n_alloc);
         q->words = alloc<unsigned long long>(c, MEM_DEVICE, m * n + 3);
@@ -422,6 +468,42 @@ void alloc_cem(l2a_controller* c, const step_cfg& f) {
     upload(c, q->lowhigh, lh, sizeof(float) * 2 * A);
 }
 
+void alloc_cem(l2a_controller* c, const step_cfg& f) {
+    cem_state* q = c->cem;
+    const int A = c->act_dim;
+    q->k = f.num_elites; q->reference = f.reference; q->alpha = f.alpha;
+    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A, nmd = n * md;
+    alloc_plan(c, f, A + 2, m * (A + 2) + 2 * md);
+    for (int s = 0; s < 2; ++s) {
+        q->mean[s] = alloc<float>(c, MEM_DEVICE, md);
+        q->a_clip[s] = alloc<float>(c, MEM_DEVICE, nmd);
+    }
+    q->std = alloc<float>(c, MEM_DEVICE, md);
+    if (q->reference) q->a_raw = alloc<float>(c, MEM_DEVICE, nmd);
+    q->rows = alloc<int>(c, MEM_DEVICE, m * f.num_elites);
+    if (f.rnn) q->act_dev = alloc<float>(c, MEM_DEVICE, m * A);
+}
+
+void alloc_mppi(l2a_controller* c, const step_cfg& f) {
+    mppi_state* q = c->mppi;
+    const int A = c->act_dim;
+    q->kappa = f.kappa; q->beta = f.beta;
+    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A;
+    alloc_plan(c, f, A + 4, m * (A + 4), 3 * md);
+    for (int s = 0; s < 3; ++s) q->mean[s] = q->rets ? q->rets - (3 - s) * md : nullptr;
+    q->result_host = alloc<float>(c, MEM_PINNED, 3 * md + (size_t)f.iters * m * n);
+    q->a_clip = alloc<float>(c, MEM_DEVICE, n * md);
+    q->sigma = alloc<float>(c, MEM_DEVICE, (size_t)A);
+    q->shift = alloc<int>(c, MEM_DEVICE, 4 * m);
+    q->shift_host = alloc<int>(c, MEM_PINNED, m);
+    q->fresh.assign(m, 1);                      // every env starts from zeros
+    for (int k = 0; k < A; ++k) q->sigma32[k] = (float)f.sigma[k];
+    upload(c, q->sigma, q->sigma32, sizeof(float) * A);
+    std::vector<int> rows(4 * m, 0);
+    for (size_t i = 0; i < m; ++i) { rows[i] = 1; rows[2 * m + i] = -1; }
+    upload(c, q->shift, rows.data(), sizeof(int) * rows.size());
+}
+
 int create(step_cfg f) {
     if (!f.mlp && !f.rnn) return L2A_EINVAL;
     resolve(f);
@@ -429,16 +511,19 @@ int create(step_cfg f) {
     if (rc != L2A_OK) return rc;
     if (!f.out) return refuse(f, L2A_EINVAL, "out is null");
     *f.out = nullptr;
+    if (f.mppi && !f.sigma) return refuse(f, L2A_EINVAL, "null sigma");
     if (!f.low || !f.high || !f.reward || (!f.np_addr && !f.device_rng))
-        return refuse(f, L2A_EINVAL, f.cem ? "null low / high / reward" : "null low / high / reward / generator state address");
+        return refuse(f, L2A_EINVAL, (f.cem || f.mppi) ? "null low / high / reward" : "null low / high / reward / generator state address");
     rc = check_shape(f);
     if (rc != L2A_OK) return rc;
     l2a_controller* c = new (std::nothrow) l2a_controller();
-    if (c && f.cem) c->cem = new (std::nothrow) cem_state();
-    if (!c || (f.cem && !c->cem)) { delete c; return refuse(f, L2A_EHIP, "out of memory"); }
+    if (c && f.cem) c->plan = c->cem = new (std::nothrow) cem_state();
+    if (c && f.mppi) c->plan = c->mppi = new (std::nothrow) mppi_state();
+    if (!c || ((f.cem || f.mppi) && !c->plan)) { delete c; return refuse(f, L2A_EHIP, "out of memory"); }
     init_common(c, f);
     l2a_device_guard guard(f.ctx->device);
     if (f.cem) alloc_cem(c, f);
+    else if (f.mppi) alloc_mppi(c, f);
     else alloc_rs(c, f);
     if (c->mem_err != hipSuccess) {
         const hipError_t e = c->mem_err;
@@ -497,7 +582,7 @@ void record_stages(l2a_controller* c, double t2, double t3) {
     c->stage_us[0] = c->t_taken - c->t_begin;               // take (compare + adopt the block; waits only if the producer is late)
     c->stage_us[1] = st[1] - c->t_taken;                    // observation cast + staging (CEM: + iteration 0's sampling launch)
     c->stage_us[2] = st[2] - st[1];                         // launch call(s)
-    c->stage_us[3] = c->cem ? 0.0 : st[3] - st[2];          // producer kick
+    c->stage_us[3] = c->plan ? 0.0 : st[3] - st[2];         // producer kick
     c->stage_us[4] = st[4] - st[3];                         // wait for the result (begin -> finish: whatever the host did in between is in here)
     c->stage_us[5] = t3 - t2;                               // decode + gather
     c->stage_us[6] = t3 - c->t_begin;                       // whole step
@@ -533,6 +618,14 @@ __global__ void __launch_bounds__(256) l2a_cem_init_k(int md, float* __restrict_
     if (e < md) { mean[e] = 0.0f; std[e] = 1.0f; }
 }
 
+// splitmix64's finaliser over the running value
+unsigned long long digest_mix(unsigned long long d, unsigned long long x) {
+    d = (d ^ x) + 0x9E3779B97F4A7C15ull;
+    d = (d ^ (d >> 30)) * 0xBF58476D1CE4E5B9ull;
+    d = (d ^ (d >> 27)) * 0x94D049BB133111EBull;
+    return d ^ (d >> 31);
+}
+
 // What every rank of a sharded CEM step must share: how the controller was built and where its Philox stream stands.
 unsigned long long cem_digest(const l2a_controller* c) {
     const cem_state* q = c->cem;
@@ -542,13 +635,53 @@ unsigned long long cem_digest(const l2a_controller* c) {
                                     (unsigned long long)q->iters, (unsigned long long)q->k, (unsigned long long)q->reference,
                                     (unsigned long long)alpha_bits, (unsigned long long)c->shard.world, (unsigned long long)(c->rnn ? 1 : 0)};
     unsigned long long d = 0x9E3779B97F4A7C15ull;
-    for (unsigned long long x : v) {            // splitmix64's finaliser over the running value
-        d = (d ^ x) + 0x9E3779B97F4A7C15ull;
-        d = (d ^ (d >> 30)) * 0xBF58476D1CE4E5B9ull;
-        d = (d ^ (d >> 27)) * 0x94D049BB133111EBull;
-        d ^= d >> 31;
-    }
+    for (unsigned long long x : v) d = digest_mix(d, x);
     return d;
+}
+
+// The same for MPPI: the controller kind (2; CEM's last word is 0 or 1), the planner's constants by their bits, and the step's
+// shift vector - ranks that reset different envs would sample around different plans.
+unsigned long long mppi_digest(const l2a_controller* c) {
+    const mppi_state* q = c->mppi;
+    unsigned int kappa_bits = 0, beta_bits = 0;
+    std::memcpy(&kappa_bits, &q->kappa, sizeof(kappa_bits));
+    std::memcpy(&beta_bits, &q->beta, sizeof(beta_bits));
+    const unsigned long long v[] = {c->device.seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n, (unsigned long long)c->h,
+                                    (unsigned long long)q->iters, (unsigned long long)kappa_bits, (unsigned long long)beta_bits,
+                                    (unsigned long long)c->shard.world, 2ull};
+    unsigned long long d = 0x9E3779B97F4A7C15ull;
+    for (unsigned long long x : v) d = digest_mix(d, x);
+    for (int k = 0; k < c->act_dim; ++k) {
+        unsigned int bits = 0;
+        std::memcpy(&bits, &q->sigma32[k], sizeof(bits));
+        d = digest_mix(d, bits);
+    }
+    for (int i = 0; i < c->m; ++i) d = digest_mix(d, q->fresh[i] ? 1ull : 0ull);
+    return d;
+}
+
+// One iteration's returns of every candidate into `rets` [m, n].  Unsharded: the rollout of all n.  Sharded: this rank's rollouts
+// -> words -> the ONE collective -> every rank's returns.
+int gather_returns(l2a_controller* c, float* rets) {
+    plan_state* q = c->plan;
+    if (!c->shard.on) return rollout(c, q->seq, c->n, 0, rets);
+    const int m = c->m, n = c->n, lo = c->shard.lo, hi = c->shard.hi;
+    int rc = L2A_OK;
+    if (hi > lo) rc = rollout(c, q->seq, hi - lo, lo, q->rets_local);
+    if (rc == L2A_OK) rc = l2a_cem_shard_pack(c->ctx, q->rets_local, m, n, lo, hi, c->shard.digest, q->words, c->stream);
+    if (rc == L2A_OK) rc = reduce_words(c, q->words, m * n + 3);
+    if (rc == L2A_OK) rc = l2a_cem_shard_unpack(c->ctx, q->words, m, n, rets, q->verdict_dev, c->stream);
+    return rc;
+}
+
+// The end of a plan step's launches: the packed result (sharded: with the verdict) to page-locked memory, the event behind it.
+int read_back(l2a_controller* c) {
+    plan_state* q = c->plan;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    L2A_HIP(c->ctx, hipMemcpyAsync(q->packed_host, q->packed_dev, sizeof(float) * q->packed_floats, hipMemcpyDeviceToHost, stream));
+    L2A_HIP(c->ctx, hipEventRecord(c->done, stream));
+    c->ctx->stamps_us[2] = l2a_now_us();
+    return L2A_OK;
 }
 
 // Everything of one CEM plan step, in stream order on `stream`; nothing on the host waits.
@@ -574,15 +707,7 @@ int cem_launch(l2a_controller* c) {
     ctx->stamps_us[1] = l2a_now_us();
     for (int it = 0; it < q->iters; ++it) {
         float* rets = q->rets + (size_t)it * m * n;
-        if (!sharded) {
-            rc = rollout(c, q->seq, n, 0, rets);
-        } else {
-            // this rank's rollouts -> words -> the ONE collective -> every rank's returns in the iteration's slot of `rets`
-            if (hi > lo) rc = rollout(c, q->seq, hi - lo, lo, q->rets_local);
-            if (rc == L2A_OK) rc = l2a_cem_shard_pack(ctx, q->rets_local, m, n, lo, hi, c->shard.digest, q->words, c->stream);
-            if (rc == L2A_OK) rc = reduce_words(c, q->words, m * n + 3);
-            if (rc == L2A_OK) rc = l2a_cem_shard_unpack(ctx, q->words, m, n, rets, q->verdict_dev, c->stream);
-        }
+        rc = gather_returns(c, rets);
         if (rc != L2A_OK) return rc;
         if (it + 1 < q->iters) {
             rc = l2a_cem_refit_sample(ctx, rets, q->a_clip[cur], n, m, h, A, q->k, q->reference, q->alpha, nullptr, seed,
@@ -606,13 +731,67 @@ int cem_launch(l2a_controller* c) {
         if (rc != L2A_OK) return rc;
     }
     q->cur = cur;
-    L2A_HIP(ctx, hipMemcpyAsync(q->packed_host, q->packed_dev, sizeof(float) * q->packed_floats, hipMemcpyDeviceToHost, stream));
-    L2A_HIP(ctx, hipEventRecord(c->done, stream));
-    ctx->stamps_us[2] = l2a_now_us();
-    return L2A_OK;
+    return read_back(c);
 }
 
-int cem_begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
+// ---- MPPI (device mode) ---------------------------------------------------------------------------------------------------------
+// Everything of one MPPI plan step, in stream order on `stream`; nothing on the host waits.  Reads the committed mean and the reset
+// marks and writes neither: a replay launches the same step again.
+int mppi_launch(l2a_controller* c) {
+    l2a_ctx* ctx = c->ctx;
+    mppi_state* q = c->mppi;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    const int m = c->m, n = c->n, h = c->h, A = c->act_dim;
+    const unsigned long long per_iter = (unsigned long long)n * m * q->D, seed = c->device.seed;
+    const bool sharded = c->shard.on;
+    const int lo = c->shard.lo, hi = c->shard.hi;
+    const float* low = q->lowhigh;
+    const float* high = q->lowhigh + A;
+    l2a_device_guard guard(ctx->device);
+    if (q->first == q->shift + 3 * m)           // the step's own mix of new and running envs
+        L2A_HIP(ctx, hipMemcpyAsync(q->shift + 3 * m, q->shift_host, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream));
+    if (sharded) L2A_HIP(ctx, hipMemsetAsync(q->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
+    int src = q->cur;
+    for (int it = 0; it < q->iters; ++it) {
+        int dst = 0;
+        while (dst == src || dst == q->cur) ++dst;          // neither the mean this iteration reads nor the committed one
+        const int* shift = it == 0 ? q->first : q->shift + m;
+        const unsigned long long offset = (q->iter_calls + it) * per_iter;
+        // (sharded: every rank samples all n rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
+        int rc = sharded ? l2a_mppi_sample_shard(ctx, nullptr, seed, offset, q->mean[src], shift, q->sigma, q->beta, low, high, n, m, h, A,
+                                                 lo, hi, q->mean[dst], q->a_clip, q->seq, c->stream)
+                         : l2a_mppi_sample(ctx, nullptr, seed, offset, q->mean[src], shift, q->sigma, q->beta, low, high, n, m, h, A,
+                                           q->mean[dst], q->a_clip, q->seq, c->stream);
+        if (rc != L2A_OK) return rc;
+        if (it == 0) ctx->stamps_us[1] = l2a_now_us();
+        float* rets = q->rets + (size_t)it * m * n;
+        rc = gather_returns(c, rets);
+        if (rc == L2A_OK) rc = l2a_mppi_update(ctx, rets, q->a_clip, n, m, h, A, q->kappa, q->mean[dst], q->packed_dev, c->stream);
+        if (rc != L2A_OK) return rc;
+        src = dst;
+    }
+    q->last = src;
+    return read_back(c);
+}
+
+// Iteration 0's shift vector of the step about to be launched: -1 for an env that is new or was reset, +1 for the others.
+void mppi_first_shift(l2a_controller* c) {
+    mppi_state* q = c->mppi;
+    const int m = c->m;
+    int fresh = 0;
+    for (int i = 0; i < m; ++i) fresh += q->fresh[i] ? 1 : 0;
+    if (fresh == 0) q->first = q->shift;
+    else if (fresh == m) q->first = q->shift + 2 * m;
+    else {
+        for (int i = 0; i < m; ++i) q->shift_host[i] = q->fresh[i] ? -1 : 1;
+        q->first = q->shift + 3 * m;
+    }
+}
+
+// ---- what the CEM and the MPPI step share: begin, the verdicts, finish ---------------------------------------------------------------
+int plan_launch(l2a_controller* c) { return c->cem ? cem_launch(c) : mppi_launch(c); }
+
+int plan_begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
     l2a_ctx* ctx = c->ctx;
     if (!obs) return fail(ctx, L2A_EINVAL, "l2a_controller_begin: null obs");
     if (c->rnn) {                       // before anything is launched
@@ -626,8 +805,9 @@ int cem_begin(l2a_controller* c, const double* obs, const float* c0, const float
     c->t_begin = c->t_taken = l2a_now_us();
     stage_obs(c, obs, c0, h0, c1, h1, stream);
     c->result = L2A_OK;
-    if (c->shard.on) c->shard.digest = cem_digest(c);
-    const int rc = cem_launch(c);
+    if (c->mppi) mppi_first_shift(c);
+    if (c->shard.on) c->shard.digest = c->cem ? cem_digest(c) : mppi_digest(c);
+    const int rc = plan_launch(c);
     if (rc != L2A_OK) return rc;
     ctx->stamps_us[3] = l2a_now_us();
     set_in_flight(c, true);
@@ -635,7 +815,7 @@ int cem_begin(l2a_controller* c, const double* obs, const float* c0, const float
 }
 
 // Unsharded: this context's own status word decides, and a flag with the tile split already disabled fails at once.
-int cem_verdict(l2a_controller* c) {
+int plan_verdict(l2a_controller* c) {
     l2a_ctx* ctx = c->ctx;
     if (*ctx->status_host == 0) return L2A_OK;
     *ctx->status_host = 0;
@@ -644,38 +824,43 @@ int cem_verdict(l2a_controller* c) {
 
 // Sharded: the REDUCED verdict alone decides - it is the same on every rank, so the ranks never disagree on the number of
 // collectives.  This rank's own status word travelled in its words; it is consumed here and never consulted.
-int cem_verdict_sharded(l2a_controller* c) {
+int plan_verdict_sharded(l2a_controller* c) {
     l2a_ctx* ctx = c->ctx;
-    const cem_state* q = c->cem;
+    const plan_state* q = c->plan;
     *ctx->status_host = 0;
     unsigned int verdict[3];
     std::memcpy(verdict, q->packed_host + (q->packed_floats - 3), sizeof(verdict));
+    const std::string kind = c->cem ? "sharded CEM" : "sharded MPPI";
     if (verdict[2] != 0)
-        return fail(ctx, L2A_ESTATE, "sharded CEM needs identically built controllers in step on every rank (same seed, step count, "
-                                     "m, n, h, iters, num_elites, mode, alpha and world): the ranks' digests differ");
+        return fail(ctx, L2A_ESTATE, kind + (c->cem ? " needs identically built controllers in step on every rank (same seed, step count, "
+                                                      "m, n, h, iters, num_elites, mode, alpha and world): the ranks' digests differ"
+                                                    : " needs identically built controllers in step on every rank (same seed, step count, "
+                                                      "m, n, h, iters, kappa, beta, sigma and world, and the same envs reset): the ranks' "
+                                                      "digests differ"));
     if (verdict[1] != 0)
-        return fail(ctx, L2A_ESTATE, "sharded CEM: " + std::to_string(verdict[1]) + " returns of this step were contributed by no rank "
+        return fail(ctx, L2A_ESTATE, kind + ": " + std::to_string(verdict[1]) + " returns of this step were contributed by no rank "
                                      "(the collective did not reduce over every rank of the plan)");
     return verdict[0] == 0 ? L2A_OK : FLAGGED;
 }
 
 // Wait for the packed result; a launch flagged invalid (a tile-split partner that was not co-resident) repeats the whole step unsplit
-// with the same Philox offsets - the same bits - as get_cem_action_device's retry does (sharded: all ranks together).
-int cem_finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out) {
+// with the same Philox offsets - the same bits - as get_cem_action_device's and get_mppi_action's retry does (sharded: all ranks
+// together).  Only a step that got this far moves the controller on: the stream position, and MPPI's mean and reset marks.
+int plan_finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out) {
     l2a_ctx* ctx = c->ctx;
     if (!action_out) return fail(ctx, L2A_EINVAL, "l2a_controller_finish: null action_out");
     if (!c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_finish: no step is in flight (l2a_controller_begin)");
     set_in_flight(c, false);
-    cem_state* q = c->cem;
+    plan_state* q = c->plan;
     int result = c->result;
-    const auto relaunch = [c] { return cem_launch(c); };
-    const int rc = c->shard.on ? settle(c, &result, [c] { return cem_verdict_sharded(c); }, relaunch)
-                               : settle(c, &result, [c] { return cem_verdict(c); }, relaunch);
+    const auto relaunch = [c] { return plan_launch(c); };
+    const int rc = c->shard.on ? settle(c, &result, [c] { return plan_verdict_sharded(c); }, relaunch)
+                               : settle(c, &result, [c] { return plan_verdict(c); }, relaunch);
     if (rc != L2A_OK) return rc;
     const double t2 = l2a_now_us();
-    const int A = c->act_dim, W = A + 2;
+    const int A = c->act_dim, W = q->row_floats;
     for (int i = 0; i < c->m; ++i) {
-        const float* r = q->packed_host + (size_t)i * W;
+        const float* r = q->packed_host + (size_t)i * W;    // the action | the return | the index's bits | ...
         int idx = 0;
         std::memcpy(&idx, r + A + 1, sizeof(int));
         for (int k = 0; k < A; ++k) action_out[(size_t)i * A + k] = (double)r[k];
@@ -683,6 +868,10 @@ int cem_finish(l2a_controller* c, double* action_out, long long* index_out, floa
         if (return_out) return_out[i] = r[A];
     }
     q->iter_calls += (unsigned long long)q->iters;
+    if (c->mppi) {
+        c->mppi->cur = c->mppi->last;
+        c->mppi->fresh.assign((size_t)c->m, 0);
+    }
     record_stages(c, t2, l2a_now_us());
     return result;
 }
@@ -766,7 +955,7 @@ int draw_now(l2a_controller* c, hipStream_t stream, int* slot_out) {
 // First half of a step: everything that touches the generator (take / draw, re-arm), the staging and the launch.  Returns
 // L2A_OK (plan in flight), L2A_STEP_MISS (nothing consumed or launched) or a negative code.
 int begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
-    if (c->cem) return cem_begin(c, obs, c0, h0, c1, h1, stream);
+    if (c->plan) return plan_begin(c, obs, c0, h0, c1, h1, stream);
     l2a_ctx* ctx = c->ctx;
     if (ctx->cem_steps_in_flight > 0)
         return fail(ctx, L2A_ESTATE, "l2a_controller_begin: a CEM step of another controller is in flight on this context (it reads and "
@@ -831,7 +1020,7 @@ int verdict_sharded(l2a_controller* c) {
 // Second half: wait for the keys (a launch that lost its tile-split partner is repeated unsplit - same bits; the generator is not
 // touched again), decode, gather the winners' float64 first actions.
 int finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out) {
-    if (c->cem) return cem_finish(c, action_out, index_out, return_out);
+    if (c->plan) return plan_finish(c, action_out, index_out, return_out);
     l2a_ctx* ctx = c->ctx;
     if (!action_out) return fail(ctx, L2A_EINVAL, "l2a_controller_finish: null action_out");
     if (!c->in_flight) return fail(ctx, L2A_ESTATE, "l2a_controller_finish: no step is in flight (l2a_controller_begin)");
@@ -889,7 +1078,7 @@ int step(l2a_controller* c, const double* obs, const float* c0, const float* h0,
 
 extern "C" {
 
-// The 12 create entry points: each names itself, its model and its options; `create` does the rest.
+// The 14 create entry points: each names itself, its model and its options; `create` does the rest.
 int l2a_controller_create(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
                           const l2a_reward* reward, void* np_state_addr, int rng_threads, l2a_controller** out) {
     return create(step_cfg{"l2a_controller_create", model, nullptr, m, n, h, low, high, discount, reward, out}.parity(np_state_addr, rng_threads));
@@ -985,6 +1174,63 @@ int l2a_cem_controller_result(l2a_controller* c, float* mean_out, float* std_out
     return L2A_OK;
 }
 
+int l2a_mppi_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                      const l2a_reward* reward, int iters, float kappa, float beta, const double* sigma,
+                                      unsigned long long seed, l2a_controller** out) {
+    return create(step_cfg{"l2a_mppi_controller_create_device", model, nullptr, m, n, h, low, high, discount, reward, out}
+                      .mppi_plan(iters, kappa, beta, sigma, seed));
+}
+
+int l2a_mppi_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                              const l2a_reward* reward, int iters, float kappa, float beta, const double* sigma,
+                                              unsigned long long seed, int rank, int world, l2a_reduce_fn reduce, void* reduce_arg,
+                                              l2a_controller** out) {
+    return create(step_cfg{"l2a_mppi_controller_create_sharded_device", model, nullptr, m, n, h, low, high, discount, reward, out}
+                      .mppi_plan(iters, kappa, beta, sigma, seed).shard(rank, world, reduce, reduce_arg));
+}
+
+int l2a_mppi_controller_reset(l2a_controller* c, const unsigned char* dones) {
+    if (!c) return L2A_EINVAL;
+    if (!c->mppi) return fail(c->ctx, L2A_EINVAL, "l2a_mppi_controller_reset: not an MPPI controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_reset: a step is in flight (l2a_controller_finish)");
+    for (int i = 0; i < c->m; ++i)
+        if (!dones || dones[i]) c->mppi->fresh[i] = 1;
+    return L2A_OK;
+}
+
+int l2a_mppi_controller_reseed(l2a_controller* c, unsigned long long seed) {
+    if (!c) return L2A_EINVAL;
+    if (!c->mppi) return fail(c->ctx, L2A_EINVAL, "l2a_mppi_controller_reseed: not an MPPI controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_reseed: a step is in flight (l2a_controller_finish)");
+    c->device.seed = seed;
+    c->mppi->iter_calls = 0;
+    return L2A_OK;
+}
+
+int l2a_mppi_controller_result(l2a_controller* c, float* mean_out, float* ess_out, int* valid_out, float* returns_out) {
+    if (!c) return L2A_EINVAL;
+    if (!c->mppi) return fail(c->ctx, L2A_EINVAL, "l2a_mppi_controller_result: not an MPPI controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_result: a step is in flight (l2a_controller_finish)");
+    if (c->steps == 0) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_result: no step has finished yet");
+    mppi_state* q = c->mppi;
+    const int A = c->act_dim;
+    for (int i = 0; i < c->m; ++i) {
+        const float* r = q->packed_host + (size_t)i * q->row_floats;
+        if (ess_out) ess_out[i] = r[A + 2];
+        if (valid_out) std::memcpy(&valid_out[i], r + A + 3, sizeof(int));
+    }
+    if (!mean_out && !returns_out) return L2A_OK;
+    // ONE copy to page-locked memory on the step's stream - the three means and, when asked for, the returns behind them - and one wait
+    const size_t md = (size_t)c->m * q->D, nr = (size_t)q->iters * c->m * c->n;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    l2a_device_guard guard(c->ctx->device);
+    L2A_HIP(c->ctx, hipMemcpyAsync(q->result_host, q->mean[0], sizeof(float) * (3 * md + (returns_out ? nr : 0)), hipMemcpyDeviceToHost, stream));
+    L2A_HIP(c->ctx, hipStreamSynchronize(stream));
+    if (mean_out) std::memcpy(mean_out, q->result_host + (size_t)q->cur * md, sizeof(float) * md);
+    if (returns_out) std::memcpy(returns_out, q->result_host + 3 * md, sizeof(float) * nr);
+    return L2A_OK;
+}
+
 void l2a_controller_destroy(l2a_controller* c) {
     if (!c) return;
     if (c->ahead.chain) l2a_ahead_destroy(c->ahead.chain);    // joins the producer: no upload is in flight afterwards
@@ -993,6 +1239,7 @@ void l2a_controller_destroy(l2a_controller* c) {
     set_in_flight(c, false);
     release(c);
     delete c->cem;
+    delete c->mppi;
     delete c;
 }
 

@@ -35,7 +35,10 @@ the device from one controller step to the next, is moved on one step, sampled w
 return-weighted mean of the clipped candidates, ``get_mppi_action``; needs ``rng="device"``; ``mppi_kappa`` the weights'
 temperature ``exp(kappa (R - Rmax))``, ``mppi_sigma`` the noise scale per action dimension - ``None``: a quarter of the action
 range -, ``mppi_beta`` the noise filter ``n_t = beta u_t + (1 - beta) n_(t-1)``, ``mppi_iters`` refinements per step;
-``reset(dones)`` restarts the marked envs' plans from zero).
+``reset(dones)`` restarts the marked envs' plans from zero), ``native_mppi_step`` (off by default: the MPPI plan step through the C
+controller, ``l2a_mppi_controller_create_device`` - the only way to shard an MPPI plan over torch.distributed ranks:
+``l2a_mppi_controller_create_sharded_device``, one rank each - bit-identical to ``get_mppi_action``, ``policies/native_mppi_step.py``;
+reward programs, reward models and recurrent models keep the Python path).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -82,6 +85,7 @@ class MPCController(Policy, Serializable):
             mppi_sigma=None,
             mppi_beta=0.6,
             mppi_iters=1,
+            native_mppi_step=False,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -108,6 +112,7 @@ class MPCController(Policy, Serializable):
         self.mppi_sigma = mppi_sigma
         self.mppi_beta = float(mppi_beta)
         self.mppi_iters = int(mppi_iters)
+        self.native_mppi_step = bool(native_mppi_step)
         if self.use_mppi:
             if use_cem:
                 raise ValueError("use_mppi and use_cem are two planners: choose one")
@@ -137,6 +142,8 @@ class MPCController(Policy, Serializable):
         self._cstep_no = None       # request key the C controller was found ineligible for
         self._cemstep = None        # NativeCemStep (CEM l2a_controller, rng="device"): the whole CEM plan step in one C call
         self._cemstep_no = None     # key of a sharded CEM controller that could not be built (the collective's dry run failed)
+        self._mppistep = None       # NativeMppiStep (MPPI l2a_controller): the whole MPPI plan step in one C call
+        self._mppi_side = None      # which side plans (and holds the persistent mean): None until the first MPPI step, then "c" / "python"
         self._cem_first_chunk = 4   # horizon steps of the first chunk of a pipelined CEM rollout (0: equal chunks)
         self.last_plan = None       # diagnostics of the latest fused plan (returns, keys, ...)
 
@@ -1284,6 +1291,9 @@ class MPCController(Policy, Serializable):
         other than the plan's, starts all of them afresh.  Without ``use_mppi`` nothing happens."""
         if not self.use_mppi:
             return
+        st = self._mppistep
+        if st is not None and st.pid == os.getpid():        # the C controller holds the plan: the marks go to it
+            st.reset(None if dones is None or len(dones) != st.m else dones)
         fresh = self._bufs.get("mppi_fresh")
         if dones is None or fresh is None or len(fresh) != len(dones):
             self._bufs["mppi_fresh"] = None
@@ -1294,6 +1304,68 @@ class MPCController(Policy, Serializable):
         """Hook for tests: return the iteration's standard normals ``[n, m, D]`` as a CUDA fp32 tensor to inject them; ``None``
         (the default) lets ``l2a_mppi_sample`` draw them on the device (Philox4x32-10 + Box-Muller, CEM's stream)."""
         return None
+
+    mppi_fetch_returns = True       # `_native_mppi_step`: copy the last iteration's returns [m, n] into `last_plan` on every step
+
+    def _native_mppi_step(self, observations):
+        """The MPPI plan step through the C controller (``l2a_mppi_controller_create_device``; at ``world > 1`` this rank's
+        ``l2a_mppi_controller_create_sharded_device``, whose per-iteration gather of the returns is the int64 MAX all-reduce of
+        ``m * n + 3`` words through ``_reduce_payload`` - or the library's communicator, ``L2A_NATIVE_COMM=1``): the Philox offsets,
+        the shift rule and the bits of ``get_mppi_action``.  The plan mean persists on the side that planned, so the choice is made
+        on the controller's first MPPI step and kept: None - the Python loop plans, now and later - for a reward program, a reward
+        model, a recurrent model, a test hook that replaced the normals or the launch path, a library without the entry points, a
+        backend that cannot reduce the words, a forked child.  ``reset(dones)`` is forwarded to the C controller, and a changed
+        ``torch.initial_seed()`` value reseeds it (the stream restarts, the mean is kept - as the Python loop does).
+        ``last_plan`` gets ``get_mppi_action``'s keys; the step itself reads back ``m * (act_dim + 4)`` floats only, the mean and
+        the returns are copies of their own afterwards: ``returns`` is fetched eagerly by default, and the class or instance
+        attribute ``mppi_fetch_returns = False`` leaves the key out and the ``m * n`` floats on the device
+        (``self._mppistep.result()`` still returns every iteration's table on request)."""
+        if self._mppi_side == "python":
+            return None
+        st = self._mppistep
+        if st is not None and st.pid != os.getpid():
+            self._mppistep, self._mppi_side = None, "python"        # (a forked child: the parent's HIP objects did not come along)
+            return None
+        rank, world = self._dist()
+        n, m, h = self.n_candidates, len(observations), self.horizon
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        native = self.dynamics_model.planner_model()
+        sigma = self._mppi_sigma_vector()
+        key = (id(native), native.handle.value, m, n, h, float(self.discount), int(self.mppi_iters), self.mppi_kappa, self.mppi_beta,
+               sigma.tobytes(), rank, world)
+        if st is not None and st.key != key:        # another plan (a different number of envs, ...): it starts afresh, as the Python loop's
+            st.close()
+            st = self._mppistep = None
+        if st is None:
+            if (self.use_reward_model or self._program() or hasattr(native, "units") or not self._native_step_stock()
+                    or getattr(self._mppi_normal_device, "__func__", None) is not MPCController._mppi_normal_device
+                    or not hasattr(native.lib, "l2a_mppi_controller_create_sharded_device")
+                    or m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16):
+                self._mppi_side = "python"
+                return None
+            shard = None
+            if world > 1:
+                shard = self._native_shard(native, rank, world, m * n + 3)
+                if shard is None:
+                    self._mppi_side = "python"
+                    return None
+            from .native_mppi_step import NativeMppiStep
+            st = NativeMppiStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
+                                self.mppi_iters, self.mppi_kappa, self.mppi_beta, sigma, seed, shard=shard)
+            st.key, st.seed = key, seed
+            self._mppistep, self._mppi_side = st, "c"
+        if st.seed != seed:
+            st.reseed(seed)
+            st.seed = seed
+        self._check_blocks(m)
+        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        mean, ess, valid, rets = st.result(with_returns=bool(self.mppi_fetch_returns))
+        self.last_plan = dict(best_index=st.idx.copy(), best_return=st.ret.copy(), mppi_mean=mean, mppi_ess=ess, mppi_valid=valid)
+        if rets is not None:
+            self.last_plan["returns"] = rets[-1]
+        if world > 1:
+            self.last_plan["shard"] = self._shard_range(n, rank, world)
+        return st.act.copy()
 
     def get_mppi_action(self, observations, retry=False):
         """One MPPI plan step on the GPU (``csrc/l2a_mppi.hip``; semantics in ``include/l2a.h``).  The plan mean ``[m, h * act_dim]``
@@ -1312,10 +1384,15 @@ class MPCController(Policy, Serializable):
         if self.rng != "device":
             raise _lib.L2AError("MPPI planning draws its normals on the device (rng='device'); NumPy normals are not supported")
         if self.native_cem_step:
-            raise _lib.L2AError("an MPPI step as one C controller call is not built: leave native_cem_step off with use_mppi")
+            raise _lib.L2AError("an MPPI step as one C controller call is native_mppi_step=True: leave native_cem_step off with use_mppi")
+        if self.native_mppi_step and not retry:
+            out = self._native_mppi_step(observations)
+            if out is not None:
+                return out
         if self._dist()[1] > 1:
-            raise _lib.L2AError("MPPI planning does not shard its candidates over torch.distributed ranks: pass shard_candidates=False "
-                                "(every rank then plans on its own)")
+            raise _lib.L2AError("MPPI planning does not shard its candidates over torch.distributed ranks in this Python loop: pass "
+                                "shard_candidates=False (every rank then plans on its own), or native_mppi_step=True (the C controller "
+                                "shards a plan with a closed-form reward spec and an MLP model)")
         n, m, h = self.n_candidates, len(observations), self.horizon
         act_dim = self.action_space.shape[0]
         D = h * act_dim

@@ -58,6 +58,7 @@ class RNNMPCController(MPCController):
             mppi_sigma=None,
             mppi_beta=0.6,
             mppi_iters=1,
+            native_mppi_step=False,     # (accepted as `MPCController`'s; the recurrent planner's MPPI step always takes the Python path)
             native_cem_step=False,      # (tests/test_rnn_cem_controller.py pins this one as the last parameter)
     ):
         Serializable.quick_init(self, locals())
@@ -71,7 +72,8 @@ class RNNMPCController(MPCController):
                                percent_elites=percent_elites, use_reward_model=use_reward_model, alpha=0.0,
                                rng=rng, cem_mode=cem_mode, shard_candidates=shard_candidates,
                                pipeline_chunks=pipeline_chunks, native_cem_step=native_cem_step, use_mppi=use_mppi,
-                               mppi_kappa=mppi_kappa, mppi_sigma=mppi_sigma, mppi_beta=mppi_beta, mppi_iters=mppi_iters)
+                               mppi_kappa=mppi_kappa, mppi_sigma=mppi_sigma, mppi_beta=mppi_beta, mppi_iters=mppi_iters,
+                               native_mppi_step=native_mppi_step)
         self._hidden_state = None
 
     # ------------------------------------------------------------------ hidden state: host view + device copy
