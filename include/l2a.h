@@ -386,6 +386,56 @@ int l2a_rollout_traj(l2a_model* model, const float* obs0, const float* actions, 
 int l2a_mlp_traj_geometry(int obs_dim, int act_dim, int n_hidden, int hidden, int mode, int n_sets, int m, int n, int h,
                           int micro_policy, int num_cu, int* out);
 
+/* ---- particle plans: trajectory sampling over the members of a mean ensemble -----------------------
+ * PETS-style TS-infinity (Chua et al. 2018); not in the reference, the semantics are build-defined.  Every member of an
+ * L2A_MODE_MEAN model of E = n_sets >= 2 weight sets rolls every candidate out as a trajectory of its own, and a candidate is
+ * scored by the mean of its E returns, less `lambda` times their standard deviation (lambda > 0 prefers plans the members
+ * agree on, lambda < 0 seeks disagreement, 0 is the plain mean).
+ *
+ * l2a_particle_score: the reduction alone (csrc/l2a_particles.hip).
+ *   member_returns  device fp32 [m, E, n]     R_e of candidate j of env i at (i * E + e) * n + j;  E >= 1
+ *   score_out       device fp32 [m, n] or NULL
+ *   spread_out      device fp32 [m, n] or NULL  the standard deviation `std` below
+ *   best_key        device u64 [m] or NULL    zeroed on `stream` in front of the launch; keys as l2a_plan_rs packs them over the
+ *                                             SCORE: index cand_offset + j, lowest index wins ties, NaN sorts highest
+ * Arithmetic (fixed, so that a host can restate it bit for bit - tests/particle_reference.py): fp32, round to nearest, nothing
+ * contracted, e ascending.  s = R_0, s = s + R_e; mean = s / (float)E; v = 0, d = R_e - mean, v = v + d * d as a separate
+ * multiply and add; std = sqrtf(v / (float)E); score = mean - lambda * std as a separate multiply and subtract - and with
+ * lambda == 0 the score is `mean` itself (a +inf mean stays +inf where 0 * NaN would not).  Non-finite member returns follow IEEE
+ * through this formula: one NaN member makes the candidate's score NaN; +inf and -inf members together likewise; a lone +inf
+ * gives mean +inf and std NaN.  The planners' rules then apply unchanged: a NaN score is the arg-max (l2a_cem_pick, the keys),
+ * l2a_mppi_update weighs NaN and -inf with 0.  No float atomics: the same inputs give the same bits on every run and grid.
+ * L2A_EINVAL (nothing launched): a NULL member_returns, all three outputs NULL, m / E / n < 1, a non-finite lambda,
+ * m * E * n > 2^30 - 1, a bad cand_offset.
+ *
+ * l2a_plan_rs_particles: the plan step.  obs0, actions, m, n, h, discount, reward, cand_offset as l2a_plan_rs.  An expansion
+ * launch copies the inputs into the model's own buffer (grown on demand, which synchronises `stream`; freed with the model) as
+ * m per-block requests of E blocks - particle row (i * E + e) * n + j - then every env's request runs as its own launch of
+ * the rollout kernels on the model's E weight sets (block e <-> set e, returns only), then l2a_particle_score: m + 2 launches
+ * on `stream` where every request is one launch (a request the launcher cuts in two - double rounds and their rest - is two),
+ * no host synchronisation.  score_out [m, n], spread_out [m, n], best_key [m] as above (score_out or best_key is
+ * required); member_returns_out [m, E, n] or NULL (the model's buffer then).  The member returns are bit-equal to l2a_plan_rs
+ * on a per-block model of the same E sets fed the expanded inputs.  The launch status word keeps its meaning: a flagged
+ * tile-split launch anywhere flags the call (l2a_launch_status).
+ * l2a_plan_rs_particles_program / _reward_model: the same with every request's trajectory rollout and scoring launch of
+ * l2a_plan_rs_program / l2a_plan_rs_reward_model in place of the fused rollout: 2 m + 2 launches where the trajectory rollout is
+ * its single launch, m (h + 1) + 2 on the carry chain.
+ * L2A_EINVAL (nothing launched, no output touched): a model that is not L2A_MODE_MEAN with n_sets >= 2, a non-finite lambda,
+ * m / n / h < 1, m * E * n > 2^30 - 1, a bad cand_offset, a NULL pointer, what the stem entry refuses of its reward, an action
+ * tensor beyond one expansion launch (2^32 - 257 words of 16 bytes, or of 4 where n * act_dim is no multiple of four).  A refused
+ * call does not grow the model's buffer either.          */
+int l2a_particle_score(l2a_ctx* ctx, const float* member_returns, int m, int E, int n, float lambda, int cand_offset,
+                       float* score_out, float* spread_out, unsigned long long* best_key, void* stream);
+int l2a_plan_rs_particles(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                          const l2a_reward* reward, float lambda, int cand_offset, float* score_out, float* spread_out,
+                          float* member_returns_out, unsigned long long* best_key, void* stream);
+int l2a_plan_rs_particles_program(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                                  const l2a_reward_program* program, float lambda, int cand_offset, float* score_out,
+                                  float* spread_out, float* member_returns_out, unsigned long long* best_key, void* stream);
+int l2a_plan_rs_particles_reward_model(l2a_model* model, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
+                                       int h, double discount, float lambda, int cand_offset, float* score_out, float* spread_out,
+                                       float* member_returns_out, unsigned long long* best_key, void* stream);
+
 /* One-step batched prediction: MLPDynamicsModel.predict / MetaMLPDynamicsModel.predict
  * (mlp_dynamics.py:204-222, meta_mlp_dynamics.py:276-294).
  *   obs device fp32 [R, obs_dim], act device fp32 [R, act_dim] -> next_obs device fp32 [R, obs_dim]

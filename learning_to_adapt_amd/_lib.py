@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry", "l2a_lstm_plan_geometry",
     "l2a_rollout_traj", "l2a_mlp_traj_geometry",
+    "l2a_particle_score", "l2a_plan_rs_particles", "l2a_plan_rs_particles_program", "l2a_plan_rs_particles_reward_model",
     "l2a_controller_create", "l2a_controller_create_sharded", "l2a_controller_create_sharded_device", "l2a_lstm_controller_create", "l2a_controller_create_device", "l2a_lstm_controller_create_device",
     "l2a_lstm_controller_create_sharded", "l2a_lstm_controller_create_sharded_device",
     "l2a_controller_destroy", "l2a_controller_step", "l2a_controller_begin", "l2a_lstm_controller_begin", "l2a_controller_finish",
@@ -365,6 +366,16 @@ def load():
         lib.l2a_rollout_traj.restype = i32
         lib.l2a_mlp_traj_geometry.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, c.POINTER(i32)]
         lib.l2a_mlp_traj_geometry.restype = i32
+    if hasattr(lib, "l2a_particle_score"):              # (absent from older variant libraries selected with L2A_LIB_PATH)
+        tail = [f32, i32, vp, vp, vp, vp, vp]           # lambda, cand_offset, score_out, spread_out, member_returns_out, best_key, stream
+        lib.l2a_particle_score.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp]
+        lib.l2a_particle_score.restype = i32
+        lib.l2a_plan_rs_particles.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardSpec)] + tail
+        lib.l2a_plan_rs_particles.restype = i32
+        lib.l2a_plan_rs_particles_program.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram)] + tail
+        lib.l2a_plan_rs_particles_program.restype = i32
+        lib.l2a_plan_rs_particles_reward_model.argtypes = [vp, vp, vp, vp, i32, i32, i32, c.c_double] + tail
+        lib.l2a_plan_rs_particles_reward_model.restype = i32
     if os.environ.get("L2A_LIB_PATH") and not hasattr(lib, "l2a_controller_step"):
         pass                                               # developer A/B against a library of an earlier round
     else:

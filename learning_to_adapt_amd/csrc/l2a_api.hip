@@ -63,6 +63,8 @@ struct l2a_model : l2a_mlp_shape {
     long long adapt_scratch_floats = 0;
     float* prog_buf = nullptr;                    // l2a_plan_rs_program: [returns of the carry launches (rows) | trajectory (h x rows x obs_dim)]
     long long prog_buf_floats = 0;
+    float* part_buf = nullptr;                    // l2a_plan_rs_particles: [obs_x (m E obs_dim) | act_x (h m E n act_dim) | member returns (m E n)]
+    long long part_buf_floats = 0;
     // l2a_model_adapt_sgd_host: two staging slots (host-mapped, read by the kernels directly)
     struct adapt_slot {
         float* stage_host = nullptr;
@@ -889,6 +891,7 @@ void l2a_model_destroy(l2a_model* md) {
     if (md->xb.buf) (void)hipFree(md->xb.buf);
     if (md->adapt_scratch) (void)hipFree(md->adapt_scratch);
     if (md->prog_buf) (void)hipFree(md->prog_buf);
+    if (md->part_buf) (void)hipFree(md->part_buf);
     for (auto& sl : md->aslot) {
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.stage_host) (void)hipHostFree(sl.stage_host);
@@ -1425,10 +1428,12 @@ int l2a_plan_finish(l2a_ctx* ctx, l2a_mail_pending* pending, unsigned long long*
     return rc;
 }
 
-int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, const float* actions, int m, int n,
-                      int h_chunk, int t0, double discount, const l2a_reward* reward, int cand_offset,
-                      const float* returns_in, float* returns_out, float* state_out, unsigned long long* best_key,
-                      void* stream_v) {
+// l2a_plan_rs_chunk with the request's mode given (`mode`: the model's own, or L2A_MODE_PER_BLOCK for the particle plans of a
+// mean ensemble - launch_rollout takes the mode from the request).
+static int plan_rs_chunk_as(l2a_model* md, int mode, const float* state, int state_per_row, const float* actions, int m, int n,
+                            int h_chunk, int t0, double discount, const l2a_reward* reward, int cand_offset,
+                            const float* returns_in, float* returns_out, float* state_out, unsigned long long* best_key,
+                            void* stream_v) {
     if (!md) return L2A_EINVAL;
     l2a_ctx* ctx = md->ctx;
     if (!state || !actions || !reward) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_chunk: null state/actions/reward");
@@ -1443,6 +1448,7 @@ int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, cons
     if (best_key) L2A_HIP(ctx, hipMemsetAsync(best_key, 0, sizeof(unsigned long long) * (size_t)m, stream));
     L2AKParams p;
     fill_model_params(md, p);
+    p.mode = mode;
     p.obs0 = state; p.obs_per_row = state_per_row ? 1 : 0;
     p.actions = actions; p.returns_out = returns_out; p.best_key = best_key; p.state_out = state_out;
     p.ret_in = (t0 > 0) ? returns_in : nullptr;
@@ -1453,10 +1459,19 @@ int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, cons
     return launch_rollout(md, p, stream_v);
 }
 
+int l2a_plan_rs_chunk(l2a_model* md, const float* state, int state_per_row, const float* actions, int m, int n,
+                      int h_chunk, int t0, double discount, const l2a_reward* reward, int cand_offset,
+                      const float* returns_in, float* returns_out, float* state_out, unsigned long long* best_key,
+                      void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    return plan_rs_chunk_as(md, md->mode, state, state_per_row, actions, m, n, h_chunk, t0, discount, reward, cand_offset, returns_in,
+                            returns_out, state_out, best_key, stream_v);
+}
+
 // The carry chain of the plans that are scored by a separate launch: h one-step launches of the rollout kernels - all-zero
 // fused reward, state_out = traj[t], the trajectory slice itself being the hand-off buffer.  *traj: traj_out, or the model's
 // own buffer (grown on demand, which synchronises the stream).  Stream-ordered throughout.
-static int plan_carry_chain(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+static int plan_carry_chain(l2a_model* md, int mode, const float* obs0, const float* actions, int m, int n, int h, double discount,
                             int cand_offset, float* traj_out, void* stream_v, float** traj) {
     l2a_ctx* ctx = md->ctx;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
@@ -1474,8 +1489,8 @@ static int plan_carry_chain(l2a_model* md, const float* obs0, const float* actio
     std::memset(&zero, 0, sizeof(zero));
     const long long step_state = rows * md->obs_dim, step_act = rows * md->act_dim;
     for (int t = 0; t < h; ++t) {
-        const int rc = l2a_plan_rs_chunk(md, t == 0 ? obs0 : *traj + (t - 1) * step_state, t > 0, actions + t * step_act, m, n, 1, 0,
-                                         discount, &zero, cand_offset, nullptr, carry_returns, *traj + t * step_state, nullptr, stream_v);
+        const int rc = plan_rs_chunk_as(md, mode, t == 0 ? obs0 : *traj + (t - 1) * step_state, t > 0, actions + t * step_act, m, n, 1, 0,
+                                        discount, &zero, cand_offset, nullptr, carry_returns, *traj + t * step_state, nullptr, stream_v);
         if (rc != L2A_OK) return rc;
     }
     return L2A_OK;
@@ -1484,14 +1499,14 @@ static int plan_carry_chain(l2a_model* md, const float* obs0, const float* actio
 // The predicted trajectory [h, m n, obs_dim] of a plan -> *traj (traj_out, or the model's own buffer behind the carry returns;
 // arguments validated by the callers).  One launch of the trajectory-writing micro-tile instance where plan_traj_rollout says so,
 // else plan_carry_chain.  Stream-ordered; the same bits on both paths.
-static int rollout_traj_launch(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+static int rollout_traj_launch(l2a_model* md, int mode, const float* obs0, const float* actions, int m, int n, int h, double discount,
                                int cand_offset, float* traj_out, void* stream_v, float** traj) {
     l2a_ctx* ctx = md->ctx;
-    const l2a_traj_plan tp = plan_traj_rollout(*md, rollout_policy(ctx), md->mode, m, n);
-    if (!tp.single) return plan_carry_chain(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, traj);
+    const l2a_traj_plan tp = plan_traj_rollout(*md, rollout_policy(ctx), mode, m, n);
+    if (!tp.single) return plan_carry_chain(md, mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, traj);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
-    const int sets_needed = (md->mode == L2A_MODE_PER_BLOCK) ? (m < md->n_sets ? m : md->n_sets) : md->n_sets;
+    const int sets_needed = (mode == L2A_MODE_PER_BLOCK) ? (m < md->n_sets ? m : md->n_sets) : md->n_sets;
     for (int e = 0; e < sets_needed; ++e) {
         if (!md->weights_set[e]) return fail(ctx, L2A_ESTATE, "weight set " + std::to_string(e) + " was never set");
         if (!md->norm_set[e]) return fail(ctx, L2A_ESTATE, "normalisation of set " + std::to_string(e) + " was never set");
@@ -1506,6 +1521,7 @@ static int rollout_traj_launch(l2a_model* md, const float* obs0, const float* ac
     *traj = traj_out ? traj_out : md->prog_buf + rows;
     L2AKParams p;
     fill_model_params(md, p);
+    p.mode = mode;
     p.obs0 = obs0; p.obs_per_row = 0; p.actions = actions;
     p.state_out = *traj;                                // (this instance: the whole trajectory)
     p.disc0 = 1.0; p.discount = 1.0;
@@ -1530,7 +1546,7 @@ int l2a_rollout_traj(l2a_model* md, const float* obs0, const float* actions, int
     if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
         return fail(ctx, L2A_EINVAL, "l2a_rollout_traj: too many candidates");
     float* traj = nullptr;
-    return rollout_traj_launch(md, obs0, actions, m, n, h, 1.0, cand_offset, traj_out, stream_v, &traj);
+    return rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, 1.0, cand_offset, traj_out, stream_v, &traj);
 }
 
 // The plan step of an env with a reward program: the rollout and one scoring launch (l2a_score.hip).
@@ -1547,7 +1563,7 @@ int l2a_plan_rs_program(l2a_model* md, const float* obs0, const float* actions, 
     if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_program: too many candidates");
     float* traj = nullptr;
-    rc = rollout_traj_launch(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
     if (rc != L2A_OK) return rc;
     return l2a_score_trajectory(ctx, obs0, traj, actions, m, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset,
                                 returns_out, best_key, stream_v);
@@ -1573,9 +1589,120 @@ int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* o
     if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
         return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model: too many candidates");
     float* traj = nullptr;
-    const int rc = rollout_traj_launch(md, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    const int rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
     if (rc != L2A_OK) return rc;
     return l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, returns_out, best_key, stream_v);
+}
+
+// ---- particle plans of a mean ensemble (l2a_particles.hip) ------------------------------------------------------------------
+// The one routine behind the three entries: expand, then per env ONE per-block request of E blocks on the model's own weight
+// sets - the fused rollout (`reward`), or the trajectory rollout and a scoring launch (`program` / `rm`) - with returns_out
+// only, then the scorer.  Exactly one of reward / program / rm is given.  Every check - the expansion launch's size limits
+// included - is made before the model's buffer is grown and before the first launch: a refused call synchronises nothing, frees
+// nothing and writes nothing.
+static int plan_particles(l2a_model* md, const char* who_c, const l2a_reward* reward, const l2a_reward_program* program,
+                          l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                          float lambda, int cand_offset, float* score_out, float* spread_out, float* member_returns_out,
+                          unsigned long long* best_key, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    const std::string who(who_c);
+    const int E = md->n_sets;
+    if (md->mode != L2A_MODE_MEAN || E < 2)
+        return fail(ctx, L2A_EINVAL, who + ": particle plans need a mean ensemble (L2A_MODE_MEAN) of at least 2 weight sets");
+    if (!std::isfinite(lambda)) return fail(ctx, L2A_EINVAL, who + ": lambda must be finite");
+    if (!obs0 || !actions) return fail(ctx, L2A_EINVAL, who + ": null obs0/actions");
+    if (!best_key && !score_out) return fail(ctx, L2A_EINVAL, who + ": nothing to write (best_key and score_out are null)");
+    if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, who + ": m, n and h must be >= 1");
+    if ((long long)m * E * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, who + ": too many candidates (m * E * n particles)");
+    if (reward) {
+        const int arc = check_candidates_and_reward(md, who_c, m * E, n, cand_offset, reward);
+        if (arc != L2A_OK) return arc;
+    } else if (program) {
+        const int rc = l2a_reward_program_check(program, md->obs_dim, md->act_dim);
+        if (rc != L2A_OK) return fail(ctx, rc, l2a_last_error(nullptr));
+    } else if (rm) {
+        l2a_ctx* rm_ctx = nullptr;
+        int rm_obs = 0, rm_act = 0;
+        l2a_reward_model_facts(rm, &rm_ctx, &rm_obs, &rm_act);
+        if (rm_ctx != ctx) return fail(ctx, L2A_EINVAL, who + ": the reward model lives on another context");
+        if (rm_obs != md->obs_dim || rm_act != md->act_dim)
+            return fail(ctx, L2A_EINVAL, who + ": the reward model and the dynamics model disagree on obs_dim / act_dim");
+    } else {
+        return fail(ctx, L2A_EINVAL, who + ": null reward");
+    }
+    for (int e = 0; e < E; ++e) {
+        if (!md->weights_set[e]) return fail(ctx, L2A_ESTATE, "weight set " + std::to_string(e) + " was never set");
+        if (!md->norm_set[e]) return fail(ctx, L2A_ESTATE, "normalisation of set " + std::to_string(e) + " was never set");
+    }
+    int rc = l2a_particle_expand_check(ctx, actions, m, E, n, h, md->obs_dim, md->act_dim);
+    if (rc != L2A_OK) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    // the expanded inputs and, unless the caller keeps them, the member returns: the model's own buffer, every part 16-byte aligned
+    auto round4 = [](long long f) { return (f + 3) / 4 * 4; };
+    const long long env_obs = (long long)E * md->obs_dim, env_act = (long long)h * E * n * md->act_dim, env_ret = (long long)E * n;
+    const long long obs_floats = round4(m * env_obs), act_floats = round4(m * env_act);
+    const long long need = obs_floats + act_floats + (member_returns_out ? 0 : m * env_ret);
+    if (need > md->part_buf_floats) {
+        if (md->part_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->part_buf)); md->part_buf = nullptr; md->part_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->part_buf), (size_t)need * sizeof(float)));
+        md->part_buf_floats = need;
+    }
+    float* const obs_x = md->part_buf;
+    float* const act_x = md->part_buf + obs_floats;
+    float* const member = member_returns_out ? member_returns_out : md->part_buf + obs_floats + act_floats;
+    rc = l2a_particle_expand(ctx, obs0, actions, m, E, n, h, md->obs_dim, md->act_dim, obs_x, act_x, stream);
+    if (rc != L2A_OK) return rc;
+    for (int i = 0; i < m; ++i) {
+        const float* ox = obs_x + i * env_obs;
+        const float* ax = act_x + i * env_act;
+        float* mr = member + i * env_ret;
+        if (reward) {
+            L2AKParams p;
+            fill_model_params(md, p);
+            p.mode = L2A_MODE_PER_BLOCK;
+            p.obs0 = ox; p.actions = ax; p.returns_out = mr; p.best_key = nullptr;
+            p.state_out = nullptr; p.obs_per_row = 0;
+            p.ret_in = nullptr; p.disc0 = 1.0;
+            p.m = E; p.n = n; p.h = h; p.cand_offset = cand_offset; p.discount = discount; p.rw = *reward;
+            rc = launch_rollout(md, p, stream_v);
+        } else {
+            float* traj = nullptr;
+            rc = rollout_traj_launch(md, L2A_MODE_PER_BLOCK, ox, ax, E, n, h, discount, cand_offset, nullptr, stream_v, &traj);
+            if (rc != L2A_OK) return rc;
+            rc = program ? l2a_score_trajectory(ctx, ox, traj, ax, E, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset,
+                                                mr, nullptr, stream_v)
+                         : l2a_score_trajectory_model(rm, ox, traj, ax, E, n, h, discount, cand_offset, mr, nullptr, stream_v);
+        }
+        if (rc != L2A_OK) return rc;
+    }
+    return l2a_particle_score(ctx, member, m, E, n, lambda, cand_offset, score_out, spread_out, best_key, stream_v);
+}
+
+int l2a_plan_rs_particles(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                          const l2a_reward* reward, float lambda, int cand_offset, float* score_out, float* spread_out,
+                          float* member_returns_out, unsigned long long* best_key, void* stream_v) {
+    if (md && !reward) return fail(md->ctx, L2A_EINVAL, "l2a_plan_rs_particles: null reward");
+    return plan_particles(md, "l2a_plan_rs_particles", reward, nullptr, nullptr, obs0, actions, m, n, h, discount, lambda, cand_offset,
+                          score_out, spread_out, member_returns_out, best_key, stream_v);
+}
+
+int l2a_plan_rs_particles_program(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                                  const l2a_reward_program* program, float lambda, int cand_offset, float* score_out,
+                                  float* spread_out, float* member_returns_out, unsigned long long* best_key, void* stream_v) {
+    if (md && !program) return fail(md->ctx, L2A_EINVAL, "l2a_plan_rs_particles_program: null program");
+    return plan_particles(md, "l2a_plan_rs_particles_program", nullptr, program, nullptr, obs0, actions, m, n, h, discount, lambda,
+                          cand_offset, score_out, spread_out, member_returns_out, best_key, stream_v);
+}
+
+int l2a_plan_rs_particles_reward_model(l2a_model* md, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
+                                       int h, double discount, float lambda, int cand_offset, float* score_out, float* spread_out,
+                                       float* member_returns_out, unsigned long long* best_key, void* stream_v) {
+    if (md && !rm) return fail(md->ctx, L2A_EINVAL, "l2a_plan_rs_particles_reward_model: null reward model");
+    return plan_particles(md, "l2a_plan_rs_particles_reward_model", nullptr, nullptr, rm, obs0, actions, m, n, h, discount, lambda,
+                          cand_offset, score_out, spread_out, member_returns_out, best_key, stream_v);
 }
 
 int l2a_predict(l2a_model* md, const float* obs, const float* act, int rows, int n_blocks,

@@ -181,6 +181,14 @@ extern "C" L2A_HIDDEN int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, 
 extern "C" L2A_HIDDEN void l2a_model_facts(const l2a_model* md, l2a_ctx** ctx, int* obs_dim, int* act_dim);
 extern "C" L2A_HIDDEN void l2a_lstm_facts(const l2a_lstm* md, l2a_ctx** ctx, int* obs_dim, int* act_dim, int* units);
 extern "C" L2A_HIDDEN void l2a_reward_model_facts(const l2a_reward_model* rm, l2a_ctx** ctx, int* obs_dim, int* act_dim);
+// The expansion launch of a particle plan (l2a_particles.hip; arguments validated by the caller, l2a_api.hip): obs0 [m, O] and
+// actions [h, m n, A] -> obs_x [m, E, O] and act_x [m, h, E n, A], each env's per-block request contiguous.
+// l2a_particle_expand_check: host only - the launch's own size refusals (L2A_EINVAL) for a destination in the model's aligned buffer,
+// so that the caller can make them before it grows that buffer.
+extern "C" L2A_HIDDEN int l2a_particle_expand_check(l2a_ctx* ctx, const float* actions, int m, int E, int n, int h, int obs_dim,
+                                                    int act_dim);
+extern "C" L2A_HIDDEN int l2a_particle_expand(l2a_ctx* ctx, const float* obs0, const float* actions, int m, int E, int n, int h,
+                                              int obs_dim, int act_dim, float* obs_x, float* act_x, hipStream_t stream);
 inline double l2a_now_us() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);

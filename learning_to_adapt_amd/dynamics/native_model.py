@@ -279,6 +279,51 @@ class NativeModel(object):
                                                _ptr(traj_out), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_plan_rs_reward_model")
 
+    def plan_rs_particles(self, obs0, actions, m, n, h, discount, reward, risk_coef=0.0, cand_offset=0, score_out=None,
+                          spread_out=None, member_returns_out=None, best_key=None):
+        """Plan step over the ensemble's particles (``l2a_plan_rs_particles`` and its two siblings): every member of this mean
+        ensemble rolls every candidate out on its own, ``score_out [m, n]`` = mean of the ``n_sets`` member returns less
+        ``risk_coef`` times their standard deviation (``spread_out [m, n]``); ``member_returns_out [m, n_sets, n]``.  ``reward``: a
+        ``RewardSpec`` (the fused rollout), a ``RewardProgram`` or a ``NativeRewardModel`` (trajectory rollout + scoring launch).
+        The other arguments as ``plan_rs``; ``best_key`` holds the arg-max of the score."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        for t, count in ((score_out, m * n), (spread_out, m * n), (member_returns_out, m * self.n_sets * n)):
+            if t is not None:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == count
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if not hasattr(self.lib, "l2a_plan_rs_particles"):
+            raise _lib.L2AError("this libl2a_hip.so has no particle plans (l2a_plan_rs_particles): rebuild it")
+        tail = (ctypes.c_float(risk_coef), int(cand_offset), _ptr(score_out), _ptr(spread_out), _ptr(member_returns_out),
+                _ptr(best_key), _stream_ptr(self.device))
+        head = (self.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h), float(discount))
+        if isinstance(reward, NativeRewardModel):
+            self.reward_model_plans += 1
+            rc = self.lib.l2a_plan_rs_particles_reward_model(self.handle, reward.handle, *(head[1:] + tail))
+            what = "l2a_plan_rs_particles_reward_model"
+        elif isinstance(reward, RewardProgram):
+            self.program_plans += 1
+            rc = self.lib.l2a_plan_rs_particles_program(*(head + (ctypes.byref(reward),) + tail))
+            what = "l2a_plan_rs_particles_program"
+        else:
+            assert isinstance(reward, RewardSpec)
+            rc = self.lib.l2a_plan_rs_particles(*(head + (ctypes.byref(reward),) + tail))
+            what = "l2a_plan_rs_particles"
+        self.particle_plans = getattr(self, "particle_plans", 0) + 1
+        self.ctx.check(rc, what)
+
+    def particle_score(self, member_returns, m, n_members, n, risk_coef=0.0, cand_offset=0, score_out=None, spread_out=None,
+                       best_key=None):
+        """The particle scorer alone (``l2a_particle_score``) on fp32 CUDA ``member_returns [m, n_members, n]``."""
+        assert member_returns.is_cuda and member_returns.dtype == torch.float32 and member_returns.is_contiguous()
+        assert member_returns.numel() == m * n_members * n
+        rc = self.lib.l2a_particle_score(self.ctx.handle, _ptr(member_returns), int(m), int(n_members), int(n),
+                                         ctypes.c_float(risk_coef), int(cand_offset), _ptr(score_out), _ptr(spread_out),
+                                         _ptr(best_key), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_particle_score")
+
     def plan_rs_sync(self, obs_host, actions, m, n, h, discount, reward, cand_offset=0, returns_out=None):
         """Blocking plan step (``l2a_plan_rs_sync``): ``obs_host`` is a HOST array ``[m, obs_dim]``; returns the
         arg-max keys as a NumPy uint64 array ``[m]``, or ``None`` when the launch was flagged invalid (tile-split

@@ -38,7 +38,13 @@ range -, ``mppi_beta`` the noise filter ``n_t = beta u_t + (1 - beta) n_(t-1)``,
 ``reset(dones)`` restarts the marked envs' plans from zero), ``native_mppi_step`` (off by default: the MPPI plan step through the C
 controller, ``l2a_mppi_controller_create_device`` - the only way to shard an MPPI plan over torch.distributed ranks:
 ``l2a_mppi_controller_create_sharded_device``, one rank each - bit-identical to ``get_mppi_action``, ``policies/native_mppi_step.py``;
-reward programs, reward models and recurrent models keep the Python path).
+reward programs, reward models and recurrent models keep the Python path),
+``ensemble_planning`` (``"mean"``, the default: the members of an ``MLPDynamicsModel(ensemble_size=E)`` share one state, their
+deltas averaged at every horizon step; ``"particles"``: PETS-style trajectory sampling - every member rolls every candidate out as a
+trajectory of its own and a candidate's score is the mean of its E returns less ``risk_coef`` times their standard deviation,
+``l2a_plan_rs_particles``; random shooting, CEM and MPPI all plan on that score, ``particle_diagnostics()`` reads the winner's
+member returns back; the C controller steps do not apply: the default ``native_step`` steps aside, an explicit ``native_cem_step``
+/ ``native_mppi_step`` raises).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -86,6 +92,8 @@ class MPCController(Policy, Serializable):
             mppi_beta=0.6,
             mppi_iters=1,
             native_mppi_step=False,
+            ensemble_planning="mean",
+            risk_coef=0.0,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -125,6 +133,15 @@ class MPCController(Policy, Serializable):
             if self.mppi_iters < 1:
                 raise ValueError("mppi_iters must be at least 1")
 
+        if ensemble_planning not in ("mean", "particles"):
+            raise ValueError("ensemble_planning is 'mean' or 'particles', not %r" % (ensemble_planning,))
+        self.ensemble_planning = ensemble_planning
+        self.risk_coef = float(risk_coef)
+        if not np.isfinite(self.risk_coef):
+            raise ValueError("risk_coef must be finite")
+        if ensemble_planning == "particles":
+            self._check_particles()
+
         self.unwrapped_env = innermost_env(env)
 
         # make sure that env has reward function (reference :39)
@@ -146,10 +163,21 @@ class MPCController(Policy, Serializable):
         self._mppi_side = None      # which side plans (and holds the persistent mean): None until the first MPPI step, then "c" / "python"
         self._cem_first_chunk = 4   # horizon steps of the first chunk of a pipelined CEM rollout (0: equal chunks)
         self.last_plan = None       # diagnostics of the latest fused plan (returns, keys, ...)
+        self._particles = None      # device tensors of the latest particle rollout (`particle_diagnostics`)
 
     @property
     def vectorized(self):
         return True
+
+    def _check_particles(self):
+        """``ensemble_planning="particles"``: the members must be there to be rolled out one by one - a mean ensemble of at least
+        two weight sets - and the plan goes through ``_rollout``, which the C controller steps bypass."""
+        model = self.dynamics_model
+        if getattr(model, "mode", None) != "mean" or int(getattr(model, "ensemble_size", 1)) < 2:
+            raise _lib.L2AError("ensemble_planning='particles' needs a mean ensemble: MLPDynamicsModel(ensemble_size >= 2)")
+        if self.native_cem_step or self.native_mppi_step:
+            raise _lib.L2AError("ensemble_planning='particles' plans through the Python loop: the C controller steps "
+                                "(native_cem_step, native_mppi_step) roll the mean ensemble out - leave them off")
 
     # ------------------------------------------------------------------ reference API
     def get_action(self, observation):
@@ -308,8 +336,10 @@ class MPCController(Policy, Serializable):
         """The plan is scored by a launch of its own behind the trajectory rollout (``l2a_rollout_traj``) - the env's reward is a
         ``RewardProgram`` (``l2a_plan_rs_program``) or a native reward model stands in for it (``l2a_plan_rs_reward_model``) -
         through ``_rollout``, and every path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking
-        launch, the horizon-chunked pipelines, the C controllers - declines."""
-        return isinstance(self._reward_spec, RewardProgram) or self._native_reward_model() is not None
+        launch, the horizon-chunked pipelines, the C controllers - declines.  A particle plan (``ensemble_planning="particles"``)
+        is scored behind its rollouts too, whatever its reward, and stays on ``_rollout`` the same way."""
+        return (self.ensemble_planning == "particles" or isinstance(self._reward_spec, RewardProgram)
+                or self._native_reward_model() is not None)
 
     def _buf(self, key, shape, dtype, device):
         t = self._bufs.get(key)
@@ -431,6 +461,17 @@ class MPCController(Policy, Serializable):
         best = self._buf("best", (m,), torch.int64, dev)
         rets = self._buf("rets", (m, n_local), torch.float32, dev) if want_returns else None
         rm = self._native_reward_model()
+        if self.ensemble_planning == "particles":
+            # every member's rollout of every candidate, then mean - risk_coef * std: the score table and its keys stand where the
+            # returns do; the member returns and the spread stay on the device (`particle_diagnostics`)
+            members = self._buf("p_members", (m, native.n_sets, n_local), torch.float32, dev)
+            spread = self._buf("p_spread", (m, n_local), torch.float32, dev)
+            native.plan_rs_particles(obs0, actions_local, m, n_local, self.horizon, self.discount,
+                                     rm.planner_reward_model() if rm is not None else self._reward_spec, risk_coef=self.risk_coef,
+                                     cand_offset=cand_offset, score_out=rets, spread_out=spread, member_returns_out=members,
+                                     best_key=best)
+            self._particles = dict(members=members, spread=spread, score=rets, best=best, cand_offset=cand_offset)
+            return best, rets
         if rm is not None:
             native.plan_rs_reward_model(obs0, actions_local, m, n_local, self.horizon, self.discount, rm.planner_reward_model(),
                                         cand_offset=cand_offset, returns_out=rets, best_key=best)
@@ -439,6 +480,31 @@ class MPCController(Policy, Serializable):
         plan(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
              cand_offset=cand_offset, returns_out=rets, best_key=best)
         return best, rets
+
+    def particle_diagnostics(self, tables=False):
+        """What the latest particle rollout on this rank knew of its winner, copied back on demand (nothing of it is on the plan
+        step's own read-back): per env ``index`` (global candidate index of the best score in this rank's shard), ``score``, the
+        winner's ``member_returns [m, E]`` and their ``std [m]``.  ``tables=True`` adds the whole ``member_returns_table
+        [m, E, n_local]``, ``spread_table`` and - where the planner asked for the scores - ``score_table [m, n_local]``.  Under CEM
+        and MPPI it is the last iteration's rollout; ``None`` before the first particle plan."""
+        st = self._particles
+        if st is None:
+            return None
+        keys = st["best"].cpu().numpy()
+        m = len(keys)
+        index = np.empty(m, dtype=np.int64)
+        score = np.empty(m, dtype=np.float32)
+        for i in range(m):
+            score[i], index[i] = _lib.key_decode(keys[i])
+        dev = st["members"].device
+        env = torch.arange(m, device=dev)
+        loc = torch.as_tensor(index - st["cand_offset"], device=dev)
+        out = dict(index=index, score=score, member_returns=st["members"][env, :, loc].cpu().numpy(),     # the winners' columns only
+                   std=st["spread"][env, loc].cpu().numpy())
+        if tables:
+            out.update(member_returns_table=st["members"].cpu().numpy(), spread_table=st["spread"].cpu().numpy(),
+                       score_table=st["score"].cpu().numpy() if st["score"] is not None else None)
+        return out
 
     def _plan_keys(self, observations, a_dev, n_local, lo, world):
         """Roll out ``a_dev`` and return the arg-max keys: as a NumPy uint64 array when the blocking single-GPU
