@@ -590,6 +590,60 @@ int l2a_mppi_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed,
                           int n, int m, int h, int act_dim, int lo, int hi, float* mean_out, float* a_clip, float* seq_local,
                           void* stream);
 
+/* ---- improved cross-entropy-method (iCEM) planner: the per-iteration work around the rollout, on the device --------
+ * iCEM (Pinneri et al. 2020): CEM with a plan that is shifted and reused at the next step, a fraction of the elites carried into
+ * the next iteration and step, time-correlated noise, a shrinking population and the best candidate's action executed.  The
+ * reference has no such planner, the semantics are build-defined.  A = act_dim, D = h * A.  Sample rows are candidate-major
+ * ([n_it, m, D]: row j * m + i), plan rows env-major (i * n_it + j): l2a_cem_sample's reference = 0.  Per env i, on the device:
+ * the plan mean mu[i] [h, A], the spread sd[i] [h, A], the kept elites kept[i] [Kk, D] and their count kc[i] <= Kk.  Sizes (the
+ * caller's, computed on the host in double precision): K = max(int(n * percent_elites), 1) elites, Kk = int(icem_keep * K) kept
+ * ones (0 is allowed), the population of iteration `it` n_it = min(n, max(int(n / icem_decay ** it), 2 K)).
+ * One iteration = l2a_icem_sample, the rollout (returns [m, n_it]), l2a_icem_refit.
+ *
+ * l2a_icem_sample (one launch: l2a_icem_sample_k)
+ *   shift  [m] device int32.  < 0 (a new or reset env): mu' = 0, sd' = sigma0[k], kc' = 0.  > 0 (first iteration of a later step):
+ *          mu'_t = mu_min(t + 1, h - 1), sd' = sigma0[k] (the spread is re-opened), the kept rows are shifted the same way (the last
+ *          step repeated), kc' = kc.  0 (later iterations): mu' = mu, sd' = sd, kept rows as they are, kc' = kc.  A stored count
+ *          outside 0 .. Kk is held to that range.
+ *   rows   row j < kc'_i is kept row j as stored (it was clipped when it was drawn).  With add_mean != 0 row n_it - 1 is
+ *          clip(mu') - and it wins where both rules name the same row (n_it <= kc').  Every other row: z[j, i, t, k] is a standard
+ *          normal for element e = (j * m + i) * D + t * A + k of the [n_it, m, D] draw - `z` (device fp32) or, z = NULL,
+ *          l2a_cem_sample's Philox4x32-10 + Box-Muller stream at counter offset + e under `seed` (the numbering is positional: a
+ *          kept row's normals are not used, the stream does not depend on kc) -, nz_0 = z_0, nz_t = rho * nz_(t-1) + c * z_t with
+ *          c = sqrtf(1 - rho * rho) formed once in fp32 (unit variance for every t), a = clip(mu' + nz_t * sd', low[k], high[k]);
+ *          each operation rounded to fp32 on its own.  rho = 0 is l2a_cem_sample's white noise.
+ *   out    a_clip [n_it, m, D] and, unless NULL, seq [h, m * n_it, A], the candidate tensor l2a_plan_rs reads; mean_out and
+ *          std_out [m, D] receive mu' and sd'.
+ *   sigma0 / low / high [act_dim] device fp32; kept_in [m, Kk, D], kc_in [m] (both may be NULL when Kk == 0).
+ *   L2A_EINVAL (nothing written, nothing launched): act_dim outside 1..16, n_it / m / h < 1, Kk outside 0..8192, rho outside [0, 1),
+ *   a NULL pointer (z and seq may be NULL; kept_in / kc_in with Kk == 0), an output that is an input or another output.
+ *
+ * l2a_icem_refit (two launches: l2a_icem_rank_k over candidates, l2a_icem_stats_k over dimensions)
+ *   returns [m, n_it] device fp32, a_clip the samples they belong to, mean / std = the sample call's mean_out / std_out, updated
+ *   in place.  A candidate is valid when its return is neither NaN nor -inf (l2a_mppi_update's rule: a diverged rollout is never
+ *   an elite).  The elites are the top Ke = min(K, valid) valid candidates in the stable descending order (ties: the lower index
+ *   first).  Per dimension em and the biased es of the elite rows of a_clip in one fixed summation order (csrc/l2a_icem.hip), then
+ *   mu = alpha * mu' + (1 - alpha) * em, sd = alpha * sd' + (1 - alpha) * es; Ke = 0 leaves both untouched.  No atomics: the same
+ *   inputs give the same bits on every run.
+ *   work      device int32 [m, K], scratch (the elites' candidate indices in rank order; entries >= Ke are not written)
+ *   kept_out  [m, Kk, D]: the first min(Kk, Ke) elite rows in rank order (NULL allowed when Kk == 0); kc_out [m]: that number
+ *   out       [m][act_dim + 4] floats: the first action of the best valid candidate (the first maximum) | its return | its index as
+ *             the bits of an int32 | Ke, int32 bits | the valid count, int32 bits.  Without a valid candidate: mu'[i, 0, :] clipped
+ *             to low / high | NaN | -1 | 0 | 0.
+ *   L2A_EINVAL (nothing written, nothing launched): act_dim outside 1..16, n_it / m / h < 1, m > 65535, K outside 1..8192, Kk outside
+ *   0..K, alpha outside [0, 1), a NULL pointer, an output that is an input or another output, or LDS: n_it * 4 bytes (the ranking's
+ *   returns) or K * 4 + L2A_ICEM_REFIT_STATIC_LDS bytes (the statistics' elite list and its static part) beyond a workgroup's
+ *   LDS (l2a_device_info: lds_per_block).
+ * Not built: a C controller step, sharding over ranks, a power-law noise spectrum (the recurrence is AR(1)).                     */
+#define L2A_ICEM_REFIT_STATIC_LDS 4288
+int l2a_icem_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                    const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0, float rho,
+                    const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk, int add_mean,
+                    float* mean_out, float* std_out, float* a_clip, float* seq, void* stream);
+int l2a_icem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, const float* low, const float* high, int n_it, int m,
+                   int h, int act_dim, int K, int Kk, float alpha, int* work, float* mean, float* std, float* kept_out,
+                   int* kc_out, float* out, void* stream);
+
 /* ---- sharded plans: the one collective ------------------------------------------------------
  * Candidates are independent, so G GPUs (one process and one context each) plan disjoint shards of one candidate
  * tensor (l2a_plan_rs with cand_offset = first global index of the shard) and combine the per-shard keys with ONE

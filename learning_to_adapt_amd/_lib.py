@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "l2a_comm_unique_id", "l2a_comm_init", "l2a_comm_destroy", "l2a_allreduce_best", "l2a_plan_payload",
     "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick", "l2a_cem_refit_sample", "l2a_cem_refit_sample_fused",
     "l2a_mppi_sample", "l2a_mppi_update", "l2a_mppi_sample_shard",
+    "l2a_icem_sample", "l2a_icem_refit",
     "l2a_mppi_controller_create_device", "l2a_mppi_controller_create_sharded_device", "l2a_mppi_controller_reset",
     "l2a_mppi_controller_reseed", "l2a_mppi_controller_result",
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
@@ -332,6 +333,12 @@ def load():
         lib.l2a_mppi_sample.restype = i32
         lib.l2a_mppi_update.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
         lib.l2a_mppi_update.restype = i32
+    if hasattr(lib, "l2a_icem_sample"):         # the iCEM planner's kernels (absent from older variant libraries)
+        lib.l2a_icem_sample.argtypes = [vp, vp, c.c_ulonglong, c.c_ulonglong, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32,
+                                        i32, vp, vp, vp, vp, vp]
+        lib.l2a_icem_sample.restype = i32
+        lib.l2a_icem_refit.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
+        lib.l2a_icem_refit.restype = i32
     lib.l2a_lstm_plan_rs_sync.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardSpec), i32, vp, vp, vp, vp]
     lib.l2a_lstm_plan_rs_sync.restype = i32
     lib.l2a_lstm_plan_rs_chunk.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, c.c_double, c.POINTER(RewardSpec), i32,

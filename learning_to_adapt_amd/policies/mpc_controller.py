@@ -39,6 +39,13 @@ range -, ``mppi_beta`` the noise filter ``n_t = beta u_t + (1 - beta) n_(t-1)``,
 controller, ``l2a_mppi_controller_create_device`` - the only way to shard an MPPI plan over torch.distributed ranks:
 ``l2a_mppi_controller_create_sharded_device``, one rank each - bit-identical to ``get_mppi_action``, ``policies/native_mppi_step.py``;
 reward programs, reward models and recurrent models keep the Python path),
+``use_icem`` (iCEM, Pinneri et al. 2020 - not in the reference: per env a plan mean, a spread and kept elites persist on the device;
+a step moves mean and kept elites on one horizon step and re-opens the spread to ``icem_sigma`` - ``None``: a quarter of the action
+range -, an iteration places the kept elites first and draws the rest with AR(1) noise ``n_t = rho n_(t-1) + sqrt(1 - rho^2) z_t``
+(``icem_rho``), the population shrinks by ``icem_decay`` per iteration down to twice the elites, ``percent_elites`` and ``alpha`` refit
+mean and spread, ``icem_keep`` of the elites are kept, ``icem_add_mean`` adds the mean itself to the last of the ``icem_iters``
+iterations, and the best candidate's first action is returned, ``get_icem_action``; needs ``rng="device"``; ``reset(dones)`` restarts
+the marked envs' plans; one GPU, the Python loop only),
 ``ensemble_planning`` (``"mean"``, the default: the members of an ``MLPDynamicsModel(ensemble_size=E)`` share one state, their
 deltas averaged at every horizon step; ``"particles"``: PETS-style trajectory sampling - every member rolls every candidate out as a
 trajectory of its own and a candidate's score is the mean of its E returns less ``risk_coef`` times their standard deviation,
@@ -94,6 +101,13 @@ class MPCController(Policy, Serializable):
             native_mppi_step=False,
             ensemble_planning="mean",
             risk_coef=0.0,
+            use_icem=False,
+            icem_iters=3,
+            icem_keep=0.3,
+            icem_decay=1.25,
+            icem_rho=0.5,
+            icem_sigma=None,
+            icem_add_mean=True,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -132,6 +146,30 @@ class MPCController(Policy, Serializable):
                 raise ValueError("mppi_beta must lie in (0, 1]")
             if self.mppi_iters < 1:
                 raise ValueError("mppi_iters must be at least 1")
+        self.use_icem = bool(use_icem)
+        self.icem_iters = int(icem_iters)
+        self.icem_keep = float(icem_keep)
+        self.icem_decay = float(icem_decay)
+        self.icem_rho = float(icem_rho)
+        self.icem_sigma = icem_sigma
+        self.icem_add_mean = bool(icem_add_mean)
+        if self.use_icem:
+            if use_cem or self.use_mppi:
+                raise ValueError("use_icem, use_cem and use_mppi are three planners: choose one")
+            if rng != "device":
+                raise ValueError("use_icem draws its normals on the device: pass rng='device'")
+            if self.icem_iters < 1:
+                raise ValueError("icem_iters must be at least 1")
+            if not 0.0 <= self.icem_keep <= 1.0:
+                raise ValueError("icem_keep must lie in [0, 1]")
+            if not (self.icem_decay >= 1.0 and np.isfinite(self.icem_decay)):
+                raise ValueError("icem_decay must be finite and at least 1")
+            if not 0.0 <= self.icem_rho < 1.0:
+                raise ValueError("icem_rho must lie in [0, 1)")
+            if not 0.0 <= float(alpha) < 1.0:
+                raise ValueError("use_icem needs alpha in [0, 1)")
+            if not percent_elites > 0:
+                raise ValueError("use_icem needs percent_elites > 0")
 
         if ensemble_planning not in ("mean", "particles"):
             raise ValueError("ensemble_planning is 'mean' or 'particles', not %r" % (ensemble_planning,))
@@ -154,6 +192,8 @@ class MPCController(Policy, Serializable):
         self._bufs = {}
         if self.use_mppi:
             self._mppi_sigma_vector()       # (a bad mppi_sigma fails here, not on the first step)
+        if self.use_icem:
+            self._icem_sigma_vector()
         self._ahead = None          # DrawAhead chain (parity mode), created on first use
         self._cstep = None          # NativeStep (l2a_controller): the whole parity-mode step in one C call
         self._cstep_no = None       # request key the C controller was found ineligible for
@@ -183,7 +223,9 @@ class MPCController(Policy, Serializable):
     def get_action(self, observation):
         if observation.ndim == 1:
             observation = observation[None]
-        if self.use_mppi:
+        if self.use_icem:
+            action = self.get_icem_action(observation)
+        elif self.use_mppi:
             action = self.get_mppi_action(observation)
         elif self.use_cem:
             action = self.get_cem_action(observation)
@@ -192,7 +234,9 @@ class MPCController(Policy, Serializable):
         return action, dict()
 
     def get_actions(self, observations):
-        if self.use_mppi:
+        if self.use_icem:
+            actions = self.get_icem_action(observations)
+        elif self.use_mppi:
             actions = self.get_mppi_action(observations)
         elif self.use_cem:
             actions = self.get_cem_action(observations)
@@ -241,6 +285,7 @@ class MPCController(Policy, Serializable):
 
     def reset(self, dones=None):
         self._mppi_reset(dones)
+        self._icem_reset(dones)
 
     # ------------------------------------------------------------------ sharding helpers
     def _dist(self):
@@ -1337,19 +1382,22 @@ class MPCController(Policy, Serializable):
     def _mppi_sigma_vector(self):
         """``mppi_sigma`` as an fp32 ``[act_dim]`` array: ``None`` = a quarter of each dimension's action range, a scalar = that
         value for every dimension, or one value per dimension; finite and non-negative."""
+        return self._sigma_vector(self.mppi_sigma, "mppi_sigma")
+
+    def _sigma_vector(self, value, name):
         low = np.asarray(self.action_space.low, dtype=np.float64)
         high = np.asarray(self.action_space.high, dtype=np.float64)
-        if self.mppi_sigma is None:
+        if value is None:
             sigma = 0.25 * (high - low)
         else:
-            sigma = np.asarray(self.mppi_sigma, dtype=np.float64)
+            sigma = np.asarray(value, dtype=np.float64)
             if sigma.ndim == 0:
                 sigma = np.full(low.shape, float(sigma))
         if sigma.shape != low.shape:
-            raise ValueError("mppi_sigma must be None, a scalar or one value per action dimension %s, got shape %s"
-                             % (low.shape, sigma.shape))
+            raise ValueError("%s must be None, a scalar or one value per action dimension %s, got shape %s"
+                             % (name, low.shape, sigma.shape))
         if not (np.isfinite(sigma).all() and (sigma >= 0).all()):
-            raise ValueError("mppi_sigma must be finite and non-negative")
+            raise ValueError("%s must be finite and non-negative" % name)
         return sigma.astype(np.float32)
 
     def _mppi_reset(self, dones):
@@ -1531,3 +1579,170 @@ class MPCController(Policy, Serializable):
                               mppi_ess=head[:, act_dim + 2].copy(),
                               mppi_valid=head[:, act_dim + 3].copy().view(np.int32).astype(np.int64))
         return head[:, :act_dim].astype(np.float64)
+
+    # ------------------------------------------------------------------ iCEM (Pinneri et al. 2020: CEM with memory and coloured noise)
+    def _icem_sigma_vector(self):
+        """``icem_sigma`` (the spread a plan starts from, and re-opens to at every step) as an fp32 ``[act_dim]`` array, resolved as
+        ``mppi_sigma`` is."""
+        return self._sigma_vector(self.icem_sigma, "icem_sigma")
+
+    def _icem_sizes(self):
+        """``(K, Kk, [n_it per iteration])``: elites ``K = max(int(n * percent_elites), 1)``, kept elites ``Kk = int(icem_keep * K)``
+        (0 is allowed), populations ``n_it = min(n, max(int(n / icem_decay ** it), 2 K))`` - in double precision, on the host."""
+        n = int(self.n_candidates)
+        K = max(int(n * self.percent_elites), 1)
+        Kk = int(self.icem_keep * K)
+        return K, Kk, [min(n, max(int(n / self.icem_decay ** it), 2 * K)) for it in range(self.icem_iters)]
+
+    def _icem_reset(self, dones):
+        """``reset(dones)`` for the iCEM planner: the marked envs' next step starts from a zero mean, the initial spread and no kept
+        elites; ``None``, or a number of envs other than the plan's, starts all of them afresh.  Without ``use_icem`` nothing happens."""
+        if not self.use_icem:
+            return
+        fresh = self._bufs.get("icem_fresh")
+        if dones is None or fresh is None or len(fresh) != len(dones):
+            self._bufs["icem_fresh"] = None
+        else:
+            fresh |= np.asarray(dones, dtype=bool)
+
+    def _icem_normal_device(self, shape, device):
+        """Hook for tests: return the iteration's standard normals ``[n_it, m, D]`` as a CUDA fp32 tensor to inject them; ``None``
+        (the default) lets ``l2a_icem_sample`` draw them on the device (Philox4x32-10 + Box-Muller, CEM's stream)."""
+        return None
+
+    icem_trace_returns = False      # copy EVERY iteration's returns into `last_plan["icem_trace"]` (tests); the last one's always come
+
+    def get_icem_action(self, observations, retry=False):
+        """One iCEM plan step on the GPU (``csrc/l2a_icem.hip``; semantics in ``include/l2a.h``).  Per env the plan mean, the spread
+        ``[m, h * act_dim]``, the kept elites ``[m, Kk, h * act_dim]`` and their counts stay on the device between controller steps.
+        Per iteration: ``l2a_icem_sample`` (shift - a fresh start for an env that is new or was reset, one step on with the spread
+        re-opened for the first iteration of a later step, none for further iterations -, the kept elites as the first rows, AR(1)
+        noise, clip, with ``icem_add_mean`` the mean itself as the last iteration's last row), the fused rollout of the iteration's
+        ``n_it`` candidates (``_rollout``: closed-form reward, reward program, reward model and particle plans alike),
+        ``l2a_icem_refit`` (top-k of the valid candidates, momentum update of mean and spread, the kept elites, the packed result).
+        The observations go up once, one copy brings the packed result back.  The action returned is the first action of the last
+        iteration's best candidate.  The normals of iteration ``it`` of the s-th step are the Philox stream under
+        ``torch.initial_seed()`` at offset ``(s * icem_iters + it) * n * m * D`` - the stride is the full ``n``, and the counter is the
+        planner's own, not CEM's or MPPI's.  State and counter are committed only when the launch status was read clean: a flagged
+        tile-split launch replays the step from the same state with the same offsets.  ``last_plan``: ``best_index``, ``best_return``,
+        ``returns`` (the last iteration's), ``icem_mean``, ``icem_std``, ``icem_elites [m, Kk, D]`` (env i's kept rows in rank order: its
+        first ``icem_elite_count[i]`` rows, zeros behind them), ``icem_valid``, ``icem_trace`` (per iteration: n, best return and index,
+        elite and valid counts)."""
+        import ctypes
+        from ..dynamics.native_model import _ptr, _stream_ptr
+        if not self._fusable():
+            raise _lib.L2AError("iCEM planning needs a fusable closed-form reward (env.reward_spec: a RewardSpec or a RewardProgram) "
+                                "or, with use_reward_model, a reward model the library scores (MLPRewardModel)")
+        if self.rng != "device":
+            raise _lib.L2AError("iCEM planning draws its normals on the device (rng='device'); NumPy normals are not supported")
+        if self.native_cem_step or self.native_mppi_step:
+            raise _lib.L2AError("iCEM planning has no C controller step: leave native_cem_step and native_mppi_step off with use_icem")
+        if self._dist()[1] > 1:
+            raise _lib.L2AError("iCEM planning does not shard its candidates over torch.distributed ranks: pass "
+                                "shard_candidates=False (every rank then plans on its own)")
+        n, m, h = self.n_candidates, len(observations), self.horizon
+        act_dim = self.action_space.shape[0]
+        D = h * act_dim
+        K, Kk, pops = self._icem_sizes()
+        iters = self.icem_iters
+        dev = self._device()
+        native = self.dynamics_model.planner_model()
+        ctx, lib = native.ctx, native.lib
+        if not hasattr(lib, "l2a_icem_sample"):
+            raise _lib.L2AError("this libl2a_hip.so has no iCEM kernels (l2a_icem_sample): rebuild it")
+        const = self._bufs.get("icem_const")
+        if const is None or const[0].device != dev:
+            up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
+            const = self._bufs["icem_const"] = (up(self.action_space.low), up(self.action_space.high), up(self._icem_sigma_vector()))
+        low, high, sigma = const
+        # the persistent state and two scratch copies of it: a step reads `cur` and commits its last outputs only when it succeeded,
+        # so a replay starts from the same plan
+        means = self._buf("icem_means", (3, m, D), torch.float32, dev)
+        stds = self._buf("icem_stds", (3, m, D), torch.float32, dev)
+        kept = self._buf("icem_kept", (3, m, max(Kk, 1), D), torch.float32, dev)
+        kcs = self._buf("icem_kc", (3, m), torch.int32, dev)
+        work = self._buf("icem_work", (m, K), torch.int32, dev)
+        shifts = self._bufs.get("icem_shifts")
+        if shifts is None or shifts.device != dev or shifts.shape[1] != m:
+            shifts = self._bufs["icem_shifts"] = torch.as_tensor(np.array([[1] * m, [0] * m, [-1] * m], dtype=np.int32), device=dev)
+            self._bufs["icem_fresh"], self._bufs["icem_cur"] = None, 0
+        fresh = self._bufs.get("icem_fresh")
+        if fresh is None:
+            first = shifts[2]                                   # every env starts afresh
+        elif fresh.any():
+            first = torch.as_tensor(np.where(fresh, -1, 1).astype(np.int32), device=dev)
+        else:
+            first = shifts[0]
+        cur = self._bufs["icem_cur"]
+        a_clip = self._buf("icem_a_clip", (n, m, D), torch.float32, dev)
+        seq_all = self._buf("icem_seq", (h * m * n * act_dim,), torch.float32, dev)
+        width = act_dim + 4
+        trace = bool(self.icem_trace_returns)
+        # one buffer, one read-back: every iteration's result rows | mean | std | kept rows | kept counts | returns
+        sizes = [iters * m * width, m * D, m * D, m * Kk * D, m, m * (sum(pops) if trace else pops[-1])]
+        at = [int(v) for v in np.concatenate([[0], np.cumsum(sizes)])]
+        packed = self._buf("icem_packed", (at[-1],), torch.float32, dev)
+        heads = packed[:at[1]].view(iters, m, width)
+        obs_dev = self._upload_obs(observations)                # once per plan step
+        # counter-based stream: (seed, iterations so far); restarts when torch's seed VALUE changes, as CEM's does
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        if self._bufs.get("icem_seed") != seed:
+            self._bufs["icem_seed"], self._bufs["icem_calls"] = seed, 0
+        call0 = self._bufs["icem_calls"]
+        src = cur
+        ret_at = at[5]
+        for it in range(iters):
+            n_it = pops[it]
+            dst = [b for b in range(3) if b != src and b != cur][0]
+            z = self._icem_normal_device((n_it, m, D), dev)
+            if z is not None:
+                z = z.to(device=dev, dtype=torch.float32).contiguous()
+            offset = (call0 + it) * n * m * D
+            seq = seq_all[:h * m * n_it * act_dim].view(h, m * n_it, act_dim)
+            ctx.check(lib.l2a_icem_sample(ctx.handle, _ptr(z), ctypes.c_ulonglong(seed), ctypes.c_ulonglong(offset & 0xFFFFFFFFFFFFFFFF),
+                                          _ptr(means[src]), _ptr(stds[src]), _ptr(kept[src]) if Kk else None,
+                                          _ptr(kcs[src]) if Kk else None, _ptr(first if it == 0 else shifts[1]), _ptr(sigma),
+                                          self.icem_rho, _ptr(low), _ptr(high), n_it, m, h, act_dim, Kk,
+                                          int(self.icem_add_mean and it == iters - 1), _ptr(means[dst]), _ptr(stds[dst]), _ptr(a_clip),
+                                          _ptr(seq), _stream_ptr(dev)), "l2a_icem_sample")
+            _, rets = self._rollout(observations, seq, n_it, 0, want_returns=True, obs_dev=obs_dev)
+            ctx.check(lib.l2a_icem_refit(ctx.handle, _ptr(rets), _ptr(a_clip), _ptr(low), _ptr(high), n_it, m, h, act_dim, K, Kk,
+                                         float(self.alpha), _ptr(work), _ptr(means[dst]), _ptr(stds[dst]),
+                                         _ptr(kept[dst]) if Kk else None, _ptr(kcs[dst]), _ptr(heads[it]), _stream_ptr(dev)),
+                      "l2a_icem_refit")
+            if trace or it == iters - 1:
+                packed[ret_at:ret_at + m * n_it].view(m, n_it).copy_(rets)
+                ret_at += m * n_it
+            src = dst
+        packed[at[1]:at[2]].view(m, D).copy_(means[src])
+        packed[at[2]:at[3]].view(m, D).copy_(stds[src])
+        if Kk:
+            packed[at[3]:at[4]].view(m, Kk, D).copy_(kept[src])
+        packed[at[4]:at[5]].view(torch.int32).copy_(kcs[src])
+        host = packed.cpu().numpy()
+        if self._check_status() is False:       # a launch lost its tile-split partner: the context is unsplit now
+            if retry:
+                raise _lib.L2AError("rollout launch failed twice")
+            return self.get_icem_action(observations, retry=True)       # same counters, same starting state: the same step again
+        self._bufs["icem_calls"] = call0 + iters
+        self._bufs["icem_cur"] = src
+        self._bufs["icem_fresh"] = np.zeros(m, dtype=bool)
+        head = host[:at[1]].reshape(iters, m, width)
+        as_int = lambda a: a.copy().view(np.int32).astype(np.int64)     # noqa: E731
+        ret_at, steps = at[5], []
+        for it in range(iters):
+            step = dict(n=pops[it], best_return=head[it, :, act_dim].copy(), best_index=as_int(head[it, :, act_dim + 1]),
+                        elites=as_int(head[it, :, act_dim + 2]), valid=as_int(head[it, :, act_dim + 3]))
+            if trace or it == iters - 1:
+                step["returns"] = host[ret_at:ret_at + m * pops[it]].reshape(m, pops[it]).copy()
+                ret_at += m * pops[it]
+            steps.append(step)
+        last = steps[-1]
+        # the refit writes an env's first `count` kept rows only: what lies behind them in the buffer is no elite of this step
+        elites, counts = host[at[3]:at[4]].reshape(m, Kk, D).copy(), as_int(host[at[4]:at[5]])
+        for i in range(m):
+            elites[i, counts[i]:] = 0.0
+        self.last_plan = dict(best_index=last["best_index"], best_return=last["best_return"], returns=last["returns"],
+                              icem_mean=host[at[1]:at[2]].reshape(m, D).copy(), icem_std=host[at[2]:at[3]].reshape(m, D).copy(),
+                              icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps)
+        return head[-1, :, :act_dim].astype(np.float64)
