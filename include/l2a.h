@@ -634,7 +634,9 @@ int l2a_mppi_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed,
  *   0..K, alpha outside [0, 1), a NULL pointer, an output that is an input or another output, or LDS: n_it * 4 bytes (the ranking's
  *   returns) or K * 4 + L2A_ICEM_REFIT_STATIC_LDS bytes (the statistics' elite list and its static part) beyond a workgroup's
  *   LDS (l2a_device_info: lds_per_block).
- * Not built: a C controller step, sharding over ranks, a power-law noise spectrum (the recurrence is AR(1)).                     */
+ * The controller step as one call, unsharded and sharded over ranks: l2a_icem_controller_create_device below.
+ * Not built: a recurrent model, reward programs and reward models through the C step, NumPy normals, a power-law noise spectrum
+ * (the recurrence is AR(1)).                                                                                                     */
 #define L2A_ICEM_REFIT_STATIC_LDS 4288
 int l2a_icem_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
                     const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0, float rho,
@@ -643,6 +645,17 @@ int l2a_icem_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsig
 int l2a_icem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, const float* low, const float* high, int n_it, int m,
                    int h, int act_dim, int K, int Kk, float alpha, int* work, float* mean, float* std, float* kept_out,
                    int* kc_out, float* out, void* stream);
+/* l2a_icem_sample for ONE rank of a sharded plan (as l2a_mppi_sample_shard): the rank fetches, draws, runs the recurrence and clips
+ * ALL n_it rows of the same stream - a_clip [n_it, m, D], mean_out and std_out are l2a_icem_sample's bit for bit, the refit runs on
+ * them unchanged - and keeps the rollout tensor of its window only: seq_local [h, m * (hi - lo), A], plan row i * (hi - lo) + (j - lo)
+ * for lo <= j < hi (the values of l2a_icem_sample's seq rows i * n_it + j).  A kept row (j < kc') or the mean row (j == n_it - 1 with
+ * add_mean) inside the window is written like any other row.  lo == hi writes no seq_local (it may be NULL then).  L2A_EINVAL
+ * (nothing written, nothing launched): l2a_icem_sample's, lo < 0, hi > n_it, lo > hi, or a NULL seq_local with lo < hi.  The same
+ * kernel body, one more instance.                                                                                                  */
+int l2a_icem_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                          const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0,
+                          float rho, const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk, int add_mean,
+                          int lo, int hi, float* mean_out, float* std_out, float* a_clip, float* seq_local, void* stream);
 
 /* ---- sharded plans: the one collective ------------------------------------------------------
  * Candidates are independent, so G GPUs (one process and one context each) plan disjoint shards of one candidate
@@ -1042,6 +1055,64 @@ int l2a_mppi_controller_create_sharded_device(l2a_model* model, int m, int n, in
 int l2a_mppi_controller_reset(l2a_controller* controller, const unsigned char* dones);
 int l2a_mppi_controller_reseed(l2a_controller* controller, unsigned long long seed);
 int l2a_mppi_controller_result(l2a_controller* controller, float* mean_out, float* ess_out, int* valid_out, float* returns_out);
+/* ---- the iCEM controller step as one call (device mode) ------------------------------------------------------------------
+ * `MPCController.get_icem_action` (policies/mpc_controller.py; the planner of l2a_icem_sample / l2a_icem_refit above): the whole
+ * plan step on the launch stream - per iteration `it` l2a_icem_sample with n_it = pops[it], the fused rollout of those n_it
+ * candidates, l2a_icem_refit into result row block `it` - and ONE read-back of the iters * m * (act_dim + 4) floats of result rows.
+ * Mean, spread [m, D], kept rows [m, Kk, D] and counts [m] live in the controller (three device copies of each rotate together: the
+ * committed copy is never written by the step that reads it) and stay on the device, as every iteration's returns do, until
+ * l2a_icem_controller_result asks.  Iteration 0 samples with the per-env shift vector - -1 for an env that is new or was reset
+ * (l2a_icem_controller_reset), +1 otherwise -, later iterations with shift 0; add_mean applies to the last iteration only.  The
+ * normals of iteration `it` are the Philox stream (seed) at offset (iter_calls + it) * n * m * D - the stride is the full n,
+ * whatever pops[it] is -, iter_calls = iterations finished so far since create / reseed: with the same seed a step equals
+ * get_icem_action bit for bit (action, index, best return, mean, spread, kept rows, counts, every iteration's result row and returns).
+ *   iters  iterations per step (`icem_iters`);  pops [iters] host int32, K, Kk: the populations, the elites and the kept elites - the
+ *          caller's (`MPCController._icem_sizes`), computed on the host in double precision and never recomputed here;  alpha, rho:
+ *          `alpha`, `icem_rho`;  sigma0 [act_dim]: the initial spread (host float64, rounded to fp32 as `_icem_sigma_vector` does);
+ *          add_mean: `icem_add_mean`.  Kk == 0: no kept rows (the kept arguments of sample and refit are NULL).
+ * Refused at create (L2A_EINVAL, nothing allocated): the argument limits of l2a_icem_sample and l2a_icem_refit on every iteration -
+ * the LDS checks pops[it] * 4 <= lds_per_block and K * 4 + L2A_ICEM_REFIT_STATIC_LDS <= lds_per_block among them, so that no step
+ * can fail on its arguments -, iters < 1, a pops[it] outside 1 .. n, NULL pops / sigma0 / low / high / reward, a sigma0 that is
+ * negative or not finite, alpha or rho outside [0, 1), m > 64 or more than 4096 observation floats; sharded:
+ * l2a_cem_controller_create_sharded_device's rank / world / collective rules.
+ * Steps through l2a_controller_step / _begin / _finish / _stats / _destroy: action_out / index_out / return_out come from the LAST
+ * iteration's result rows - the best valid candidate's first action as float64, its index and return; without a valid candidate the
+ * clipped mu'[i, 0, :], -1 and NaN, as l2a_icem_refit packs them.  The l2a_lstm_* step functions return L2A_EINVAL.  The committed
+ * copy's index, iter_calls and the cleared reset marks move in _finish behind the verdict only: a launch flagged invalid (a tile-split
+ * partner was lost) repeats the WHOLE step unsplit from the same state with the same offsets (L2A_STEP_UNSPLIT, same bits; flagged
+ * again: L2A_ESPLIT), and a failed step leaves the controller where it was.  The in-flight exclusion rules of the CEM step apply
+ * (the step reads and clears the context's status word).
+ * Sharded (one rank of `world`): in iteration `it` l2a_icem_sample_shard over the window [rank n_it / world, (rank + 1) n_it / world)
+ * - it moves with the population; an empty window rolls nothing out -, and the gather of the returns exactly as sharded CEM's with
+ * n_it in place of n - l2a_cem_shard_pack, the int64 MAX all-reduce of m * n_it + 3 words (`reduce`, or the context's communicator),
+ * l2a_cem_shard_unpack - in front of the UNCHANGED refit over all n_it: every rank's step equals the unsharded one bit for bit.  The
+ * read-back gains the three verdict words.  The digest carries the controller kind, seed, iter_calls, m, n, h, iters, world, every
+ * pops[it], K, Kk, add_mean, the bits of alpha, rho and sigma0, and the step's fresh marks: a mismatch, or a hole, is L2A_ESTATE on
+ * every rank and nothing is consumed; a flag on any rank makes all of them repeat the step unsplit, together.
+ *   l2a_icem_controller_reset  : dones [m] (non-zero: env i's next step starts afresh - shift -1), NULL = every env
+ *   l2a_icem_controller_reseed : the stream restarts at 0 under `seed`; mean, spread, kept rows and counts are kept (what
+ *                                get_icem_action does when torch.initial_seed() changes)
+ *   l2a_icem_controller_result : of the latest finished step - mean and spread (host fp32 [m, D]), the kept rows [m, Kk, D] as
+ *                                stored (env i's first kc[i] rows are this step's, what lies behind them is not), the counts [m],
+ *                                every iteration's result rows [iters, m, act_dim + 4] and every iteration's returns, the tables
+ *                                [m, pops[it]] one after another (sharded: the GATHERED tables); any pointer may be NULL; the rows
+ *                                are the step's own read-back, everything else comes back in ONE copy on the latest step's stream,
+ *                                waited for
+ * _reset / _reseed / _result return L2A_ESTATE while a step is in flight, _result also before the first step has finished, and
+ * L2A_EINVAL on a controller of another kind (as l2a_mppi_controller_* and l2a_cem_controller_result do on an iCEM controller).
+ * Not built: a recurrent model, reward programs and reward models (l2a_reward only), particle plans, NumPy normals.               */
+int l2a_icem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
+                                      double discount, const l2a_reward* reward, int iters, const int* pops, int K, int Kk,
+                                      float alpha, float rho, const double* sigma0, int add_mean, unsigned long long seed,
+                                      l2a_controller** out);
+int l2a_icem_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
+                                              double discount, const l2a_reward* reward, int iters, const int* pops, int K, int Kk,
+                                              float alpha, float rho, const double* sigma0, int add_mean, unsigned long long seed,
+                                              int rank, int world, l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out);
+int l2a_icem_controller_reset(l2a_controller* controller, const unsigned char* dones);
+int l2a_icem_controller_reseed(l2a_controller* controller, unsigned long long seed);
+int l2a_icem_controller_result(l2a_controller* controller, float* mean_out, float* std_out, float* kept_out, int* kc_out,
+                               float* heads_out, float* returns_out);
 void l2a_controller_destroy(l2a_controller* controller);
 int l2a_controller_step(l2a_controller* controller, const double* obs, double* action_out, long long* index_out,
                         float* return_out, void* stream);

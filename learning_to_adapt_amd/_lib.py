@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = (
     "l2a_icem_sample", "l2a_icem_refit",
     "l2a_mppi_controller_create_device", "l2a_mppi_controller_create_sharded_device", "l2a_mppi_controller_reset",
     "l2a_mppi_controller_reseed", "l2a_mppi_controller_result",
+    "l2a_icem_sample_shard", "l2a_icem_controller_create_device", "l2a_icem_controller_create_sharded_device", "l2a_icem_controller_reset",
+    "l2a_icem_controller_reseed", "l2a_icem_controller_result",
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry", "l2a_lstm_plan_geometry",
@@ -466,6 +468,22 @@ def load():
         lib.l2a_mppi_controller_reseed.restype = i32
         lib.l2a_mppi_controller_result.argtypes = [vp, vp, vp, vp, vp]
         lib.l2a_mppi_controller_result.restype = i32
+    if hasattr(lib, "l2a_icem_controller_create_device"):    # the iCEM step as one call (absent from older variant libraries)
+        lib.l2a_icem_sample_shard.argtypes = [vp, vp, c.c_ulonglong, c.c_ulonglong, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32,
+                                              i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        lib.l2a_icem_sample_shard.restype = i32
+        lib.l2a_icem_controller_create_device.argtypes = [vp, i32, i32, i32, vp, vp, c.c_double, c.POINTER(RewardSpec), i32, vp, i32, i32,
+                                                          f32, f32, vp, i32, c.c_ulonglong, c.POINTER(vp)]
+        lib.l2a_icem_controller_create_device.restype = i32
+        lib.l2a_icem_controller_create_sharded_device.argtypes = [vp, i32, i32, i32, vp, vp, c.c_double, c.POINTER(RewardSpec), i32, vp, i32,
+                                                                  i32, f32, f32, vp, i32, c.c_ulonglong, i32, i32, vp, vp, c.POINTER(vp)]
+        lib.l2a_icem_controller_create_sharded_device.restype = i32
+        lib.l2a_icem_controller_reset.argtypes = [vp, vp]
+        lib.l2a_icem_controller_reset.restype = i32
+        lib.l2a_icem_controller_reseed.argtypes = [vp, c.c_ulonglong]
+        lib.l2a_icem_controller_reseed.restype = i32
+        lib.l2a_icem_controller_result.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.l2a_icem_controller_result.restype = i32
     _lib = lib
     return lib
 

@@ -1,5 +1,5 @@
 // l2a_icem.hip - the improved cross-entropy-method planner's (iCEM, Pinneri et al. 2020) per-iteration work around the fused rollout,
-// on the device (include/l2a.h: l2a_icem_sample, l2a_icem_refit).  gfx950 only, wave64.  The sample arithmetic is restated bit for bit
+// on the device (include/l2a.h: l2a_icem_sample, l2a_icem_sample_shard, l2a_icem_refit).  gfx950 only, wave64.  The sample arithmetic is restated bit for bit
 // on the host (tests/icem_reference.py: sample_f32), so every operation of the kernels rounds once, on its own: each kernel body
 // opens with `#pragma clang fp contract(off)`.  The unit itself is compiled with l2a_cem.hip's flags, NOT with -ffp-contract=off
 // as l2a_mppi.hip is: that flag also keeps the math library's internal multiply-adds (logf, cosf) from fusing, and the Box-Muller
@@ -94,7 +94,8 @@ struct IcemSampleParams {
     float* mean_out;            // [m, D]
     float* std_out;             // [m, D]
     float* a_clip;              // [n, m, D]
-    float* seq;                 // [h, m * n, act_dim] or null
+    float* seq;                 // [h, m * n, act_dim] or null; SHARD: [h, m * (hi - lo), act_dim] (null when hi == lo)
+    int lo, hi;                 // SHARD: the candidates whose rollout rows this rank keeps
 };
 
 #define L2A_ICEM_ROWS 4         // at most; the entry point takes fewer on short plans, so that a thread draws one normal where it can
@@ -117,7 +118,11 @@ __device__ __forceinline__ int icem_row_kind(const IcemSampleParams& p, long lon
 // (1) all 256 threads fetch their elements' mu' and sd' and the source value (a normal, a kept element, the clipped mean) - the
 // Box-Muller transcendentals are the cost of this kernel and run in parallel; (2) the rows' act_dim chains run the recurrence over
 // the tiles, LDS only (the noise state stays in a register from pass to pass), and leave the clipped sample in place; a kept row and
-// the mean row are final already; (3) all threads store the tile.
+// the mean row are final already; (3) all threads store the tile.  The SHARD instance (l2a_icem_sample_shard: one rank of a sharded
+// plan) does all of that for all n rows - a_clip, mean_out and std_out are the same bits - and stores only its window lo <= j < hi of
+// the rollout tensor, as seq_local [h, m * (hi - lo), A] (plan row i * (hi - lo) + (j - lo)); a kept row or the mean row inside the
+// window is a row like any other.
+template <bool SHARD>
 __global__ void __launch_bounds__(256) l2a_icem_sample_k(const IcemSampleParams p) {
 #pragma clang fp contract(off)
     __shared__ float tile[L2A_ICEM_TILE];       // z (or a final value), then the clipped sample
@@ -206,11 +211,12 @@ __global__ void __launch_bounds__(256) l2a_icem_sample_k(const IcemSampleParams 
             const int i = (int)(g - j * p.m);
             const float v = tile[q];
             p.a_clip[g * D + t0 * A + rem] = v;
-            if (p.seq) {
-                // plan row of this candidate (env-major) among the rows of one horizon step
-                const long long prow = (long long)i * p.n + j;
+            if (p.seq && (!SHARD || (j >= p.lo && j < p.hi))) {
+                // plan row of this candidate (env-major) among the rows of one horizon step: all n candidates, SHARD: the window's
+                const long long width = SHARD ? p.hi - p.lo : p.n;
+                const long long prow = (long long)i * width + (SHARD ? j - p.lo : j);
                 const int tt = rem / A;
-                p.seq[((long long)(t0 + tt) * ((long long)p.n * p.m) + prow) * A + (rem - tt * A)] = v;
+                p.seq[((long long)(t0 + tt) * (width * p.m) + prow) * A + (rem - tt * A)] = v;
             }
             if (j == 0) {
                 p.mean_out[(long long)i * D + t0 * A + rem] = mtile[q];
@@ -219,6 +225,48 @@ __global__ void __launch_bounds__(256) l2a_icem_sample_k(const IcemSampleParams 
         }
         __syncthreads();
     }
+}
+
+// What l2a_icem_sample and l2a_icem_sample_shard share: the argument checks (nothing is written or launched when one fails), c, the
+// rows per workgroup and the launch of the kernel's instance.
+template <bool SHARD>
+int icem_sample_launch(l2a_ctx* ctx, const char* who, IcemSampleParams p, void* stream_v) {
+#pragma clang fp contract(off)
+    const std::string w(who);
+    if (!p.mean_in || !p.std_in || !p.shift || !p.sigma0 || !p.low || !p.high || !p.mean_out || !p.std_out || !p.a_clip)
+        return l2a_fail(ctx, L2A_EINVAL, w + ": null pointer");
+    if (p.n < 1 || p.m < 1 || p.h < 1 || p.act_dim < 1 || p.act_dim > 16)
+        return l2a_fail(ctx, L2A_EINVAL, w + ": bad n_it / m / h / act_dim (1 <= act_dim <= 16)");
+    if (p.Kk < 0 || p.Kk > 8192) return l2a_fail(ctx, L2A_EINVAL, w + ": 0 <= Kk <= 8192");
+    if (p.Kk > 0 && (!p.kept_in || !p.kc_in)) return l2a_fail(ctx, L2A_EINVAL, w + ": null kept rows or counts with Kk > 0");
+    if (!(p.rho >= 0.0f) || !(p.rho < 1.0f)) return l2a_fail(ctx, L2A_EINVAL, w + ": rho must lie in [0, 1)");
+    if (SHARD) {
+        if (p.lo < 0 || p.hi > p.n || p.lo > p.hi) return l2a_fail(ctx, L2A_EINVAL, w + ": the window needs 0 <= lo <= hi <= n_it");
+        if (p.hi > p.lo && !p.seq) return l2a_fail(ctx, L2A_EINVAL, w + ": null seq_local for a window that holds candidates");
+        if (p.hi == p.lo) p.seq = nullptr;
+    }
+    const void* ins[] = {p.z, p.mean_in, p.std_in, p.kept_in, p.kc_in, p.shift, p.sigma0, p.low, p.high};
+    const void* outs[] = {p.mean_out, p.std_out, p.a_clip, p.seq};
+    for (size_t a = 0; a < sizeof(outs) / sizeof(outs[0]); ++a) {
+        if (!outs[a]) continue;
+        for (const void* in : ins)
+            if (in == outs[a]) return l2a_fail(ctx, L2A_EINVAL, w + ": an output aliases an input");
+        for (size_t b = 0; b < a; ++b)
+            if (outs[b] == outs[a]) return l2a_fail(ctx, L2A_EINVAL, w + ": two outputs alias");
+    }
+    const long long total = (long long)p.n * p.m * p.h * p.act_dim;
+    if (total > 0x7fffffffLL * 256 || (long long)p.n * p.m > 0x7fffffffLL) return l2a_fail(ctx, L2A_EINVAL, w + ": too many samples");
+    const float r2 = p.rho * p.rho, om = 1.0f - r2;
+    p.c = sqrtf(om);
+    l2a_device_guard guard(ctx->device);
+    // rows per workgroup: as many (up to L2A_ICEM_ROWS) as still leave every thread at most one element per pass
+    const long long rows = (long long)p.n * p.m;
+    const int D = p.h * p.act_dim;
+    p.rpb = 256 / D < 1 ? 1 : (256 / D > L2A_ICEM_ROWS ? L2A_ICEM_ROWS : 256 / D);
+    hipLaunchKernelGGL(l2a_icem_sample_k<SHARD>, dim3((unsigned)((rows + p.rpb - 1) / p.rpb)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream_v), p);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
 }
 
 // ---- the refit -----------------------------------------------------------------------------------------------------------------------
@@ -401,44 +449,29 @@ int l2a_icem_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsig
                     const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0, float rho,
                     const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk, int add_mean, float* mean_out,
                     float* std_out, float* a_clip, float* seq, void* stream_v) {
-#pragma clang fp contract(off)
     if (!ctx) return L2A_EINVAL;
-    const std::string w("l2a_icem_sample");
-    if (!mean_in || !std_in || !shift || !sigma0 || !low || !high || !mean_out || !std_out || !a_clip)
-        return l2a_fail(ctx, L2A_EINVAL, w + ": null pointer");
-    if (n_it < 1 || m < 1 || h < 1 || act_dim < 1 || act_dim > 16)
-        return l2a_fail(ctx, L2A_EINVAL, w + ": bad n_it / m / h / act_dim (1 <= act_dim <= 16)");
-    if (Kk < 0 || Kk > 8192) return l2a_fail(ctx, L2A_EINVAL, w + ": 0 <= Kk <= 8192");
-    if (Kk > 0 && (!kept_in || !kc_in)) return l2a_fail(ctx, L2A_EINVAL, w + ": null kept rows or counts with Kk > 0");
-    if (!(rho >= 0.0f) || !(rho < 1.0f)) return l2a_fail(ctx, L2A_EINVAL, w + ": rho must lie in [0, 1)");
-    const void* ins[] = {z, mean_in, std_in, kept_in, kc_in, shift, sigma0, low, high};
-    const void* outs[] = {mean_out, std_out, a_clip, seq};
-    for (size_t a = 0; a < sizeof(outs) / sizeof(outs[0]); ++a) {
-        if (!outs[a]) continue;
-        for (const void* in : ins)
-            if (in == outs[a]) return l2a_fail(ctx, L2A_EINVAL, w + ": an output aliases an input");
-        for (size_t b = 0; b < a; ++b)
-            if (outs[b] == outs[a]) return l2a_fail(ctx, L2A_EINVAL, w + ": two outputs alias");
-    }
-    const long long total = (long long)n_it * m * h * act_dim;
-    if (total > 0x7fffffffLL * 256 || (long long)n_it * m > 0x7fffffffLL) return l2a_fail(ctx, L2A_EINVAL, w + ": too many samples");
     IcemSampleParams p;
     std::memset(&p, 0, sizeof(p));
     p.z = z; p.seed = seed; p.offset = offset; p.mean_in = mean_in; p.std_in = std_in; p.kept_in = kept_in; p.kc_in = kc_in;
     p.shift = shift; p.sigma0 = sigma0; p.low = low; p.high = high; p.rho = rho;
-    const float r2 = rho * rho, om = 1.0f - r2;
-    p.c = sqrtf(om);
     p.n = n_it; p.m = m; p.h = h; p.act_dim = act_dim; p.Kk = Kk; p.add_mean = add_mean ? 1 : 0;
     p.mean_out = mean_out; p.std_out = std_out; p.a_clip = a_clip; p.seq = seq;
-    l2a_device_guard guard(ctx->device);
-    // rows per workgroup: as many (up to L2A_ICEM_ROWS) as still leave every thread at most one element per pass
-    const long long rows = (long long)n_it * m;
-    const int D = h * act_dim;
-    p.rpb = 256 / D < 1 ? 1 : (256 / D > L2A_ICEM_ROWS ? L2A_ICEM_ROWS : 256 / D);
-    hipLaunchKernelGGL(l2a_icem_sample_k, dim3((unsigned)((rows + p.rpb - 1) / p.rpb)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream_v), p);
-    L2A_HIP(ctx, hipGetLastError());
-    return L2A_OK;
+    return icem_sample_launch<false>(ctx, "l2a_icem_sample", p, stream_v);
+}
+
+int l2a_icem_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                          const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0, float rho,
+                          const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk, int add_mean, int lo, int hi,
+                          float* mean_out, float* std_out, float* a_clip, float* seq_local, void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    IcemSampleParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.z = z; p.seed = seed; p.offset = offset; p.mean_in = mean_in; p.std_in = std_in; p.kept_in = kept_in; p.kc_in = kc_in;
+    p.shift = shift; p.sigma0 = sigma0; p.low = low; p.high = high; p.rho = rho;
+    p.n = n_it; p.m = m; p.h = h; p.act_dim = act_dim; p.Kk = Kk; p.add_mean = add_mean ? 1 : 0;
+    p.mean_out = mean_out; p.std_out = std_out; p.a_clip = a_clip; p.seq = seq_local;
+    p.lo = lo; p.hi = hi;
+    return icem_sample_launch<true>(ctx, "l2a_icem_sample_shard", p, stream_v);
 }
 
 int l2a_icem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, const float* low, const float* high, int n_it, int m,

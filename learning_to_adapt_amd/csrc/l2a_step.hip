@@ -78,7 +78,7 @@ struct l2a_controller {
     // int64 MAX all-reduce - RS: ONE per step, of [keys (m), launch flag, digest, MASK - digest]; CEM: one per iteration, of the returns
     struct {
         bool on = false;                        // (also with world = 1: the same code path with a one-rank collective)
-        int world = 1, lo = 0, hi = 0;
+        int rank = 0, world = 1, lo = 0, hi = 0;
         l2a_reduce_fn reduce = nullptr;         // null: RCCL through the context's communicator (l2a_comm_init)
         void* reduce_arg = nullptr;
         unsigned long long digest = 0;          // what every rank must agree on before the reduced words mean anything
@@ -105,16 +105,19 @@ struct l2a_controller {
     struct cem_state* cem = nullptr;
     // MPPI plan (l2a_mppi_controller_create_device): K iterations of l2a_mppi_sample -> rollout -> l2a_mppi_update, one read-back
     struct mppi_state* mppi = nullptr;
-    struct plan_state* plan = nullptr;          // whichever of the two: what both kinds of plan step share
+    // iCEM plan (l2a_icem_controller_create_device): per iteration l2a_icem_sample -> rollout of pops[it] -> l2a_icem_refit, one read-back
+    struct icem_state* icem = nullptr;
+    struct plan_state* plan = nullptr;          // whichever of the three: what every kind of plan step shares
 };
 
-// What the device-mode plan steps (CEM, MPPI) share: the iterations' returns, the packed result behind ONE read-back and, for one
+// What the device-mode plan steps (CEM, MPPI, iCEM) share: the iterations' returns, the packed result behind ONE read-back and, for one
 // rank of a sharded plan, the words of the per-iteration gather and the verdict accumulated over them.
 struct plan_state {
-    int iters = 0, D = 0, row_floats = 0;       // a result row: the action | return | index bits | ... (CEM: A + 2, MPPI: A + 4 floats)
+    int iters = 0, D = 0, row_floats = 0;       // a result row: the action | return | index bits | ... (CEM: A + 2, MPPI and iCEM: A + 4 floats)
+    size_t rows_at = 0;                         // the rows `plan_finish` decodes start here in `packed` (iCEM: the last iteration's block)
     unsigned long long iter_calls = 0;          // iterations planned so far (the Philox stream's position)
     float* seq = nullptr;                       // [h, m * (hi - lo), act_dim]
-    float* rets = nullptr;                      // [iters, m, n]: every iteration's returns of the latest step
+    float* rets = nullptr;                      // [iters, m, n]: every iteration's returns of the latest step (iCEM: [m, pops[it]] one after another)
     float* lowhigh = nullptr;                   // [2][act_dim] fp32 bounds
     float* packed_dev = nullptr;                // m result rows (CEM: + mean [m, D], std [m, D])
     float* packed_host = nullptr;               // page-locked
@@ -160,6 +163,34 @@ struct mppi_state : plan_state {
     std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts from zeros
     int cur = 0, last = 0;                      // the committed mean | the mean the step in flight ends on
     float* result_host = nullptr;               // page-locked [3 m D + iters m n]: l2a_mppi_controller_result's one copy
+};
+
+// Device-mode iCEM (`MPCController.get_icem_action`): per iteration l2a_icem_sample (sharded: l2a_icem_sample_shard over this rank's
+// window of the iteration's population pops[it]), the rollout of pops[it] candidates (sharded: + the gather), l2a_icem_refit over all
+// of them into result row block `it`; the iters * m result rows are the step's one read-back.  Philox offsets (iter_calls + it) * n *
+// m * D: the stride is the full n.  Mean, spread, kept rows and counts persist on the device, three copies each that rotate together:
+// a step reads copy `cur` and writes the two others in turn, and `cur`, iter_calls and the reset marks move in `finish` only.
+struct icem_state : plan_state {
+    int K = 0, Kk = 0, add_mean = 0;
+    float alpha = 0.0f, rho = 0.0f;
+    std::vector<int> pops;                      // [iters]: the caller's populations
+    std::vector<size_t> ret_at;                 // [iters + 1]: iteration it's table [m, pops[it]] starts at rets + ret_at[it]
+    float sigma32[16] = {0};                    // (the digest carries its bits)
+    float* sigma = nullptr;                     // [act_dim] device
+    // one allocation in front of `rets`: mean [3][m, D] | std [3][m, D] | kept [3][m, max(Kk, 1), D] | kc [3][m]
+    float* mean[3] = {nullptr, nullptr, nullptr};
+    float* std[3] = {nullptr, nullptr, nullptr};
+    float* kept[3] = {nullptr, nullptr, nullptr};
+    int* kc[3] = {nullptr, nullptr, nullptr};
+    size_t head_floats = 0;                     // the floats of that allocation in front of `rets`
+    float* a_clip = nullptr;                    // [n, m, D]
+    int* work = nullptr;                        // [m, K]: the refit's scratch
+    int* shift = nullptr;                       // device [4][m]: all +1 | all 0 | all -1 | the step's own mix
+    int* shift_host = nullptr;                  // page-locked [m]: the mix of the step in flight (it stays for a replay)
+    const int* first = nullptr;                 // iteration 0's shift vector of the step in flight
+    std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts afresh
+    int cur = 0, last = 0;                      // the committed copy | the copy the step in flight ends on
+    float* result_host = nullptr;               // page-locked [head_floats + m * sum(pops)]: l2a_icem_controller_result's one copy
 };
 
 extern "C" unsigned long long l2a_mt19937_state_digest(const void* addr);      // csrc/l2a_rng.c
@@ -285,7 +316,7 @@ void kick_arm(void* arg) {
     (void)l2a_ahead_arm(a.chain, a.np_addr);
 }
 
-// ---- create: all 14 entry points fill a step_cfg and share everything below ----------------------------------------------------------
+// ---- create: all 16 entry points fill a step_cfg and share everything below ----------------------------------------------------------
 struct step_cfg {
     const char* who;                            // the entry point (the prefix of its error texts)
     l2a_model* mlp;
@@ -311,7 +342,11 @@ struct step_cfg {
     float alpha = 0.0f;
     bool mppi = false;                          // an MPPI plan (`iters` as CEM's)
     float kappa = 0.0f, beta = 0.0f;
-    const double* sigma = nullptr;              // [act_dim]
+    const double* sigma = nullptr;              // [act_dim] (iCEM: sigma0)
+    bool icem = false;                          // an iCEM plan (`iters`, `alpha` as CEM's, `sigma` as MPPI's)
+    const int* pops = nullptr;                  // [iters]
+    int K = 0, Kk = 0, add_mean = 0;
+    float rho = 0.0f;
 
     step_cfg& parity(void* addr, int threads) { np_addr = addr; rng_threads = threads; return *this; }
     step_cfg& device(unsigned long long s) { device_rng = true; seed = s; return *this; }
@@ -322,6 +357,10 @@ struct step_cfg {
     }
     step_cfg& mppi_plan(int it, float kap, float bet, const double* sig, unsigned long long s) {
         mppi = true; iters = it; kappa = kap; beta = bet; sigma = sig;
+        return device(s);
+    }
+    step_cfg& icem_plan(int it, const int* pop, int k, int kk, float a, float r, const double* sig, int add, unsigned long long s) {
+        icem = true; iters = it; pops = pop; K = k; Kk = kk; alpha = a; rho = r; sigma = sig; add_mean = add ? 1 : 0;
         return device(s);
     }
 };
@@ -362,6 +401,28 @@ int check_shape(const step_cfg& f) {
             return refuse(f, L2A_EINVAL, "too many samples");
         return L2A_OK;
     }
+    if (f.icem) {
+        // the limits of l2a_icem_sample and l2a_icem_refit on every iteration, so that no step can fail on its arguments
+        if (bad_mnh || bad_act)
+            return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1, 1 <= act_dim <= 16");
+        if (f.iters < 1) return refuse(f, L2A_EINVAL, "needs iters >= 1");
+        if (f.K < 1 || f.K > 8192) return refuse(f, L2A_EINVAL, "needs 1 <= K <= 8192 elites");
+        if (f.Kk < 0 || f.Kk > f.K) return refuse(f, L2A_EINVAL, "needs 0 <= Kk <= K kept elites");
+        if (!(f.alpha >= 0.0f) || !(f.alpha < 1.0f)) return refuse(f, L2A_EINVAL, "alpha must lie in [0, 1)");
+        if (!(f.rho >= 0.0f) || !(f.rho < 1.0f)) return refuse(f, L2A_EINVAL, "rho must lie in [0, 1)");
+        for (int k = 0; k < f.act_dim; ++k)
+            if (!std::isfinite((float)f.sigma[k]) || !(f.sigma[k] >= 0.0)) return refuse(f, L2A_EINVAL, "sigma0 must be finite and non-negative");
+        if ((size_t)f.K * sizeof(int) + L2A_ICEM_REFIT_STATIC_LDS > (size_t)f.ctx->lds_per_block)
+            return refuse(f, L2A_EINVAL, "more elites than the statistics' list fits in LDS (l2a_icem_refit)");
+        for (int it = 0; it < f.iters; ++it) {
+            if (f.pops[it] < 1 || f.pops[it] > n) return refuse(f, L2A_EINVAL, "every pops[it] must lie in 1 .. n");
+            if ((size_t)f.pops[it] * sizeof(float) > (size_t)f.ctx->lds_per_block)
+                return refuse(f, L2A_EINVAL, "more candidates than an env's returns fit in LDS (l2a_icem_refit)");
+        }
+        if ((long long)n * m * h * f.act_dim > 0x7fffffffLL * 256 || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
+            return refuse(f, L2A_EINVAL, "too many samples");
+        return L2A_OK;
+    }
     if (!f.cem) {
         if (bad_mnh) return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1");
         if (bad_act) return refuse(f, L2A_EINVAL, "the host draw takes 1 <= act_dim <= 16");
@@ -388,7 +449,7 @@ void init_common(l2a_controller* c, const step_cfg& f) {
     c->ahead.np_addr = f.np_addr;
     c->ahead.rng_threads = f.rng_threads < 1 ? 1 : f.rng_threads;
     c->device.on = f.device_rng; c->device.seed = f.seed;
-    c->shard.on = f.sharded; c->shard.world = f.world; c->shard.reduce = f.reduce; c->shard.reduce_arg = f.reduce_arg;
+    c->shard.on = f.sharded; c->shard.rank = f.rank; c->shard.world = f.world; c->shard.reduce = f.reduce; c->shard.reduce_arg = f.reduce_arg;
     c->shard.lo = (int)((long long)f.rank * f.n / f.world);         // contiguous candidate ranges (MPCController._shard_range)
     c->shard.hi = (int)((long long)(f.rank + 1) * f.n / f.world);
     const int n_local = c->shard.hi - c->shard.lo;
@@ -441,15 +502,16 @@ void alloc_rs(l2a_controller* c, const step_cfg& f) {
     c->shard.payload_host = alloc<unsigned long long>(c, MEM_PINNED, (size_t)c->m + 3);
 }
 
-// A device-mode plan (CEM, MPPI): what both kinds allocate, `packed` floats of result behind the one read-back.  The unsharded
+// A device-mode plan (CEM, MPPI, iCEM): what every kind allocates, `packed` floats of result behind the one read-back.  The unsharded
 // controller is rank 0 of a world of 1 without the collective's buffers.  `rets_head`: floats the caller keeps in front of the
-// returns in the same allocation (MPPI: its means, so that ONE copy brings means and returns back on request).
-void alloc_plan(l2a_controller* c, const step_cfg& f, int row_floats, size_t packed, size_t rets_head = 0) {
+// returns in the same allocation (MPPI: its means, iCEM: its state, so that ONE copy brings them and the returns back on request).
+// `window`: the most candidates this rank rolls out in one iteration, where that is not hi - lo (iCEM: the window moves with pops[it]).
+void alloc_plan(l2a_controller* c, const step_cfg& f, int row_floats, size_t packed, size_t rets_head = 0, size_t window = 0) {
     plan_state* q = c->plan;
     const int A = c->act_dim;
     q->iters = f.iters; q->D = c->h * A; q->row_floats = row_floats;
     const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * q->D;
-    const size_t n_local = (size_t)(c->shard.hi - c->shard.lo), n_alloc = n_local > 0 ? n_local : 1;
+    const size_t n_local = window ? window : (size_t)(c->shard.hi - c->shard.lo), n_alloc = n_local > 0 ? n_local : 1;
     q->packed_floats = packed + (f.sharded ? 3 : 0);
     alloc_launch(c);
     q->seq = alloc<float>(c, MEM_DEVICE, n_alloc * md);
@@ -504,6 +566,51 @@ void alloc_mppi(l2a_controller* c, const step_cfg& f) {
     upload(c, q->shift, rows.data(), sizeof(int) * rows.size());
 }
 
+// This rank's window of a population of `n_it`: contiguous ranges in integer arithmetic, `init_common`'s rule.
+void icem_window(const l2a_controller* c, int n_it, int* lo, int* hi) {
+    *lo = (int)((long long)c->shard.rank * n_it / c->shard.world);
+    *hi = (int)((long long)(c->shard.rank + 1) * n_it / c->shard.world);
+}
+
+void alloc_icem(l2a_controller* c, const step_cfg& f) {
+    icem_state* q = c->icem;
+    const int A = c->act_dim;
+    q->K = f.K; q->Kk = f.Kk; q->add_mean = f.add_mean; q->alpha = f.alpha; q->rho = f.rho;
+    q->pops.assign(f.pops, f.pops + f.iters);
+    q->ret_at.assign((size_t)f.iters + 1, 0);
+    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A, kd = m * (size_t)(f.Kk > 0 ? f.Kk : 1) * c->h * A;
+    size_t window = 0;
+    for (int it = 0; it < f.iters; ++it) {
+        q->ret_at[it + 1] = q->ret_at[it] + m * (size_t)f.pops[it];
+        int lo = 0, hi = 0;
+        icem_window(c, f.pops[it], &lo, &hi);
+        if ((size_t)(hi - lo) > window) window = (size_t)(hi - lo);
+    }
+    q->head_floats = 3 * (2 * md + kd + m);
+    alloc_plan(c, f, A + 4, (size_t)f.iters * m * (A + 4), q->head_floats, window ? window : 1);
+    q->rows_at = (size_t)(f.iters - 1) * m * (A + 4);
+    float* head = q->rets ? q->rets - q->head_floats : nullptr;
+    for (int s = 0; s < 3 && head; ++s) {
+        q->mean[s] = head + s * md;
+        q->std[s] = head + 3 * md + s * md;
+        q->kept[s] = head + 6 * md + s * kd;
+        q->kc[s] = reinterpret_cast<int*>(head + 6 * md + 3 * kd) + s * m;
+    }
+    if (head && c->mem_err == hipSuccess) c->mem_err = hipMemset(head, 0, sizeof(float) * q->head_floats);
+    q->result_host = alloc<float>(c, MEM_PINNED, q->head_floats + q->ret_at[f.iters]);
+    q->a_clip = alloc<float>(c, MEM_DEVICE, n * md);
+    q->work = alloc<int>(c, MEM_DEVICE, m * (size_t)f.K);
+    q->sigma = alloc<float>(c, MEM_DEVICE, (size_t)A);
+    q->shift = alloc<int>(c, MEM_DEVICE, 4 * m);
+    q->shift_host = alloc<int>(c, MEM_PINNED, m);
+    q->fresh.assign(m, 1);                      // every env starts afresh
+    for (int k = 0; k < A; ++k) q->sigma32[k] = (float)f.sigma[k];
+    upload(c, q->sigma, q->sigma32, sizeof(float) * A);
+    std::vector<int> rows(4 * m, 0);
+    for (size_t i = 0; i < m; ++i) { rows[i] = 1; rows[2 * m + i] = -1; }
+    upload(c, q->shift, rows.data(), sizeof(int) * rows.size());
+}
+
 int create(step_cfg f) {
     if (!f.mlp && !f.rnn) return L2A_EINVAL;
     resolve(f);
@@ -512,18 +619,22 @@ int create(step_cfg f) {
     if (!f.out) return refuse(f, L2A_EINVAL, "out is null");
     *f.out = nullptr;
     if (f.mppi && !f.sigma) return refuse(f, L2A_EINVAL, "null sigma");
+    if (f.icem && f.rnn) return refuse(f, L2A_EINVAL, "an iCEM plan takes an MLP model");
+    if (f.icem && (!f.sigma || !f.pops)) return refuse(f, L2A_EINVAL, "null pops / sigma0");
     if (!f.low || !f.high || !f.reward || (!f.np_addr && !f.device_rng))
-        return refuse(f, L2A_EINVAL, (f.cem || f.mppi) ? "null low / high / reward" : "null low / high / reward / generator state address");
+        return refuse(f, L2A_EINVAL, (f.cem || f.mppi || f.icem) ? "null low / high / reward" : "null low / high / reward / generator state address");
     rc = check_shape(f);
     if (rc != L2A_OK) return rc;
     l2a_controller* c = new (std::nothrow) l2a_controller();
     if (c && f.cem) c->plan = c->cem = new (std::nothrow) cem_state();
     if (c && f.mppi) c->plan = c->mppi = new (std::nothrow) mppi_state();
-    if (!c || ((f.cem || f.mppi) && !c->plan)) { delete c; return refuse(f, L2A_EHIP, "out of memory"); }
+    if (c && f.icem) c->plan = c->icem = new (std::nothrow) icem_state();
+    if (!c || ((f.cem || f.mppi || f.icem) && !c->plan)) { delete c; return refuse(f, L2A_EHIP, "out of memory"); }
     init_common(c, f);
     l2a_device_guard guard(f.ctx->device);
     if (f.cem) alloc_cem(c, f);
     else if (f.mppi) alloc_mppi(c, f);
+    else if (f.icem) alloc_icem(c, f);
     else alloc_rs(c, f);
     if (c->mem_err != hipSuccess) {
         const hipError_t e = c->mem_err;
@@ -660,12 +771,13 @@ unsigned long long mppi_digest(const l2a_controller* c) {
     return d;
 }
 
-// One iteration's returns of every candidate into `rets` [m, n].  Unsharded: the rollout of all n.  Sharded: this rank's rollouts
-// -> words -> the ONE collective -> every rank's returns.
-int gather_returns(l2a_controller* c, float* rets) {
+// One iteration's returns of every candidate of a population of `n` into `rets` [m, n].  Unsharded: the rollout of all n.  Sharded:
+// this rank's rollouts of its window [lo, hi) -> words -> the ONE collective -> every rank's returns.  (CEM and MPPI: the plan's n
+// and the controller's window, every iteration; iCEM: the iteration's population and its window of it.)
+int gather_returns(l2a_controller* c, float* rets, int n, int lo, int hi) {
     plan_state* q = c->plan;
-    if (!c->shard.on) return rollout(c, q->seq, c->n, 0, rets);
-    const int m = c->m, n = c->n, lo = c->shard.lo, hi = c->shard.hi;
+    if (!c->shard.on) return rollout(c, q->seq, n, 0, rets);
+    const int m = c->m;
     int rc = L2A_OK;
     if (hi > lo) rc = rollout(c, q->seq, hi - lo, lo, q->rets_local);
     if (rc == L2A_OK) rc = l2a_cem_shard_pack(c->ctx, q->rets_local, m, n, lo, hi, c->shard.digest, q->words, c->stream);
@@ -707,7 +819,7 @@ int cem_launch(l2a_controller* c) {
     ctx->stamps_us[1] = l2a_now_us();
     for (int it = 0; it < q->iters; ++it) {
         float* rets = q->rets + (size_t)it * m * n;
-        rc = gather_returns(c, rets);
+        rc = gather_returns(c, rets, n, lo, hi);
         if (rc != L2A_OK) return rc;
         if (it + 1 < q->iters) {
             rc = l2a_cem_refit_sample(ctx, rets, q->a_clip[cur], n, m, h, A, q->k, q->reference, q->alpha, nullptr, seed,
@@ -765,7 +877,7 @@ int mppi_launch(l2a_controller* c) {
         if (rc != L2A_OK) return rc;
         if (it == 0) ctx->stamps_us[1] = l2a_now_us();
         float* rets = q->rets + (size_t)it * m * n;
-        rc = gather_returns(c, rets);
+        rc = gather_returns(c, rets, n, lo, hi);
         if (rc == L2A_OK) rc = l2a_mppi_update(ctx, rets, q->a_clip, n, m, h, A, q->kappa, q->mean[dst], q->packed_dev, c->stream);
         if (rc != L2A_OK) return rc;
         src = dst;
@@ -788,8 +900,91 @@ void mppi_first_shift(l2a_controller* c) {
     }
 }
 
-// ---- what the CEM and the MPPI step share: begin, the verdicts, finish ---------------------------------------------------------------
-int plan_launch(l2a_controller* c) { return c->cem ? cem_launch(c) : mppi_launch(c); }
+// ---- iCEM (device mode) ---------------------------------------------------------------------------------------------------------
+// What every rank of a sharded iCEM step must share: the controller kind (3), how the controller was built - the populations and the
+// planner's constants by their bits -, where its Philox stream stands, and the step's fresh marks.
+unsigned long long icem_digest(const l2a_controller* c) {
+    const icem_state* q = c->icem;
+    const auto bits = [](float x) { unsigned int b = 0; std::memcpy(&b, &x, sizeof(b)); return (unsigned long long)b; };
+    const unsigned long long v[] = {3ull, c->device.seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n,
+                                    (unsigned long long)c->h, (unsigned long long)q->iters, (unsigned long long)c->shard.world};
+    unsigned long long d = 0x9E3779B97F4A7C15ull;
+    for (unsigned long long x : v) d = digest_mix(d, x);
+    for (int it = 0; it < q->iters; ++it) d = digest_mix(d, (unsigned long long)q->pops[it]);
+    d = digest_mix(d, (unsigned long long)q->K);
+    d = digest_mix(d, (unsigned long long)q->Kk);
+    d = digest_mix(d, (unsigned long long)q->add_mean);
+    d = digest_mix(d, bits(q->alpha));
+    d = digest_mix(d, bits(q->rho));
+    for (int k = 0; k < c->act_dim; ++k) d = digest_mix(d, bits(q->sigma32[k]));
+    for (int i = 0; i < c->m; ++i) d = digest_mix(d, q->fresh[i] ? 1ull : 0ull);
+    return d;
+}
+
+// Everything of one iCEM plan step, in stream order on `stream`; nothing on the host waits.  Reads the committed copy of the state and
+// the reset marks and writes neither: a replay launches the same step again.
+int icem_launch(l2a_controller* c) {
+    l2a_ctx* ctx = c->ctx;
+    icem_state* q = c->icem;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    const int m = c->m, n = c->n, h = c->h, A = c->act_dim, Kk = q->Kk;
+    const unsigned long long per_iter = (unsigned long long)n * m * q->D, seed = c->device.seed;      // (the stride is the full n)
+    const bool sharded = c->shard.on;
+    const float* low = q->lowhigh;
+    const float* high = q->lowhigh + A;
+    l2a_device_guard guard(ctx->device);
+    if (q->first == q->shift + 3 * m)           // the step's own mix of new and running envs
+        L2A_HIP(ctx, hipMemcpyAsync(q->shift + 3 * m, q->shift_host, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream));
+    if (sharded) L2A_HIP(ctx, hipMemsetAsync(q->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
+    int src = q->cur;
+    for (int it = 0; it < q->iters; ++it) {
+        int dst = 0;
+        while (dst == src || dst == q->cur) ++dst;          // neither the copy this iteration reads nor the committed one
+        const int n_it = q->pops[it];
+        int lo = 0, hi = n_it;
+        if (sharded) icem_window(c, n_it, &lo, &hi);
+        const int* shift = it == 0 ? q->first : q->shift + m;
+        const unsigned long long offset = (q->iter_calls + it) * per_iter;
+        const int add_mean = (q->add_mean && it == q->iters - 1) ? 1 : 0;
+        const float* kept_in = Kk ? q->kept[src] : nullptr;
+        const int* kc_in = Kk ? q->kc[src] : nullptr;
+        // (sharded: every rank samples all n_it rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
+        int rc = sharded ? l2a_icem_sample_shard(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma, q->rho,
+                                                 low, high, n_it, m, h, A, Kk, add_mean, lo, hi, q->mean[dst], q->std[dst], q->a_clip, q->seq,
+                                                 c->stream)
+                         : l2a_icem_sample(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma, q->rho, low,
+                                           high, n_it, m, h, A, Kk, add_mean, q->mean[dst], q->std[dst], q->a_clip, q->seq, c->stream);
+        if (rc != L2A_OK) return rc;
+        if (it == 0) ctx->stamps_us[1] = l2a_now_us();
+        float* rets = q->rets + q->ret_at[it];
+        rc = gather_returns(c, rets, n_it, lo, hi);
+        if (rc == L2A_OK)
+            rc = l2a_icem_refit(ctx, rets, q->a_clip, low, high, n_it, m, h, A, q->K, Kk, q->alpha, q->work, q->mean[dst], q->std[dst],
+                                Kk ? q->kept[dst] : nullptr, q->kc[dst], q->packed_dev + (size_t)it * m * q->row_floats, c->stream);
+        if (rc != L2A_OK) return rc;
+        src = dst;
+    }
+    q->last = src;
+    return read_back(c);
+}
+
+// Iteration 0's shift vector of the step about to be launched (mppi_first_shift's scheme): -1 for an env that is new or was reset,
+// +1 for the others.
+void icem_first_shift(l2a_controller* c) {
+    icem_state* q = c->icem;
+    const int m = c->m;
+    int fresh = 0;
+    for (int i = 0; i < m; ++i) fresh += q->fresh[i] ? 1 : 0;
+    if (fresh == 0) q->first = q->shift;
+    else if (fresh == m) q->first = q->shift + 2 * m;
+    else {
+        for (int i = 0; i < m; ++i) q->shift_host[i] = q->fresh[i] ? -1 : 1;
+        q->first = q->shift + 3 * m;
+    }
+}
+
+// ---- what the CEM, the MPPI and the iCEM step share: begin, the verdicts, finish -----------------------------------------------------
+int plan_launch(l2a_controller* c) { return c->cem ? cem_launch(c) : c->mppi ? mppi_launch(c) : icem_launch(c); }
 
 int plan_begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
     l2a_ctx* ctx = c->ctx;
@@ -806,7 +1001,8 @@ int plan_begin(l2a_controller* c, const double* obs, const float* c0, const floa
     stage_obs(c, obs, c0, h0, c1, h1, stream);
     c->result = L2A_OK;
     if (c->mppi) mppi_first_shift(c);
-    if (c->shard.on) c->shard.digest = c->cem ? cem_digest(c) : mppi_digest(c);
+    if (c->icem) icem_first_shift(c);
+    if (c->shard.on) c->shard.digest = c->cem ? cem_digest(c) : c->mppi ? mppi_digest(c) : icem_digest(c);
     const int rc = plan_launch(c);
     if (rc != L2A_OK) return rc;
     ctx->stamps_us[3] = l2a_now_us();
@@ -830,13 +1026,16 @@ int plan_verdict_sharded(l2a_controller* c) {
     *ctx->status_host = 0;
     unsigned int verdict[3];
     std::memcpy(verdict, q->packed_host + (q->packed_floats - 3), sizeof(verdict));
-    const std::string kind = c->cem ? "sharded CEM" : "sharded MPPI";
+    const std::string kind = c->cem ? "sharded CEM" : c->mppi ? "sharded MPPI" : "sharded iCEM";
     if (verdict[2] != 0)
         return fail(ctx, L2A_ESTATE, kind + (c->cem ? " needs identically built controllers in step on every rank (same seed, step count, "
                                                       "m, n, h, iters, num_elites, mode, alpha and world): the ranks' digests differ"
-                                                    : " needs identically built controllers in step on every rank (same seed, step count, "
-                                                      "m, n, h, iters, kappa, beta, sigma and world, and the same envs reset): the ranks' "
-                                                      "digests differ"));
+                                           : c->mppi ? " needs identically built controllers in step on every rank (same seed, step count, "
+                                                       "m, n, h, iters, kappa, beta, sigma and world, and the same envs reset): the ranks' "
+                                                       "digests differ"
+                                                     : " needs identically built controllers in step on every rank (same seed, step count, "
+                                                       "m, n, h, iters, populations, K, Kk, add_mean, alpha, rho, sigma0 and world, and the "
+                                                       "same envs reset): the ranks' digests differ"));
     if (verdict[1] != 0)
         return fail(ctx, L2A_ESTATE, kind + ": " + std::to_string(verdict[1]) + " returns of this step were contributed by no rank "
                                      "(the collective did not reduce over every rank of the plan)");
@@ -845,7 +1044,8 @@ int plan_verdict_sharded(l2a_controller* c) {
 
 // Wait for the packed result; a launch flagged invalid (a tile-split partner that was not co-resident) repeats the whole step unsplit
 // with the same Philox offsets - the same bits - as get_cem_action_device's and get_mppi_action's retry does (sharded: all ranks
-// together).  Only a step that got this far moves the controller on: the stream position, and MPPI's mean and reset marks.
+// together).  Only a step that got this far moves the controller on: the stream position, MPPI's mean and reset marks, iCEM's state
+// (mean, spread, kept rows and counts move as one index) and reset marks.
 int plan_finish(l2a_controller* c, double* action_out, long long* index_out, float* return_out) {
     l2a_ctx* ctx = c->ctx;
     if (!action_out) return fail(ctx, L2A_EINVAL, "l2a_controller_finish: null action_out");
@@ -860,7 +1060,7 @@ int plan_finish(l2a_controller* c, double* action_out, long long* index_out, flo
     const double t2 = l2a_now_us();
     const int A = c->act_dim, W = q->row_floats;
     for (int i = 0; i < c->m; ++i) {
-        const float* r = q->packed_host + (size_t)i * W;    // the action | the return | the index's bits | ...
+        const float* r = q->packed_host + q->rows_at + (size_t)i * W;   // the action | the return | the index's bits | ...
         int idx = 0;
         std::memcpy(&idx, r + A + 1, sizeof(int));
         for (int k = 0; k < A; ++k) action_out[(size_t)i * A + k] = (double)r[k];
@@ -871,6 +1071,10 @@ int plan_finish(l2a_controller* c, double* action_out, long long* index_out, flo
     if (c->mppi) {
         c->mppi->cur = c->mppi->last;
         c->mppi->fresh.assign((size_t)c->m, 0);
+    }
+    if (c->icem) {
+        c->icem->cur = c->icem->last;
+        c->icem->fresh.assign((size_t)c->m, 0);
     }
     record_stages(c, t2, l2a_now_us());
     return result;
@@ -1078,7 +1282,7 @@ int step(l2a_controller* c, const double* obs, const float* c0, const float* h0,
 
 extern "C" {
 
-// The 14 create entry points: each names itself, its model and its options; `create` does the rest.
+// The 16 create entry points: each names itself, its model and its options; `create` does the rest.
 int l2a_controller_create(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
                           const l2a_reward* reward, void* np_state_addr, int rng_threads, l2a_controller** out) {
     return create(step_cfg{"l2a_controller_create", model, nullptr, m, n, h, low, high, discount, reward, out}.parity(np_state_addr, rng_threads));
@@ -1231,6 +1435,67 @@ int l2a_mppi_controller_result(l2a_controller* c, float* mean_out, float* ess_ou
     return L2A_OK;
 }
 
+int l2a_icem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                      const l2a_reward* reward, int iters, const int* pops, int K, int Kk, float alpha, float rho,
+                                      const double* sigma0, int add_mean, unsigned long long seed, l2a_controller** out) {
+    return create(step_cfg{"l2a_icem_controller_create_device", model, nullptr, m, n, h, low, high, discount, reward, out}
+                      .icem_plan(iters, pops, K, Kk, alpha, rho, sigma0, add_mean, seed));
+}
+
+int l2a_icem_controller_create_sharded_device(l2a_model* model, int m, int n, int h, const double* low, const double* high, double discount,
+                                              const l2a_reward* reward, int iters, const int* pops, int K, int Kk, float alpha, float rho,
+                                              const double* sigma0, int add_mean, unsigned long long seed, int rank, int world,
+                                              l2a_reduce_fn reduce, void* reduce_arg, l2a_controller** out) {
+    return create(step_cfg{"l2a_icem_controller_create_sharded_device", model, nullptr, m, n, h, low, high, discount, reward, out}
+                      .icem_plan(iters, pops, K, Kk, alpha, rho, sigma0, add_mean, seed).shard(rank, world, reduce, reduce_arg));
+}
+
+int l2a_icem_controller_reset(l2a_controller* c, const unsigned char* dones) {
+    if (!c) return L2A_EINVAL;
+    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_reset: not an iCEM controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_reset: a step is in flight (l2a_controller_finish)");
+    for (int i = 0; i < c->m; ++i)
+        if (!dones || dones[i]) c->icem->fresh[i] = 1;
+    return L2A_OK;
+}
+
+int l2a_icem_controller_reseed(l2a_controller* c, unsigned long long seed) {
+    if (!c) return L2A_EINVAL;
+    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_reseed: not an iCEM controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_reseed: a step is in flight (l2a_controller_finish)");
+    c->device.seed = seed;
+    c->icem->iter_calls = 0;
+    return L2A_OK;
+}
+
+int l2a_icem_controller_result(l2a_controller* c, float* mean_out, float* std_out, float* kept_out, int* kc_out, float* heads_out,
+                               float* returns_out) {
+    if (!c) return L2A_EINVAL;
+    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_result: not an iCEM controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_result: a step is in flight (l2a_controller_finish)");
+    if (c->steps == 0) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_result: no step has finished yet");
+    icem_state* q = c->icem;
+    const size_t m = (size_t)c->m, md = m * q->D, kd = m * (size_t)q->Kk * q->D;
+    if (heads_out) std::memcpy(heads_out, q->packed_host, sizeof(float) * (size_t)q->iters * m * q->row_floats);
+    if (!mean_out && !std_out && !kept_out && !kc_out && !returns_out) return L2A_OK;
+    // ONE copy to page-locked memory on the step's stream - the state's three copies and, when asked for, the returns behind them - and
+    // one wait
+    const size_t nr = q->ret_at[q->iters];
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    l2a_device_guard guard(c->ctx->device);
+    L2A_HIP(c->ctx, hipMemcpyAsync(q->result_host, q->mean[0], sizeof(float) * (q->head_floats + (returns_out ? nr : 0)),
+                                   hipMemcpyDeviceToHost, stream));
+    L2A_HIP(c->ctx, hipStreamSynchronize(stream));
+    const float* host = q->result_host;
+    const size_t cur = (size_t)q->cur;
+    if (mean_out) std::memcpy(mean_out, host + (q->mean[cur] - q->mean[0]), sizeof(float) * md);
+    if (std_out) std::memcpy(std_out, host + (q->std[cur] - q->mean[0]), sizeof(float) * md);
+    if (kept_out && kd) std::memcpy(kept_out, host + (q->kept[cur] - q->mean[0]), sizeof(float) * kd);
+    if (kc_out) std::memcpy(kc_out, host + (reinterpret_cast<float*>(q->kc[cur]) - q->mean[0]), sizeof(int) * m);
+    if (returns_out) std::memcpy(returns_out, host + q->head_floats, sizeof(float) * nr);
+    return L2A_OK;
+}
+
 void l2a_controller_destroy(l2a_controller* c) {
     if (!c) return;
     if (c->ahead.chain) l2a_ahead_destroy(c->ahead.chain);    // joins the producer: no upload is in flight afterwards
@@ -1240,6 +1505,7 @@ void l2a_controller_destroy(l2a_controller* c) {
     release(c);
     delete c->cem;
     delete c->mppi;
+    delete c->icem;
     delete c;
 }
 

@@ -45,7 +45,10 @@ range -, an iteration places the kept elites first and draws the rest with AR(1)
 (``icem_rho``), the population shrinks by ``icem_decay`` per iteration down to twice the elites, ``percent_elites`` and ``alpha`` refit
 mean and spread, ``icem_keep`` of the elites are kept, ``icem_add_mean`` adds the mean itself to the last of the ``icem_iters``
 iterations, and the best candidate's first action is returned, ``get_icem_action``; needs ``rng="device"``; ``reset(dones)`` restarts
-the marked envs' plans; one GPU, the Python loop only),
+the marked envs' plans), ``native_icem_step`` (off by default: the iCEM plan step through the C controller,
+``l2a_icem_controller_create_device`` - the only way to shard an iCEM plan over torch.distributed ranks:
+``l2a_icem_controller_create_sharded_device``, one rank each - bit-identical to ``get_icem_action``, ``policies/native_icem_step.py``;
+reward programs, reward models and particle plans keep the Python loop),
 ``ensemble_planning`` (``"mean"``, the default: the members of an ``MLPDynamicsModel(ensemble_size=E)`` share one state, their
 deltas averaged at every horizon step; ``"particles"``: PETS-style trajectory sampling - every member rolls every candidate out as a
 trajectory of its own and a candidate's score is the mean of its E returns less ``risk_coef`` times their standard deviation,
@@ -108,6 +111,7 @@ class MPCController(Policy, Serializable):
             icem_rho=0.5,
             icem_sigma=None,
             icem_add_mean=True,
+            native_icem_step=False,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -153,6 +157,10 @@ class MPCController(Policy, Serializable):
         self.icem_rho = float(icem_rho)
         self.icem_sigma = icem_sigma
         self.icem_add_mean = bool(icem_add_mean)
+        self.native_icem_step = bool(native_icem_step)
+        if self.native_icem_step and (use_cem or self.use_mppi):
+            raise _lib.L2AError("native_icem_step is the iCEM planner's C controller step (use_icem=True): with use_cem it is "
+                                "native_cem_step, with use_mppi native_mppi_step")
         if self.use_icem:
             if use_cem or self.use_mppi:
                 raise ValueError("use_icem, use_cem and use_mppi are three planners: choose one")
@@ -201,6 +209,8 @@ class MPCController(Policy, Serializable):
         self._cemstep_no = None     # key of a sharded CEM controller that could not be built (the collective's dry run failed)
         self._mppistep = None       # NativeMppiStep (MPPI l2a_controller): the whole MPPI plan step in one C call
         self._mppi_side = None      # which side plans (and holds the persistent mean): None until the first MPPI step, then "c" / "python"
+        self._icemstep = None       # NativeIcemStep (iCEM l2a_controller): the whole iCEM plan step in one C call
+        self._icem_side = None      # which side plans (and holds mean, spread and kept elites): None until the first iCEM step, then "c" / "python"
         self._cem_first_chunk = 4   # horizon steps of the first chunk of a pipelined CEM rollout (0: equal chunks)
         self.last_plan = None       # diagnostics of the latest fused plan (returns, keys, ...)
         self._particles = None      # device tensors of the latest particle rollout (`particle_diagnostics`)
@@ -1599,6 +1609,9 @@ class MPCController(Policy, Serializable):
         elites; ``None``, or a number of envs other than the plan's, starts all of them afresh.  Without ``use_icem`` nothing happens."""
         if not self.use_icem:
             return
+        st = self._icemstep
+        if st is not None and st.pid == os.getpid():        # the C controller holds the plan: the marks go to it
+            st.reset(None if dones is None or len(dones) != st.m else dones)
         fresh = self._bufs.get("icem_fresh")
         if dones is None or fresh is None or len(fresh) != len(dones):
             self._bufs["icem_fresh"] = None
@@ -1611,6 +1624,84 @@ class MPCController(Policy, Serializable):
         return None
 
     icem_trace_returns = False      # copy EVERY iteration's returns into `last_plan["icem_trace"]` (tests); the last one's always come
+
+    icem_fetch_returns = True       # `_native_icem_step`: copy the returns into `last_plan` on every step (the last iteration's table;
+                                    # with `icem_trace_returns` every iteration's)
+
+    def _native_icem_step(self, observations):
+        """The iCEM plan step through the C controller (``l2a_icem_controller_create_device``; at ``world > 1`` this rank's
+        ``l2a_icem_controller_create_sharded_device``, whose per-iteration gather of the returns is the int64 MAX all-reduce of
+        ``m * pops[it] + 3`` words through ``_reduce_payload`` - or the library's communicator, ``L2A_NATIVE_COMM=1``): the Philox
+        offsets, the shift rule, the rotation of the state and the bits of ``get_icem_action``.  Mean, spread and kept elites
+        persist on the side that planned, so the choice is made on the controller's first iCEM step and kept: None - the Python
+        loop plans, now and later - for a reward program, a reward model, a particle plan, a recurrent model, a test hook that
+        replaced the normals or the launch path, a library without the entry points, a backend that cannot reduce the words, a
+        forked child.  ``reset(dones)`` is forwarded to the C controller, and a changed ``torch.initial_seed()`` value reseeds it
+        (the stream restarts, the state is kept - as the Python loop does).  ``last_plan`` gets ``get_icem_action``'s keys; the
+        step itself reads back ``icem_iters * m * (act_dim + 4)`` floats only, the state and the returns are one copy of their
+        own afterwards: the class or instance attribute ``icem_fetch_returns = False`` leaves every ``returns`` key out and the
+        tables on the device (``self._icemstep.result()`` still returns every iteration's table on request); with
+        ``icem_trace_returns`` every iteration's table is filled in, otherwise the last one's."""
+        if self._icem_side == "python":
+            return None
+        st = self._icemstep
+        if st is not None and st.pid != os.getpid():
+            self._icemstep, self._icem_side = None, "python"        # (a forked child: the parent's HIP objects did not come along)
+            return None
+        rank, world = self._dist()
+        n, m, h = self.n_candidates, len(observations), self.horizon
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        native = self.dynamics_model.planner_model()
+        sigma = self._icem_sigma_vector()
+        K, Kk, pops = self._icem_sizes()
+        key = (id(native), native.handle.value, m, n, h, float(self.discount), K, Kk, tuple(pops), float(self.alpha), self.icem_rho,
+               sigma.tobytes(), self.icem_add_mean, rank, world)
+        if st is not None and st.key != key:        # another plan (a different number of envs, ...): it starts afresh, as the Python loop's
+            st.close()
+            st = self._icemstep = None
+        if st is None:
+            if (self.use_reward_model or self._program() or self.ensemble_planning == "particles" or hasattr(native, "units")
+                    or not self._native_step_stock()
+                    or getattr(self._icem_normal_device, "__func__", None) is not MPCController._icem_normal_device
+                    or not hasattr(native.lib, "l2a_icem_controller_create_sharded_device")
+                    or m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16):
+                self._icem_side = "python"
+                return None
+            shard = None
+            if world > 1:
+                shard = self._native_shard(native, rank, world, m * n + 3)
+                if shard is None:
+                    self._icem_side = "python"
+                    return None
+            from .native_icem_step import NativeIcemStep
+            st = NativeIcemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
+                                pops, K, Kk, self.alpha, self.icem_rho, sigma, self.icem_add_mean, seed, shard=shard)
+            st.key, st.seed = key, seed
+            self._icemstep, self._icem_side = st, "c"
+        if st.seed != seed:
+            st.reseed(seed)
+            st.seed = seed
+        self._check_blocks(m)
+        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        fetch, trace = bool(self.icem_fetch_returns), bool(self.icem_trace_returns)
+        mean, std, elites, counts, head, rets = st.result(with_returns=fetch)
+        act_dim = native.act_dim
+        as_int = lambda a: a.copy().view(np.int32).astype(np.int64)     # noqa: E731
+        steps = []
+        for it in range(st.iters):
+            step = dict(n=pops[it], best_return=head[it, :, act_dim].copy(), best_index=as_int(head[it, :, act_dim + 1]),
+                        elites=as_int(head[it, :, act_dim + 2]), valid=as_int(head[it, :, act_dim + 3]))
+            if fetch and (trace or it == st.iters - 1):
+                step["returns"] = rets[it].copy()
+            steps.append(step)
+        last = steps[-1]
+        self.last_plan = dict(best_index=last["best_index"], best_return=last["best_return"], icem_mean=mean, icem_std=std,
+                              icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps)
+        if fetch:
+            self.last_plan["returns"] = last["returns"]
+        if world > 1:
+            self.last_plan["shard"] = [self._shard_range(n_it, rank, world) for n_it in pops]
+        return st.act.copy()
 
     def get_icem_action(self, observations, retry=False):
         """One iCEM plan step on the GPU (``csrc/l2a_icem.hip``; semantics in ``include/l2a.h``).  Per env the plan mean, the spread
@@ -1636,10 +1727,16 @@ class MPCController(Policy, Serializable):
         if self.rng != "device":
             raise _lib.L2AError("iCEM planning draws its normals on the device (rng='device'); NumPy normals are not supported")
         if self.native_cem_step or self.native_mppi_step:
-            raise _lib.L2AError("iCEM planning has no C controller step: leave native_cem_step and native_mppi_step off with use_icem")
+            raise _lib.L2AError("an iCEM step as one C controller call is native_icem_step=True: leave native_cem_step and "
+                                "native_mppi_step off with use_icem")
+        if self.native_icem_step and not retry:
+            out = self._native_icem_step(observations)
+            if out is not None:
+                return out
         if self._dist()[1] > 1:
-            raise _lib.L2AError("iCEM planning does not shard its candidates over torch.distributed ranks: pass "
-                                "shard_candidates=False (every rank then plans on its own)")
+            raise _lib.L2AError("iCEM planning does not shard its candidates over torch.distributed ranks in this Python loop: pass "
+                                "shard_candidates=False (every rank then plans on its own), or native_icem_step=True (the C controller "
+                                "shards a plan with a closed-form reward spec and an MLP model)")
         n, m, h = self.n_candidates, len(observations), self.horizon
         act_dim = self.action_space.shape[0]
         D = h * act_dim

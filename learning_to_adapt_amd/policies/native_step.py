@@ -65,7 +65,8 @@ def _seed(seed):
 
 
 class StepHandle(object):
-    """What `NativeStep`, `NativeCemStep` (policies/native_cem_step.py) and `NativeMppiStep` (policies/native_mppi_step.py) share: the create call, the I/O arrays of a step, the
+    """What `NativeStep`, `NativeCemStep` (policies/native_cem_step.py), `NativeMppiStep` (policies/native_mppi_step.py) and
+    `NativeIcemStep` (policies/native_icem_step.py) share: the create call, the I/O arrays of a step, the
     step's return code, the stats call and the teardown."""
 
     def _open(self, native, create, m, n, h, low, high, discount, reward, extra, shard):
