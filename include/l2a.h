@@ -635,8 +635,9 @@ int l2a_mppi_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed,
  *   returns) or K * 4 + L2A_ICEM_REFIT_STATIC_LDS bytes (the statistics' elite list and its static part) beyond a workgroup's
  *   LDS (l2a_device_info: lds_per_block).
  * The controller step as one call, unsharded and sharded over ranks: l2a_icem_controller_create_device below.
- * Not built: a recurrent model, reward programs and reward models through the C step, NumPy normals, a power-law noise spectrum
- * (the recurrence is AR(1)).                                                                                                     */
+ * Noise with a power-law spectrum (the paper's coloured noise, PSD ~ f^-beta): l2a_icem_noise_matrix / l2a_icem_sample_noise below.
+ * Not built: a recurrent model, reward programs and reward models through the C step, NumPy normals, power-law noise on horizons
+ * above L2A_ICEM_NOISE_MAX_H, a beta per action dimension.                                                                        */
 #define L2A_ICEM_REFIT_STATIC_LDS 4288
 int l2a_icem_sample(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
                     const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0, float rho,
@@ -656,6 +657,41 @@ int l2a_icem_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed,
                           const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0,
                           float rho, const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk, int add_mean,
                           int lo, int hi, float* mean_out, float* std_out, float* a_clip, float* seq_local, void* stream);
+
+/* ---- iCEM: the noise as a matrix, and the power-law matrix ---------------------------------------------------------
+ * The noise sequence of one (candidate, action dimension) is nz = M z: z the h standard normals l2a_icem_sample draws for it (the
+ * Philox numbering stays positional: element e = (j * m + i) * D + t * A + k), M [h, h] row-major fp32.  One fixed order, every
+ * operation rounded to fp32 on its own:
+ *     acc = M[t, 0] * z_0;  for s = 1 .. h - 1: acc = acc + (M[t, s] * z_s);  nz_t = acc;  a = clip(mu'_t + nz_t * sd'_t, low, high)
+ * The bits of an element depend on its row of M and its normals alone - not on the launch geometry, the rows per workgroup or a
+ * shard's window.  Shift, the re-opened spread, kept rows, the mean row and its precedence, mean_out / std_out and the layouts of
+ * a_clip and seq are l2a_icem_sample's; a kept row's and the mean row's normals are not used.  M = I is l2a_icem_sample at rho = 0
+ * (as values: the sum adds signed zeros).
+ *
+ * l2a_icem_noise_matrix (host only, no context, no GPU): the power-law matrix for PSD ~ f^-beta, built in double precision and
+ * rounded once to fp32.  s_k = max(k, 1)^(-beta / 2) * h^(beta / 2) for k = 0 .. floor(h / 2) (the DC term gets the lowest
+ * frequency's amplitude), "mid" = 1 <= k <= floor((h - 1) / 2), N = sqrt(s_0^2 + 2 sum_mid s_k^2 + [h even, h > 1] s_(h/2)^2);
+ *     M[t, 0] = s_0 / N;  M[t, 2k - 1] = sqrt(2) s_k cos(2 pi k t / h) / N,  M[t, 2k] = -sqrt(2) s_k sin(2 pi k t / h) / N  (mid k);
+ *     even h > 1: M[t, h - 1] = s_(h/2) (-1)^t / N.
+ *   Every row has norm 1 (unit variance for every t, as the AR(1) noise), M M^T is circulant (a stationary process), beta = 0 gives
+ *   an orthogonal M (white noise), h = 2 is white for every beta.  L2A_EINVAL, nothing written: h outside 1 .. L2A_ICEM_NOISE_MAX_H,
+ *   beta not finite or outside [0, 8], a NULL pointer.
+ * l2a_icem_sample_noise / l2a_icem_sample_noise_shard (one launch: l2a_icem_sample_noise_k, the whole horizon of a row in LDS, M
+ *   read from global memory): l2a_icem_sample's / l2a_icem_sample_shard's arguments with `float rho` replaced by `noise`, device
+ *   fp32 [h, h] - ANY matrix, not only the power-law one.  L2A_EINVAL (nothing written, nothing launched): every refusal of
+ *   l2a_icem_sample / l2a_icem_sample_shard except rho's, h > L2A_ICEM_NOISE_MAX_H, a NULL noise, noise being one of the outputs.
+ * l2a_icem_controller_set_noise: further down, with the iCEM controller step.                                                        */
+#define L2A_ICEM_NOISE_MAX_H 128
+int l2a_icem_noise_matrix(int h, double beta, float* M_host);
+int l2a_icem_sample_noise(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                          const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0,
+                          const float* noise, const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk,
+                          int add_mean, float* mean_out, float* std_out, float* a_clip, float* seq, void* stream);
+int l2a_icem_sample_noise_shard(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset,
+                                const float* mean_in, const float* std_in, const float* kept_in, const int* kc_in, const int* shift,
+                                const float* sigma0, const float* noise, const float* low, const float* high, int n_it, int m, int h,
+                                int act_dim, int Kk, int add_mean, int lo, int hi, float* mean_out, float* std_out, float* a_clip,
+                                float* seq_local, void* stream);
 
 /* ---- sharded plans: the one collective ------------------------------------------------------
  * Candidates are independent, so G GPUs (one process and one context each) plan disjoint shards of one candidate
@@ -1098,8 +1134,15 @@ int l2a_mppi_controller_result(l2a_controller* controller, float* mean_out, floa
  *                                [m, pops[it]] one after another (sharded: the GATHERED tables); any pointer may be NULL; the rows
  *                                are the step's own read-back, everything else comes back in ONE copy on the latest step's stream,
  *                                waited for
- * _reset / _reseed / _result return L2A_ESTATE while a step is in flight, _result also before the first step has finished, and
- * L2A_EINVAL on a controller of another kind (as l2a_mppi_controller_* and l2a_cem_controller_result do on an iCEM controller).
+ *   l2a_icem_controller_set_noise : M_host [h, h] (host fp32, the controller's h; any matrix - l2a_icem_noise_matrix's for power-law
+ *                                noise) is copied to the device, and from the next step on every iteration samples with
+ *                                l2a_icem_sample_noise (sharded: l2a_icem_sample_noise_shard) in place of the AR(1) entries; NULL
+ *                                returns the controller to its rho.  Stream offsets, commit / replay, result rows, reset and
+ *                                reseed are unchanged; a sharded step's digest additionally carries a hash of the matrix's bits
+ *                                (every rank must have set the same one).  L2A_EINVAL with h > L2A_ICEM_NOISE_MAX_H.
+ * _reset / _reseed / _result / _set_noise return L2A_ESTATE while a step is in flight, _result also before the first step has
+ * finished, and L2A_EINVAL on a controller of another kind (as l2a_mppi_controller_* and l2a_cem_controller_result do on an iCEM
+ * controller).
  * Not built: a recurrent model, reward programs and reward models (l2a_reward only), particle plans, NumPy normals.               */
 int l2a_icem_controller_create_device(l2a_model* model, int m, int n, int h, const double* low, const double* high,
                                       double discount, const l2a_reward* reward, int iters, const int* pops, int K, int Kk,
@@ -1113,6 +1156,7 @@ int l2a_icem_controller_reset(l2a_controller* controller, const unsigned char* d
 int l2a_icem_controller_reseed(l2a_controller* controller, unsigned long long seed);
 int l2a_icem_controller_result(l2a_controller* controller, float* mean_out, float* std_out, float* kept_out, int* kc_out,
                                float* heads_out, float* returns_out);
+int l2a_icem_controller_set_noise(l2a_controller* controller, const float* M_host);
 void l2a_controller_destroy(l2a_controller* controller);
 int l2a_controller_step(l2a_controller* controller, const double* obs, double* action_out, long long* index_out,
                         float* return_out, void* stream);

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "l2a_mppi_controller_reseed", "l2a_mppi_controller_result",
     "l2a_icem_sample_shard", "l2a_icem_controller_create_device", "l2a_icem_controller_create_sharded_device", "l2a_icem_controller_reset",
     "l2a_icem_controller_reseed", "l2a_icem_controller_result",
+    "l2a_icem_noise_matrix", "l2a_icem_sample_noise", "l2a_icem_sample_noise_shard", "l2a_icem_controller_set_noise",
     "l2a_lstm_create", "l2a_rnn_create", "l2a_lstm_destroy", "l2a_lstm_set_weights", "l2a_lstm_set_norm", "l2a_lstm_plan_rs", "l2a_lstm_plan_rs_sync", "l2a_lstm_plan_rs_chunk",
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry", "l2a_lstm_plan_geometry",
@@ -484,6 +485,18 @@ def load():
         lib.l2a_icem_controller_reseed.restype = i32
         lib.l2a_icem_controller_result.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         lib.l2a_icem_controller_result.restype = i32
+    if hasattr(lib, "l2a_icem_sample_noise"):    # iCEM's noise as a matrix (absent from older variant libraries)
+        lib.l2a_icem_noise_matrix.argtypes = [i32, c.c_double, vp]
+        lib.l2a_icem_noise_matrix.restype = i32
+        # (l2a_icem_sample's / l2a_icem_sample_shard's arguments with `float rho` replaced by the device matrix)
+        lib.l2a_icem_sample_noise.argtypes = [vp, vp, c.c_ulonglong, c.c_ulonglong, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
+                                              i32, i32, vp, vp, vp, vp, vp]
+        lib.l2a_icem_sample_noise.restype = i32
+        lib.l2a_icem_sample_noise_shard.argtypes = [vp, vp, c.c_ulonglong, c.c_ulonglong, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                                    i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        lib.l2a_icem_sample_noise_shard.restype = i32
+        lib.l2a_icem_controller_set_noise.argtypes = [vp, vp]
+        lib.l2a_icem_controller_set_noise.restype = i32
     _lib = lib
     return lib
 

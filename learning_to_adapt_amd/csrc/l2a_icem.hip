@@ -20,7 +20,10 @@
 //                       (c = sqrtf(1 - rho^2), formed once on the host in fp32), and all threads store the tile twice: a_clip
 //                       [n_it, m, D] (sample row j * m + i) and the rollout's candidate tensor seq [h, m * n_it, A] (plan row
 //                       i * n_it + j).  The rows of candidate 0 write mu' and sd' out of place (mean_out, std_out).
-//   l2a_icem_rank_k   : grid (ceil(n_it / 4) capped at 256, m), 4 waves.  The env's returns are staged in LDS with every invalid one
+//   l2a_icem_sample_noise_k : the same sample with nz = M z for a given matrix M [h, h] in place of the recurrence (l2a_icem_sample_noise,
+//                       l2a_icem_sample_noise_shard; h <= 128, the whole horizon of a row in LDS) - further down, with the power-law
+//                       matrix's host builder l2a_icem_noise_matrix.
+//   l2a_icem_rank_k  : grid (ceil(n_it / 4) capped at 256, m), 4 waves.  The env's returns are staged in LDS with every invalid one
 //                       (NaN, -inf) as -inf; one wave per VALID candidate j counts the candidates that sort before it in the stable
 //                       descending order (ballot + popcount per 64, l2a_cem.hip's cem_rank; the count stops at K - such a
 //                       candidate is no elite) and, with rank < K, writes j to work[i, rank].  The ranks of the valid candidates
@@ -269,6 +272,133 @@ int icem_sample_launch(l2a_ctx* ctx, const char* who, IcemSampleParams p, void* 
     return L2A_OK;
 }
 
+// ---- noise given as a matrix (l2a_icem_sample_noise, l2a_icem_sample_noise_shard) -----------------------------------------------------
+// nz = M z per (candidate, action dimension) in place of the recurrence: M [h, h] row-major fp32 in global memory, any matrix (the
+// power-law one is l2a_icem_noise_matrix's).  The AR(1) kernel above and its parameter block are left exactly as they are: the
+// matrix travels in a block of its own around them.
+struct IcemNoiseParams {
+    IcemSampleParams s;         // (rho, c: unused)
+    const float* noise;         // [h, h]
+};
+
+// Workgroup = p.s.rpb <= L2A_ICEM_ROWS sample rows with their WHOLE horizon resident (h <= L2A_ICEM_NOISE_MAX_H: rows x D <= the tile),
+// so there are no passes and no state between them.  (1) is l2a_icem_sample_k's fetch and draw into LDS - the Box-Muller
+// transcendentals in parallel.  (2) every thread owns whole output elements (row, t, k): the h-term sum over the row's normals of
+// dimension k in ONE order, s = 0 .. h - 1, a product and an add per term, each rounded on its own - the bits of an element depend on
+// nothing but its row of M and its normals, not on the rows per workgroup, the grid or the window -, then scale, add, clip; a kept row
+// and the mean row are final as fetched.  (3) the same thread stores the element twice, as l2a_icem_sample_k does (nothing is
+// written back to LDS: the normals stay as they are for the other threads' sums).
+// M is read from global memory: one workgroup reads each of its h x h entries D / h = act_dim times per sample row, the lanes of
+// a wave that share a step t read one address (the 16 lanes of an act_dim = 16 plan), a lane walks its row of M upwards, and the
+// matrix - 3.6 KB at h = 30, 64 KB at h = 128 - is shared by every workgroup of the launch, so it is served by L1 / L2.  An LDS
+// copy would cost every workgroup those 64 KB of reads again plus, at h = 128, more LDS than the 64 KB a workgroup gets without
+// the dynamic-LDS attribute - and one workgroup multiplies at most 2048 x 128 terms.
+template <bool SHARD>
+__global__ void __launch_bounds__(256) l2a_icem_sample_noise_k(const IcemNoiseParams pn) {
+#pragma clang fp contract(off)
+    __shared__ float tile[L2A_ICEM_TILE];       // z (or a final value)
+    __shared__ float mtile[L2A_ICEM_TILE];      // mu'
+    __shared__ float stile[L2A_ICEM_TILE];      // sd'
+    const IcemSampleParams& p = pn.s;
+    const int tid = threadIdx.x;
+    const int h = p.h, A = p.act_dim, D = h * A;
+    const long long rows = (long long)p.n * p.m;
+    const long long g0 = (long long)blockIdx.x * p.rpb;     // first flat sample row j * m + i (the draw's [n, m, D] order)
+    const int nr = (int)(rows - g0 < p.rpb ? rows - g0 : p.rpb);
+    const int count = nr * D;                               // <= L2A_ICEM_TILE: the entry point's rpb and its limit on h
+    for (int q = tid; q < count; q += 256) {
+        const int r = q / D, rem = q - r * D;               // rem = t * A + k
+        const int t = rem / A, k = rem - t * A;
+        const long long g = g0 + r, j = g / p.m;
+        const int i = (int)(g - j * p.m);
+        const int sh = p.shift[i];
+        const int ts = (sh > 0) ? (t + 1 < h ? t + 1 : h - 1) : t;
+        const float mv = (sh < 0) ? 0.0f : p.mean_in[(long long)i * D + ts * A + k];
+        mtile[q] = mv;
+        stile[q] = (sh != 0) ? p.sigma0[k] : p.std_in[(long long)i * D + t * A + k];
+        const int kind = icem_row_kind(p, j, icem_kept_count(p, i, sh));
+        float v;
+        if (kind == 2) v = fminf(fmaxf(mv, p.low[k]), p.high[k]);
+        else if (kind == 1) v = p.kept_in[((long long)i * p.Kk + j) * D + ts * A + k];
+        else {
+            const long long e = g * D + rem;
+            v = p.z ? p.z[e] : icem_philox_normal(p.seed, p.offset + (unsigned long long)e);
+        }
+        tile[q] = v;
+    }
+    __syncthreads();
+    for (int q = tid; q < count; q += 256) {
+        const int r = q / D, rem = q - r * D;
+        const int t = rem / A, k = rem - t * A;
+        const long long g = g0 + r, j = g / p.m;
+        const int i = (int)(g - j * p.m);
+        float v = tile[q];
+        if (icem_row_kind(p, j, icem_kept_count(p, i, p.shift[i])) == 0) {
+            const float* mrow = pn.noise + (long long)t * h;
+            const float* zk = tile + r * D + k;             // this row's normals of dimension k: one per step, A floats apart
+            float acc = mrow[0] * zk[0];
+            for (int s = 1; s < h; ++s) {
+                const float pr = mrow[s] * zk[s * A];
+                acc = acc + pr;
+            }
+            const float sc = acc * stile[q];
+            const float a = mtile[q] + sc;
+            v = fminf(fmaxf(a, p.low[k]), p.high[k]);
+        }
+        p.a_clip[g * D + rem] = v;
+        if (p.seq && (!SHARD || (j >= p.lo && j < p.hi))) {
+            // plan row of this candidate (env-major) among the rows of one horizon step: all n candidates, SHARD: the window's
+            const long long width = SHARD ? p.hi - p.lo : p.n;
+            const long long prow = (long long)i * width + (SHARD ? j - p.lo : j);
+            p.seq[((long long)t * (width * p.m) + prow) * A + k] = v;
+        }
+        if (j == 0) {
+            p.mean_out[(long long)i * D + rem] = mtile[q];
+            p.std_out[(long long)i * D + rem] = stile[q];
+        }
+    }
+}
+
+// What l2a_icem_sample_noise and l2a_icem_sample_noise_shard share: icem_sample_launch's checks without rho's, the limit on h, the
+// matrix's own, the rows per workgroup (l2a_icem_sample's rule) and the launch.
+template <bool SHARD>
+int icem_sample_noise_launch(l2a_ctx* ctx, const char* who, IcemNoiseParams pn, void* stream_v) {
+    IcemSampleParams& p = pn.s;
+    const std::string w(who);
+    if (!p.mean_in || !p.std_in || !p.shift || !p.sigma0 || !p.low || !p.high || !p.mean_out || !p.std_out || !p.a_clip || !pn.noise)
+        return l2a_fail(ctx, L2A_EINVAL, w + ": null pointer");
+    if (p.n < 1 || p.m < 1 || p.h < 1 || p.act_dim < 1 || p.act_dim > 16)
+        return l2a_fail(ctx, L2A_EINVAL, w + ": bad n_it / m / h / act_dim (1 <= act_dim <= 16)");
+    if (p.h > L2A_ICEM_NOISE_MAX_H) return l2a_fail(ctx, L2A_EINVAL, w + ": h beyond L2A_ICEM_NOISE_MAX_H (a row's whole horizon stays in LDS)");
+    if (p.Kk < 0 || p.Kk > 8192) return l2a_fail(ctx, L2A_EINVAL, w + ": 0 <= Kk <= 8192");
+    if (p.Kk > 0 && (!p.kept_in || !p.kc_in)) return l2a_fail(ctx, L2A_EINVAL, w + ": null kept rows or counts with Kk > 0");
+    if (SHARD) {
+        if (p.lo < 0 || p.hi > p.n || p.lo > p.hi) return l2a_fail(ctx, L2A_EINVAL, w + ": the window needs 0 <= lo <= hi <= n_it");
+        if (p.hi > p.lo && !p.seq) return l2a_fail(ctx, L2A_EINVAL, w + ": null seq_local for a window that holds candidates");
+        if (p.hi == p.lo) p.seq = nullptr;
+    }
+    const void* ins[] = {p.z, p.mean_in, p.std_in, p.kept_in, p.kc_in, p.shift, p.sigma0, p.low, p.high, pn.noise};
+    const void* outs[] = {p.mean_out, p.std_out, p.a_clip, p.seq};
+    for (size_t a = 0; a < sizeof(outs) / sizeof(outs[0]); ++a) {
+        if (!outs[a]) continue;
+        for (const void* in : ins)
+            if (in == outs[a]) return l2a_fail(ctx, L2A_EINVAL, w + ": an output aliases an input");
+        for (size_t b = 0; b < a; ++b)
+            if (outs[b] == outs[a]) return l2a_fail(ctx, L2A_EINVAL, w + ": two outputs alias");
+    }
+    const long long total = (long long)p.n * p.m * p.h * p.act_dim;
+    if (total > 0x7fffffffLL * 256 || (long long)p.n * p.m > 0x7fffffffLL) return l2a_fail(ctx, L2A_EINVAL, w + ": too many samples");
+    l2a_device_guard guard(ctx->device);
+    const long long rows = (long long)p.n * p.m;
+    const int D = p.h * p.act_dim;
+    static_assert(L2A_ICEM_NOISE_MAX_H * 16 <= L2A_ICEM_TILE, "one row's whole horizon must fit the LDS tile");
+    p.rpb = 256 / D < 1 ? 1 : (256 / D > L2A_ICEM_ROWS ? L2A_ICEM_ROWS : 256 / D);     // rpb * D <= max(256, D) <= L2A_ICEM_TILE
+    hipLaunchKernelGGL(l2a_icem_sample_noise_k<SHARD>, dim3((unsigned)((rows + p.rpb - 1) / p.rpb)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream_v), pn);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
+}
+
 // ---- the refit -----------------------------------------------------------------------------------------------------------------------
 // Stable descending rank of the valid candidate j among env i's valid returns, counted up to `cap` (rs holds -inf for every invalid
 // candidate, and v = rs[j] > -inf: an invalid one is never "before").  One wave per j, l2a_cem.hip's cem_rank, 256 candidates (four
@@ -472,6 +602,65 @@ int l2a_icem_sample_shard(l2a_ctx* ctx, const float* z, unsigned long long seed,
     p.mean_out = mean_out; p.std_out = std_out; p.a_clip = a_clip; p.seq = seq_local;
     p.lo = lo; p.hi = hi;
     return icem_sample_launch<true>(ctx, "l2a_icem_sample_shard", p, stream_v);
+}
+
+// The power-law matrix of include/l2a.h, on the host in double precision, rounded once: column 0 the mean, columns 2k - 1 and 2k the
+// cosine and the sine of frequency k, the last column of an even h the Nyquist term.  (k t is reduced modulo h in integers before
+// it meets pi: the angle stays below 2 pi.)
+int l2a_icem_noise_matrix(int h, double beta, float* M_host) {
+#pragma clang fp contract(off)
+    if (h < 1 || h > L2A_ICEM_NOISE_MAX_H || !std::isfinite(beta) || beta < 0.0 || beta > 8.0 || !M_host) return L2A_EINVAL;
+    const int half = h / 2, mid = (h - 1) / 2;
+    const bool nyquist = h % 2 == 0 && h > 1;
+    double s[L2A_ICEM_NOISE_MAX_H / 2 + 1];
+    for (int k = 0; k <= half; ++k) s[k] = std::pow((double)(k > 1 ? k : 1), -0.5 * beta) * std::pow((double)h, 0.5 * beta);
+    double sum = s[0] * s[0];
+    for (int k = 1; k <= mid; ++k) sum += 2.0 * (s[k] * s[k]);
+    if (nyquist) sum += s[half] * s[half];
+    const double N = std::sqrt(sum), r2 = std::sqrt(2.0), two_pi = 6.283185307179586476925286766559;
+    for (int t = 0; t < h; ++t) {
+        float* row = M_host + (size_t)t * h;
+        row[0] = (float)(s[0] / N);
+        for (int k = 1; k <= mid; ++k) {
+            const double ang = two_pi * (double)((k * t) % h) / (double)h;
+            row[2 * k - 1] = (float)(r2 * s[k] * std::cos(ang) / N);
+            row[2 * k] = (float)(-r2 * s[k] * std::sin(ang) / N);
+        }
+        if (nyquist) row[h - 1] = (float)((t % 2 ? -s[half] : s[half]) / N);
+    }
+    return L2A_OK;
+}
+
+int l2a_icem_sample_noise(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                          const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0,
+                          const float* noise, const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk,
+                          int add_mean, float* mean_out, float* std_out, float* a_clip, float* seq, void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    IcemNoiseParams pn;
+    std::memset(&pn, 0, sizeof(pn));
+    IcemSampleParams& p = pn.s;
+    p.z = z; p.seed = seed; p.offset = offset; p.mean_in = mean_in; p.std_in = std_in; p.kept_in = kept_in; p.kc_in = kc_in;
+    p.shift = shift; p.sigma0 = sigma0; p.low = low; p.high = high; pn.noise = noise;
+    p.n = n_it; p.m = m; p.h = h; p.act_dim = act_dim; p.Kk = Kk; p.add_mean = add_mean ? 1 : 0;
+    p.mean_out = mean_out; p.std_out = std_out; p.a_clip = a_clip; p.seq = seq;
+    return icem_sample_noise_launch<false>(ctx, "l2a_icem_sample_noise", pn, stream_v);
+}
+
+int l2a_icem_sample_noise_shard(l2a_ctx* ctx, const float* z, unsigned long long seed, unsigned long long offset, const float* mean_in,
+                                const float* std_in, const float* kept_in, const int* kc_in, const int* shift, const float* sigma0,
+                                const float* noise, const float* low, const float* high, int n_it, int m, int h, int act_dim, int Kk,
+                                int add_mean, int lo, int hi, float* mean_out, float* std_out, float* a_clip, float* seq_local,
+                                void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    IcemNoiseParams pn;
+    std::memset(&pn, 0, sizeof(pn));
+    IcemSampleParams& p = pn.s;
+    p.z = z; p.seed = seed; p.offset = offset; p.mean_in = mean_in; p.std_in = std_in; p.kept_in = kept_in; p.kc_in = kc_in;
+    p.shift = shift; p.sigma0 = sigma0; p.low = low; p.high = high; pn.noise = noise;
+    p.n = n_it; p.m = m; p.h = h; p.act_dim = act_dim; p.Kk = Kk; p.add_mean = add_mean ? 1 : 0;
+    p.mean_out = mean_out; p.std_out = std_out; p.a_clip = a_clip; p.seq = seq_local;
+    p.lo = lo; p.hi = hi;
+    return icem_sample_noise_launch<true>(ctx, "l2a_icem_sample_noise_shard", pn, stream_v);
 }
 
 int l2a_icem_refit(l2a_ctx* ctx, const float* returns, const float* a_clip, const float* low, const float* high, int n_it, int m,

@@ -191,6 +191,10 @@ struct icem_state : plan_state {
     std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts afresh
     int cur = 0, last = 0;                      // the committed copy | the copy the step in flight ends on
     float* result_host = nullptr;               // page-locked [head_floats + m * sum(pops)]: l2a_icem_controller_result's one copy
+    // l2a_icem_controller_set_noise: the matrix the sample reads in place of the recurrence (allocated at the first set)
+    float* noise = nullptr;                     // device [h, h]
+    bool noise_on = false;
+    unsigned long long noise_hash = 0;          // of the matrix's bits (the digest carries it while noise_on)
 };
 
 extern "C" unsigned long long l2a_mt19937_state_digest(const void* addr);      // csrc/l2a_rng.c
@@ -918,6 +922,7 @@ unsigned long long icem_digest(const l2a_controller* c) {
     d = digest_mix(d, bits(q->rho));
     for (int k = 0; k < c->act_dim; ++k) d = digest_mix(d, bits(q->sigma32[k]));
     for (int i = 0; i < c->m; ++i) d = digest_mix(d, q->fresh[i] ? 1ull : 0ull);
+    if (q->noise_on) d = digest_mix(d, q->noise_hash);      // (without a matrix the digest is the AR(1) step's)
     return d;
 }
 
@@ -949,7 +954,16 @@ int icem_launch(l2a_controller* c) {
         const float* kept_in = Kk ? q->kept[src] : nullptr;
         const int* kc_in = Kk ? q->kc[src] : nullptr;
         // (sharded: every rank samples all n_it rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
-        int rc = sharded ? l2a_icem_sample_shard(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma, q->rho,
+        int rc;
+        if (q->noise_on)                        // l2a_icem_controller_set_noise: nz = M z in place of the recurrence
+            rc = sharded ? l2a_icem_sample_noise_shard(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma,
+                                                       q->noise, low, high, n_it, m, h, A, Kk, add_mean, lo, hi, q->mean[dst], q->std[dst],
+                                                       q->a_clip, q->seq, c->stream)
+                         : l2a_icem_sample_noise(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma,
+                                                 q->noise, low, high, n_it, m, h, A, Kk, add_mean, q->mean[dst], q->std[dst], q->a_clip,
+                                                 q->seq, c->stream);
+        else
+            rc = sharded ? l2a_icem_sample_shard(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma, q->rho,
                                                  low, high, n_it, m, h, A, Kk, add_mean, lo, hi, q->mean[dst], q->std[dst], q->a_clip, q->seq,
                                                  c->stream)
                          : l2a_icem_sample(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma, q->rho, low,
@@ -1493,6 +1507,35 @@ int l2a_icem_controller_result(l2a_controller* c, float* mean_out, float* std_ou
     if (kept_out && kd) std::memcpy(kept_out, host + (q->kept[cur] - q->mean[0]), sizeof(float) * kd);
     if (kc_out) std::memcpy(kc_out, host + (reinterpret_cast<float*>(q->kc[cur]) - q->mean[0]), sizeof(int) * m);
     if (returns_out) std::memcpy(returns_out, host + q->head_floats, sizeof(float) * nr);
+    return L2A_OK;
+}
+
+int l2a_icem_controller_set_noise(l2a_controller* c, const float* M_host) {
+    if (!c) return L2A_EINVAL;
+    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_set_noise: not an iCEM controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_set_noise: a step is in flight (l2a_controller_finish)");
+    icem_state* q = c->icem;
+    if (!M_host) { q->noise_on = false; return L2A_OK; }
+    if (c->h > L2A_ICEM_NOISE_MAX_H) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_set_noise: h beyond L2A_ICEM_NOISE_MAX_H");
+    const size_t count = (size_t)c->h * c->h;
+    l2a_device_guard guard(c->ctx->device);
+    if (!q->noise) q->noise = alloc<float>(c, MEM_DEVICE, count);
+    // (no step is in flight, and a finished step was waited for: nothing on the device reads the matrix now)
+    upload(c, q->noise, M_host, sizeof(float) * count);
+    if (c->mem_err != hipSuccess) {
+        const hipError_t e = c->mem_err;
+        c->mem_err = hipSuccess;
+        q->noise_on = false;
+        return fail(c->ctx, L2A_EHIP, std::string("l2a_icem_controller_set_noise: ") + hipGetErrorString(e));
+    }
+    unsigned long long d = 0x9E3779B97F4A7C15ull;
+    for (size_t e = 0; e < count; ++e) {
+        unsigned int b = 0;
+        std::memcpy(&b, M_host + e, sizeof(b));
+        d = digest_mix(d, (unsigned long long)b);
+    }
+    q->noise_hash = d;
+    q->noise_on = true;
     return L2A_OK;
 }
 

@@ -42,7 +42,10 @@ reward programs, reward models and recurrent models keep the Python path),
 ``use_icem`` (iCEM, Pinneri et al. 2020 - not in the reference: per env a plan mean, a spread and kept elites persist on the device;
 a step moves mean and kept elites on one horizon step and re-opens the spread to ``icem_sigma`` - ``None``: a quarter of the action
 range -, an iteration places the kept elites first and draws the rest with AR(1) noise ``n_t = rho n_(t-1) + sqrt(1 - rho^2) z_t``
-(``icem_rho``), the population shrinks by ``icem_decay`` per iteration down to twice the elites, ``percent_elites`` and ``alpha`` refit
+(``icem_rho``) or, with ``icem_noise="powerlaw"``, with the paper's coloured noise of power spectral density ``f^-icem_beta``
+(``l2a_icem_noise_matrix`` / ``l2a_icem_sample_noise``, horizons up to 128; ``icem_rho`` is ignored then; ``icem_beta = 0`` is white
+noise, the default 2 a lag-1 correlation of 0.88 at ``horizon = 30``), the population shrinks by ``icem_decay`` per iteration down
+to twice the elites, ``percent_elites`` and ``alpha`` refit
 mean and spread, ``icem_keep`` of the elites are kept, ``icem_add_mean`` adds the mean itself to the last of the ``icem_iters``
 iterations, and the best candidate's first action is returned, ``get_icem_action``; needs ``rng="device"``; ``reset(dones)`` restarts
 the marked envs' plans), ``native_icem_step`` (off by default: the iCEM plan step through the C controller,
@@ -112,6 +115,8 @@ class MPCController(Policy, Serializable):
             icem_sigma=None,
             icem_add_mean=True,
             native_icem_step=False,
+            icem_noise="ar1",
+            icem_beta=2.0,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -158,6 +163,8 @@ class MPCController(Policy, Serializable):
         self.icem_sigma = icem_sigma
         self.icem_add_mean = bool(icem_add_mean)
         self.native_icem_step = bool(native_icem_step)
+        self.icem_noise = icem_noise
+        self.icem_beta = float(icem_beta)
         if self.native_icem_step and (use_cem or self.use_mppi):
             raise _lib.L2AError("native_icem_step is the iCEM planner's C controller step (use_icem=True): with use_cem it is "
                                 "native_cem_step, with use_mppi native_mppi_step")
@@ -174,6 +181,10 @@ class MPCController(Policy, Serializable):
                 raise ValueError("icem_decay must be finite and at least 1")
             if not 0.0 <= self.icem_rho < 1.0:
                 raise ValueError("icem_rho must lie in [0, 1)")
+            if self.icem_noise not in ("ar1", "powerlaw"):
+                raise ValueError("icem_noise is 'ar1' or 'powerlaw', not %r" % (icem_noise,))
+            if not (np.isfinite(self.icem_beta) and 0.0 <= self.icem_beta <= 8.0):
+                raise ValueError("icem_beta must be finite and lie in [0, 8]")
             if not 0.0 <= float(alpha) < 1.0:
                 raise ValueError("use_icem needs alpha in [0, 1)")
             if not percent_elites > 0:
@@ -1604,6 +1615,18 @@ class MPCController(Policy, Serializable):
         Kk = int(self.icem_keep * K)
         return K, Kk, [min(n, max(int(n / self.icem_decay ** it), 2 * K)) for it in range(self.icem_iters)]
 
+    def _icem_noise_matrix(self, h):
+        """The power-law matrix ``M [h, h]`` (host fp32) of ``icem_beta``: ``l2a_icem_noise_matrix`` (``include/l2a.h``), built on
+        the host in double precision.  ``L2AError`` for a horizon above 128 or a library without the entry point."""
+        lib = _lib.load()
+        if not hasattr(lib, "l2a_icem_noise_matrix"):
+            raise _lib.L2AError("this libl2a_hip.so has no power-law iCEM noise (l2a_icem_sample_noise): rebuild it")
+        M = np.empty((int(h), int(h)), dtype=np.float32)
+        if lib.l2a_icem_noise_matrix(int(h), float(self.icem_beta), M.ctypes.data) != _lib.L2A_OK:
+            raise _lib.L2AError("icem_noise='powerlaw' plans over horizons of 1 .. 128 steps (L2A_ICEM_NOISE_MAX_H) with icem_beta in "
+                                "[0, 8]: horizon %d, icem_beta %r" % (h, self.icem_beta))
+        return M
+
     def _icem_reset(self, dones):
         """``reset(dones)`` for the iCEM planner: the marked envs' next step starts from a zero mean, the initial spread and no kept
         elites; ``None``, or a number of envs other than the plan's, starts all of them afresh.  Without ``use_icem`` nothing happens."""
@@ -1655,7 +1678,7 @@ class MPCController(Policy, Serializable):
         sigma = self._icem_sigma_vector()
         K, Kk, pops = self._icem_sizes()
         key = (id(native), native.handle.value, m, n, h, float(self.discount), K, Kk, tuple(pops), float(self.alpha), self.icem_rho,
-               sigma.tobytes(), self.icem_add_mean, rank, world)
+               sigma.tobytes(), self.icem_add_mean, rank, world, self.icem_noise, self.icem_beta)
         if st is not None and st.key != key:        # another plan (a different number of envs, ...): it starts afresh, as the Python loop's
             st.close()
             st = self._icemstep = None
@@ -1677,6 +1700,12 @@ class MPCController(Policy, Serializable):
             st = NativeIcemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
                                 pops, K, Kk, self.alpha, self.icem_rho, sigma, self.icem_add_mean, seed, shard=shard)
             st.key, st.seed = key, seed
+            if self.icem_noise == "powerlaw":
+                try:
+                    st.set_noise(self._icem_noise_matrix(h))
+                except Exception:
+                    st.close()
+                    raise
             self._icemstep, self._icem_side = st, "c"
         if st.seed != seed:
             st.reseed(seed)
@@ -1696,7 +1725,8 @@ class MPCController(Policy, Serializable):
             steps.append(step)
         last = steps[-1]
         self.last_plan = dict(best_index=last["best_index"], best_return=last["best_return"], icem_mean=mean, icem_std=std,
-                              icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps)
+                              icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps,
+                              icem_noise=np.str_(self.icem_noise), icem_beta=np.float64(self.icem_beta))
         if fetch:
             self.last_plan["returns"] = last["returns"]
         if world > 1:
@@ -1708,7 +1738,8 @@ class MPCController(Policy, Serializable):
         ``[m, h * act_dim]``, the kept elites ``[m, Kk, h * act_dim]`` and their counts stay on the device between controller steps.
         Per iteration: ``l2a_icem_sample`` (shift - a fresh start for an env that is new or was reset, one step on with the spread
         re-opened for the first iteration of a later step, none for further iterations -, the kept elites as the first rows, AR(1)
-        noise, clip, with ``icem_add_mean`` the mean itself as the last iteration's last row), the fused rollout of the iteration's
+        noise - with ``icem_noise="powerlaw"`` ``l2a_icem_sample_noise`` and the power-law matrix of ``icem_beta`` instead -, clip,
+        with ``icem_add_mean`` the mean itself as the last iteration's last row), the fused rollout of the iteration's
         ``n_it`` candidates (``_rollout``: closed-form reward, reward program, reward model and particle plans alike),
         ``l2a_icem_refit`` (top-k of the valid candidates, momentum update of mean and spread, the kept elites, the packed result).
         The observations go up once, one copy brings the packed result back.  The action returned is the first action of the last
@@ -1718,7 +1749,7 @@ class MPCController(Policy, Serializable):
         tile-split launch replays the step from the same state with the same offsets.  ``last_plan``: ``best_index``, ``best_return``,
         ``returns`` (the last iteration's), ``icem_mean``, ``icem_std``, ``icem_elites [m, Kk, D]`` (env i's kept rows in rank order: its
         first ``icem_elite_count[i]`` rows, zeros behind them), ``icem_valid``, ``icem_trace`` (per iteration: n, best return and index,
-        elite and valid counts)."""
+        elite and valid counts), ``icem_noise``, ``icem_beta`` (as NumPy scalars: every entry but the trace has a dtype)."""
         import ctypes
         from ..dynamics.native_model import _ptr, _stream_ptr
         if not self._fusable():
@@ -1752,6 +1783,12 @@ class MPCController(Policy, Serializable):
             up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
             const = self._bufs["icem_const"] = (up(self.action_space.low), up(self.action_space.high), up(self._icem_sigma_vector()))
         low, high, sigma = const
+        noise = None
+        if self.icem_noise == "powerlaw":       # M once per (h, beta), kept on the device next to the constants
+            held = self._bufs.get("icem_noise")
+            if held is None or held[0] != (h, self.icem_beta) or held[1].device != dev:
+                held = self._bufs["icem_noise"] = ((h, self.icem_beta), torch.as_tensor(self._icem_noise_matrix(h), device=dev))
+            noise = held[1]
         # the persistent state and two scratch copies of it: a step reads `cur` and commits its last outputs only when it succeeded,
         # so a replay starts from the same plan
         means = self._buf("icem_means", (3, m, D), torch.float32, dev)
@@ -1796,12 +1833,14 @@ class MPCController(Policy, Serializable):
                 z = z.to(device=dev, dtype=torch.float32).contiguous()
             offset = (call0 + it) * n * m * D
             seq = seq_all[:h * m * n_it * act_dim].view(h, m * n_it, act_dim)
-            ctx.check(lib.l2a_icem_sample(ctx.handle, _ptr(z), ctypes.c_ulonglong(seed), ctypes.c_ulonglong(offset & 0xFFFFFFFFFFFFFFFF),
-                                          _ptr(means[src]), _ptr(stds[src]), _ptr(kept[src]) if Kk else None,
-                                          _ptr(kcs[src]) if Kk else None, _ptr(first if it == 0 else shifts[1]), _ptr(sigma),
-                                          self.icem_rho, _ptr(low), _ptr(high), n_it, m, h, act_dim, Kk,
-                                          int(self.icem_add_mean and it == iters - 1), _ptr(means[dst]), _ptr(stds[dst]), _ptr(a_clip),
-                                          _ptr(seq), _stream_ptr(dev)), "l2a_icem_sample")
+            # (the two entries differ in one argument: the AR(1) coefficient, or the device matrix of nz = M z)
+            sample, name = (lib.l2a_icem_sample, "l2a_icem_sample") if noise is None else (lib.l2a_icem_sample_noise, "l2a_icem_sample_noise")
+            ctx.check(sample(ctx.handle, _ptr(z), ctypes.c_ulonglong(seed), ctypes.c_ulonglong(offset & 0xFFFFFFFFFFFFFFFF),
+                             _ptr(means[src]), _ptr(stds[src]), _ptr(kept[src]) if Kk else None,
+                             _ptr(kcs[src]) if Kk else None, _ptr(first if it == 0 else shifts[1]), _ptr(sigma),
+                             self.icem_rho if noise is None else _ptr(noise), _ptr(low), _ptr(high), n_it, m, h, act_dim, Kk,
+                             int(self.icem_add_mean and it == iters - 1), _ptr(means[dst]), _ptr(stds[dst]), _ptr(a_clip),
+                             _ptr(seq), _stream_ptr(dev)), name)
             _, rets = self._rollout(observations, seq, n_it, 0, want_returns=True, obs_dev=obs_dev)
             ctx.check(lib.l2a_icem_refit(ctx.handle, _ptr(rets), _ptr(a_clip), _ptr(low), _ptr(high), n_it, m, h, act_dim, K, Kk,
                                          float(self.alpha), _ptr(work), _ptr(means[dst]), _ptr(stds[dst]),
@@ -1841,5 +1880,6 @@ class MPCController(Policy, Serializable):
             elites[i, counts[i]:] = 0.0
         self.last_plan = dict(best_index=last["best_index"], best_return=last["best_return"], returns=last["returns"],
                               icem_mean=host[at[1]:at[2]].reshape(m, D).copy(), icem_std=host[at[2]:at[3]].reshape(m, D).copy(),
-                              icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps)
+                              icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps,
+                              icem_noise=np.str_(self.icem_noise), icem_beta=np.float64(self.icem_beta))
         return head[-1, :, :act_dim].astype(np.float64)

@@ -17,6 +17,7 @@ Every rank's step equals the unsharded one bit for bit.
 
 import numpy as np
 
+from .._lib import L2AError
 from .native_step import StepHandle, _seed
 
 
@@ -56,6 +57,19 @@ class NativeIcemStep(StepHandle):
     def reseed(self, seed):
         """The Philox stream restarts at 0 under ``seed``; mean, spread, kept elites and counts are kept."""
         self.ctx.check(self.lib.l2a_icem_controller_reseed(self.handle, _seed(seed)), "l2a_icem_controller_reseed")
+
+    def set_noise(self, M):
+        """From the next step on every iteration samples with ``nz = M z`` (``l2a_icem_sample_noise``; sharded:
+        ``l2a_icem_sample_noise_shard``) in place of the AR(1) recurrence: ``M [h, h]``, any matrix - ``l2a_icem_noise_matrix``'s for
+        power-law noise -, copied to the device as fp32.  ``None`` returns the controller to its ``rho``."""
+        if not hasattr(self.lib, "l2a_icem_controller_set_noise"):
+            raise L2AError("this libl2a_hip.so has no power-law iCEM noise (l2a_icem_controller_set_noise): rebuild it")
+        if M is not None:
+            M = np.ascontiguousarray(M, dtype=np.float32)
+            if M.shape != (self.h, self.h):
+                raise ValueError("the noise matrix must be [h, h] = [%d, %d], got shape %s" % (self.h, self.h, M.shape))
+        self.ctx.check(self.lib.l2a_icem_controller_set_noise(self.handle, None if M is None else M.ctypes.data),
+                       "l2a_icem_controller_set_noise")
 
     def heads(self):
         """The latest step's result rows ``[iters, m, act_dim + 4]`` - the step's own read-back, no copy from the device."""

@@ -14,6 +14,11 @@ statistics, and the launches per iteration they add up to, to the same file:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o SHAPE -- python tools/probe_icem.py --kernels SHAPE --steps 200
     python tools/probe_icem.py --stats DIR/.../SHAPE_kernel_stats.csv --shape SHAPE [--out profiles/icem.jsonl]
 
+``--noise`` turns every mode to the planner's two noises instead: AR(1) (``icem_noise="ar1"``) next to power-law noise
+(``icem_noise="powerlaw"``, ``icem_beta = 2``; ``--quality`` adds ``icem_beta = 1``), the step time through the Python loop and through
+the C step (``native_icem_step=True``; a shape the C step declines is recorded as planned by the Python loop), the traced kernels
+``l2a_icem_sample_k`` and ``l2a_icem_sample_noise_k``; the lines go to ``profiles/icem_noise.jsonl``.
+
 Plan quality (``--quality``): the toy linear system and the fitted 5-member ensemble of ``tools/demo_closed_loop.py mb_mpc``, 50
 closed-loop steps per episode, iCEM against device CEM at (as nearly as the integers allow) equal rollouts per step.
 """
@@ -34,12 +39,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 SHAPES = {"config2": "c2_hc_rs_n2000_h30_e5", "grbal_default": "c3b_ant_rs_n500_h10_pb5_3x512"}
 VARIANTS = {"icem_3iter": dict(rng="device", use_icem=True, icem_iters=3),
             "cem_3iter_device": dict(rng="device", use_cem=True, num_cem_iters=3, cem_mode="fixed")}
+NOISE_VARIANTS = {"ar1_python": dict(rng="device", use_icem=True, icem_iters=3),
+                  "powerlaw_python": dict(rng="device", use_icem=True, icem_iters=3, icem_noise="powerlaw", icem_beta=2.0),
+                  "ar1_c_step": dict(rng="device", use_icem=True, icem_iters=3, native_icem_step=True),
+                  "powerlaw_c_step": dict(rng="device", use_icem=True, icem_iters=3, native_icem_step=True, icem_noise="powerlaw",
+                                          icem_beta=2.0)}
+NOISE_KERNELS = ("l2a_icem_sample_k", "l2a_icem_sample_noise_k")
 ICEM_KERNELS = ("l2a_icem_sample_k", "l2a_icem_rank_k", "l2a_icem_stats_k")
 CEM_KERNELS = ("l2a_cem_sample_k", "l2a_cem_rank_k", "l2a_cem_stats_k", "l2a_cem_refit_sample_k", "l2a_cem_pick_k")
 
 
-def _build(shape, variants):
+def _build(shape, variants, table=None):
     """``(case, obs, {variant: controller})`` on one shared model."""
+    table = VARIANTS if table is None else table
     import cases
     from learning_to_adapt_amd.policies import MPCController
     name = SHAPES[shape]
@@ -47,7 +59,7 @@ def _build(shape, variants):
     gold = cases.load_golden("%s_s%d" % (name, case["seeds"][0]))
     env, model = cases.product_model(case)
     ctrls = {v: MPCController(name="policy", env=env, dynamics_model=model, discount=case.get("discount", 1.0), n_candidates=case["n"],
-                              horizon=case["h"], **VARIANTS[v]) for v in variants}
+                              horizon=case["h"], **table[v]) for v in variants}
     return case, gold["obs0"], ctrls
 
 
@@ -56,7 +68,8 @@ def latency(args):
     lines = []
     for shape in args.shapes.split(","):
         torch.manual_seed(1)
-        case, obs, ctrls = _build(shape, list(VARIANTS))
+        table = NOISE_VARIANTS if args.noise else VARIANTS
+        case, obs, ctrls = _build(shape, [v for v in table if not args.variants or v in args.variants.split(",")], table)
         for _ in range(args.warmup):
             for c in ctrls.values():
                 c.get_actions(obs)
@@ -77,6 +90,8 @@ def latency(args):
                        rollouts_per_step=int(rollouts), steps=args.steps, repeats=args.repeats,
                        p50_ms=round(float(np.median(p50[v])), 4), p50_ms_repeats=[round(x, 4) for x in p50[v]],
                        spread_ms=round(max(p50[v]) - min(p50[v]), 4), device=torch.cuda.get_device_name(0))
+            if args.noise:
+                rec.update(icem_noise=getattr(c, "icem_noise", "ar1"), icem_beta=getattr(c, "icem_beta", None), planned_by="c step" if c._icem_side == "c" else "python loop")
             print(json.dumps(rec), flush=True)
             lines.append(rec)
         del ctrls
@@ -87,7 +102,10 @@ def kernels(args):
     """The program to trace: iCEM steps and three-iteration CEM steps on one shape."""
     import torch
     torch.manual_seed(1)
-    _, obs, ctrls = _build(args.kernels, list(VARIANTS))
+    if args.noise:
+        _, obs, ctrls = _build(args.kernels, ["ar1_python", "powerlaw_python"], NOISE_VARIANTS)
+    else:
+        _, obs, ctrls = _build(args.kernels, list(VARIANTS))
     for _ in range(args.steps):
         for c in ctrls.values():
             c.get_actions(obs)
@@ -99,8 +117,8 @@ def stats(args):
     lines, avg = [], {}
     with open(args.stats) as f:
         for row in csv.DictReader(f):
-            for k in ICEM_KERNELS + CEM_KERNELS:
-                if k + "(" in row["Name"]:
+            for k in (NOISE_KERNELS if args.noise else ICEM_KERNELS + CEM_KERNELS):
+                if k + "(" in row["Name"] or k + "<" in row["Name"]:
                     avg[k] = float(row["AverageNs"]) / 1e3
                     lines.append(dict(kind="kernel", shape=args.shape, case=SHAPES[args.shape], kernel=k, calls=int(row["Calls"]),
                                       avg_us=round(avg[k], 3), min_us=round(float(row["MinNs"]) / 1e3, 3),
@@ -139,7 +157,13 @@ def quality(args):
     cem = MPCController(name="policy", env=env, dynamics_model=model, n_candidates=rollouts // iters, horizon=h, rng="device",
                         use_cem=True, num_cem_iters=iters, cem_mode="fixed")
     lines = []
-    for name, policy, per_step in (("icem_3iter", icem, rollouts), ("cem_3iter_device", cem, (rollouts // iters) * iters)):
+    planners = (("icem_3iter", icem, rollouts), ("cem_3iter_device", cem, (rollouts // iters) * iters))
+    if args.noise:          # the same rollouts per step: the noise does not change the populations
+        planners = (("icem_3iter_ar1", icem, rollouts),) + tuple(
+            ("icem_3iter_powerlaw_beta%g" % beta,
+             MPCController(name="policy", env=env, dynamics_model=model, n_candidates=n, horizon=h, rng="device", use_icem=True,
+                           icem_iters=iters, icem_noise="powerlaw", icem_beta=beta), rollouts) for beta in (1.0, 2.0))
+    for name, policy, per_step in planners:
         totals = []
         for ep in range(args.episodes):
             np.random.seed(100 + ep)
@@ -169,6 +193,8 @@ def main():
     ap.add_argument("--kernels", default="", choices=[""] + list(SHAPES), help="run this shape's iCEM and CEM steps for a profiler")
     ap.add_argument("--stats", default="", help="a rocprofv3 kernel-statistics CSV to take the planner kernels' rows from")
     ap.add_argument("--shape", default="config2", choices=list(SHAPES), help="the shape the --stats file was traced on")
+    ap.add_argument("--noise", action="store_true", help="AR(1) next to power-law noise, in every mode (profiles/icem_noise.jsonl)")
+    ap.add_argument("--variants", default="", help="step time: only these variants (comma-separated; default: all of the mode's)")
     ap.add_argument("--quality", action="store_true", help="closed-loop plan quality on the toy system")
     ap.add_argument("--quality-steps", type=int, default=50)
     ap.add_argument("--episodes", type=int, default=5)
