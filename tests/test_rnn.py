@@ -736,7 +736,10 @@ def test_gpu_rnn_generic_micro_tiles_match_the_16_candidate_kernel_and_the_oracl
     """The micro-tile form of the generic recurrent kernel (csrc/l2a_rnn_micro.h: GRU / BasicRNN / LSTM stacks of 256-unit layers on
     candidate tiles of four, workgroups of up to three of them - or, for larger plans, of four, in several rounds) against the 16-candidate kernel (l2a_rnn_mfma.h; the hidden layers sum in the same order, the output
     layer per wave and then over the waves) and against the oracle's cells (oracle/rnn_cells.py <- dynamics/core/utils.py:192-236):
-    every return, the arg-max key, from non-zero hidden states, with a discount, ragged last tiles, keys-only launches."""
+    every return, the arg-max key, from non-zero hidden states, with a discount, ragged last tiles, keys-only launches.
+    These are workload-sized plans on three input shapes; every body of the kernel (instance x micro tiles per workgroup, the
+    512-unit instances included), the edges of the input shapes, a guarded `returns_out` and a second `set_weights` are in
+    tests/test_gpu_rnn_micro_matrix.py (table: tests/rnn_micro_matrix.py, routing without a GPU: tests/test_rnn_micro_matrix.py)."""
     from learning_to_adapt_amd import _lib
     from oracle.rnn_planner import rnn_rollout_returns
     case = dict(cases.CASES["hc_rnn_rs_gru2_n48_h4"], units=sum(hidden), m=m, n=n, h=h, cell_type=cell, hidden_sizes=list(hidden),
