@@ -387,7 +387,8 @@ int l2a_mlp_traj_geometry(int obs_dim, int act_dim, int n_hidden, int hidden, in
                           int micro_policy, int num_cu, int* out);
 
 /* ---- particle plans: trajectory sampling over the members of a mean ensemble -----------------------
- * PETS-style TS-infinity (Chua et al. 2018); not in the reference, the semantics are build-defined.  Every member of an
+ * PETS-style TS-infinity and TS1 (Chua et al. 2018); not in the reference, the semantics are build-defined.  TS-infinity first
+ * (a particle stays on one member for the whole horizon; TS1, which deals the particles anew at every step, follows).  Every member of an
  * L2A_MODE_MEAN model of E = n_sets >= 2 weight sets rolls every candidate out as a trajectory of its own, and a candidate is
  * scored by the mean of its E returns, less `lambda` times their standard deviation (lambda > 0 prefers plans the members
  * agree on, lambda < 0 seeks disagreement, 0 is the plain mean).
@@ -435,6 +436,57 @@ int l2a_plan_rs_particles_program(l2a_model* model, const float* obs0, const flo
 int l2a_plan_rs_particles_reward_model(l2a_model* model, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
                                        int h, double discount, float lambda, int cand_offset, float* score_out, float* spread_out,
                                        float* member_returns_out, unsigned long long* best_key, void* stream);
+
+/* ---- particle plans, TS1: the particles are dealt anew over the members at every horizon step ------------
+ * Between horizon steps t and t + 1 ("boundary t", t = 0 .. h - 2) every candidate's E particles - state and accumulated return -
+ * move among the E blocks by a random permutation; block e <-> weight set e stays what the rollout kernels know.  A permutation
+ * keeps every member at exactly one particle per candidate (PETS' own implementation shuffles the same way).
+ *
+ * The permutation pi = pi(seed, offset, t, i, gj), gj = cand_offset + j: pi(e) is the block that the particle of block e CAME FROM.
+ * Fisher-Yates from the identity, k = E - 1 down to 1: r = (word * (k + 1)) >> 32 (64-bit product), entries k and r change
+ * places.  Draw d = E - 1 - k is word d & 3 of Philox4x32-10 with key `seed`, counter words
+ * { lo, hi, 0x7065726d ('perm') + (d >> 2), 0 } of ctr = ((offset + t * m + i) << 31) | gj.  The domain word differs from the
+ * uniform stream's ('unif') and from CEM's.  A 32-bit word gives r a bias of at most k / 2^32 against the uniform draw - below
+ * 4e-9 at E = 16.  `offset` counts (step, env) slots: every slot offset + t * m + i must stay below 2^33 - a whole plan needs
+ * offset + h * m <= 2^33 - and E <= 16.  pi is positional: it depends on those five values and on nothing else - not on n, the
+ * grid, the shard or the run.
+ *
+ * l2a_particle_perm: host only, needs no GPU; the same code the kernel runs.  out_host uint8 [i_count, cand_count, E]: row
+ * (i * cand_count + j) * E + e = pi(e) of env i_first + i, candidate cand_first + j at boundary t.  L2A_EINVAL, out_host untouched:
+ * E < 1, E > 16, a NULL out_host, t < 0, m < 1, a negative range, i_first + i_count > m, cand_first + cand_count > 2^31 - 1,
+ * a slot offset + t * m + i at or beyond 2^33.
+ *
+ * l2a_particle_shuffle: the kernel alone (csrc/l2a_particles.hip), ONE launch for all m envs, out of place:
+ *   state_out[i][e][j][:] = state_in[i][pi(e)][j][:]     states device fp32 [m][E * n][obs_dim]
+ *   ret_out[i][e][j]      = ret_in[i][pi(e)][j]          returns device fp32 [m][E][n]
+ * A pure copy of 32-bit words: NaN payloads, infinities and -0 pass bit for bit.  perm: NULL (Philox, above), or device uint8
+ * [m, n, E], row (i * n + j) * E + e = pi(e), which replaces the draw.  Injected entries are not validated on the device: an entry
+ * >= E is clamped to E - 1 (never a read out of bounds), and a row that is no permutation duplicates and drops particles.
+ * L2A_EINVAL, nothing launched, no output touched: a NULL buffer, state_out overlapping state_in or ret_out overlapping ret_in,
+ * m / E / n / obs_dim < 1, t < 0, E > 16, m * E * n > 2^30 - 1, a bad cand_offset (l2a_particle_score's limits), a slot at or beyond 2^33.
+ *
+ * l2a_plan_rs_particles_ts1: the plan step.  l2a_plan_rs_particles' checks and expansion, then for t = 0 .. h - 1 every env's
+ * request as ONE-step launches of the rollout kernels (l2a_plan_rs_chunk's hand-off, per-block mode, E blocks) and between t and
+ * t + 1 ONE shuffle launch over all envs, then l2a_particle_score: m * h + h + 1 launches where every request is one launch, on
+ * `stream`, no host synchronisation.  States and returns ping-pong in the model's own buffer (grown on demand before the first
+ * launch, which synchronises `stream`).  perm: NULL, or device uint8 [h - 1, m, n, E] (boundary t at t * m * n * E).  With identity
+ * permutations, and at h = 1 (no shuffle is launched), every output is bit-equal to l2a_plan_rs_particles.  score_out, spread_out,
+ * best_key as there; particle_returns_out [m, E, n] or NULL: the returns of the particles that END in block e - row e is no
+ * longer member e's: every step of such a return was predicted by the member its particle sat on at that step.  Only the fused
+ * l2a_reward formula: reward programs and reward models read a step's two states from one trajectory row, which a shuffle breaks.
+ * The launch status word keeps its meaning: a flagged tile-split launch anywhere flags the call (l2a_launch_status); the caller
+ * repeats it unsplit with the same seed / offset, which replays the same permutations.
+ * L2A_EINVAL (nothing launched, no output touched, the buffer not grown): what l2a_plan_rs_particles refuses, n_sets > 16,
+ * a NULL reward, offset + h * m > 2^33.                                                                                    */
+int l2a_particle_perm(unsigned long long seed, unsigned long long offset, int t, int m, int i_first, int i_count, int cand_first,
+                      int cand_count, int E, unsigned char* out_host);
+int l2a_particle_shuffle(l2a_ctx* ctx, const float* state_in, const float* ret_in, float* state_out, float* ret_out,
+                         const unsigned char* perm, unsigned long long seed, unsigned long long offset, int t, int m, int E, int n,
+                         int obs_dim, int cand_offset, void* stream);
+int l2a_plan_rs_particles_ts1(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                              const l2a_reward* reward, float lambda, unsigned long long seed, unsigned long long offset,
+                              const unsigned char* perm, int cand_offset, float* score_out, float* spread_out,
+                              float* particle_returns_out, unsigned long long* best_key, void* stream);
 
 /* One-step batched prediction: MLPDynamicsModel.predict / MetaMLPDynamicsModel.predict
  * (mlp_dynamics.py:204-222, meta_mlp_dynamics.py:276-294).

@@ -1600,11 +1600,10 @@ int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* o
 // only, then the scorer.  Exactly one of reward / program / rm is given.  Every check - the expansion launch's size limits
 // included - is made before the model's buffer is grown and before the first launch: a refused call synchronises nothing, frees
 // nothing and writes nothing.
-static int plan_particles(l2a_model* md, const char* who_c, const l2a_reward* reward, const l2a_reward_program* program,
-                          l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n, int h, double discount,
-                          float lambda, int cand_offset, float* score_out, float* spread_out, float* member_returns_out,
-                          unsigned long long* best_key, void* stream_v) {
-    if (!md) return L2A_EINVAL;
+// The checks every particle plan entry makes, before anything is grown or launched.  Exactly one of reward / program / rm is given.
+static int particle_plan_checks(l2a_model* md, const char* who_c, const l2a_reward* reward, const l2a_reward_program* program,
+                                l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n, int h, float lambda,
+                                int cand_offset, const float* score_out, const unsigned long long* best_key) {
     l2a_ctx* ctx = md->ctx;
     const std::string who(who_c);
     const int E = md->n_sets;
@@ -1636,7 +1635,27 @@ static int plan_particles(l2a_model* md, const char* who_c, const l2a_reward* re
         if (!md->weights_set[e]) return fail(ctx, L2A_ESTATE, "weight set " + std::to_string(e) + " was never set");
         if (!md->norm_set[e]) return fail(ctx, L2A_ESTATE, "normalisation of set " + std::to_string(e) + " was never set");
     }
-    int rc = l2a_particle_expand_check(ctx, actions, m, E, n, h, md->obs_dim, md->act_dim);
+    return l2a_particle_expand_check(ctx, actions, m, E, n, h, md->obs_dim, md->act_dim);
+}
+
+// The model's particle buffer, grown to `need` floats (which synchronises `stream`); the caller holds the device guard.
+static int grow_part_buf(l2a_model* md, long long need, hipStream_t stream) {
+    l2a_ctx* ctx = md->ctx;
+    if (need <= md->part_buf_floats) return L2A_OK;
+    if (md->part_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->part_buf)); md->part_buf = nullptr; md->part_buf_floats = 0; }
+    L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->part_buf), (size_t)need * sizeof(float)));
+    md->part_buf_floats = need;
+    return L2A_OK;
+}
+
+static int plan_particles(l2a_model* md, const char* who_c, const l2a_reward* reward, const l2a_reward_program* program,
+                          l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                          float lambda, int cand_offset, float* score_out, float* spread_out, float* member_returns_out,
+                          unsigned long long* best_key, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    const int E = md->n_sets;
+    int rc = particle_plan_checks(md, who_c, reward, program, rm, obs0, actions, m, n, h, lambda, cand_offset, score_out, best_key);
     if (rc != L2A_OK) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
@@ -1644,12 +1663,8 @@ static int plan_particles(l2a_model* md, const char* who_c, const l2a_reward* re
     auto round4 = [](long long f) { return (f + 3) / 4 * 4; };
     const long long env_obs = (long long)E * md->obs_dim, env_act = (long long)h * E * n * md->act_dim, env_ret = (long long)E * n;
     const long long obs_floats = round4(m * env_obs), act_floats = round4(m * env_act);
-    const long long need = obs_floats + act_floats + (member_returns_out ? 0 : m * env_ret);
-    if (need > md->part_buf_floats) {
-        if (md->part_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->part_buf)); md->part_buf = nullptr; md->part_buf_floats = 0; }
-        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->part_buf), (size_t)need * sizeof(float)));
-        md->part_buf_floats = need;
-    }
+    rc = grow_part_buf(md, obs_floats + act_floats + (member_returns_out ? 0 : m * env_ret), stream);
+    if (rc != L2A_OK) return rc;
     float* const obs_x = md->part_buf;
     float* const act_x = md->part_buf + obs_floats;
     float* const member = member_returns_out ? member_returns_out : md->part_buf + obs_floats + act_floats;
@@ -1703,6 +1718,61 @@ int l2a_plan_rs_particles_reward_model(l2a_model* md, l2a_reward_model* rm, cons
     if (md && !rm) return fail(md->ctx, L2A_EINVAL, "l2a_plan_rs_particles_reward_model: null reward model");
     return plan_particles(md, "l2a_plan_rs_particles_reward_model", nullptr, nullptr, rm, obs0, actions, m, n, h, discount, lambda,
                           cand_offset, score_out, spread_out, member_returns_out, best_key, stream_v);
+}
+
+// TS1: plan_particles' checks and expansion, then the horizon one step at a time - per step every env's request as a one-step
+// chunk launch that hands its states and returns on, and between two steps ONE shuffle launch over all envs.  The chunk launches
+// write buffer X, the shuffle moves X to Y, the next step's launches read Y; the last step writes its returns where the scorer
+// reads them.  Every check is made before the model's buffer is grown and before the first launch.
+int l2a_plan_rs_particles_ts1(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                              const l2a_reward* reward, float lambda, unsigned long long seed, unsigned long long offset,
+                              const unsigned char* perm, int cand_offset, float* score_out, float* spread_out,
+                              float* particle_returns_out, unsigned long long* best_key, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    const std::string who("l2a_plan_rs_particles_ts1");
+    const int E = md->n_sets;
+    if (!reward) return fail(ctx, L2A_EINVAL, who + ": null reward");
+    int rc = particle_plan_checks(md, who.c_str(), reward, nullptr, nullptr, obs0, actions, m, n, h, lambda, cand_offset, score_out, best_key);
+    if (rc != L2A_OK) return rc;
+    if (E > 16) return fail(ctx, L2A_EINVAL, who + ": the shuffle holds at most 16 members");
+    if (offset > (1ull << 33) || offset + (unsigned long long)h * (unsigned long long)m > (1ull << 33))
+        return fail(ctx, L2A_EINVAL, who + ": offset + h * m must not exceed 2^33");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    auto round4 = [](long long f) { return (f + 3) / 4 * 4; };
+    const long long env_obs = (long long)E * md->obs_dim, env_act = (long long)h * E * n * md->act_dim, env_ret = (long long)E * n;
+    const long long env_state = env_ret * md->obs_dim, step_act = (long long)E * n * md->act_dim;
+    const long long obs_floats = round4(m * env_obs), act_floats = round4(m * env_act);
+    const long long state_floats = (h > 1) ? round4(m * env_state) : 0, ret_floats = round4(m * env_ret);
+    // [obs_x | act_x | states X | states Y | returns X | returns Y | final returns unless the caller keeps them]
+    const long long need = obs_floats + act_floats + 2 * state_floats + (h > 1 ? 2 * ret_floats : 0) + (particle_returns_out ? 0 : m * env_ret);
+    rc = grow_part_buf(md, need, stream);
+    if (rc != L2A_OK) return rc;
+    float* const obs_x = md->part_buf;
+    float* const act_x = obs_x + obs_floats;
+    float* const state_X = act_x + act_floats;
+    float* const state_Y = state_X + state_floats;
+    float* const ret_X = state_Y + state_floats;
+    float* const ret_Y = ret_X + (h > 1 ? ret_floats : 0);
+    float* const last = particle_returns_out ? particle_returns_out : ret_Y + (h > 1 ? ret_floats : 0);
+    rc = l2a_particle_expand(ctx, obs0, actions, m, E, n, h, md->obs_dim, md->act_dim, obs_x, act_x, stream);
+    if (rc != L2A_OK) return rc;
+    for (int t = 0; t < h; ++t) {
+        const bool end = (t == h - 1);
+        for (int i = 0; i < m; ++i) {
+            rc = plan_rs_chunk_as(md, L2A_MODE_PER_BLOCK, t == 0 ? obs_x + i * env_obs : state_Y + i * env_state, t > 0,
+                                  act_x + i * env_act + t * step_act, E, n, 1, t, discount, reward, cand_offset,
+                                  t > 0 ? ret_Y + i * env_ret : nullptr, (end ? last : ret_X) + i * env_ret,
+                                  end ? nullptr : state_X + i * env_state, nullptr, stream_v);
+            if (rc != L2A_OK) return rc;
+        }
+        if (end) break;
+        rc = l2a_particle_shuffle(ctx, state_X, ret_X, state_Y, ret_Y, perm ? perm + (size_t)t * m * n * E : nullptr, seed, offset, t,
+                                  m, E, n, md->obs_dim, cand_offset, stream_v);
+        if (rc != L2A_OK) return rc;
+    }
+    return l2a_particle_score(ctx, last, m, E, n, lambda, cand_offset, score_out, spread_out, best_key, stream_v);
 }
 
 int l2a_predict(l2a_model* md, const float* obs, const float* act, int rows, int n_blocks,

@@ -18,6 +18,7 @@
 
 #include "l2a_host.h"
 #include "l2a_kernels.h"
+#include "l2a_philox.h"
 
 #include <cmath>
 #include <cstdint>
@@ -114,6 +115,63 @@ __global__ __launch_bounds__(L2A_PART_THREADS) void l2a_particle_score_k(const L
     }
 }
 
+// ---- TS1: the shuffle between two horizon steps ----------------------------------------------------------------------------------
+// A workgroup owns L2A_SHUF_CANDS consecutive candidates of one env.  Its first threads work the candidates' permutations out - one
+// thread per (env, candidate), ONCE: Philox and Fisher-Yates in registers (l2a_philox.h), or the injected row, clamped - park them
+// in LDS as sixteen 4-bit fields of one 64-bit word, and move the candidate's E returns.  Behind the barrier the whole workgroup
+// copies the states: within every member block the workgroup's candidates are ONE contiguous run of cnt * O words at the same
+// offset in source and destination, so thread w moves word w of that run for e = 0 .. E - 1 from block pi(e) to block e - the
+// stores of a wave are 256 contiguous bytes, its loads contiguous within each candidate's row.  Words move as 32-bit integers:
+// no float operation ever sees them.
+#define L2A_SHUF_CANDS 32
+
+struct L2AParticleShuffleParams {
+    const unsigned int* state_in;   // [m][E n][O]
+    const unsigned int* ret_in;     // [m][E][n]
+    unsigned int* state_out;
+    unsigned int* ret_out;
+    const unsigned char* perm;      // [m, n, E] or null
+    unsigned long long seed;
+    unsigned long long slot0;       // offset + t m: env i's slot is slot0 + i
+    int E, n, O, cand_offset;
+    int bpe;                        // workgroups per env: ceil(n / L2A_SHUF_CANDS)
+};
+
+__global__ __launch_bounds__(L2A_PART_THREADS) void l2a_particle_shuffle_k(const L2AParticleShuffleParams p) {
+    __shared__ unsigned long long tab[L2A_SHUF_CANDS];
+    const int env = (int)blockIdx.x / p.bpe;
+    const int j0 = ((int)blockIdx.x - env * p.bpe) * L2A_SHUF_CANDS;
+    const int cnt = (p.n - j0 < L2A_SHUF_CANDS) ? p.n - j0 : L2A_SHUF_CANDS;
+    if ((int)threadIdx.x < cnt) {
+        const int j = j0 + (int)threadIdx.x;
+        unsigned long long pk;
+        if (p.perm) {
+            const unsigned char* row = p.perm + ((size_t)env * p.n + j) * p.E;
+            pk = 0ull;
+            for (int e = 0; e < p.E; ++e) {
+                const unsigned int v = row[e];
+                pk |= (unsigned long long)(v < (unsigned int)p.E ? v : (unsigned int)p.E - 1u) << (4 * e);
+            }
+        } else {
+            pk = l2a_particle_perm_pack(p.seed, p.slot0 + (unsigned long long)env, (unsigned int)(p.cand_offset + j), p.E);
+        }
+        tab[threadIdx.x] = pk;
+        const unsigned int* __restrict__ ri = p.ret_in + (size_t)env * p.E * p.n + j;
+        unsigned int* __restrict__ ro = p.ret_out + (size_t)env * p.E * p.n + j;
+        for (int e = 0; e < p.E; ++e) ro[(size_t)e * p.n] = ri[(size_t)((pk >> (4 * e)) & 15ull) * p.n];
+    }
+    __syncthreads();
+    const size_t block_words = (size_t)p.n * p.O;                   // one member block of one env
+    const size_t base = (size_t)env * p.E * block_words + (size_t)j0 * p.O;
+    const unsigned int* __restrict__ si = p.state_in + base;
+    unsigned int* __restrict__ so = p.state_out + base;
+    const int words = cnt * p.O;
+    for (int w = (int)threadIdx.x; w < words; w += L2A_PART_THREADS) {
+        const unsigned long long pk = tab[w / p.O];
+        for (int e = 0; e < p.E; ++e) so[(size_t)e * block_words + w] = si[(size_t)((pk >> (4 * e)) & 15ull) * block_words + w];
+    }
+}
+
 // The expansion launch's geometry for source actions at `actions` and a destination at `act_x`: f32x4 words when a (step, env)
 // run is a multiple of four floats and both pointers are 16-byte aligned, else floats.  L2A_EINVAL when a run or the launch's
 // thread count does not fit 32 bits.
@@ -171,6 +229,57 @@ int l2a_particle_score(l2a_ctx* ctx, const float* member_returns, int m, int E, 
     p.lambda = lambda; p.E = E; p.n = n; p.cand_offset = cand_offset;
     p.bpe = l2a_ceil_div(n, L2A_PART_THREADS);
     hipLaunchKernelGGL(l2a_particle_score_k, dim3((unsigned)((long long)m * p.bpe)), dim3(L2A_PART_THREADS), 0, stream, p);
+    L2A_HIP(ctx, hipGetLastError());
+    return L2A_OK;
+}
+
+// every slot offset + t m + i, i < m, below 2^33?  (offset <= 2^33 is tested first: nothing below overflows 64 bits)
+static bool slots_fit(unsigned long long offset, int t, int m, long long i_end) {
+    if (offset > L2A_PERM_SLOT_LIMIT) return false;
+    return offset + (unsigned long long)t * (unsigned long long)m + (unsigned long long)i_end <= L2A_PERM_SLOT_LIMIT;
+}
+
+int l2a_particle_perm(unsigned long long seed, unsigned long long offset, int t, int m, int i_first, int i_count, int cand_first,
+                      int cand_count, int E, unsigned char* out_host) {
+    if (!out_host || E < 1 || E > L2A_PERM_MAX_E) return L2A_EINVAL;
+    if (t < 0 || m < 1 || i_first < 0 || i_count < 0 || cand_first < 0 || cand_count < 0) return L2A_EINVAL;
+    if ((long long)i_first + i_count > m || (long long)cand_first + cand_count > 0x7fffffffLL) return L2A_EINVAL;
+    if (!slots_fit(offset, t, m, (long long)i_first + i_count)) return L2A_EINVAL;
+    const unsigned long long slot0 = offset + (unsigned long long)t * (unsigned long long)m;
+    for (int i = 0; i < i_count; ++i)
+        for (int j = 0; j < cand_count; ++j) {
+            const unsigned long long pk = l2a_particle_perm_pack(seed, slot0 + (unsigned long long)(i_first + i),
+                                                                 (unsigned int)(cand_first + j), E);
+            unsigned char* row = out_host + ((size_t)i * cand_count + j) * E;
+            for (int e = 0; e < E; ++e) row[e] = (unsigned char)((pk >> (4 * e)) & 15ull);
+        }
+    return L2A_OK;
+}
+
+int l2a_particle_shuffle(l2a_ctx* ctx, const float* state_in, const float* ret_in, float* state_out, float* ret_out,
+                         const unsigned char* perm, unsigned long long seed, unsigned long long offset, int t, int m, int E, int n,
+                         int obs_dim, int cand_offset, void* stream_v) {
+    if (!ctx) return L2A_EINVAL;
+    if (!state_in || !ret_in || !state_out || !ret_out) return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: null buffer");
+    if (m < 1 || E < 1 || n < 1 || obs_dim < 1 || t < 0) return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: m, E, n and obs_dim must be >= 1, t >= 0");
+    if (E > L2A_PERM_MAX_E) return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: at most 16 members");
+    if ((long long)m * E * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: too many candidates");
+    if ((long long)L2A_SHUF_CANDS * obs_dim > 0x7fffffffLL) return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: obs_dim too large");
+    if (!slots_fit(offset, t, m, m)) return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: offset + t * m + i must stay below 2^33");
+    const size_t rets = (size_t)m * E * n, states = rets * (size_t)obs_dim;
+    auto overlap = [](const float* a, const float* b, size_t count) { return a < b + count && b < a + count; };
+    if (overlap(state_in, state_out, states) || overlap(ret_in, ret_out, rets))
+        return l2a_fail(ctx, L2A_EINVAL, "l2a_particle_shuffle: the shuffle is out of place (an output overlaps its input)");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    L2AParticleShuffleParams p;
+    p.state_in = reinterpret_cast<const unsigned int*>(state_in); p.ret_in = reinterpret_cast<const unsigned int*>(ret_in);
+    p.state_out = reinterpret_cast<unsigned int*>(state_out); p.ret_out = reinterpret_cast<unsigned int*>(ret_out);
+    p.perm = perm; p.seed = seed; p.slot0 = offset + (unsigned long long)t * (unsigned long long)m;
+    p.E = E; p.n = n; p.O = obs_dim; p.cand_offset = cand_offset;
+    p.bpe = l2a_ceil_div(n, L2A_SHUF_CANDS);
+    hipLaunchKernelGGL(l2a_particle_shuffle_k, dim3((unsigned)((long long)m * p.bpe)), dim3(L2A_PART_THREADS), 0, stream, p);
     L2A_HIP(ctx, hipGetLastError());
     return L2A_OK;
 }

@@ -32,3 +32,34 @@ __host__ __device__ inline float l2a_philox_uniform(unsigned long long seed, uns
     l2a_philox4x32_10(seed, e >> 2, L2A_PHILOX_UNIFORM, c);
     return l2a_uniform_from_word(c[e & 3ull], low, range);
 }
+
+#define L2A_PHILOX_PERM 0x7065726du         // 'perm' .. 'perm' + 3: the TS1 particle shuffle's four word groups
+#define L2A_PERM_MAX_E 16
+#define L2A_PERM_SLOT_LIMIT (1ull << 33)    // (step, env) slots: the slot fills the counter's 33 bits above the candidate's 31
+
+// The permutation of 0 .. E - 1 (1 <= E <= 16) of horizon boundary `slot` = offset + t m + i and candidate gj < 2^31, packed four
+// bits per entry: entry e - bits 4 e .. 4 e + 3 - is the block the particle that lands in block e comes from.  Fisher-Yates from
+// the identity, k = E - 1 down to 1: r = (word (k + 1)) >> 32 (64-bit product), entries k and r change places.  Draw d = E - 1 - k
+// is word d & 3 of l2a_philox4x32_10(seed, slot << 31 | gj, L2A_PHILOX_PERM + (d >> 2)).  A 32-bit word leaves r a bias of at most
+// k / 2^32 against the uniform draw.  Fully unrolled: the words and the table stay in registers.
+__host__ __device__ inline unsigned long long l2a_particle_perm_pack(unsigned long long seed, unsigned long long slot,
+                                                                     unsigned int gj, int E) {
+    unsigned long long p = 0xfedcba9876543210ull;
+    const unsigned long long ctr = (slot << 31) | (unsigned long long)gj;
+#pragma unroll
+    for (int q = 0; q < (L2A_PERM_MAX_E - 1 + 3) / 4; ++q) {
+        if (4 * q >= E - 1) break;
+        unsigned int c[4];
+        l2a_philox4x32_10(seed, ctr, L2A_PHILOX_PERM + (unsigned int)q, c);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int k = E - 1 - (4 * q + w);
+            if (k >= 1) {
+                const int r = (int)(((unsigned long long)c[w] * (unsigned long long)(k + 1)) >> 32);
+                const unsigned long long x = ((p >> (4 * k)) ^ (p >> (4 * r))) & 15ull;
+                p ^= (x << (4 * k)) | (x << (4 * r));
+            }
+        }
+    }
+    return p;
+}

@@ -314,6 +314,49 @@ class NativeModel(object):
         self.particle_plans = getattr(self, "particle_plans", 0) + 1
         self.ctx.check(rc, what)
 
+    def plan_rs_particles_ts1(self, obs0, actions, m, n, h, discount, reward, risk_coef=0.0, seed=0, offset=0, perm=None,
+                              cand_offset=0, score_out=None, spread_out=None, particle_returns_out=None, best_key=None):
+        """TS1 plan step over the ensemble's particles (``l2a_plan_rs_particles_ts1``): as ``plan_rs_particles`` with a ``RewardSpec``,
+        but between two horizon steps every candidate's particles are dealt anew over the members - the Philox permutations of
+        ``(seed, offset)``, or ``perm``, a uint8 CUDA tensor ``[h - 1, m, n, n_sets]``.  ``particle_returns_out [m, n_sets, n]``: the
+        returns of the particles that END in block e (row e is no longer member e's)."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        for t, count in ((score_out, m * n), (spread_out, m * n), (particle_returns_out, m * self.n_sets * n)):
+            if t is not None:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == count
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if perm is not None:
+            assert perm.is_cuda and perm.dtype == torch.uint8 and perm.is_contiguous() and perm.numel() == (h - 1) * m * n * self.n_sets
+        if not hasattr(self.lib, "l2a_plan_rs_particles_ts1"):
+            raise _lib.L2AError("this libl2a_hip.so has no TS1 particle plans (l2a_plan_rs_particles_ts1): rebuild it")
+        if not isinstance(reward, RewardSpec):
+            raise _lib.L2AError("TS1 particle plans score the fused reward formula only (a RewardSpec), not %s" % type(reward).__name__)
+        rc = self.lib.l2a_plan_rs_particles_ts1(self.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h), float(discount),
+                                                ctypes.byref(reward), ctypes.c_float(risk_coef), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                int(offset), _ptr(perm), int(cand_offset), _ptr(score_out), _ptr(spread_out),
+                                                _ptr(particle_returns_out), _ptr(best_key), _stream_ptr(self.device))
+        self.particle_plans = getattr(self, "particle_plans", 0) + 1
+        self.ctx.check(rc, "l2a_plan_rs_particles_ts1")
+
+    def particle_shuffle(self, state_in, ret_in, state_out, ret_out, m, n, t=0, seed=0, offset=0, perm=None, cand_offset=0):
+        """The TS1 shuffle alone (``l2a_particle_shuffle``): fp32 CUDA states ``[m, n_sets * n, obs_dim]`` and returns
+        ``[m, n_sets, n]``, out of place; ``perm``: uint8 CUDA ``[m, n, n_sets]`` or ``None`` (Philox of ``seed, offset, t``)."""
+        E = self.n_sets
+        for x, count in ((state_in, m * E * n * self.obs_dim), (state_out, m * E * n * self.obs_dim), (ret_in, m * E * n),
+                         (ret_out, m * E * n)):
+            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == count
+        if perm is not None:
+            assert perm.is_cuda and perm.dtype == torch.uint8 and perm.is_contiguous() and perm.numel() == m * n * E
+        if not hasattr(self.lib, "l2a_particle_shuffle"):
+            raise _lib.L2AError("this libl2a_hip.so has no particle shuffle (l2a_particle_shuffle): rebuild it")
+        rc = self.lib.l2a_particle_shuffle(self.ctx.handle, _ptr(state_in), _ptr(ret_in), _ptr(state_out), _ptr(ret_out), _ptr(perm),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), int(t), int(m), E, int(n), self.obs_dim,
+                                           int(cand_offset), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_particle_shuffle")
+
     def particle_score(self, member_returns, m, n_members, n, risk_coef=0.0, cand_offset=0, score_out=None, spread_out=None,
                        best_key=None):
         """The particle scorer alone (``l2a_particle_score``) on fp32 CUDA ``member_returns [m, n_members, n]``."""

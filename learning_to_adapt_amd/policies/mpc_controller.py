@@ -57,7 +57,11 @@ deltas averaged at every horizon step; ``"particles"``: PETS-style trajectory sa
 trajectory of its own and a candidate's score is the mean of its E returns less ``risk_coef`` times their standard deviation,
 ``l2a_plan_rs_particles``; random shooting, CEM and MPPI all plan on that score, ``particle_diagnostics()`` reads the winner's
 member returns back; the C controller steps do not apply: the default ``native_step`` steps aside, an explicit ``native_cem_step``
-/ ``native_mppi_step`` raises).
+/ ``native_mppi_step`` raises),
+``particle_sampling`` (with ``ensemble_planning="particles"``: ``"tsinf"``, the default - a particle stays on one member for the
+whole horizon - or ``"ts1"``: between two horizon steps every candidate's particles are dealt anew over the members by a random
+permutation, ``l2a_plan_rs_particles_ts1``; seeded by ``torch.initial_seed()`` under either ``rng``, every rollout takes the next
+``horizon * m`` permutation slots; the fused reward formula only, one rank only).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -117,6 +121,7 @@ class MPCController(Policy, Serializable):
             native_icem_step=False,
             icem_noise="ar1",
             icem_beta=2.0,
+            particle_sampling="tsinf",
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -196,6 +201,12 @@ class MPCController(Policy, Serializable):
         self.risk_coef = float(risk_coef)
         if not np.isfinite(self.risk_coef):
             raise ValueError("risk_coef must be finite")
+        if particle_sampling not in ("tsinf", "ts1"):
+            raise ValueError("particle_sampling is 'tsinf' or 'ts1', not %r" % (particle_sampling,))
+        if particle_sampling == "ts1" and ensemble_planning != "particles":
+            raise ValueError("particle_sampling='ts1' deals an ensemble's particles anew at every horizon step: it needs "
+                             "ensemble_planning='particles'")
+        self.particle_sampling = particle_sampling
         if ensemble_planning == "particles":
             self._check_particles()
 
@@ -208,6 +219,11 @@ class MPCController(Policy, Serializable):
         super(MPCController, self).__init__(env=env)
 
         self._reward_spec = None if use_reward_model else reward_spec_for_env(env)
+        if particle_sampling == "ts1" and (use_reward_model or isinstance(self._reward_spec, RewardProgram)):
+            raise _lib.L2AError("particle_sampling='ts1' scores the fused reward formula only: a reward program or a reward model "
+                                "reads a step's two states from one trajectory row, which the shuffle between steps breaks")
+        self._ts1_calls = 0         # `_rollout` calls under particle_sampling="ts1" since the seed below was first seen
+        self._ts1_seed = None       # torch.initial_seed() the count belongs to: a changed seed restarts it
         self._bufs = {}
         if self.use_mppi:
             self._mppi_sigma_vector()       # (a bad mppi_sigma fails here, not on the first step)
@@ -532,6 +548,23 @@ class MPCController(Policy, Serializable):
             # returns do; the member returns and the spread stay on the device (`particle_diagnostics`)
             members = self._buf("p_members", (m, native.n_sets, n_local), torch.float32, dev)
             spread = self._buf("p_spread", (m, n_local), torch.float32, dev)
+            if self.particle_sampling == "ts1":
+                # the permutations are positional in (seed, offset, step, env, candidate): every `_rollout` call - an RS step, a
+                # CEM / MPPI / iCEM iteration, a relaunch after a flagged tile split - takes the next h * m slots
+                if self._dist()[1] > 1:
+                    raise _lib.L2AError("particle_sampling='ts1' is not sharded at the controller level: plan on one rank "
+                                        "(shard_candidates=False), or call l2a_plan_rs_particles_ts1 per shard")
+                seed = int(torch.initial_seed())
+                if seed != self._ts1_seed:
+                    self._ts1_seed, self._ts1_calls = seed, 0
+                offset = self._ts1_calls * self.horizon * m
+                self._ts1_calls += 1
+                native.plan_rs_particles_ts1(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
+                                             risk_coef=self.risk_coef, seed=seed, offset=offset, cand_offset=cand_offset,
+                                             score_out=rets, spread_out=spread, particle_returns_out=members, best_key=best)
+                self._particles = dict(members=members, spread=spread, score=rets, best=best, cand_offset=cand_offset,
+                                       ts1_offset=offset)
+                return best, rets
             native.plan_rs_particles(obs0, actions_local, m, n_local, self.horizon, self.discount,
                                      rm.planner_reward_model() if rm is not None else self._reward_spec, risk_coef=self.risk_coef,
                                      cand_offset=cand_offset, score_out=rets, spread_out=spread, member_returns_out=members,
@@ -552,7 +585,9 @@ class MPCController(Policy, Serializable):
         step's own read-back): per env ``index`` (global candidate index of the best score in this rank's shard), ``score``, the
         winner's ``member_returns [m, E]`` and their ``std [m]``.  ``tables=True`` adds the whole ``member_returns_table
         [m, E, n_local]``, ``spread_table`` and - where the planner asked for the scores - ``score_table [m, n_local]``.  Under CEM
-        and MPPI it is the last iteration's rollout; ``None`` before the first particle plan."""
+        and MPPI it is the last iteration's rollout; ``None`` before the first particle plan.  Under ``particle_sampling="ts1"`` row
+        ``e`` of the member returns is the return of the particle that ENDED in block ``e`` - every step of it predicted by the
+        member the particle sat on then - not member ``e``'s own; score and ``std`` are taken over those E returns."""
         st = self._particles
         if st is None:
             return None

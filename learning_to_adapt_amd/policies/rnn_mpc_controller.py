@@ -61,12 +61,16 @@ class RNNMPCController(MPCController):
             mppi_iters=1,
             native_mppi_step=False,     # (accepted as `MPCController`'s; the recurrent planner's MPPI step always takes the Python path)
             ensemble_planning="mean",   # (a recurrent model is no ensemble: "particles" raises; there is no `risk_coef` here)
+            particle_sampling="tsinf",  # (as `ensemble_planning`: there are no particles to deal, "ts1" raises)
             native_cem_step=False,      # (tests/test_rnn_cem_controller.py pins this one as the last parameter)
     ):
         Serializable.quick_init(self, locals())
         if ensemble_planning != "mean":
             raise _lib.L2AError("the recurrent planner has no ensemble to sample trajectories from: ensemble_planning=%r"
                                 % (ensemble_planning,))
+        if particle_sampling != "tsinf":
+            raise _lib.L2AError("the recurrent planner has no ensemble to sample trajectories from: particle_sampling=%r"
+                                % (particle_sampling,))
         if native_reward_model:             # opt-in (as `native_cem_step`): score `use_reward_model=True` plans on the GPU
             self._takes_reward_models = True
         # alpha = 0 makes the shared CEM update `mean * alpha + (1 - alpha) * mean(elites)` the
