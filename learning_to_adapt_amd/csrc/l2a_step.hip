@@ -19,6 +19,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -107,12 +108,18 @@ struct l2a_controller {
     struct mppi_state* mppi = nullptr;
     // iCEM plan (l2a_icem_controller_create_device): per iteration l2a_icem_sample -> rollout of pops[it] -> l2a_icem_refit, one read-back
     struct icem_state* icem = nullptr;
+    struct warm_state* warm = nullptr;          // the MPPI or the iCEM plan: what a plan that persists from step to step shares
     struct plan_state* plan = nullptr;          // whichever of the three: what every kind of plan step shares
 };
+
+enum plan_kind { PLAN_NONE, PLAN_CEM, PLAN_MPPI, PLAN_ICEM };       // (PLAN_NONE: random shooting)
 
 // What the device-mode plan steps (CEM, MPPI, iCEM) share: the iterations' returns, the packed result behind ONE read-back and, for one
 // rank of a sharded plan, the words of the per-iteration gather and the verdict accumulated over them.
 struct plan_state {
+    plan_kind kind = PLAN_NONE;
+    const char* name = "";                      // "sharded CEM" / "sharded MPPI" / "sharded iCEM" in a sharded step's error texts
+    const char* facts = "";                     // what beside seed, step count, m, n, h and iters the ranks' digests cover, in words
     int iters = 0, D = 0, row_floats = 0;       // a result row: the action | return | index bits | ... (CEM: A + 2, MPPI and iCEM: A + 4 floats)
     size_t rows_at = 0;                         // the rows `plan_finish` decodes start here in `packed` (iCEM: the last iteration's block)
     unsigned long long iter_calls = 0;          // iterations planned so far (the Philox stream's position)
@@ -146,51 +153,46 @@ struct cem_state : plan_state {
     float* act_dev = nullptr;                   // recurrent: the winners' first actions [m, act_dim] (l2a_cem_pick_act -> l2a_lstm_advance)
 };
 
-// Device-mode MPPI (`MPCController.get_mppi_action`): per iteration l2a_mppi_sample (sharded: l2a_mppi_sample_shard over this rank's
-// window), the rollout (sharded: + the gather of the returns, as CEM's), l2a_mppi_update over all n; the update's packed head is
-// the step's one read-back.  Philox offsets (iter_calls + it) * n * m * D.  The plan mean persists from step to step on the device:
-// a step reads mean[cur] and writes the two others in turn, and `cur`, iter_calls and the reset marks move in `finish` only - a
-// replayed or failed step starts from the same plan.
-struct mppi_state : plan_state {
-    float kappa = 1.0f, beta = 1.0f;
+// What a plan that persists from step to step on the device (MPPI's mean, iCEM's mean, spread, kept rows and counts) needs: three
+// copies of the state that rotate together - a step reads copy `cur` and writes the two others in turn -, the marks of the envs
+// that are new or were reset with iteration 0's shift vector made from them, and the Philox position (`iter_calls`).  `cur`,
+// iter_calls and the reset marks move in `finish` only: a replayed or failed step starts from the same plan.
+struct warm_state : plan_state {
     float sigma32[16] = {0};                    // (the digest carries its bits)
     float* sigma = nullptr;                     // [act_dim] device
-    float* mean[3] = {nullptr, nullptr, nullptr};   // [m, D] each, in one allocation in front of `rets`
     float* a_clip = nullptr;                    // [n, m, D]
     int* shift = nullptr;                       // device [4][m]: all +1 | all 0 | all -1 | the step's own mix
     int* shift_host = nullptr;                  // page-locked [m]: the mix of the step in flight (it stays for a replay)
     const int* first = nullptr;                 // iteration 0's shift vector of the step in flight
-    std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts from zeros
-    int cur = 0, last = 0;                      // the committed mean | the mean the step in flight ends on
-    float* result_host = nullptr;               // page-locked [3 m D + iters m n]: l2a_mppi_controller_result's one copy
+    std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts afresh (MPPI: from zeros)
+    int cur = 0, last = 0;                      // the committed copy | the copy the step in flight ends on
+    float* result_host = nullptr;               // page-locked: the one copy of l2a_mppi_controller_result / l2a_icem_controller_result
+};
+
+// Device-mode MPPI (`MPCController.get_mppi_action`): per iteration l2a_mppi_sample (sharded: l2a_mppi_sample_shard over this rank's
+// window), the rollout (sharded: + the gather of the returns, as CEM's), l2a_mppi_update over all n; the update's packed head is
+// the step's one read-back.  Philox offsets (iter_calls + it) * n * m * D.  The plan mean is the state that persists (warm_state).
+struct mppi_state : warm_state {
+    float kappa = 1.0f, beta = 1.0f;
+    float* mean[3] = {nullptr, nullptr, nullptr};   // [m, D] each, in one allocation in front of `rets`; result_host: [3 m D + iters m n]
 };
 
 // Device-mode iCEM (`MPCController.get_icem_action`): per iteration l2a_icem_sample (sharded: l2a_icem_sample_shard over this rank's
 // window of the iteration's population pops[it]), the rollout of pops[it] candidates (sharded: + the gather), l2a_icem_refit over all
 // of them into result row block `it`; the iters * m result rows are the step's one read-back.  Philox offsets (iter_calls + it) * n *
-// m * D: the stride is the full n.  Mean, spread, kept rows and counts persist on the device, three copies each that rotate together:
-// a step reads copy `cur` and writes the two others in turn, and `cur`, iter_calls and the reset marks move in `finish` only.
-struct icem_state : plan_state {
+// m * D: the stride is the full n.  Mean, spread, kept rows and counts are the state that persists (warm_state).
+struct icem_state : warm_state {
     int K = 0, Kk = 0, add_mean = 0;
     float alpha = 0.0f, rho = 0.0f;
     std::vector<int> pops;                      // [iters]: the caller's populations
     std::vector<size_t> ret_at;                 // [iters + 1]: iteration it's table [m, pops[it]] starts at rets + ret_at[it]
-    float sigma32[16] = {0};                    // (the digest carries its bits)
-    float* sigma = nullptr;                     // [act_dim] device
     // one allocation in front of `rets`: mean [3][m, D] | std [3][m, D] | kept [3][m, max(Kk, 1), D] | kc [3][m]
     float* mean[3] = {nullptr, nullptr, nullptr};
     float* std[3] = {nullptr, nullptr, nullptr};
     float* kept[3] = {nullptr, nullptr, nullptr};
     int* kc[3] = {nullptr, nullptr, nullptr};
-    size_t head_floats = 0;                     // the floats of that allocation in front of `rets`
-    float* a_clip = nullptr;                    // [n, m, D]
+    size_t head_floats = 0;                     // the floats of that allocation in front of `rets` (result_host: + m * sum(pops))
     int* work = nullptr;                        // [m, K]: the refit's scratch
-    int* shift = nullptr;                       // device [4][m]: all +1 | all 0 | all -1 | the step's own mix
-    int* shift_host = nullptr;                  // page-locked [m]: the mix of the step in flight (it stays for a replay)
-    const int* first = nullptr;                 // iteration 0's shift vector of the step in flight
-    std::vector<unsigned char> fresh;           // [m]: the env is new or was reset - its next step starts afresh
-    int cur = 0, last = 0;                      // the committed copy | the copy the step in flight ends on
-    float* result_host = nullptr;               // page-locked [head_floats + m * sum(pops)]: l2a_icem_controller_result's one copy
     // l2a_icem_controller_set_noise: the matrix the sample reads in place of the recurrence (allocated at the first set)
     float* noise = nullptr;                     // device [h, h]
     bool noise_on = false;
@@ -341,14 +343,12 @@ struct step_cfg {
     int rank = 0, world = 1;
     l2a_reduce_fn reduce = nullptr;
     void* reduce_arg = nullptr;
-    bool cem = false;                           // a CEM plan
-    int iters = 0, num_elites = 0, reference = 0;
+    plan_kind kind = PLAN_NONE;                 // a CEM, an MPPI or an iCEM plan
+    int iters = 0, num_elites = 0, reference = 0;   // CEM (`iters`: every kind)
     float alpha = 0.0f;
-    bool mppi = false;                          // an MPPI plan (`iters` as CEM's)
-    float kappa = 0.0f, beta = 0.0f;
+    float kappa = 0.0f, beta = 0.0f;            // MPPI
     const double* sigma = nullptr;              // [act_dim] (iCEM: sigma0)
-    bool icem = false;                          // an iCEM plan (`iters`, `alpha` as CEM's, `sigma` as MPPI's)
-    const int* pops = nullptr;                  // [iters]
+    const int* pops = nullptr;                  // iCEM (`alpha` as CEM's, `sigma` as MPPI's): [iters]
     int K = 0, Kk = 0, add_mean = 0;
     float rho = 0.0f;
 
@@ -356,15 +356,15 @@ struct step_cfg {
     step_cfg& device(unsigned long long s) { device_rng = true; seed = s; return *this; }
     step_cfg& shard(int r, int w, l2a_reduce_fn fn, void* arg) { sharded = true; rank = r; world = w; reduce = fn; reduce_arg = arg; return *this; }
     step_cfg& cem_plan(int it, int elites, float a, int ref, unsigned long long s) {
-        cem = true; iters = it; num_elites = elites; alpha = a; reference = ref ? 1 : 0;
+        kind = PLAN_CEM; iters = it; num_elites = elites; alpha = a; reference = ref ? 1 : 0;
         return device(s);
     }
     step_cfg& mppi_plan(int it, float kap, float bet, const double* sig, unsigned long long s) {
-        mppi = true; iters = it; kappa = kap; beta = bet; sigma = sig;
+        kind = PLAN_MPPI; iters = it; kappa = kap; beta = bet; sigma = sig;
         return device(s);
     }
     step_cfg& icem_plan(int it, const int* pop, int k, int kk, float a, float r, const double* sig, int add, unsigned long long s) {
-        icem = true; iters = it; pops = pop; K = k; Kk = kk; alpha = a; rho = r; sigma = sig; add_mean = add ? 1 : 0;
+        kind = PLAN_ICEM; iters = it; pops = pop; K = k; Kk = kk; alpha = a; rho = r; sigma = sig; add_mean = add ? 1 : 0;
         return device(s);
     }
 };
@@ -390,44 +390,7 @@ int check_shape(const step_cfg& f) {
     const int m = f.m, n = f.n, h = f.h;
     const bool bad_mnh = m < 1 || m > L2A_MAIL_KEYS || (long long)m * f.obs_dim > L2A_MAIL_OBS || n < 1 || h < 1;
     const bool bad_act = f.act_dim < 1 || f.act_dim > 16;
-    if (f.mppi) {
-        // the limits of l2a_mppi_sample and l2a_mppi_update, so that no step can fail on its arguments
-        if (bad_mnh || bad_act)
-            return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1, 1 <= act_dim <= 16");
-        if (f.iters < 1) return refuse(f, L2A_EINVAL, "needs iters >= 1");
-        if (!(f.beta > 0.0f) || !(f.beta <= 1.0f)) return refuse(f, L2A_EINVAL, "beta must lie in (0, 1]");
-        if (!(f.kappa > 0.0f) || !std::isfinite(f.kappa)) return refuse(f, L2A_EINVAL, "kappa must be positive and finite");
-        for (int k = 0; k < f.act_dim; ++k)
-            if (!std::isfinite((float)f.sigma[k]) || !(f.sigma[k] >= 0.0)) return refuse(f, L2A_EINVAL, "sigma must be finite and non-negative");
-        if ((size_t)n * sizeof(float) + L2A_MPPI_UPDATE_STATIC_LDS > (size_t)f.ctx->lds_per_block)
-            return refuse(f, L2A_EINVAL, "more candidates than an env's weights fit in LDS (l2a_mppi_update)");
-        if ((long long)n * m * h * f.act_dim > 0x7fffffffLL * 256 || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
-            return refuse(f, L2A_EINVAL, "too many samples");
-        return L2A_OK;
-    }
-    if (f.icem) {
-        // the limits of l2a_icem_sample and l2a_icem_refit on every iteration, so that no step can fail on its arguments
-        if (bad_mnh || bad_act)
-            return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1, 1 <= act_dim <= 16");
-        if (f.iters < 1) return refuse(f, L2A_EINVAL, "needs iters >= 1");
-        if (f.K < 1 || f.K > 8192) return refuse(f, L2A_EINVAL, "needs 1 <= K <= 8192 elites");
-        if (f.Kk < 0 || f.Kk > f.K) return refuse(f, L2A_EINVAL, "needs 0 <= Kk <= K kept elites");
-        if (!(f.alpha >= 0.0f) || !(f.alpha < 1.0f)) return refuse(f, L2A_EINVAL, "alpha must lie in [0, 1)");
-        if (!(f.rho >= 0.0f) || !(f.rho < 1.0f)) return refuse(f, L2A_EINVAL, "rho must lie in [0, 1)");
-        for (int k = 0; k < f.act_dim; ++k)
-            if (!std::isfinite((float)f.sigma[k]) || !(f.sigma[k] >= 0.0)) return refuse(f, L2A_EINVAL, "sigma0 must be finite and non-negative");
-        if ((size_t)f.K * sizeof(int) + L2A_ICEM_REFIT_STATIC_LDS > (size_t)f.ctx->lds_per_block)
-            return refuse(f, L2A_EINVAL, "more elites than the statistics' list fits in LDS (l2a_icem_refit)");
-        for (int it = 0; it < f.iters; ++it) {
-            if (f.pops[it] < 1 || f.pops[it] > n) return refuse(f, L2A_EINVAL, "every pops[it] must lie in 1 .. n");
-            if ((size_t)f.pops[it] * sizeof(float) > (size_t)f.ctx->lds_per_block)
-                return refuse(f, L2A_EINVAL, "more candidates than an env's returns fit in LDS (l2a_icem_refit)");
-        }
-        if ((long long)n * m * h * f.act_dim > 0x7fffffffLL * 256 || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
-            return refuse(f, L2A_EINVAL, "too many samples");
-        return L2A_OK;
-    }
-    if (!f.cem) {
+    if (f.kind == PLAN_NONE) {
         if (bad_mnh) return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1");
         if (bad_act) return refuse(f, L2A_EINVAL, "the host draw takes 1 <= act_dim <= 16");
         if ((long long)m * n > 0x3fffffffLL) return refuse(f, L2A_EINVAL, "too many candidates");
@@ -436,11 +399,39 @@ int check_shape(const step_cfg& f) {
     }
     if (bad_mnh || bad_act)
         return refuse(f, L2A_EINVAL, "needs 1 <= m <= 64 envs (at most 4096 observation floats), n >= 1, h >= 1, 1 <= act_dim <= 16");
-    if (f.iters < 1 || f.num_elites < 1 || f.num_elites > n) return refuse(f, L2A_EINVAL, "needs iters >= 1 and 1 <= num_elites <= n");
-    if ((long long)(f.reference ? m : 1) * f.num_elites > 8192 || (size_t)n * sizeof(float) > (size_t)f.ctx->lds_per_block)
-        return refuse(f, L2A_EINVAL, "more elite rows or candidates than l2a_cem_refit takes");
     const long long D = (long long)h * f.act_dim;
-    if ((long long)n * m * D > 0x7fffffffLL || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
+    if (f.kind == PLAN_CEM) {
+        if (f.iters < 1 || f.num_elites < 1 || f.num_elites > n) return refuse(f, L2A_EINVAL, "needs iters >= 1 and 1 <= num_elites <= n");
+        if ((long long)(f.reference ? m : 1) * f.num_elites > 8192 || (size_t)n * sizeof(float) > (size_t)f.ctx->lds_per_block)
+            return refuse(f, L2A_EINVAL, "more elite rows or candidates than l2a_cem_refit takes");
+        if ((long long)n * m * D > 0x7fffffffLL || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
+            return refuse(f, L2A_EINVAL, "too many samples");
+        return L2A_OK;
+    }
+    // MPPI, iCEM: the limits of the kind's sample and update / refit kernels on every iteration, so that no step can fail on its arguments
+    if (f.iters < 1) return refuse(f, L2A_EINVAL, "needs iters >= 1");
+    for (int k = 0; k < f.act_dim; ++k)
+        if (!std::isfinite((float)f.sigma[k]) || !(f.sigma[k] >= 0.0))
+            return refuse(f, L2A_EINVAL, f.kind == PLAN_MPPI ? "sigma must be finite and non-negative" : "sigma0 must be finite and non-negative");
+    if (f.kind == PLAN_MPPI) {
+        if (!(f.beta > 0.0f) || !(f.beta <= 1.0f)) return refuse(f, L2A_EINVAL, "beta must lie in (0, 1]");
+        if (!(f.kappa > 0.0f) || !std::isfinite(f.kappa)) return refuse(f, L2A_EINVAL, "kappa must be positive and finite");
+        if ((size_t)n * sizeof(float) + L2A_MPPI_UPDATE_STATIC_LDS > (size_t)f.ctx->lds_per_block)
+            return refuse(f, L2A_EINVAL, "more candidates than an env's weights fit in LDS (l2a_mppi_update)");
+    } else {
+        if (f.K < 1 || f.K > 8192) return refuse(f, L2A_EINVAL, "needs 1 <= K <= 8192 elites");
+        if (f.Kk < 0 || f.Kk > f.K) return refuse(f, L2A_EINVAL, "needs 0 <= Kk <= K kept elites");
+        if (!(f.alpha >= 0.0f) || !(f.alpha < 1.0f)) return refuse(f, L2A_EINVAL, "alpha must lie in [0, 1)");
+        if (!(f.rho >= 0.0f) || !(f.rho < 1.0f)) return refuse(f, L2A_EINVAL, "rho must lie in [0, 1)");
+        if ((size_t)f.K * sizeof(int) + L2A_ICEM_REFIT_STATIC_LDS > (size_t)f.ctx->lds_per_block)
+            return refuse(f, L2A_EINVAL, "more elites than the statistics' list fits in LDS (l2a_icem_refit)");
+        for (int it = 0; it < f.iters; ++it) {
+            if (f.pops[it] < 1 || f.pops[it] > n) return refuse(f, L2A_EINVAL, "every pops[it] must lie in 1 .. n");
+            if ((size_t)f.pops[it] * sizeof(float) > (size_t)f.ctx->lds_per_block)
+                return refuse(f, L2A_EINVAL, "more candidates than an env's returns fit in LDS (l2a_icem_refit)");
+        }
+    }
+    if ((long long)n * m * D > 0x7fffffffLL * 256 || (long long)f.iters * m * n > 0x7fffffffLL || (long long)m * n > 0x3fffffffLL)
         return refuse(f, L2A_EINVAL, "too many samples");
     return L2A_OK;
 }
@@ -512,6 +503,7 @@ void alloc_rs(l2a_controller* c, const step_cfg& f) {
 // `window`: the most candidates this rank rolls out in one iteration, where that is not hi - lo (iCEM: the window moves with pops[it]).
 void alloc_plan(l2a_controller* c, const step_cfg& f, int row_floats, size_t packed, size_t rets_head = 0, size_t window = 0) {
     plan_state* q = c->plan;
+    q->kind = f.kind;
     const int A = c->act_dim;
     q->iters = f.iters; q->D = c->h * A; q->row_floats = row_floats;
     const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * q->D;
@@ -534,8 +526,19 @@ void alloc_plan(l2a_controller* c, const step_cfg& f, int row_floats, size_t pac
     upload(c, q->lowhigh, lh, sizeof(float) * 2 * A);
 }
 
+// The state object of a plan of one kind, `name` and `facts` for its sharded step's texts (plan_verdict_sharded); null: out of memory.
+template <typename State>
+State* new_plan(l2a_controller* c, const char* name, const char* facts) {
+    State* q = new (std::nothrow) State();
+    if (!q) { c->mem_err = hipErrorOutOfMemory; return nullptr; }
+    q->name = name; q->facts = facts;
+    c->plan = q;
+    return q;
+}
+
 void alloc_cem(l2a_controller* c, const step_cfg& f) {
-    cem_state* q = c->cem;
+    cem_state* q = c->cem = new_plan<cem_state>(c, "sharded CEM", "num_elites, mode, alpha and world");
+    if (!q) return;
     const int A = c->act_dim;
     q->k = f.num_elites; q->reference = f.reference; q->alpha = f.alpha;
     const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A, nmd = n * md;
@@ -550,24 +553,42 @@ void alloc_cem(l2a_controller* c, const step_cfg& f) {
     if (f.rnn) q->act_dev = alloc<float>(c, MEM_DEVICE, m * A);
 }
 
-void alloc_mppi(l2a_controller* c, const step_cfg& f) {
-    mppi_state* q = c->mppi;
+// The reset marks: the envs of `dones` (null: every env) start their next step afresh.
+void mark_fresh(l2a_controller* c, const unsigned char* dones) {
+    for (int i = 0; i < c->m; ++i)
+        if (!dones || dones[i]) c->warm->fresh[i] = 1;
+}
+
+// The tail of the two allocators of a plan that persists (warm_state): `result_floats` of page-locked memory for the kind's result
+// call, the clipped samples, the noise scale, the four shift rows, and every env marked new.
+void alloc_warm(l2a_controller* c, const step_cfg& f, size_t result_floats) {
+    warm_state* q = c->warm;
     const int A = c->act_dim;
-    q->kappa = f.kappa; q->beta = f.beta;
-    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A;
-    alloc_plan(c, f, A + 4, m * (A + 4), 3 * md);
-    for (int s = 0; s < 3; ++s) q->mean[s] = q->rets ? q->rets - (3 - s) * md : nullptr;
-    q->result_host = alloc<float>(c, MEM_PINNED, 3 * md + (size_t)f.iters * m * n);
-    q->a_clip = alloc<float>(c, MEM_DEVICE, n * md);
+    const size_t m = (size_t)c->m;
+    q->result_host = alloc<float>(c, MEM_PINNED, result_floats);
+    q->a_clip = alloc<float>(c, MEM_DEVICE, (size_t)c->n * m * q->D);
     q->sigma = alloc<float>(c, MEM_DEVICE, (size_t)A);
     q->shift = alloc<int>(c, MEM_DEVICE, 4 * m);
     q->shift_host = alloc<int>(c, MEM_PINNED, m);
-    q->fresh.assign(m, 1);                      // every env starts from zeros
+    q->fresh.resize(m);
+    mark_fresh(c, nullptr);
     for (int k = 0; k < A; ++k) q->sigma32[k] = (float)f.sigma[k];
     upload(c, q->sigma, q->sigma32, sizeof(float) * A);
     std::vector<int> rows(4 * m, 0);
     for (size_t i = 0; i < m; ++i) { rows[i] = 1; rows[2 * m + i] = -1; }
     upload(c, q->shift, rows.data(), sizeof(int) * rows.size());
+}
+
+void alloc_mppi(l2a_controller* c, const step_cfg& f) {
+    mppi_state* q = c->mppi = new_plan<mppi_state>(c, "sharded MPPI", "kappa, beta, sigma and world, and the same envs reset");
+    if (!q) return;
+    c->warm = q;
+    const int A = c->act_dim;
+    q->kappa = f.kappa; q->beta = f.beta;
+    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A;
+    alloc_plan(c, f, A + 4, m * (A + 4), 3 * md);
+    for (int s = 0; s < 3; ++s) q->mean[s] = q->rets ? q->rets - (3 - s) * md : nullptr;
+    alloc_warm(c, f, 3 * md + (size_t)f.iters * m * n);
 }
 
 // This rank's window of a population of `n_it`: contiguous ranges in integer arithmetic, `init_common`'s rule.
@@ -577,12 +598,15 @@ void icem_window(const l2a_controller* c, int n_it, int* lo, int* hi) {
 }
 
 void alloc_icem(l2a_controller* c, const step_cfg& f) {
-    icem_state* q = c->icem;
+    icem_state* q = c->icem = new_plan<icem_state>(c, "sharded iCEM", "populations, K, Kk, add_mean, alpha, rho, sigma0 and world, and the same "
+                                                                      "envs reset");
+    if (!q) return;
+    c->warm = q;
     const int A = c->act_dim;
     q->K = f.K; q->Kk = f.Kk; q->add_mean = f.add_mean; q->alpha = f.alpha; q->rho = f.rho;
     q->pops.assign(f.pops, f.pops + f.iters);
     q->ret_at.assign((size_t)f.iters + 1, 0);
-    const size_t m = (size_t)c->m, n = (size_t)c->n, md = m * c->h * A, kd = m * (size_t)(f.Kk > 0 ? f.Kk : 1) * c->h * A;
+    const size_t m = (size_t)c->m, md = m * c->h * A, kd = m * (size_t)(f.Kk > 0 ? f.Kk : 1) * c->h * A;
     size_t window = 0;
     for (int it = 0; it < f.iters; ++it) {
         q->ret_at[it + 1] = q->ret_at[it] + m * (size_t)f.pops[it];
@@ -601,18 +625,8 @@ void alloc_icem(l2a_controller* c, const step_cfg& f) {
         q->kc[s] = reinterpret_cast<int*>(head + 6 * md + 3 * kd) + s * m;
     }
     if (head && c->mem_err == hipSuccess) c->mem_err = hipMemset(head, 0, sizeof(float) * q->head_floats);
-    q->result_host = alloc<float>(c, MEM_PINNED, q->head_floats + q->ret_at[f.iters]);
-    q->a_clip = alloc<float>(c, MEM_DEVICE, n * md);
     q->work = alloc<int>(c, MEM_DEVICE, m * (size_t)f.K);
-    q->sigma = alloc<float>(c, MEM_DEVICE, (size_t)A);
-    q->shift = alloc<int>(c, MEM_DEVICE, 4 * m);
-    q->shift_host = alloc<int>(c, MEM_PINNED, m);
-    q->fresh.assign(m, 1);                      // every env starts afresh
-    for (int k = 0; k < A; ++k) q->sigma32[k] = (float)f.sigma[k];
-    upload(c, q->sigma, q->sigma32, sizeof(float) * A);
-    std::vector<int> rows(4 * m, 0);
-    for (size_t i = 0; i < m; ++i) { rows[i] = 1; rows[2 * m + i] = -1; }
-    upload(c, q->shift, rows.data(), sizeof(int) * rows.size());
+    alloc_warm(c, f, q->head_floats + q->ret_at[f.iters]);
 }
 
 int create(step_cfg f) {
@@ -622,24 +636,23 @@ int create(step_cfg f) {
     if (rc != L2A_OK) return rc;
     if (!f.out) return refuse(f, L2A_EINVAL, "out is null");
     *f.out = nullptr;
-    if (f.mppi && !f.sigma) return refuse(f, L2A_EINVAL, "null sigma");
-    if (f.icem && f.rnn) return refuse(f, L2A_EINVAL, "an iCEM plan takes an MLP model");
-    if (f.icem && (!f.sigma || !f.pops)) return refuse(f, L2A_EINVAL, "null pops / sigma0");
+    if (f.kind == PLAN_MPPI && !f.sigma) return refuse(f, L2A_EINVAL, "null sigma");
+    if (f.kind == PLAN_ICEM && f.rnn) return refuse(f, L2A_EINVAL, "an iCEM plan takes an MLP model");
+    if (f.kind == PLAN_ICEM && (!f.sigma || !f.pops)) return refuse(f, L2A_EINVAL, "null pops / sigma0");
     if (!f.low || !f.high || !f.reward || (!f.np_addr && !f.device_rng))
-        return refuse(f, L2A_EINVAL, (f.cem || f.mppi || f.icem) ? "null low / high / reward" : "null low / high / reward / generator state address");
+        return refuse(f, L2A_EINVAL, f.kind != PLAN_NONE ? "null low / high / reward" : "null low / high / reward / generator state address");
     rc = check_shape(f);
     if (rc != L2A_OK) return rc;
     l2a_controller* c = new (std::nothrow) l2a_controller();
-    if (c && f.cem) c->plan = c->cem = new (std::nothrow) cem_state();
-    if (c && f.mppi) c->plan = c->mppi = new (std::nothrow) mppi_state();
-    if (c && f.icem) c->plan = c->icem = new (std::nothrow) icem_state();
-    if (!c || ((f.cem || f.mppi || f.icem) && !c->plan)) { delete c; return refuse(f, L2A_EHIP, "out of memory"); }
+    if (!c) return refuse(f, L2A_EHIP, "out of memory");
     init_common(c, f);
     l2a_device_guard guard(f.ctx->device);
-    if (f.cem) alloc_cem(c, f);
-    else if (f.mppi) alloc_mppi(c, f);
-    else if (f.icem) alloc_icem(c, f);
-    else alloc_rs(c, f);
+    switch (f.kind) {                   // (a plan's allocator makes its state object first)
+    case PLAN_CEM: alloc_cem(c, f); break;
+    case PLAN_MPPI: alloc_mppi(c, f); break;
+    case PLAN_ICEM: alloc_icem(c, f); break;
+    case PLAN_NONE: alloc_rs(c, f); break;
+    }
     if (c->mem_err != hipSuccess) {
         const hipError_t e = c->mem_err;
         l2a_controller_destroy(c);
@@ -741,37 +754,47 @@ unsigned long long digest_mix(unsigned long long d, unsigned long long x) {
     return d ^ (d >> 31);
 }
 
-// What every rank of a sharded CEM step must share: how the controller was built and where its Philox stream stands.
-unsigned long long cem_digest(const l2a_controller* c) {
-    const cem_state* q = c->cem;
-    unsigned int alpha_bits = 0;
-    std::memcpy(&alpha_bits, &q->alpha, sizeof(alpha_bits));
-    const unsigned long long v[] = {c->device.seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n, (unsigned long long)c->h,
-                                    (unsigned long long)q->iters, (unsigned long long)q->k, (unsigned long long)q->reference,
-                                    (unsigned long long)alpha_bits, (unsigned long long)c->shard.world, (unsigned long long)(c->rnn ? 1 : 0)};
-    unsigned long long d = 0x9E3779B97F4A7C15ull;
-    for (unsigned long long x : v) d = digest_mix(d, x);
+const unsigned long long DIGEST_SEED = 0x9E3779B97F4A7C15ull;
+
+unsigned long long digest_words(unsigned long long d, std::initializer_list<unsigned long long> words) {
+    for (unsigned long long x : words) d = digest_mix(d, x);
     return d;
 }
 
-// The same for MPPI: the controller kind (2; CEM's last word is 0 or 1), the planner's constants by their bits, and the step's
-// shift vector - ranks that reset different envs would sample around different plans.
-unsigned long long mppi_digest(const l2a_controller* c) {
-    const mppi_state* q = c->mppi;
-    unsigned int kappa_bits = 0, beta_bits = 0;
-    std::memcpy(&kappa_bits, &q->kappa, sizeof(kappa_bits));
-    std::memcpy(&beta_bits, &q->beta, sizeof(beta_bits));
-    const unsigned long long v[] = {c->device.seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n, (unsigned long long)c->h,
-                                    (unsigned long long)q->iters, (unsigned long long)kappa_bits, (unsigned long long)beta_bits,
-                                    (unsigned long long)c->shard.world, 2ull};
-    unsigned long long d = 0x9E3779B97F4A7C15ull;
-    for (unsigned long long x : v) d = digest_mix(d, x);
-    for (int k = 0; k < c->act_dim; ++k) {
-        unsigned int bits = 0;
-        std::memcpy(&bits, &q->sigma32[k], sizeof(bits));
-        d = digest_mix(d, bits);
+unsigned long long bits(float x) {
+    unsigned int b = 0;
+    std::memcpy(&b, &x, sizeof(b));
+    return b;
+}
+
+// What every rank of a sharded plan step must share: the controller kind, how the controller was built - the planner's constants by
+// their bits - and where its Philox stream stands; for a plan that persists, the noise scale and the step's reset marks too - ranks
+// that reset different envs would sample around different plans.
+unsigned long long plan_digest(const l2a_controller* c) {
+    const plan_state* q = c->plan;
+    const auto word = [](long long x) { return (unsigned long long)x; };
+    unsigned long long d = digest_words(DIGEST_SEED, {word(q->kind), c->device.seed, q->iter_calls, word(c->m), word(c->n), word(c->h),
+                                                      word(q->iters), word(c->shard.world)});
+    switch (q->kind) {
+    case PLAN_CEM:
+        d = digest_words(d, {word(c->cem->k), word(c->cem->reference), bits(c->cem->alpha), word(c->rnn ? 1 : 0)});
+        break;
+    case PLAN_MPPI:
+        d = digest_words(d, {bits(c->mppi->kappa), bits(c->mppi->beta)});
+        break;
+    case PLAN_ICEM: {
+        const icem_state* s = c->icem;
+        for (int n_it : s->pops) d = digest_mix(d, word(n_it));
+        d = digest_words(d, {word(s->K), word(s->Kk), word(s->add_mean), bits(s->alpha), bits(s->rho)});
+        if (s->noise_on) d = digest_mix(d, s->noise_hash);      // (without a matrix the digest is the AR(1) step's)
+        break;
     }
-    for (int i = 0; i < c->m; ++i) d = digest_mix(d, q->fresh[i] ? 1ull : 0ull);
+    case PLAN_NONE: break;
+    }
+    if (const warm_state* w = c->warm) {
+        for (int k = 0; k < c->act_dim; ++k) d = digest_mix(d, bits(w->sigma32[k]));
+        for (int i = 0; i < c->m; ++i) d = digest_mix(d, w->fresh[i] ? 1ull : 0ull);
+    }
     return d;
 }
 
@@ -800,6 +823,39 @@ int read_back(l2a_controller* c) {
     return L2A_OK;
 }
 
+// The head of a plan step's launches (the caller holds the device): a sharded step's verdict cleared, and the step's own mix of new
+// and running envs - where iteration 0 shifts by one - uploaded.
+int launch_prelude(l2a_controller* c) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    const warm_state* w = c->warm;
+    const size_t m = (size_t)c->m;
+    if (w && w->first == w->shift + 3 * m)
+        L2A_HIP(c->ctx, hipMemcpyAsync(w->shift + 3 * m, w->shift_host, sizeof(int) * m, hipMemcpyHostToDevice, stream));
+    if (c->shard.on) L2A_HIP(c->ctx, hipMemsetAsync(c->plan->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
+    return L2A_OK;
+}
+
+// Iteration 0's shift vector of the step about to be launched: -1 for an env that is new or was reset, +1 for the others.
+void first_shift(l2a_controller* c) {
+    warm_state* q = c->warm;
+    const int m = c->m;
+    int fresh = 0;
+    for (int i = 0; i < m; ++i) fresh += q->fresh[i] ? 1 : 0;
+    if (fresh == 0) q->first = q->shift;
+    else if (fresh == m) q->first = q->shift + 2 * m;
+    else {
+        for (int i = 0; i < m; ++i) q->shift_host[i] = q->fresh[i] ? -1 : 1;
+        q->first = q->shift + 3 * m;
+    }
+}
+
+// The copy of the persistent state an iteration writes: neither the one it reads (`src`) nor the committed one.
+int spare_copy(const warm_state* q, int src) {
+    int dst = 0;
+    while (dst == src || dst == q->cur) ++dst;
+    return dst;
+}
+
 // Everything of one CEM plan step, in stream order on `stream`; nothing on the host waits.
 int cem_launch(l2a_controller* c) {
     l2a_ctx* ctx = c->ctx;
@@ -807,7 +863,6 @@ int cem_launch(l2a_controller* c) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
     const int m = c->m, n = c->n, h = c->h, A = c->act_dim, D = q->D;
     const unsigned long long per_iter = (unsigned long long)n * m * D, seed = c->device.seed;
-    const bool sharded = c->shard.on;
     l2a_device_guard guard(ctx->device);
     hipLaunchKernelGGL(l2a_cem_init_k, dim3((unsigned)l2a_ceil_div(m * D, 256)), dim3(256), 0, stream, m * D, q->mean[0], q->std);
     L2A_HIP(ctx, hipGetLastError());
@@ -816,8 +871,9 @@ int cem_launch(l2a_controller* c) {
     int cur = 0;
     // (sharded: every rank samples all n rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
     const int lo = c->shard.lo, hi = c->shard.hi;
-    if (sharded) L2A_HIP(ctx, hipMemsetAsync(q->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
-    int rc = l2a_cem_sample(ctx, nullptr, seed, q->iter_calls * per_iter, q->mean[0], q->std, low, high, n, m, h, A, q->reference, lo, hi,
+    int rc = launch_prelude(c);
+    if (rc == L2A_OK)
+        rc = l2a_cem_sample(ctx, nullptr, seed, q->iter_calls * per_iter, q->mean[0], q->std, low, high, n, m, h, A, q->reference, lo, hi,
                             q->a_clip[0], q->reference ? q->a_raw : nullptr, q->seq, c->stream);
     if (rc != L2A_OK) return rc;
     ctx->stamps_us[1] = l2a_now_us();
@@ -856,7 +912,6 @@ int cem_launch(l2a_controller* c) {
 int mppi_launch(l2a_controller* c) {
     l2a_ctx* ctx = c->ctx;
     mppi_state* q = c->mppi;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
     const int m = c->m, n = c->n, h = c->h, A = c->act_dim;
     const unsigned long long per_iter = (unsigned long long)n * m * q->D, seed = c->device.seed;
     const bool sharded = c->shard.on;
@@ -864,20 +919,18 @@ int mppi_launch(l2a_controller* c) {
     const float* low = q->lowhigh;
     const float* high = q->lowhigh + A;
     l2a_device_guard guard(ctx->device);
-    if (q->first == q->shift + 3 * m)           // the step's own mix of new and running envs
-        L2A_HIP(ctx, hipMemcpyAsync(q->shift + 3 * m, q->shift_host, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream));
-    if (sharded) L2A_HIP(ctx, hipMemsetAsync(q->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
+    int rc = launch_prelude(c);
+    if (rc != L2A_OK) return rc;
     int src = q->cur;
     for (int it = 0; it < q->iters; ++it) {
-        int dst = 0;
-        while (dst == src || dst == q->cur) ++dst;          // neither the mean this iteration reads nor the committed one
+        const int dst = spare_copy(q, src);
         const int* shift = it == 0 ? q->first : q->shift + m;
         const unsigned long long offset = (q->iter_calls + it) * per_iter;
         // (sharded: every rank samples all n rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
-        int rc = sharded ? l2a_mppi_sample_shard(ctx, nullptr, seed, offset, q->mean[src], shift, q->sigma, q->beta, low, high, n, m, h, A,
-                                                 lo, hi, q->mean[dst], q->a_clip, q->seq, c->stream)
-                         : l2a_mppi_sample(ctx, nullptr, seed, offset, q->mean[src], shift, q->sigma, q->beta, low, high, n, m, h, A,
-                                           q->mean[dst], q->a_clip, q->seq, c->stream);
+        rc = sharded ? l2a_mppi_sample_shard(ctx, nullptr, seed, offset, q->mean[src], shift, q->sigma, q->beta, low, high, n, m, h, A, lo,
+                                             hi, q->mean[dst], q->a_clip, q->seq, c->stream)
+                     : l2a_mppi_sample(ctx, nullptr, seed, offset, q->mean[src], shift, q->sigma, q->beta, low, high, n, m, h, A,
+                                       q->mean[dst], q->a_clip, q->seq, c->stream);
         if (rc != L2A_OK) return rc;
         if (it == 0) ctx->stamps_us[1] = l2a_now_us();
         float* rets = q->rets + (size_t)it * m * n;
@@ -890,61 +943,23 @@ int mppi_launch(l2a_controller* c) {
     return read_back(c);
 }
 
-// Iteration 0's shift vector of the step about to be launched: -1 for an env that is new or was reset, +1 for the others.
-void mppi_first_shift(l2a_controller* c) {
-    mppi_state* q = c->mppi;
-    const int m = c->m;
-    int fresh = 0;
-    for (int i = 0; i < m; ++i) fresh += q->fresh[i] ? 1 : 0;
-    if (fresh == 0) q->first = q->shift;
-    else if (fresh == m) q->first = q->shift + 2 * m;
-    else {
-        for (int i = 0; i < m; ++i) q->shift_host[i] = q->fresh[i] ? -1 : 1;
-        q->first = q->shift + 3 * m;
-    }
-}
-
 // ---- iCEM (device mode) ---------------------------------------------------------------------------------------------------------
-// What every rank of a sharded iCEM step must share: the controller kind (3), how the controller was built - the populations and the
-// planner's constants by their bits -, where its Philox stream stands, and the step's fresh marks.
-unsigned long long icem_digest(const l2a_controller* c) {
-    const icem_state* q = c->icem;
-    const auto bits = [](float x) { unsigned int b = 0; std::memcpy(&b, &x, sizeof(b)); return (unsigned long long)b; };
-    const unsigned long long v[] = {3ull, c->device.seed, q->iter_calls, (unsigned long long)c->m, (unsigned long long)c->n,
-                                    (unsigned long long)c->h, (unsigned long long)q->iters, (unsigned long long)c->shard.world};
-    unsigned long long d = 0x9E3779B97F4A7C15ull;
-    for (unsigned long long x : v) d = digest_mix(d, x);
-    for (int it = 0; it < q->iters; ++it) d = digest_mix(d, (unsigned long long)q->pops[it]);
-    d = digest_mix(d, (unsigned long long)q->K);
-    d = digest_mix(d, (unsigned long long)q->Kk);
-    d = digest_mix(d, (unsigned long long)q->add_mean);
-    d = digest_mix(d, bits(q->alpha));
-    d = digest_mix(d, bits(q->rho));
-    for (int k = 0; k < c->act_dim; ++k) d = digest_mix(d, bits(q->sigma32[k]));
-    for (int i = 0; i < c->m; ++i) d = digest_mix(d, q->fresh[i] ? 1ull : 0ull);
-    if (q->noise_on) d = digest_mix(d, q->noise_hash);      // (without a matrix the digest is the AR(1) step's)
-    return d;
-}
-
 // Everything of one iCEM plan step, in stream order on `stream`; nothing on the host waits.  Reads the committed copy of the state and
 // the reset marks and writes neither: a replay launches the same step again.
 int icem_launch(l2a_controller* c) {
     l2a_ctx* ctx = c->ctx;
     icem_state* q = c->icem;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
     const int m = c->m, n = c->n, h = c->h, A = c->act_dim, Kk = q->Kk;
     const unsigned long long per_iter = (unsigned long long)n * m * q->D, seed = c->device.seed;      // (the stride is the full n)
     const bool sharded = c->shard.on;
     const float* low = q->lowhigh;
     const float* high = q->lowhigh + A;
     l2a_device_guard guard(ctx->device);
-    if (q->first == q->shift + 3 * m)           // the step's own mix of new and running envs
-        L2A_HIP(ctx, hipMemcpyAsync(q->shift + 3 * m, q->shift_host, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream));
-    if (sharded) L2A_HIP(ctx, hipMemsetAsync(q->verdict_dev, 0, 3 * sizeof(unsigned int), stream));
+    int rc = launch_prelude(c);
+    if (rc != L2A_OK) return rc;
     int src = q->cur;
     for (int it = 0; it < q->iters; ++it) {
-        int dst = 0;
-        while (dst == src || dst == q->cur) ++dst;          // neither the copy this iteration reads nor the committed one
+        const int dst = spare_copy(q, src);
         const int n_it = q->pops[it];
         int lo = 0, hi = n_it;
         if (sharded) icem_window(c, n_it, &lo, &hi);
@@ -954,8 +969,7 @@ int icem_launch(l2a_controller* c) {
         const float* kept_in = Kk ? q->kept[src] : nullptr;
         const int* kc_in = Kk ? q->kc[src] : nullptr;
         // (sharded: every rank samples all n_it rows of the same stream and keeps the rollout tensor of its candidates [lo, hi) only)
-        int rc;
-        if (q->noise_on)                        // l2a_icem_controller_set_noise: nz = M z in place of the recurrence
+        if (q->noise_on)                       // l2a_icem_controller_set_noise: nz = M z in place of the recurrence
             rc = sharded ? l2a_icem_sample_noise_shard(ctx, nullptr, seed, offset, q->mean[src], q->std[src], kept_in, kc_in, shift, q->sigma,
                                                        q->noise, low, high, n_it, m, h, A, Kk, add_mean, lo, hi, q->mean[dst], q->std[dst],
                                                        q->a_clip, q->seq, c->stream)
@@ -982,23 +996,14 @@ int icem_launch(l2a_controller* c) {
     return read_back(c);
 }
 
-// Iteration 0's shift vector of the step about to be launched (mppi_first_shift's scheme): -1 for an env that is new or was reset,
-// +1 for the others.
-void icem_first_shift(l2a_controller* c) {
-    icem_state* q = c->icem;
-    const int m = c->m;
-    int fresh = 0;
-    for (int i = 0; i < m; ++i) fresh += q->fresh[i] ? 1 : 0;
-    if (fresh == 0) q->first = q->shift;
-    else if (fresh == m) q->first = q->shift + 2 * m;
-    else {
-        for (int i = 0; i < m; ++i) q->shift_host[i] = q->fresh[i] ? -1 : 1;
-        q->first = q->shift + 3 * m;
+// ---- what the CEM, the MPPI and the iCEM step share: begin, the verdicts, finish -----------------------------------------------------
+int plan_launch(l2a_controller* c) {
+    switch (c->plan->kind) {
+    case PLAN_CEM: return cem_launch(c);
+    case PLAN_MPPI: return mppi_launch(c);
+    default: return icem_launch(c);
     }
 }
-
-// ---- what the CEM, the MPPI and the iCEM step share: begin, the verdicts, finish -----------------------------------------------------
-int plan_launch(l2a_controller* c) { return c->cem ? cem_launch(c) : c->mppi ? mppi_launch(c) : icem_launch(c); }
 
 int plan_begin(l2a_controller* c, const double* obs, const float* c0, const float* h0, float* c1, float* h1, void* stream) {
     l2a_ctx* ctx = c->ctx;
@@ -1014,9 +1019,8 @@ int plan_begin(l2a_controller* c, const double* obs, const float* c0, const floa
     c->t_begin = c->t_taken = l2a_now_us();
     stage_obs(c, obs, c0, h0, c1, h1, stream);
     c->result = L2A_OK;
-    if (c->mppi) mppi_first_shift(c);
-    if (c->icem) icem_first_shift(c);
-    if (c->shard.on) c->shard.digest = c->cem ? cem_digest(c) : c->mppi ? mppi_digest(c) : icem_digest(c);
+    if (c->warm) first_shift(c);
+    if (c->shard.on) c->shard.digest = plan_digest(c);
     const int rc = plan_launch(c);
     if (rc != L2A_OK) return rc;
     ctx->stamps_us[3] = l2a_now_us();
@@ -1040,16 +1044,10 @@ int plan_verdict_sharded(l2a_controller* c) {
     *ctx->status_host = 0;
     unsigned int verdict[3];
     std::memcpy(verdict, q->packed_host + (q->packed_floats - 3), sizeof(verdict));
-    const std::string kind = c->cem ? "sharded CEM" : c->mppi ? "sharded MPPI" : "sharded iCEM";
+    const std::string kind = q->name;
     if (verdict[2] != 0)
-        return fail(ctx, L2A_ESTATE, kind + (c->cem ? " needs identically built controllers in step on every rank (same seed, step count, "
-                                                      "m, n, h, iters, num_elites, mode, alpha and world): the ranks' digests differ"
-                                           : c->mppi ? " needs identically built controllers in step on every rank (same seed, step count, "
-                                                       "m, n, h, iters, kappa, beta, sigma and world, and the same envs reset): the ranks' "
-                                                       "digests differ"
-                                                     : " needs identically built controllers in step on every rank (same seed, step count, "
-                                                       "m, n, h, iters, populations, K, Kk, add_mean, alpha, rho, sigma0 and world, and the "
-                                                       "same envs reset): the ranks' digests differ"));
+        return fail(ctx, L2A_ESTATE, kind + " needs identically built controllers in step on every rank (same seed, step count, m, n, h, iters, "
+                                         + q->facts + "): the ranks' digests differ");
     if (verdict[1] != 0)
         return fail(ctx, L2A_ESTATE, kind + ": " + std::to_string(verdict[1]) + " returns of this step were contributed by no rank "
                                      "(the collective did not reduce over every rank of the plan)");
@@ -1082,13 +1080,9 @@ int plan_finish(l2a_controller* c, double* action_out, long long* index_out, flo
         if (return_out) return_out[i] = r[A];
     }
     q->iter_calls += (unsigned long long)q->iters;
-    if (c->mppi) {
-        c->mppi->cur = c->mppi->last;
-        c->mppi->fresh.assign((size_t)c->m, 0);
-    }
-    if (c->icem) {
-        c->icem->cur = c->icem->last;
-        c->icem->fresh.assign((size_t)c->m, 0);
+    if (warm_state* w = c->warm) {
+        w->cur = w->last;
+        w->fresh.assign((size_t)c->m, 0);
     }
     record_stages(c, t2, l2a_now_us());
     return result;
@@ -1292,6 +1286,32 @@ int step(l2a_controller* c, const double* obs, const float* c0, const float* h0,
     return finish(c, action_out, index_out, return_out);
 }
 
+// ---- the plans' entry points between two steps: result, reset, reseed, set_noise ----------------------------------------------------
+// `who` (the entry point) takes a controller of `kind` with no step in flight: the refusal of anything else, its text on the context.
+int check_idle(l2a_controller* c, plan_kind kind, const char* who) {
+    static const char* const NOUN[] = {"", "a CEM", "an MPPI", "an iCEM"};
+    if (!c) return L2A_EINVAL;
+    if (!c->plan || c->plan->kind != kind) return fail(c->ctx, L2A_EINVAL, std::string(who) + ": not " + NOUN[kind] + " controller");
+    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, std::string(who) + ": a step is in flight (l2a_controller_finish)");
+    return L2A_OK;
+}
+
+// The marked envs' (null: every env's) next step starts afresh.
+int warm_reset(l2a_controller* c, plan_kind kind, const char* who, const unsigned char* dones) {
+    const int rc = check_idle(c, kind, who);
+    if (rc == L2A_OK) mark_fresh(c, dones);
+    return rc;
+}
+
+// The Philox stream restarts at 0 under `seed`; the plan is kept.
+int warm_reseed(l2a_controller* c, plan_kind kind, const char* who, unsigned long long seed) {
+    const int rc = check_idle(c, kind, who);
+    if (rc != L2A_OK) return rc;
+    c->device.seed = seed;
+    c->plan->iter_calls = 0;
+    return L2A_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1376,9 +1396,8 @@ int l2a_lstm_cem_controller_create_sharded_device(l2a_lstm* model, int m, int n,
 }
 
 int l2a_cem_controller_result(l2a_controller* c, float* mean_out, float* std_out, float* returns_out) {
-    if (!c) return L2A_EINVAL;
-    if (!c->cem) return fail(c->ctx, L2A_EINVAL, "l2a_cem_controller_result: not a CEM controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_cem_controller_result: a step is in flight (l2a_controller_finish)");
+    const int rc = check_idle(c, PLAN_CEM, "l2a_cem_controller_result");
+    if (rc != L2A_OK) return rc;
     if (c->steps == 0) return fail(c->ctx, L2A_ESTATE, "l2a_cem_controller_result: no step has finished yet");
     cem_state* q = c->cem;
     const size_t md = (size_t)c->m * q->D;
@@ -1408,27 +1427,16 @@ int l2a_mppi_controller_create_sharded_device(l2a_model* model, int m, int n, in
 }
 
 int l2a_mppi_controller_reset(l2a_controller* c, const unsigned char* dones) {
-    if (!c) return L2A_EINVAL;
-    if (!c->mppi) return fail(c->ctx, L2A_EINVAL, "l2a_mppi_controller_reset: not an MPPI controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_reset: a step is in flight (l2a_controller_finish)");
-    for (int i = 0; i < c->m; ++i)
-        if (!dones || dones[i]) c->mppi->fresh[i] = 1;
-    return L2A_OK;
+    return warm_reset(c, PLAN_MPPI, "l2a_mppi_controller_reset", dones);
 }
 
 int l2a_mppi_controller_reseed(l2a_controller* c, unsigned long long seed) {
-    if (!c) return L2A_EINVAL;
-    if (!c->mppi) return fail(c->ctx, L2A_EINVAL, "l2a_mppi_controller_reseed: not an MPPI controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_reseed: a step is in flight (l2a_controller_finish)");
-    c->device.seed = seed;
-    c->mppi->iter_calls = 0;
-    return L2A_OK;
+    return warm_reseed(c, PLAN_MPPI, "l2a_mppi_controller_reseed", seed);
 }
 
 int l2a_mppi_controller_result(l2a_controller* c, float* mean_out, float* ess_out, int* valid_out, float* returns_out) {
-    if (!c) return L2A_EINVAL;
-    if (!c->mppi) return fail(c->ctx, L2A_EINVAL, "l2a_mppi_controller_result: not an MPPI controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_result: a step is in flight (l2a_controller_finish)");
+    const int rc = check_idle(c, PLAN_MPPI, "l2a_mppi_controller_result");
+    if (rc != L2A_OK) return rc;
     if (c->steps == 0) return fail(c->ctx, L2A_ESTATE, "l2a_mppi_controller_result: no step has finished yet");
     mppi_state* q = c->mppi;
     const int A = c->act_dim;
@@ -1465,28 +1473,17 @@ int l2a_icem_controller_create_sharded_device(l2a_model* model, int m, int n, in
 }
 
 int l2a_icem_controller_reset(l2a_controller* c, const unsigned char* dones) {
-    if (!c) return L2A_EINVAL;
-    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_reset: not an iCEM controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_reset: a step is in flight (l2a_controller_finish)");
-    for (int i = 0; i < c->m; ++i)
-        if (!dones || dones[i]) c->icem->fresh[i] = 1;
-    return L2A_OK;
+    return warm_reset(c, PLAN_ICEM, "l2a_icem_controller_reset", dones);
 }
 
 int l2a_icem_controller_reseed(l2a_controller* c, unsigned long long seed) {
-    if (!c) return L2A_EINVAL;
-    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_reseed: not an iCEM controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_reseed: a step is in flight (l2a_controller_finish)");
-    c->device.seed = seed;
-    c->icem->iter_calls = 0;
-    return L2A_OK;
+    return warm_reseed(c, PLAN_ICEM, "l2a_icem_controller_reseed", seed);
 }
 
 int l2a_icem_controller_result(l2a_controller* c, float* mean_out, float* std_out, float* kept_out, int* kc_out, float* heads_out,
                                float* returns_out) {
-    if (!c) return L2A_EINVAL;
-    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_result: not an iCEM controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_result: a step is in flight (l2a_controller_finish)");
+    const int rc = check_idle(c, PLAN_ICEM, "l2a_icem_controller_result");
+    if (rc != L2A_OK) return rc;
     if (c->steps == 0) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_result: no step has finished yet");
     icem_state* q = c->icem;
     const size_t m = (size_t)c->m, md = m * q->D, kd = m * (size_t)q->Kk * q->D;
@@ -1511,9 +1508,8 @@ int l2a_icem_controller_result(l2a_controller* c, float* mean_out, float* std_ou
 }
 
 int l2a_icem_controller_set_noise(l2a_controller* c, const float* M_host) {
-    if (!c) return L2A_EINVAL;
-    if (!c->icem) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_set_noise: not an iCEM controller");
-    if (c->in_flight) return fail(c->ctx, L2A_ESTATE, "l2a_icem_controller_set_noise: a step is in flight (l2a_controller_finish)");
+    const int rc = check_idle(c, PLAN_ICEM, "l2a_icem_controller_set_noise");
+    if (rc != L2A_OK) return rc;
     icem_state* q = c->icem;
     if (!M_host) { q->noise_on = false; return L2A_OK; }
     if (c->h > L2A_ICEM_NOISE_MAX_H) return fail(c->ctx, L2A_EINVAL, "l2a_icem_controller_set_noise: h beyond L2A_ICEM_NOISE_MAX_H");
@@ -1528,12 +1524,8 @@ int l2a_icem_controller_set_noise(l2a_controller* c, const float* M_host) {
         q->noise_on = false;
         return fail(c->ctx, L2A_EHIP, std::string("l2a_icem_controller_set_noise: ") + hipGetErrorString(e));
     }
-    unsigned long long d = 0x9E3779B97F4A7C15ull;
-    for (size_t e = 0; e < count; ++e) {
-        unsigned int b = 0;
-        std::memcpy(&b, M_host + e, sizeof(b));
-        d = digest_mix(d, (unsigned long long)b);
-    }
+    unsigned long long d = DIGEST_SEED;
+    for (size_t e = 0; e < count; ++e) d = digest_mix(d, bits(M_host[e]));
     q->noise_hash = d;
     q->noise_on = true;
     return L2A_OK;

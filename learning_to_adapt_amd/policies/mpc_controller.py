@@ -1434,6 +1434,112 @@ class MPCController(Policy, Serializable):
         self.last_plan = dict(best_index=idx, best_return=returns[range(m), idx], cem_trace=trace)
         return cand_a[range(m), idx]
 
+    # ------------------------------------------------------------------ what MPPI and iCEM share: a plan that persists from step to step
+    # `prefix` ("mppi" / "icem") names the planner's `_bufs` keys, its `_<prefix>step` / `_<prefix>_side` attributes and its hooks.
+    def _warm_reset(self, prefix, step, dones):
+        """``reset(dones)`` for a planner whose plan persists: the marked envs' next step starts afresh; ``None``, or a number of envs
+        other than the plan's, starts all of them afresh.  ``step``: the planner's C controller, or None."""
+        if step is not None and step.pid == os.getpid():    # the C controller holds the plan: the marks go to it
+            step.reset(None if dones is None or len(dones) != step.m else dones)
+        fresh = self._bufs.get(prefix + "_fresh")
+        if dones is None or fresh is None or len(fresh) != len(dones):
+            self._bufs[prefix + "_fresh"] = None
+        else:
+            fresh |= np.asarray(dones, dtype=bool)
+
+    def _warm_open(self, prefix, m, dev):
+        """Opens a plan step of the planner's Python loop: ``(low, high, sigma, shifts, first, cur, seed, call0)`` - the constants
+        on the device, the shift table ``[+1 | 0 | -1][m]``, iteration 0's shift vector (a fresh start for an env that is new or was
+        reset, one step on for the others), the committed copy of the three rotating copies of the plan - a step reads ``cur`` and
+        commits its last outputs only when it succeeded (``_warm_commit``), so a replay starts from the same plan -, and the
+        counter-based stream ``(seed, iterations so far)``, which restarts when torch's seed VALUE changes, as CEM's does."""
+        bufs = self._bufs
+        const = bufs.get(prefix + "_const")
+        if const is None or const[0].device != dev:
+            up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
+            sigma = getattr(self, "_%s_sigma_vector" % prefix)()
+            const = bufs[prefix + "_const"] = (up(self.action_space.low), up(self.action_space.high), up(sigma))
+        shifts = bufs.get(prefix + "_shifts")
+        if shifts is None or shifts.device != dev or shifts.shape[1] != m:
+            shifts = bufs[prefix + "_shifts"] = torch.as_tensor(np.array([[1] * m, [0] * m, [-1] * m], dtype=np.int32), device=dev)
+            bufs[prefix + "_fresh"], bufs[prefix + "_cur"] = None, 0
+        fresh = bufs.get(prefix + "_fresh")
+        if fresh is None:
+            first = shifts[2]                                   # every env starts afresh
+        elif fresh.any():
+            first = torch.as_tensor(np.where(fresh, -1, 1).astype(np.int32), device=dev)
+        else:
+            first = shifts[0]
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        if bufs.get(prefix + "_seed") != seed:
+            bufs[prefix + "_seed"], bufs[prefix + "_calls"] = seed, 0
+        return const + (shifts, first, bufs[prefix + "_cur"], seed, bufs[prefix + "_calls"])
+
+    @staticmethod
+    def _spare_copy(src, cur):
+        """The copy of the plan an iteration writes: neither the one it reads nor the committed one."""
+        return [b for b in range(3) if b != src and b != cur][0]
+
+    def _flagged(self, retry):
+        """True when a launch of this step lost its tile-split partner - the context is unsplit now, and the caller plans the same
+        step again (same counters, same starting plan) with ``retry=True``; a second flag raises."""
+        if self._check_status() is not False:
+            return False
+        if retry:
+            raise _lib.L2AError("rollout launch failed twice")
+        return True
+
+    def _warm_commit(self, prefix, m, calls, cur):
+        """A step that succeeded moves the planner on: the stream position, the committed copy, and no env is new any more."""
+        self._bufs[prefix + "_calls"] = calls
+        self._bufs[prefix + "_cur"] = cur
+        self._bufs[prefix + "_fresh"] = np.zeros(m, dtype=bool)
+
+    def _native_warm_step(self, prefix, observations, plan):
+        """One plan step through the planner's C controller (``_native_mppi_step`` / ``_native_icem_step``), up to and including the
+        step call.  The plan persists on the side that planned, so the choice is made on the controller's first step of this kind
+        and kept; ``reset(dones)`` is forwarded to the C controller (``_warm_reset``), and a changed ``torch.initial_seed()`` value
+        reseeds it (the stream restarts, the plan is kept - as the Python loop does).  ``plan(native, m, n, h)`` returns ``(facts,
+        eligible, make)``: the planner's own part of the key a C controller is kept under (a controller under another key is
+        dropped: another plan starts afresh, as the Python loop's), what of its own keeps the C controller from planning, and
+        ``make(seed, shard)``, which builds it.  Returns ``(step, n, rank, world)``, or None: the Python loop plans, now and later."""
+        side, attr = "_%s_side" % prefix, "_%sstep" % prefix
+        if getattr(self, side) == "python":
+            return None
+        st = getattr(self, attr)
+        if st is not None and st.pid != os.getpid():
+            setattr(self, attr, None)       # (a forked child: the parent's HIP objects did not come along)
+            setattr(self, side, "python")
+            return None
+        rank, world = self._dist()
+        n, m, h = self.n_candidates, len(observations), self.horizon
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        native = self.dynamics_model.planner_model()
+        facts, eligible, make = plan(native, m, n, h)
+        key = (id(native), native.handle.value, m, n, h, float(self.discount)) + facts + (rank, world)
+        if st is not None and st.key != key:
+            st.close()
+            st = None
+            setattr(self, attr, None)
+        if st is None:
+            ok = eligible and not (self.use_reward_model or self._program() or hasattr(native, "units") or not self._native_step_stock()
+                                   or not hasattr(native.lib, "l2a_%s_controller_create_sharded_device" % prefix)
+                                   or m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16)
+            shard = self._native_shard(native, rank, world, m * n + 3) if ok and world > 1 else None    # (the shard dry run)
+            if not ok or (world > 1 and shard is None):
+                setattr(self, side, "python")
+                return None
+            st = make(seed, shard)
+            st.key, st.seed = key, seed
+            setattr(self, attr, st)
+            setattr(self, side, "c")
+        if st.seed != seed:
+            st.reseed(seed)
+            st.seed = seed
+        self._check_blocks(m)
+        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        return st, n, rank, world
+
     # ------------------------------------------------------------------ MPPI (PDDM's filtered, reward-weighted refinement)
     def _mppi_sigma_vector(self):
         """``mppi_sigma`` as an fp32 ``[act_dim]`` array: ``None`` = a quarter of each dimension's action range, a scalar = that
@@ -1459,16 +1565,8 @@ class MPCController(Policy, Serializable):
     def _mppi_reset(self, dones):
         """``reset(dones)`` for the MPPI planner: the marked envs' next step starts from a zero mean; ``None``, or a number of envs
         other than the plan's, starts all of them afresh.  Without ``use_mppi`` nothing happens."""
-        if not self.use_mppi:
-            return
-        st = self._mppistep
-        if st is not None and st.pid == os.getpid():        # the C controller holds the plan: the marks go to it
-            st.reset(None if dones is None or len(dones) != st.m else dones)
-        fresh = self._bufs.get("mppi_fresh")
-        if dones is None or fresh is None or len(fresh) != len(dones):
-            self._bufs["mppi_fresh"] = None
-        else:
-            fresh |= np.asarray(dones, dtype=bool)
+        if self.use_mppi:
+            self._warm_reset("mppi", self._mppistep, dones)
 
     def _mppi_normal_device(self, shape, device):
         """Hook for tests: return the iteration's standard normals ``[n, m, D]`` as a CUDA fp32 tensor to inject them; ``None``
@@ -1481,54 +1579,27 @@ class MPCController(Policy, Serializable):
         """The MPPI plan step through the C controller (``l2a_mppi_controller_create_device``; at ``world > 1`` this rank's
         ``l2a_mppi_controller_create_sharded_device``, whose per-iteration gather of the returns is the int64 MAX all-reduce of
         ``m * n + 3`` words through ``_reduce_payload`` - or the library's communicator, ``L2A_NATIVE_COMM=1``): the Philox offsets,
-        the shift rule and the bits of ``get_mppi_action``.  The plan mean persists on the side that planned, so the choice is made
-        on the controller's first MPPI step and kept: None - the Python loop plans, now and later - for a reward program, a reward
-        model, a recurrent model, a test hook that replaced the normals or the launch path, a library without the entry points, a
-        backend that cannot reduce the words, a forked child.  ``reset(dones)`` is forwarded to the C controller, and a changed
-        ``torch.initial_seed()`` value reseeds it (the stream restarts, the mean is kept - as the Python loop does).
-        ``last_plan`` gets ``get_mppi_action``'s keys; the step itself reads back ``m * (act_dim + 4)`` floats only, the mean and
-        the returns are copies of their own afterwards: ``returns`` is fetched eagerly by default, and the class or instance
-        attribute ``mppi_fetch_returns = False`` leaves the key out and the ``m * n`` floats on the device
-        (``self._mppistep.result()`` still returns every iteration's table on request)."""
-        if self._mppi_side == "python":
+        the shift rule and the bits of ``get_mppi_action``.  None (``_native_warm_step``: the Python loop plans, now and later) for
+        a reward program, a reward model, a recurrent model, a test hook that replaced the normals or the launch path, a library
+        without the entry points, a backend that cannot reduce the words, a forked child.  ``last_plan`` gets
+        ``get_mppi_action``'s keys; the step itself reads back ``m * (act_dim + 4)`` floats only, the mean and the returns are
+        copies of their own afterwards: ``returns`` is fetched eagerly by default, and the class or instance attribute
+        ``mppi_fetch_returns = False`` leaves the key out and the ``m * n`` floats on the device (``self._mppistep.result()`` still
+        returns every iteration's table on request)."""
+        def plan(native, m, n, h):
+            sigma = self._mppi_sigma_vector()
+            hooked = getattr(self._mppi_normal_device, "__func__", None) is not MPCController._mppi_normal_device
+
+            def make(seed, shard):
+                from .native_mppi_step import NativeMppiStep
+                return NativeMppiStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
+                                      self.mppi_iters, self.mppi_kappa, self.mppi_beta, sigma, seed, shard=shard)
+            return (int(self.mppi_iters), self.mppi_kappa, self.mppi_beta, sigma.tobytes()), not hooked, make
+
+        stepped = self._native_warm_step("mppi", observations, plan)
+        if stepped is None:
             return None
-        st = self._mppistep
-        if st is not None and st.pid != os.getpid():
-            self._mppistep, self._mppi_side = None, "python"        # (a forked child: the parent's HIP objects did not come along)
-            return None
-        rank, world = self._dist()
-        n, m, h = self.n_candidates, len(observations), self.horizon
-        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        native = self.dynamics_model.planner_model()
-        sigma = self._mppi_sigma_vector()
-        key = (id(native), native.handle.value, m, n, h, float(self.discount), int(self.mppi_iters), self.mppi_kappa, self.mppi_beta,
-               sigma.tobytes(), rank, world)
-        if st is not None and st.key != key:        # another plan (a different number of envs, ...): it starts afresh, as the Python loop's
-            st.close()
-            st = self._mppistep = None
-        if st is None:
-            if (self.use_reward_model or self._program() or hasattr(native, "units") or not self._native_step_stock()
-                    or getattr(self._mppi_normal_device, "__func__", None) is not MPCController._mppi_normal_device
-                    or not hasattr(native.lib, "l2a_mppi_controller_create_sharded_device")
-                    or m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16):
-                self._mppi_side = "python"
-                return None
-            shard = None
-            if world > 1:
-                shard = self._native_shard(native, rank, world, m * n + 3)
-                if shard is None:
-                    self._mppi_side = "python"
-                    return None
-            from .native_mppi_step import NativeMppiStep
-            st = NativeMppiStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
-                                self.mppi_iters, self.mppi_kappa, self.mppi_beta, sigma, seed, shard=shard)
-            st.key, st.seed = key, seed
-            self._mppistep, self._mppi_side = st, "c"
-        if st.seed != seed:
-            st.reseed(seed)
-            st.seed = seed
-        self._check_blocks(m)
-        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        st, n, rank, world = stepped
         mean, ess, valid, rets = st.result(with_returns=bool(self.mppi_fetch_returns))
         self.last_plan = dict(best_index=st.idx.copy(), best_return=st.ret.copy(), mppi_mean=mean, mppi_ess=ess, mppi_valid=valid)
         if rets is not None:
@@ -1571,40 +1642,17 @@ class MPCController(Policy, Serializable):
         ctx, lib = native.ctx, native.lib
         if not hasattr(lib, "l2a_mppi_sample"):
             raise _lib.L2AError("this libl2a_hip.so has no MPPI kernels (l2a_mppi_sample): rebuild it")
-        const = self._bufs.get("mppi_const")
-        if const is None or const[0].device != dev:
-            up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
-            const = self._bufs["mppi_const"] = (up(self.action_space.low), up(self.action_space.high), up(self._mppi_sigma_vector()))
-        low, high, sigma = const
-        # the persistent mean and two scratch means: a step reads `cur` and commits its last `mean_out` only when it succeeded,
-        # so a replay starts from the same plan
-        means = self._buf("mppi_means", (3, m, D), torch.float32, dev)
-        shifts = self._bufs.get("mppi_shifts")
-        if shifts is None or shifts.device != dev or shifts.shape[1] != m:
-            shifts = self._bufs["mppi_shifts"] = torch.as_tensor(np.array([[1] * m, [0] * m, [-1] * m], dtype=np.int32), device=dev)
-            self._bufs["mppi_fresh"], self._bufs["mppi_cur"] = None, 0
-        fresh = self._bufs.get("mppi_fresh")
-        if fresh is None:
-            first = shifts[2]                                   # every env starts from zeros
-        elif fresh.any():
-            first = torch.as_tensor(np.where(fresh, -1, 1).astype(np.int32), device=dev)
-        else:
-            first = shifts[0]
-        cur = self._bufs["mppi_cur"]
+        low, high, sigma, shifts, first, cur, seed, call0 = self._warm_open("mppi", m, dev)
+        means = self._buf("mppi_means", (3, m, D), torch.float32, dev)      # the persistent mean and two scratch means
         a_clip = self._buf("mppi_a_clip", (n, m, D), torch.float32, dev)
         seq = self._buf("mppi_seq", (h, m * n, act_dim), torch.float32, dev)
         width = act_dim + 4
         packed = self._buf("mppi_packed", (m * width + m * D + m * n,), torch.float32, dev)
         obs_dev = self._upload_obs(observations)                # once per plan step
-        # counter-based stream: (seed, iterations so far); restarts when torch's seed VALUE changes, as CEM's does
-        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        if self._bufs.get("mppi_seed") != seed:
-            self._bufs["mppi_seed"], self._bufs["mppi_calls"] = seed, 0
-        call0 = self._bufs["mppi_calls"]
         src = cur
         rets = None
         for it in range(self.mppi_iters):
-            dst = [b for b in range(3) if b != src and b != cur][0]
+            dst = self._spare_copy(src, cur)
             z = self._mppi_normal_device((n, m, D), dev)
             if z is not None:
                 z = z.to(device=dev, dtype=torch.float32).contiguous()
@@ -1620,13 +1668,9 @@ class MPCController(Policy, Serializable):
         packed[m * width:m * width + m * D].view(m, D).copy_(means[src])
         packed[m * width + m * D:].view(m, n).copy_(rets)
         host = packed.cpu().numpy()
-        if self._check_status() is False:       # a launch lost its tile-split partner: the context is unsplit now
-            if retry:
-                raise _lib.L2AError("rollout launch failed twice")
+        if self._flagged(retry):
             return self.get_mppi_action(observations, retry=True)       # same counters, same starting mean: the same step again
-        self._bufs["mppi_calls"] = call0 + self.mppi_iters
-        self._bufs["mppi_cur"] = src
-        self._bufs["mppi_fresh"] = np.zeros(m, dtype=bool)
+        self._warm_commit("mppi", m, call0 + self.mppi_iters, src)
         head = host[:m * width].reshape(m, width)
         self.last_plan = dict(best_index=head[:, act_dim + 1].copy().view(np.int32).astype(np.int64),
                               best_return=head[:, act_dim].copy(),
@@ -1665,16 +1709,8 @@ class MPCController(Policy, Serializable):
     def _icem_reset(self, dones):
         """``reset(dones)`` for the iCEM planner: the marked envs' next step starts from a zero mean, the initial spread and no kept
         elites; ``None``, or a number of envs other than the plan's, starts all of them afresh.  Without ``use_icem`` nothing happens."""
-        if not self.use_icem:
-            return
-        st = self._icemstep
-        if st is not None and st.pid == os.getpid():        # the C controller holds the plan: the marks go to it
-            st.reset(None if dones is None or len(dones) != st.m else dones)
-        fresh = self._bufs.get("icem_fresh")
-        if dones is None or fresh is None or len(fresh) != len(dones):
-            self._bufs["icem_fresh"] = None
-        else:
-            fresh |= np.asarray(dones, dtype=bool)
+        if self.use_icem:
+            self._warm_reset("icem", self._icemstep, dones)
 
     def _icem_normal_device(self, shape, device):
         """Hook for tests: return the iteration's standard normals ``[n_it, m, D]`` as a CUDA fp32 tensor to inject them; ``None``
@@ -1686,78 +1722,61 @@ class MPCController(Policy, Serializable):
     icem_fetch_returns = True       # `_native_icem_step`: copy the returns into `last_plan` on every step (the last iteration's table;
                                     # with `icem_trace_returns` every iteration's)
 
+    @staticmethod
+    def _icem_trace(heads, pops, tables):
+        """``last_plan["icem_trace"]`` from the refits' result rows ``heads [iters, m, act_dim + 4]`` (the action | best return | best
+        index | elite count | valid count, the integers by their bits): per iteration n, best return and index, elite and valid
+        counts, and as ``returns`` a copy of ``tables[it] [m, pops[it]]`` where that is not None."""
+        at = heads.shape[2] - 4
+        as_int = lambda a: a.copy().view(np.int32).astype(np.int64)     # noqa: E731
+        steps = []
+        for it, n_it in enumerate(pops):
+            step = dict(n=n_it, best_return=heads[it, :, at].copy(), best_index=as_int(heads[it, :, at + 1]),
+                        elites=as_int(heads[it, :, at + 2]), valid=as_int(heads[it, :, at + 3]))
+            if tables[it] is not None:
+                step["returns"] = tables[it].copy()
+            steps.append(step)
+        return steps
+
     def _native_icem_step(self, observations):
         """The iCEM plan step through the C controller (``l2a_icem_controller_create_device``; at ``world > 1`` this rank's
         ``l2a_icem_controller_create_sharded_device``, whose per-iteration gather of the returns is the int64 MAX all-reduce of
         ``m * pops[it] + 3`` words through ``_reduce_payload`` - or the library's communicator, ``L2A_NATIVE_COMM=1``): the Philox
-        offsets, the shift rule, the rotation of the state and the bits of ``get_icem_action``.  Mean, spread and kept elites
-        persist on the side that planned, so the choice is made on the controller's first iCEM step and kept: None - the Python
-        loop plans, now and later - for a reward program, a reward model, a particle plan, a recurrent model, a test hook that
+        offsets, the shift rule, the rotation of the state and the bits of ``get_icem_action``.  None (``_native_warm_step``: the
+        Python loop plans, now and later) for a reward program, a reward model, a particle plan, a recurrent model, a test hook that
         replaced the normals or the launch path, a library without the entry points, a backend that cannot reduce the words, a
-        forked child.  ``reset(dones)`` is forwarded to the C controller, and a changed ``torch.initial_seed()`` value reseeds it
-        (the stream restarts, the state is kept - as the Python loop does).  ``last_plan`` gets ``get_icem_action``'s keys; the
-        step itself reads back ``icem_iters * m * (act_dim + 4)`` floats only, the state and the returns are one copy of their
-        own afterwards: the class or instance attribute ``icem_fetch_returns = False`` leaves every ``returns`` key out and the
-        tables on the device (``self._icemstep.result()`` still returns every iteration's table on request); with
-        ``icem_trace_returns`` every iteration's table is filled in, otherwise the last one's."""
-        if self._icem_side == "python":
+        forked child.  ``last_plan`` gets ``get_icem_action``'s keys; the step itself reads back ``icem_iters * m * (act_dim + 4)``
+        floats only, the state and the returns are one copy of their own afterwards: the class or instance attribute
+        ``icem_fetch_returns = False`` leaves every ``returns`` key out and the tables on the device (``self._icemstep.result()``
+        still returns every iteration's table on request); with ``icem_trace_returns`` every iteration's table is filled in,
+        otherwise the last one's."""
+        def plan(native, m, n, h):
+            sigma = self._icem_sigma_vector()
+            K, Kk, pops = self._icem_sizes()
+            hooked = getattr(self._icem_normal_device, "__func__", None) is not MPCController._icem_normal_device
+
+            def make(seed, shard):
+                from .native_icem_step import NativeIcemStep
+                st = NativeIcemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
+                                    pops, K, Kk, self.alpha, self.icem_rho, sigma, self.icem_add_mean, seed, shard=shard)
+                if self.icem_noise == "powerlaw":
+                    try:
+                        st.set_noise(self._icem_noise_matrix(h))
+                    except Exception:
+                        st.close()
+                        raise
+                return st
+            return (K, Kk, tuple(pops), float(self.alpha), self.icem_rho, sigma.tobytes(), self.icem_add_mean, self.icem_noise,
+                    self.icem_beta), not hooked and self.ensemble_planning != "particles", make
+
+        stepped = self._native_warm_step("icem", observations, plan)
+        if stepped is None:
             return None
-        st = self._icemstep
-        if st is not None and st.pid != os.getpid():
-            self._icemstep, self._icem_side = None, "python"        # (a forked child: the parent's HIP objects did not come along)
-            return None
-        rank, world = self._dist()
-        n, m, h = self.n_candidates, len(observations), self.horizon
-        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        native = self.dynamics_model.planner_model()
-        sigma = self._icem_sigma_vector()
-        K, Kk, pops = self._icem_sizes()
-        key = (id(native), native.handle.value, m, n, h, float(self.discount), K, Kk, tuple(pops), float(self.alpha), self.icem_rho,
-               sigma.tobytes(), self.icem_add_mean, rank, world, self.icem_noise, self.icem_beta)
-        if st is not None and st.key != key:        # another plan (a different number of envs, ...): it starts afresh, as the Python loop's
-            st.close()
-            st = self._icemstep = None
-        if st is None:
-            if (self.use_reward_model or self._program() or self.ensemble_planning == "particles" or hasattr(native, "units")
-                    or not self._native_step_stock()
-                    or getattr(self._icem_normal_device, "__func__", None) is not MPCController._icem_normal_device
-                    or not hasattr(native.lib, "l2a_icem_controller_create_sharded_device")
-                    or m > 64 or m * native.obs_dim > 4096 or native.act_dim > 16):
-                self._icem_side = "python"
-                return None
-            shard = None
-            if world > 1:
-                shard = self._native_shard(native, rank, world, m * n + 3)
-                if shard is None:
-                    self._icem_side = "python"
-                    return None
-            from .native_icem_step import NativeIcemStep
-            st = NativeIcemStep(native, m, n, h, self.action_space.low, self.action_space.high, self.discount, self._reward_spec,
-                                pops, K, Kk, self.alpha, self.icem_rho, sigma, self.icem_add_mean, seed, shard=shard)
-            st.key, st.seed = key, seed
-            if self.icem_noise == "powerlaw":
-                try:
-                    st.set_noise(self._icem_noise_matrix(h))
-                except Exception:
-                    st.close()
-                    raise
-            self._icemstep, self._icem_side = st, "c"
-        if st.seed != seed:
-            st.reseed(seed)
-            st.seed = seed
-        self._check_blocks(m)
-        st.step(observations, torch.cuda.current_stream(native.device).cuda_stream)
+        st, _, rank, world = stepped
+        pops =[int(n_it) for n_it in st.pops]
         fetch, trace = bool(self.icem_fetch_returns), bool(self.icem_trace_returns)
         mean, std, elites, counts, head, rets = st.result(with_returns=fetch)
-        act_dim = native.act_dim
-        as_int = lambda a: a.copy().view(np.int32).astype(np.int64)     # noqa: E731
-        steps = []
-        for it in range(st.iters):
-            step = dict(n=pops[it], best_return=head[it, :, act_dim].copy(), best_index=as_int(head[it, :, act_dim + 1]),
-                        elites=as_int(head[it, :, act_dim + 2]), valid=as_int(head[it, :, act_dim + 3]))
-            if fetch and (trace or it == st.iters - 1):
-                step["returns"] = rets[it].copy()
-            steps.append(step)
+        steps = self._icem_trace(head, pops, [rets[it] if fetch and (trace or it == st.iters - 1) else None for it in range(st.iters)])
         last = steps[-1]
         self.last_plan = dict(best_index=last["best_index"], best_return=last["best_return"], icem_mean=mean, icem_std=std,
                               icem_elites=elites, icem_elite_count=counts, icem_valid=last["valid"], icem_trace=steps,
@@ -1813,37 +1832,20 @@ class MPCController(Policy, Serializable):
         ctx, lib = native.ctx, native.lib
         if not hasattr(lib, "l2a_icem_sample"):
             raise _lib.L2AError("this libl2a_hip.so has no iCEM kernels (l2a_icem_sample): rebuild it")
-        const = self._bufs.get("icem_const")
-        if const is None or const[0].device != dev:
-            up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
-            const = self._bufs["icem_const"] = (up(self.action_space.low), up(self.action_space.high), up(self._icem_sigma_vector()))
-        low, high, sigma = const
+        low, high, sigma, shifts, first, cur, seed, call0 = self._warm_open("icem", m, dev)
         noise = None
         if self.icem_noise == "powerlaw":       # M once per (h, beta), kept on the device next to the constants
             held = self._bufs.get("icem_noise")
             if held is None or held[0] != (h, self.icem_beta) or held[1].device != dev:
                 held = self._bufs["icem_noise"] = ((h, self.icem_beta), torch.as_tensor(self._icem_noise_matrix(h), device=dev))
             noise = held[1]
-        # the persistent state and two scratch copies of it: a step reads `cur` and commits its last outputs only when it succeeded,
-        # so a replay starts from the same plan
+        # the persistent state and two scratch copies of it
         means = self._buf("icem_means", (3, m, D), torch.float32, dev)
         stds = self._buf("icem_stds", (3, m, D), torch.float32, dev)
         kept = self._buf("icem_kept", (3, m, max(Kk, 1), D), torch.float32, dev)
         kcs = self._buf("icem_kc", (3, m), torch.int32, dev)
         work = self._buf("icem_work", (m, K), torch.int32, dev)
-        shifts = self._bufs.get("icem_shifts")
-        if shifts is None or shifts.device != dev or shifts.shape[1] != m:
-            shifts = self._bufs["icem_shifts"] = torch.as_tensor(np.array([[1] * m, [0] * m, [-1] * m], dtype=np.int32), device=dev)
-            self._bufs["icem_fresh"], self._bufs["icem_cur"] = None, 0
-        fresh = self._bufs.get("icem_fresh")
-        if fresh is None:
-            first = shifts[2]                                   # every env starts afresh
-        elif fresh.any():
-            first = torch.as_tensor(np.where(fresh, -1, 1).astype(np.int32), device=dev)
-        else:
-            first = shifts[0]
-        cur = self._bufs["icem_cur"]
-        a_clip = self._buf("icem_a_clip", (n, m, D), torch.float32, dev)
+        a_clip =self._buf("icem_a_clip", (n, m, D), torch.float32, dev)
         seq_all = self._buf("icem_seq", (h * m * n * act_dim,), torch.float32, dev)
         width = act_dim + 4
         trace = bool(self.icem_trace_returns)
@@ -1853,16 +1855,11 @@ class MPCController(Policy, Serializable):
         packed = self._buf("icem_packed", (at[-1],), torch.float32, dev)
         heads = packed[:at[1]].view(iters, m, width)
         obs_dev = self._upload_obs(observations)                # once per plan step
-        # counter-based stream: (seed, iterations so far); restarts when torch's seed VALUE changes, as CEM's does
-        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        if self._bufs.get("icem_seed") != seed:
-            self._bufs["icem_seed"], self._bufs["icem_calls"] = seed, 0
-        call0 = self._bufs["icem_calls"]
         src = cur
         ret_at = at[5]
         for it in range(iters):
             n_it = pops[it]
-            dst = [b for b in range(3) if b != src and b != cur][0]
+            dst = self._spare_copy(src, cur)
             z = self._icem_normal_device((n_it, m, D), dev)
             if z is not None:
                 z = z.to(device=dev, dtype=torch.float32).contiguous()
@@ -1891,26 +1888,19 @@ class MPCController(Policy, Serializable):
             packed[at[3]:at[4]].view(m, Kk, D).copy_(kept[src])
         packed[at[4]:at[5]].view(torch.int32).copy_(kcs[src])
         host = packed.cpu().numpy()
-        if self._check_status() is False:       # a launch lost its tile-split partner: the context is unsplit now
-            if retry:
-                raise _lib.L2AError("rollout launch failed twice")
+        if self._flagged(retry):
             return self.get_icem_action(observations, retry=True)       # same counters, same starting state: the same step again
-        self._bufs["icem_calls"] = call0 + iters
-        self._bufs["icem_cur"] = src
-        self._bufs["icem_fresh"] = np.zeros(m, dtype=bool)
+        self._warm_commit("icem", m, call0 + iters, src)
         head = host[:at[1]].reshape(iters, m, width)
-        as_int = lambda a: a.copy().view(np.int32).astype(np.int64)     # noqa: E731
-        ret_at, steps = at[5], []
-        for it in range(iters):
-            step = dict(n=pops[it], best_return=head[it, :, act_dim].copy(), best_index=as_int(head[it, :, act_dim + 1]),
-                        elites=as_int(head[it, :, act_dim + 2]), valid=as_int(head[it, :, act_dim + 3]))
-            if trace or it == iters - 1:
-                step["returns"] = host[ret_at:ret_at + m * pops[it]].reshape(m, pops[it]).copy()
-                ret_at += m * pops[it]
-            steps.append(step)
+        ret_at, tables = at[5], []
+        for it in range(iters):             # the returns tables that came back: every iteration's, or the last one's
+            size = m * pops[it] if trace or it == iters - 1 else 0
+            tables.append(host[ret_at:ret_at + size].reshape(m, pops[it]) if size else None)
+            ret_at += size
+        steps = self._icem_trace(head, pops, tables)
         last = steps[-1]
         # the refit writes an env's first `count` kept rows only: what lies behind them in the buffer is no elite of this step
-        elites, counts = host[at[3]:at[4]].reshape(m, Kk, D).copy(), as_int(host[at[4]:at[5]])
+        elites, counts = host[at[3]:at[4]].reshape(m, Kk, D).copy(), host[at[4]:at[5]].copy().view(np.int32).astype(np.int64)
         for i in range(m):
             elites[i, counts[i]:] = 0.0
         self.last_plan = dict(best_index=last["best_index"], best_return=last["best_return"], returns=last["returns"],

@@ -18,10 +18,15 @@ also advances that state with the chosen actions, behind the pick and in front o
 
 import numpy as np
 
-from .native_step import StepHandle, _seed
+from .native_step import PlanStep, _seed
 
 
-class NativeCemStep(StepHandle):
+class NativeCemStep(PlanStep):
+    """``step(observations, stream, state=None)`` - ``state`` (recurrent): ``(c0, h0, c_next, h_next)`` device pointers; ``c_next`` and
+    ``h_next`` both None plan without advancing the state."""
+
+    label = "CEM"
+
     def __init__(self, native, m, n, h, low, high, discount, reward, iters, num_elites, alpha, reference, seed, shard=None):
         self.iters = int(iters)
         create = "l2a_%scem_controller_create%s_device" % ("lstm_" if hasattr(native, "units") else "", "_sharded" if shard is not None else "")
@@ -29,15 +34,6 @@ class NativeCemStep(StepHandle):
         self._open(native, create, m, n, h, low, high, discount, reward, extra, shard)
         self.D = self.h * native.act_dim
         self.steps = 0
-
-    def step(self, observations, stream, state=None):
-        """One plan step; ``self.act`` / ``self.idx`` / ``self.ret`` hold the result afterwards.  ``state`` (recurrent):
-        ``(c0, h0, c_next, h_next)`` device pointers; ``c_next`` and ``h_next`` both None plan without advancing the state."""
-        np.copyto(self.obs, observations, casting="same_kind")
-        rc = self._call(state, stream)
-        self._settle(rc, "l2a_controller_step (CEM)")
-        self.steps += 1
-        return rc
 
     def result(self, with_returns=True):
         """``(mean [m, D], std [m, D], returns [iters, m, n] or None)`` of the latest step (host fp32)."""
@@ -48,7 +44,3 @@ class NativeCemStep(StepHandle):
                                                           rets.ctypes.data if rets is not None else None),
                        "l2a_cem_controller_result")
         return mean, std, rets
-
-    def stats(self):
-        v = self._stat_slots()
-        return dict(stage_us=dict(sample=v[1], launch=v[2], wait=v[4], decode=v[5], call=v[6]), steps=int(v[7]), relaunches=int(v[8]))

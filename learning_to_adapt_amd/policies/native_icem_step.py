@@ -18,10 +18,15 @@ Every rank's step equals the unsharded one bit for bit.
 import numpy as np
 
 from .._lib import L2AError
-from .native_step import StepHandle, _seed
+from .native_step import WarmStep, _seed
 
 
-class NativeIcemStep(StepHandle):
+class NativeIcemStep(WarmStep):
+    """After ``step``: ``self.act`` is the first action of the last iteration's best candidate, ``self.idx`` / ``self.ret`` its index and
+    return."""
+
+    prefix, label = "icem", "iCEM"
+
     def __init__(self, native, m, n, h, low, high, discount, reward, pops, K, Kk, alpha, rho, sigma0, add_mean, seed, shard=None):
         """``pops``, ``K``, ``Kk``: ``MPCController._icem_sizes`` (the populations per iteration, the elites, the kept elites);
         ``sigma0``: the initial spread per action dimension (``MPCController._icem_sigma_vector``)."""
@@ -36,27 +41,6 @@ class NativeIcemStep(StepHandle):
         self.A = native.act_dim
         self.D = self.h * self.A
         self.steps = 0
-
-    def step(self, observations, stream):
-        """One plan step; ``self.act`` (the first action of the last iteration's best candidate) / ``self.idx`` / ``self.ret`` (its
-        index and return) hold the result afterwards.  Returns the C step's code (``L2A_OK`` or ``L2A_STEP_UNSPLIT``)."""
-        np.copyto(self.obs, observations, casting="same_kind")
-        rc = self._call(None, stream)
-        self._settle(rc, "l2a_controller_step (iCEM)")
-        self.steps += 1
-        return rc
-
-    def reset(self, dones=None):
-        """The marked envs' next step starts afresh (zero mean, the initial spread, no kept elites); ``None``: every env's."""
-        flags = None if dones is None else np.ascontiguousarray(np.asarray(dones, dtype=bool), dtype=np.uint8)
-        if flags is not None and flags.shape != (self.m,):
-            raise ValueError("dones must hold one flag per env (%d), got shape %s" % (self.m, flags.shape))
-        self.ctx.check(self.lib.l2a_icem_controller_reset(self.handle, None if flags is None else flags.ctypes.data),
-                       "l2a_icem_controller_reset")
-
-    def reseed(self, seed):
-        """The Philox stream restarts at 0 under ``seed``; mean, spread, kept elites and counts are kept."""
-        self.ctx.check(self.lib.l2a_icem_controller_reseed(self.handle, _seed(seed)), "l2a_icem_controller_reseed")
 
     def set_noise(self, M):
         """From the next step on every iteration samples with ``nz = M z`` (``l2a_icem_sample_noise``; sharded:
@@ -103,7 +87,3 @@ class NativeIcemStep(StepHandle):
                 rets.append(flat[at:at + self.m * int(n_it)].reshape(self.m, int(n_it)))
                 at += self.m * int(n_it)
         return mean, std, kept, counts, heads, rets
-
-    def stats(self):
-        v = self._stat_slots()
-        return dict(stage_us=dict(sample=v[1], launch=v[2], wait=v[4], decode=v[5], call=v[6]), steps=int(v[7]), relaunches=int(v[8]))

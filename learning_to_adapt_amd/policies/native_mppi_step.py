@@ -16,10 +16,14 @@ for bit.
 
 import numpy as np
 
-from .native_step import StepHandle, _seed
+from .native_step import WarmStep, _seed
 
 
-class NativeMppiStep(StepHandle):
+class NativeMppiStep(WarmStep):
+    """After ``step``: ``self.act`` is the new mean's first step, ``self.idx`` / ``self.ret`` the best valid candidate's index and return."""
+
+    prefix, label = "mppi", "MPPI"
+
     def __init__(self, native, m, n, h, low, high, discount, reward, iters, kappa, beta, sigma, seed, shard=None):
         """``sigma``: the noise scale per action dimension (``MPCController._mppi_sigma_vector``)."""
         self.iters = int(iters)
@@ -29,27 +33,6 @@ class NativeMppiStep(StepHandle):
         self._open(native, create, m, n, h, low, high, discount, reward, extra, shard)
         self.D = self.h * native.act_dim
         self.steps = 0
-
-    def step(self, observations, stream):
-        """One plan step; ``self.act`` (the new mean's first step) / ``self.idx`` / ``self.ret`` (the best valid candidate's index
-        and return) hold the result afterwards.  Returns the C step's code (``L2A_OK`` or ``L2A_STEP_UNSPLIT``)."""
-        np.copyto(self.obs, observations, casting="same_kind")
-        rc = self._call(None, stream)
-        self._settle(rc, "l2a_controller_step (MPPI)")
-        self.steps += 1
-        return rc
-
-    def reset(self, dones=None):
-        """The marked envs' next step starts from a zero mean; ``None``: every env's."""
-        flags = None if dones is None else np.ascontiguousarray(np.asarray(dones, dtype=bool), dtype=np.uint8)
-        if flags is not None and flags.shape != (self.m,):
-            raise ValueError("dones must hold one flag per env (%d), got shape %s" % (self.m, flags.shape))
-        self.ctx.check(self.lib.l2a_mppi_controller_reset(self.handle, None if flags is None else flags.ctypes.data),
-                       "l2a_mppi_controller_reset")
-
-    def reseed(self, seed):
-        """The Philox stream restarts at 0 under ``seed``; the mean is kept."""
-        self.ctx.check(self.lib.l2a_mppi_controller_reseed(self.handle, _seed(seed)), "l2a_mppi_controller_reseed")
 
     def result(self, with_returns=True):
         """``(mean [m, D], ess [m], valid [m] int64, returns [iters, m, n] or None)`` of the latest step (host; the mean and the
@@ -62,7 +45,3 @@ class NativeMppiStep(StepHandle):
                                                            rets.ctypes.data if rets is not None else None),
                        "l2a_mppi_controller_result")
         return mean, ess, valid.astype(np.int64), rets
-
-    def stats(self):
-        v = self._stat_slots()
-        return dict(stage_us=dict(sample=v[1], launch=v[2], wait=v[4], decode=v[5], call=v[6]), steps=int(v[7]), relaunches=int(v[8]))

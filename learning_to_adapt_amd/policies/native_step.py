@@ -67,7 +67,7 @@ def _seed(seed):
 class StepHandle(object):
     """What `NativeStep`, `NativeCemStep` (policies/native_cem_step.py), `NativeMppiStep` (policies/native_mppi_step.py) and
     `NativeIcemStep` (policies/native_icem_step.py) share: the create call, the I/O arrays of a step, the
-    step's return code, the stats call and the teardown."""
+    step's return code, the stats call and the teardown.  (`PlanStep` and `WarmStep` below: what the latter three share beyond that.)"""
 
     def _open(self, native, create, m, n, h, low, high, discount, reward, extra, shard):
         """``lib.<create>(model, m, n, h, low, high, discount, reward, *extra[, rank, world, reduce, NULL], &handle)``."""
@@ -130,6 +130,51 @@ class StepHandle(object):
             self.close()
         except Exception:
             pass
+
+
+class PlanStep(StepHandle):
+    """What the device-mode plan steps (`NativeCemStep`, `NativeMppiStep`, `NativeIcemStep`) share: the step call and its stats.
+    ``label``: the planner's name in error messages."""
+
+    label = None
+
+    def step(self, observations, stream, state=None):
+        """One plan step; ``self.act`` / ``self.idx`` / ``self.ret`` hold the result afterwards.  Returns the C step's code
+        (``L2A_OK`` or ``L2A_STEP_UNSPLIT``)."""
+        np.copyto(self.obs, observations, casting="same_kind")
+        rc = self._call(state, stream)
+        self._settle(rc, "l2a_controller_step (%s)" % self.label)
+        self.steps += 1
+        return rc
+
+    def stats(self):
+        v = self._stat_slots()
+        return dict(stage_us=dict(sample=v[1], launch=v[2], wait=v[4], decode=v[5], call=v[6]), steps=int(v[7]), relaunches=int(v[8]))
+
+
+class WarmStep(PlanStep):
+    """A plan that persists from step to step on the device (`NativeMppiStep`, `NativeIcemStep`): the reset marks and the reseed.
+    ``prefix``: the planner's entry points are ``l2a_<prefix>_controller_*``."""
+
+    prefix = None
+
+    def step(self, observations, stream):       # (no recurrent state: these planners take an MLP model)
+        return PlanStep.step(self, observations, stream)
+
+    def reset(self, dones=None):
+        """The marked envs' next step starts afresh (MPPI: from a zero mean; iCEM: zero mean, the initial spread, no kept elites);
+        ``None``: every env's."""
+        flags = None if dones is None else np.ascontiguousarray(np.asarray(dones, dtype=bool), dtype=np.uint8)
+        if flags is not None and flags.shape != (self.m,):
+            raise ValueError("dones must hold one flag per env (%d), got shape %s" % (self.m, flags.shape))
+        name = "l2a_%s_controller_reset" % self.prefix
+        self.ctx.check(getattr(self.lib, name)(self.handle, None if flags is None else flags.ctypes.data), name)
+
+    def reseed(self, seed):
+        """The Philox stream restarts at 0 under ``seed``; the plan (MPPI: the mean; iCEM: mean, spread, kept elites and counts) is
+        kept."""
+        name = "l2a_%s_controller_reseed" % self.prefix
+        self.ctx.check(getattr(self.lib, name)(self.handle, _seed(seed)), name)
 
 
 class NativeStep(StepHandle):
