@@ -472,12 +472,43 @@ int l2a_plan_rs_particles_reward_model(l2a_model* model, l2a_reward_model* rm, c
  * launch, which synchronises `stream`).  perm: NULL, or device uint8 [h - 1, m, n, E] (boundary t at t * m * n * E).  With identity
  * permutations, and at h = 1 (no shuffle is launched), every output is bit-equal to l2a_plan_rs_particles.  score_out, spread_out,
  * best_key as there; particle_returns_out [m, E, n] or NULL: the returns of the particles that END in block e - row e is no
- * longer member e's: every step of such a return was predicted by the member its particle sat on at that step.  Only the fused
- * l2a_reward formula: reward programs and reward models read a step's two states from one trajectory row, which a shuffle breaks.
+ * longer member e's: every step of such a return was predicted by the member its particle sat on at that step.  This entry takes
+ * the fused l2a_reward formula; reward programs and reward models - whose scorers read a step's two states from one trajectory row,
+ * which a shuffle breaks - plan through the two entries below, which take each step's reward at the boundary.
  * The launch status word keeps its meaning: a flagged tile-split launch anywhere flags the call (l2a_launch_status); the caller
  * repeats it unsplit with the same seed / offset, which replays the same permutations.
  * L2A_EINVAL (nothing launched, no output touched, the buffer not grown): what l2a_plan_rs_particles refuses, n_sets > 16,
- * a NULL reward, offset + h * m > 2^33.                                                                                    */
+ * a NULL reward, offset + h * m > 2^33.
+ *
+ * TS1 with a reward program or a reward model.  At the boundary behind horizon step t the step's pre-state, action and post-state
+ * of every particle lie in device memory, so the step's reward is taken in the launch that moves the particles:
+ * l2a_particle_step: the kernel alone (csrc/l2a_particle_step.hip), ONE launch for all m envs, out of place.  For every particle
+ * (env i, block e, candidate j), BEFORE anything moves:
+ *   r  = program(pre, action, post)    l2a_score_trajectory's arithmetic, operation for operation (RewardProgram.evaluate_f32
+ *                                      restates it bit for bit), or rewards[i][e][j] - exactly one of `program` / `rewards` is given
+ *   R' = R + (float)disc_t * r         a separate multiply and add; R = ret_in[i][e][j], or the literal 0.0f when ret_in is NULL
+ *                                      (the addition is still made: a -0 reward gives +0, as in the trajectory scorer)
+ * then   ret_out[i][e][j] = R'[i][pi(e)][j],   state_out[i][e][j][:] = post[i][pi(e)][j][:]   (32-bit words, as the shuffle's)
+ * with pi of boundary t as l2a_particle_shuffle takes it (perm NULL: Philox of seed / offset / t; else device uint8 [m, n, E],
+ * entries >= E clamped to E - 1).  state_out NULL is the last step: nothing is dealt, perm is neither read nor checked, ret_out[e] = R'[e].
+ *   pre      device fp32 [m][E][obs_dim] (pre_per_row 0: one row per member block, the expansion's obs_x) or [m][E * n][obs_dim]
+ *   post     device fp32 [m][E * n][obs_dim]
+ *   actions  device fp32, env i's [E * n][act_dim] at actions + i * act_env_stride floats (act_env_stride >= E * n * act_dim)
+ *   rewards, ret_in, ret_out   device fp32 [m][E][n];  disc_t: discount ** t as the host's repeated product d *= discount
+ * L2A_EINVAL, nothing launched, no output touched: what l2a_particle_shuffle refuses (a NULL pre / post / actions / ret_out,
+ * act_dim < 1 likewise), both or neither of rewards / program, a program l2a_reward_program_check refuses, dimensions of which 64
+ * staged rows (each 2 (obs_dim | 1) + (act_dim | 1) words) do not fit 61 KiB of LDS (program mode), a bad act_env_stride, an output overlapping an input
+ * or the other output.
+ *
+ * l2a_plan_rs_particles_ts1_program / _reward_model: l2a_plan_rs_particles_ts1 with the program, or the reward model, in place of
+ * the l2a_reward.  The expansion once; per step and env ONE one-step launch of the rollout kernels with an all-zero fused reward
+ * that writes the step's post-states (the carry chain's form); the reward-model entry then scores every env's step with a one-step
+ * launch of the reward model's kernel at discount 1 into a rewards buffer; per step ONE l2a_particle_step over all envs; then
+ * l2a_particle_score: m * h + h + 2 launches (program), 2 * m * h + h + 2 (reward model).  Three state buffers (pre / post / dealt)
+ * and two return buffers rotate in the model's own buffer.  With identity permutations, and at h = 1, every output is bit-equal to
+ * l2a_plan_rs_particles_program / _reward_model.  Outputs, perm, seed, offset, cand_offset and the refusals as
+ * l2a_plan_rs_particles_ts1 (the reward's own checks as l2a_plan_rs_particles_program / _reward_model make them), and a
+ * particle_returns_out that overlaps perm.  The last step reads no table: perm's h - 1 boundaries are all that is touched. */
 int l2a_particle_perm(unsigned long long seed, unsigned long long offset, int t, int m, int i_first, int i_count, int cand_first,
                       int cand_count, int E, unsigned char* out_host);
 int l2a_particle_shuffle(l2a_ctx* ctx, const float* state_in, const float* ret_in, float* state_out, float* ret_out,
@@ -487,6 +518,20 @@ int l2a_plan_rs_particles_ts1(l2a_model* model, const float* obs0, const float* 
                               const l2a_reward* reward, float lambda, unsigned long long seed, unsigned long long offset,
                               const unsigned char* perm, int cand_offset, float* score_out, float* spread_out,
                               float* particle_returns_out, unsigned long long* best_key, void* stream);
+int l2a_particle_step(l2a_ctx* ctx, const float* pre, int pre_per_row, const float* post, const float* actions,
+                      long long act_env_stride, const float* rewards, const l2a_reward_program* program, double disc_t,
+                      const float* ret_in, float* state_out, float* ret_out, const unsigned char* perm, unsigned long long seed,
+                      unsigned long long offset, int t, int m, int E, int n, int obs_dim, int act_dim, int cand_offset,
+                      void* stream);
+int l2a_plan_rs_particles_ts1_program(l2a_model* model, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                                      const l2a_reward_program* program, float lambda, unsigned long long seed,
+                                      unsigned long long offset, const unsigned char* perm, int cand_offset, float* score_out,
+                                      float* spread_out, float* particle_returns_out, unsigned long long* best_key, void* stream);
+int l2a_plan_rs_particles_ts1_reward_model(l2a_model* model, l2a_reward_model* rm, const float* obs0, const float* actions, int m,
+                                           int n, int h, double discount, float lambda, unsigned long long seed,
+                                           unsigned long long offset, const unsigned char* perm, int cand_offset, float* score_out,
+                                           float* spread_out, float* particle_returns_out, unsigned long long* best_key,
+                                           void* stream);
 
 /* One-step batched prediction: MLPDynamicsModel.predict / MetaMLPDynamicsModel.predict
  * (mlp_dynamics.py:204-222, meta_mlp_dynamics.py:276-294).

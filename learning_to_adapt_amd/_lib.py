@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "l2a_rollout_traj", "l2a_mlp_traj_geometry",
     "l2a_particle_score", "l2a_plan_rs_particles", "l2a_plan_rs_particles_program", "l2a_plan_rs_particles_reward_model",
     "l2a_particle_perm", "l2a_particle_shuffle", "l2a_plan_rs_particles_ts1",
+    "l2a_particle_step", "l2a_plan_rs_particles_ts1_program", "l2a_plan_rs_particles_ts1_reward_model",
     "l2a_controller_create", "l2a_controller_create_sharded", "l2a_controller_create_sharded_device", "l2a_lstm_controller_create", "l2a_controller_create_device", "l2a_lstm_controller_create_device",
     "l2a_lstm_controller_create_sharded", "l2a_lstm_controller_create_sharded_device",
     "l2a_controller_destroy", "l2a_controller_step", "l2a_controller_begin", "l2a_lstm_controller_begin", "l2a_controller_finish",
@@ -399,6 +400,19 @@ def load():
         lib.l2a_plan_rs_particles_ts1.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardSpec), f32, u64, u64, vp,
                                                   i32, vp, vp, vp, vp, vp]
         lib.l2a_plan_rs_particles_ts1.restype = i32
+    if hasattr(lib, "l2a_particle_step"):               # (absent from older variant libraries selected with L2A_LIB_PATH)
+        u64 = c.c_ulonglong
+        # ctx, pre, pre_per_row, post, actions, act_env_stride, rewards, program, disc_t, ret_in, state_out, ret_out, perm, seed,
+        # offset, t, m, E, n, obs_dim, act_dim, cand_offset, stream
+        lib.l2a_particle_step.argtypes = [vp, vp, i32, vp, vp, c.c_longlong, vp, c.POINTER(RewardProgram), c.c_double, vp, vp, vp, vp,
+                                          u64, u64, i32, i32, i32, i32, i32, i32, i32, vp]
+        lib.l2a_particle_step.restype = i32
+        # l2a_plan_rs_particles_ts1's arguments with the program, or the reward model, in place of the reward
+        ts1_tail = [f32, u64, u64, vp, i32, vp, vp, vp, vp, vp]
+        lib.l2a_plan_rs_particles_ts1_program.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram)] + ts1_tail
+        lib.l2a_plan_rs_particles_ts1_program.restype = i32
+        lib.l2a_plan_rs_particles_ts1_reward_model.argtypes = [vp, vp, vp, vp, i32, i32, i32, c.c_double] + ts1_tail
+        lib.l2a_plan_rs_particles_ts1_reward_model.restype = i32
     if os.environ.get("L2A_LIB_PATH") and not hasattr(lib, "l2a_controller_step"):
         pass                                               # developer A/B against a library of an earlier round
     else:

@@ -1775,6 +1775,112 @@ int l2a_plan_rs_particles_ts1(l2a_model* md, const float* obs0, const float* act
     return l2a_particle_score(ctx, last, m, E, n, lambda, cand_offset, score_out, spread_out, best_key, stream_v);
 }
 
+// TS1 of a reward program or a reward model (exactly one is given): the scorers of those read a step's two states from one
+// trajectory row, so each step's reward is taken at the step's boundary instead, where both states lie in memory - per step every
+// env's request as a one-step launch of the carry chain's form (all-zero fused reward, state_out), for a reward model every env's
+// one-step scoring launch at discount 1 into `rewards`, then ONE l2a_particle_step over all envs that accumulates and deals.
+// Three state buffers rotate - a step reads `pre`, the rollout writes `post`, the step kernel deals into the third, which is the
+// next step's `pre` - and two return buffers.  Every check is made before the model's buffer is grown and before the first launch.
+static int plan_particles_ts1_step_rewards(l2a_model* md, const char* who_c, const l2a_reward_program* program, l2a_reward_model* rm,
+                                           const float* obs0, const float* actions, int m, int n, int h, double discount, float lambda,
+                                           unsigned long long seed, unsigned long long offset, const unsigned char* perm,
+                                           int cand_offset, float* score_out, float* spread_out, float* particle_returns_out,
+                                           unsigned long long* best_key, void* stream_v) {
+    l2a_ctx* ctx = md->ctx;
+    const std::string who(who_c);
+    const int E = md->n_sets;
+    int rc = particle_plan_checks(md, who_c, nullptr, program, rm, obs0, actions, m, n, h, lambda, cand_offset, score_out, best_key);
+    if (rc != L2A_OK) return rc;
+    if (E > 16) return fail(ctx, L2A_EINVAL, who + ": the shuffle holds at most 16 members");
+    if (offset > (1ull << 33) || offset + (unsigned long long)h * (unsigned long long)m > (1ull << 33))
+        return fail(ctx, L2A_EINVAL, who + ": offset + h * m must not exceed 2^33");
+    if (program) {
+        rc = l2a_particle_step_lds_check(ctx, md->obs_dim, md->act_dim);
+        if (rc != L2A_OK) return rc;
+    }
+    if (perm && particle_returns_out && h > 1) {       // (the one pair of the caller's buffers that l2a_particle_step would refuse)
+        const uintptr_t p0 = (uintptr_t)perm, p1 = p0 + (size_t)(h - 1) * m * n * E;
+        const uintptr_t r0 = (uintptr_t)particle_returns_out, r1 = r0 + sizeof(float) * (size_t)m * E * n;
+        if (p0 < r1 && r0 < p1) return fail(ctx, L2A_EINVAL, who + ": particle_returns_out overlaps perm");
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    auto round4 = [](long long f) { return (f + 3) / 4 * 4; };
+    const long long env_obs = (long long)E * md->obs_dim, env_act = (long long)h * E * n * md->act_dim, env_ret = (long long)E * n;
+    const long long env_state = env_ret * md->obs_dim, step_act = (long long)E * n * md->act_dim;
+    const long long obs_floats = round4(m * env_obs), act_floats = round4(m * env_act);
+    const long long state_floats = round4(m * env_state), ret_floats = round4(m * env_ret);
+    const int n_states = (h > 1) ? 3 : 1, n_rets = (h > 1) ? 2 : 0;
+    // [obs_x | act_x | states 0 .. 2 | returns 0, 1 | the rollouts' unread returns | rewards (reward model) | final returns unless kept]
+    const long long need = obs_floats + act_floats + n_states * state_floats + n_rets * ret_floats + round4(env_ret) +
+                           (rm ? ret_floats : 0) + (particle_returns_out ? 0 : m * env_ret);
+    rc = grow_part_buf(md, need, stream);
+    if (rc != L2A_OK) return rc;
+    float* const obs_x = md->part_buf;
+    float* const act_x = obs_x + obs_floats;
+    float* const states = act_x + act_floats;
+    float* const rets = states + n_states * state_floats;
+    float* const carry_returns = rets + n_rets * ret_floats;        // the chunk launches' required returns_out: never read
+    float* const rewards = rm ? carry_returns + round4(env_ret) : nullptr;
+    float* const last = particle_returns_out ? particle_returns_out : carry_returns + round4(env_ret) + (rm ? ret_floats : 0);
+    rc = l2a_particle_expand(ctx, obs0, actions, m, E, n, h, md->obs_dim, md->act_dim, obs_x, act_x, stream);
+    if (rc != L2A_OK) return rc;
+    l2a_reward zero;
+    std::memset(&zero, 0, sizeof(zero));
+    double disc = 1.0;
+    int k = 0;                                                      // the step's post-states: buffer k, dealt into k + 1
+    for (int t = 0; t < h; ++t) {
+        const bool end = (t == h - 1);
+        const float* const pre = (t == 0) ? obs_x : states + ((k + 2) % 3) * state_floats;      // (the buffer dealt into a step ago)
+        const long long pre_stride = (t == 0) ? env_obs : env_state;
+        float* const post = states + k * state_floats;
+        for (int i = 0; i < m; ++i) {
+            const float* const ax = act_x + i * env_act + t * step_act;
+            rc = plan_rs_chunk_as(md, L2A_MODE_PER_BLOCK, pre + i * pre_stride, t > 0, ax, E, n, 1, 0, discount, &zero, cand_offset,
+                                  nullptr, carry_returns, post + i * env_state, nullptr, stream_v);
+            if (rc != L2A_OK) return rc;
+            if (!rm) continue;
+            rc = (t == 0) ? l2a_score_trajectory_model(rm, pre + i * pre_stride, post + i * env_state, ax, E, n, 1, 1.0, cand_offset,
+                                                       rewards + i * env_ret, nullptr, stream_v)
+                          : l2a_reward_model_predict(rm, pre + i * pre_stride, ax, post + i * env_state, (int)env_ret,
+                                                     rewards + i * env_ret, stream_v);
+            if (rc != L2A_OK) return rc;
+        }
+        rc = l2a_particle_step(ctx, pre, t > 0, post, act_x + t * step_act, env_act, rewards, program, disc,
+                               t > 0 ? rets + ((t - 1) & 1) * ret_floats : nullptr, end ? nullptr : states + ((k + 1) % 3) * state_floats,
+                               end ? last : rets + (t & 1) * ret_floats,
+                               (perm && !end) ? perm + (size_t)t * m * n * E : nullptr,     // (the table has h - 1 boundaries)
+                               seed, offset, t,
+                               m, E, n, md->obs_dim, md->act_dim, cand_offset, stream_v);
+        if (rc != L2A_OK) return rc;
+        disc *= discount;
+        k = (k + 2) % 3;
+    }
+    return l2a_particle_score(ctx, last, m, E, n, lambda, cand_offset, score_out, spread_out, best_key, stream_v);
+}
+
+int l2a_plan_rs_particles_ts1_program(l2a_model* md, const float* obs0, const float* actions, int m, int n, int h, double discount,
+                                      const l2a_reward_program* program, float lambda, unsigned long long seed,
+                                      unsigned long long offset, const unsigned char* perm, int cand_offset, float* score_out,
+                                      float* spread_out, float* particle_returns_out, unsigned long long* best_key, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    if (!program) return fail(md->ctx, L2A_EINVAL, "l2a_plan_rs_particles_ts1_program: null program");
+    return plan_particles_ts1_step_rewards(md, "l2a_plan_rs_particles_ts1_program", program, nullptr, obs0, actions, m, n, h, discount,
+                                           lambda, seed, offset, perm, cand_offset, score_out, spread_out, particle_returns_out,
+                                           best_key, stream_v);
+}
+
+int l2a_plan_rs_particles_ts1_reward_model(l2a_model* md, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
+                                           int h, double discount, float lambda, unsigned long long seed, unsigned long long offset,
+                                           const unsigned char* perm, int cand_offset, float* score_out, float* spread_out,
+                                           float* particle_returns_out, unsigned long long* best_key, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    if (!rm) return fail(md->ctx, L2A_EINVAL, "l2a_plan_rs_particles_ts1_reward_model: null reward model");
+    return plan_particles_ts1_step_rewards(md, "l2a_plan_rs_particles_ts1_reward_model", nullptr, rm, obs0, actions, m, n, h, discount,
+                                           lambda, seed, offset, perm, cand_offset, score_out, spread_out, particle_returns_out,
+                                           best_key, stream_v);
+}
+
 int l2a_predict(l2a_model* md, const float* obs, const float* act, int rows, int n_blocks,
                 float* next_obs_out, void* stream_v) {
     if (!md) return L2A_EINVAL;

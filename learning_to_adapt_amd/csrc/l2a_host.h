@@ -189,6 +189,9 @@ extern "C" L2A_HIDDEN int l2a_particle_expand_check(l2a_ctx* ctx, const float* a
                                                     int act_dim);
 extern "C" L2A_HIDDEN int l2a_particle_expand(l2a_ctx* ctx, const float* obs0, const float* actions, int m, int E, int n, int h,
                                               int obs_dim, int act_dim, float* obs_x, float* act_x, hipStream_t stream);
+// l2a_particle_step's program mode (l2a_particle_step.hip): host only - do 64 staged rows of these dimensions fit the LDS?
+// (L2A_EINVAL otherwise: the TS1 plan entries ask before they grow the model's buffer.)
+extern "C" L2A_HIDDEN int l2a_particle_step_lds_check(l2a_ctx* ctx, int obs_dim, int act_dim);
 inline double l2a_now_us() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);

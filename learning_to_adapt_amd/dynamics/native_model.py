@@ -316,10 +316,12 @@ class NativeModel(object):
 
     def plan_rs_particles_ts1(self, obs0, actions, m, n, h, discount, reward, risk_coef=0.0, seed=0, offset=0, perm=None,
                               cand_offset=0, score_out=None, spread_out=None, particle_returns_out=None, best_key=None):
-        """TS1 plan step over the ensemble's particles (``l2a_plan_rs_particles_ts1``): as ``plan_rs_particles`` with a ``RewardSpec``,
-        but between two horizon steps every candidate's particles are dealt anew over the members - the Philox permutations of
-        ``(seed, offset)``, or ``perm``, a uint8 CUDA tensor ``[h - 1, m, n, n_sets]``.  ``particle_returns_out [m, n_sets, n]``: the
-        returns of the particles that END in block e (row e is no longer member e's)."""
+        """TS1 plan step over the ensemble's particles (``l2a_plan_rs_particles_ts1`` and its two siblings): as
+        ``plan_rs_particles``, but between two horizon steps every candidate's particles are dealt anew over the members - the
+        Philox permutations of ``(seed, offset)``, or ``perm``, a uint8 CUDA tensor ``[h - 1, m, n, n_sets]``.  ``reward``: a
+        ``RewardSpec`` (fused into the rollout), a ``RewardProgram`` or a ``NativeRewardModel`` (scored step by step, where the
+        particles are dealt).  ``particle_returns_out [m, n_sets, n]``: the returns of the particles that END in block e (row e
+        is no longer member e's)."""
         assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
         assert obs0.is_contiguous() and actions.is_contiguous()
         assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
@@ -332,14 +334,58 @@ class NativeModel(object):
             assert perm.is_cuda and perm.dtype == torch.uint8 and perm.is_contiguous() and perm.numel() == (h - 1) * m * n * self.n_sets
         if not hasattr(self.lib, "l2a_plan_rs_particles_ts1"):
             raise _lib.L2AError("this libl2a_hip.so has no TS1 particle plans (l2a_plan_rs_particles_ts1): rebuild it")
-        if not isinstance(reward, RewardSpec):
-            raise _lib.L2AError("TS1 particle plans score the fused reward formula only (a RewardSpec), not %s" % type(reward).__name__)
-        rc = self.lib.l2a_plan_rs_particles_ts1(self.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h), float(discount),
-                                                ctypes.byref(reward), ctypes.c_float(risk_coef), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                int(offset), _ptr(perm), int(cand_offset), _ptr(score_out), _ptr(spread_out),
-                                                _ptr(particle_returns_out), _ptr(best_key), _stream_ptr(self.device))
+        head = (self.handle, _ptr(obs0), _ptr(actions), int(m), int(n), int(h), float(discount))
+        tail = (ctypes.c_float(risk_coef), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), _ptr(perm), int(cand_offset), _ptr(score_out),
+                _ptr(spread_out), _ptr(particle_returns_out), _ptr(best_key), _stream_ptr(self.device))
+        if isinstance(reward, (NativeRewardModel, RewardProgram)):
+            # the step's reward is taken at every boundary (``l2a_particle_step``), in the launch that deals the particles
+            if not hasattr(self.lib, "l2a_particle_step"):
+                raise _lib.L2AError("this libl2a_hip.so scores TS1 particle plans by the fused reward formula only "
+                                    "(no l2a_particle_step): rebuild it")
+            if isinstance(reward, NativeRewardModel):
+                self.reward_model_plans += 1
+                rc = self.lib.l2a_plan_rs_particles_ts1_reward_model(self.handle, reward.handle, *(head[1:] + tail))
+                what = "l2a_plan_rs_particles_ts1_reward_model"
+            else:
+                self.program_plans += 1
+                rc = self.lib.l2a_plan_rs_particles_ts1_program(*(head + (ctypes.byref(reward),) + tail))
+                what = "l2a_plan_rs_particles_ts1_program"
+        elif isinstance(reward, RewardSpec):
+            rc = self.lib.l2a_plan_rs_particles_ts1(*(head + (ctypes.byref(reward),) + tail))
+            what = "l2a_plan_rs_particles_ts1"
+        else:
+            raise _lib.L2AError("TS1 particle plans take a RewardSpec, a RewardProgram or a NativeRewardModel, not %s"
+                                % type(reward).__name__)
         self.particle_plans = getattr(self, "particle_plans", 0) + 1
-        self.ctx.check(rc, "l2a_plan_rs_particles_ts1")
+        self.ctx.check(rc, what)
+
+    def particle_step(self, pre, post, actions, ret_out, m, n, disc_t=1.0, rewards=None, program=None, ret_in=None, state_out=None,
+                      pre_per_row=True, act_env_stride=None, t=0, seed=0, offset=0, perm=None, cand_offset=0):
+        """One TS1 step boundary alone (``l2a_particle_step``): the step reward of every particle - ``program`` on its ``pre``
+        state, action and ``post`` state, or the given ``rewards [m, n_sets, n]`` - is added to ``ret_in`` (``None``: zero) times
+        ``disc_t``, then returns and ``post`` states are dealt over the member blocks into ``ret_out`` / ``state_out`` (``None``:
+        the last step, nothing is dealt).  ``pre``: ``[m, n_sets * n, obs_dim]``, or ``[m, n_sets, obs_dim]`` with
+        ``pre_per_row=False``; ``actions``: env ``i``'s ``[n_sets * n, act_dim]`` at ``i * act_env_stride`` floats."""
+        E = self.n_sets
+        rows = m * E * n
+        stride = E * n * self.act_dim if act_env_stride is None else int(act_env_stride)
+        for x, count in ((pre, rows * self.obs_dim if pre_per_row else m * E * self.obs_dim), (post, rows * self.obs_dim),
+                         (state_out, rows * self.obs_dim), (rewards, rows), (ret_in, rows), (ret_out, rows)):
+            if x is not None:
+                assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == count
+        assert actions.is_cuda and actions.dtype == torch.float32 and actions.is_contiguous()
+        assert actions.numel() >= (m - 1) * stride + E * n * self.act_dim
+        if perm is not None:
+            assert perm.is_cuda and perm.dtype == torch.uint8 and perm.is_contiguous() and perm.numel() == m * n * E
+        assert program is None or isinstance(program, RewardProgram)
+        if not hasattr(self.lib, "l2a_particle_step"):
+            raise _lib.L2AError("this libl2a_hip.so has no TS1 step kernel (l2a_particle_step): rebuild it")
+        rc = self.lib.l2a_particle_step(self.ctx.handle, _ptr(pre), 1 if pre_per_row else 0, _ptr(post), _ptr(actions), stride,
+                                        _ptr(rewards), None if program is None else ctypes.byref(program), float(disc_t),
+                                        _ptr(ret_in), _ptr(state_out), _ptr(ret_out), _ptr(perm), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(offset), int(t), int(m), E, int(n), self.obs_dim, self.act_dim, int(cand_offset),
+                                        _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_particle_step")
 
     def particle_shuffle(self, state_in, ret_in, state_out, ret_out, m, n, t=0, seed=0, offset=0, perm=None, cand_offset=0):
         """The TS1 shuffle alone (``l2a_particle_shuffle``): fp32 CUDA states ``[m, n_sets * n, obs_dim]`` and returns

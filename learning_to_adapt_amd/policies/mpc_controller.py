@@ -61,7 +61,10 @@ member returns back; the C controller steps do not apply: the default ``native_s
 ``particle_sampling`` (with ``ensemble_planning="particles"``: ``"tsinf"``, the default - a particle stays on one member for the
 whole horizon - or ``"ts1"``: between two horizon steps every candidate's particles are dealt anew over the members by a random
 permutation, ``l2a_plan_rs_particles_ts1``; seeded by ``torch.initial_seed()`` under either ``rng``, every rollout takes the next
-``horizon * m`` permutation slots; the fused reward formula only, one rank only).
+``horizon * m`` permutation slots; one rank only, and the fused reward formula only unless the next keyword is set),
+``ts1_step_rewards`` (off by default: ``particle_sampling="ts1"`` refuses an env with a ``RewardProgram`` and ``use_reward_model``
+at construction; on: such a plan takes every step's reward where the particles are dealt, ``l2a_plan_rs_particles_ts1_program`` /
+``_reward_model`` - random shooting, CEM, MPPI and iCEM alike; with a ``RewardSpec`` env the keyword changes nothing).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -122,6 +125,7 @@ class MPCController(Policy, Serializable):
             icem_noise="ar1",
             icem_beta=2.0,
             particle_sampling="tsinf",
+            ts1_step_rewards=False,
     ):
         self.dynamics_model = dynamics_model
         self.reward_model = reward_model
@@ -207,6 +211,7 @@ class MPCController(Policy, Serializable):
             raise ValueError("particle_sampling='ts1' deals an ensemble's particles anew at every horizon step: it needs "
                              "ensemble_planning='particles'")
         self.particle_sampling = particle_sampling
+        self.ts1_step_rewards = bool(ts1_step_rewards)
         if ensemble_planning == "particles":
             self._check_particles()
 
@@ -219,7 +224,8 @@ class MPCController(Policy, Serializable):
         super(MPCController, self).__init__(env=env)
 
         self._reward_spec = None if use_reward_model else reward_spec_for_env(env)
-        if particle_sampling == "ts1" and (use_reward_model or isinstance(self._reward_spec, RewardProgram)):
+        if particle_sampling == "ts1" and not self.ts1_step_rewards and \
+                (use_reward_model or isinstance(self._reward_spec, RewardProgram)):
             raise _lib.L2AError("particle_sampling='ts1' scores the fused reward formula only: a reward program or a reward model "
                                 "reads a step's two states from one trajectory row, which the shuffle between steps breaks")
         self._ts1_calls = 0         # `_rollout` calls under particle_sampling="ts1" since the seed below was first seen
@@ -559,7 +565,8 @@ class MPCController(Policy, Serializable):
                     self._ts1_seed, self._ts1_calls = seed, 0
                 offset = self._ts1_calls * self.horizon * m
                 self._ts1_calls += 1
-                native.plan_rs_particles_ts1(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
+                native.plan_rs_particles_ts1(obs0, actions_local, m, n_local, self.horizon, self.discount,
+                                             rm.planner_reward_model() if rm is not None else self._reward_spec,
                                              risk_coef=self.risk_coef, seed=seed, offset=offset, cand_offset=cand_offset,
                                              score_out=rets, spread_out=spread, particle_returns_out=members, best_key=best)
                 self._particles = dict(members=members, spread=spread, score=rets, best=best, cand_offset=cand_offset,
