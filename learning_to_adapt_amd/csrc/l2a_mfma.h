@@ -133,6 +133,11 @@ __device__ __forceinline__ float l2a_sum_xor32(float x) {
 // pre-loop fills of the software-pipeline registers: without it InstCombine folds the
 // loop-carried phi(load, load) into load(phi(addr)) and the prefetch distance collapses to 0.
 #define L2A_OPAQUE(v) asm volatile("" : "+v"(v))
+// The same for a wave-uniform value (an SGPR).  Used on the scalar base of a group of weight-fragment loads right where they
+// are issued: each load's scalar offset is then base + literal, one SALU add with a short life, where the optimiser would
+// otherwise hoist every loop-invariant (base + tile offset) sum into an SGPR of its own - with the scalar file oversubscribed
+// as it is in this kernel those sums were spilled to VGPR lanes and came back as v_readlane between the GEMM's MFMAs.
+#define L2A_OPAQUE_S(v) asm("" : "+s"(v))
 
 // Phase timeline for tools/timeline.py: every wave of candidate tile 0 stamps the shader clock at
 // phase boundaries, dbg[(((grp * h + t) * 8 + e) * 8 + wave) * 16 + slot].  One uniform branch per stamp - which
@@ -171,29 +176,44 @@ __device__ __forceinline__ float l2a_sum_xor32(float x) {
             _Pragma("unroll") for (int tt = TW - 1; tt >= 0; --tt)   /* last-loaded tile first: one vmcnt wait per stage */ \
                 acc[nt][tt] = L2A_MFMA(CA[tt][ii], CB[nt][ii], acc[nt][tt]);
 
+// The stage's LDS reads and MFMAs, and the issue order of its NA weight loads: one per 4 NT MFMAs (8 back-to-back VMEM issues
+// stall the pipe)
+#define L2A_STAGE_REST(CA, CB, FB, GF, NA)                                                 \
+        _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                  \
+            FB[nt] = hin[(nt * HT + (GF)) * 64 + lane];                                    \
+        L2A_STAGE_MFMA(CA, CB)                                                             \
+        __builtin_amdgcn_sched_group_barrier(0x100, NT, 0);                                \
+        _Pragma("unroll") for (int tt = 0; tt < (NA); ++tt) {                              \
+            __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT, 0);                        \
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                             \
+        }                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);
+
+// (per-lane tile offsets `voff[tt]`: the recurrent kernel's form, l2a_lstm.h)
 #define L2A_STAGE(CA, CB, FA, FB, SOFF, IMM, GF)                                           \
     {                                                                                      \
         _Pragma("unroll") for (int tt = 0; tt < TW; ++tt)                                  \
             FA[tt] = l2a_ldw(rs, voff[tt] + (IMM), (SOFF));                                \
-        _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                  \
-            FB[nt] = hin[(nt * HT + (GF)) * 64 + lane];                                    \
-        L2A_STAGE_MFMA(CA, CB)                                                             \
-        /* interleave: one weight load per 4 NT MFMAs (8 back-to-back VMEM issues stall the pipe) */ \
-        __builtin_amdgcn_sched_group_barrier(0x100, NT, 0);                                \
-        _Pragma("unroll") for (int tt = 0; tt < TW; ++tt) {                                \
-            __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT, 0);                        \
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                             \
-        }                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                 \
+        L2A_STAGE_REST(CA, CB, FB, GF, TW)                                                 \
     }
-
+// (one lane-base VGPR `lane16`, the tile and k-group offsets scalar: this kernel's form)
+#define L2A_STAGE_S(CA, CB, FA, FB, SOFF, IMM, GF)                                         \
+    {                                                                                      \
+        int so_ = sb + (SOFF);                                                             \
+        L2A_OPAQUE_S(so_);                                                                 \
+        _Pragma("unroll") for (int tt = 0; tt < TW; ++tt)                                  \
+            FA[tt] = l2a_ldw(rs, lane16 + (IMM), so_ + tt * (HT * 1024));                  \
+        L2A_STAGE_REST(CA, CB, FB, GF, TW)                                                 \
+    }
 // olane : per obs tile, the byte offset of the lane whose output-layer fragment this lane fetches (16 lane; see O4)
 // bias_lds : this lane's bias slice of the wave's first output tile (LDS, + 16 floats per tile) -> bias[0 .. TW)
 // TW    : output tiles this wave computes here (TPW, or TPW / 2 for a half member)
 // rs    : descriptor of this layer's packed weights [tile][k-group][64 lanes][4]
 // rsn   : descriptor of the next phase's packed weights (next hidden layer, or the output layer)
-// voff  : byte offset of this lane in the layer for each of its tiles, 16 lane + tile * HT * 1024
-// LAST == false: voffn / twn = offsets / count of the tiles this wave computes in the NEXT layer
+// lane16: 16 lane - the only per-lane part of a weight fragment's address, one VGPR for every load of the kernel
+// sb    : byte offset of this wave's first tile in the layer, tile * HT * 1024 (wave uniform: with the tile and k-group
+//         offsets it forms the load's scalar offset on the SALU; the k-group inside a stage is the 12-bit immediate)
+// LAST == false: sbn / twn = first-tile offset / count of the tiles this wave computes in the NEXT layer
 // LAST == true : tile0 = global index of this wave's first tile (selects the output fragments)
 // Output-layer fragments fetched a phase ahead: the first L2A_PFT tiles only (the rest are loaded
 // when the output phase starts and land under the MFMAs of the first tiles) - register budget.
@@ -202,10 +222,10 @@ __device__ __forceinline__ float l2a_sum_xor32(float x) {
 
 template <int NT, int TW, int TPW, int OT, bool LAST>
 __device__ __forceinline__ void l2a_hidden_gemm(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rsn,
-                                                const int (&voff)[TPW], const int (&voffn)[TPW], int twn,
+                                                int sb, int sbn, int twn,
                                                 int tile0, const f32x4* hin,
                                                 f32x4 (&aA)[TPW], f32x4 (&aB)[TPW],
-                                                f32x4 (&pfO)[TPW][OT], f32x4 (&acc)[NT][TPW], int lane,
+                                                f32x4 (&pfO)[TPW][OT], f32x4 (&acc)[NT][TPW], int lane, int lane16,
                                                 const float* bias_lds, f32x4 (&bias)[TPW], const int (&olane)[OT]) {
     constexpr int HT = L2A_NW * TPW;
     static_assert(HT % 4 == 0, "the k-group pipeline is unrolled by 4");
@@ -226,26 +246,28 @@ __device__ __forceinline__ void l2a_hidden_gemm(__amdgpu_buffer_rsrc_t rs, __amd
 #pragma unroll 1
     for (int g = 0; g < HT - 4; g += 4) {
         const int soff = (g + 2) * 1024;      // byte offset of k-group g + 2 inside a tile
-        L2A_STAGE(aA, bA, aC, bC, soff, 0, g + 2)
-        L2A_STAGE(aB, bB, aD, bD, soff, 1024, g + 3)
-        L2A_STAGE(aC, bC, aA, bA, soff, 2048, g + 4)
-        L2A_STAGE(aD, bD, aB, bB, soff, 3072, g + 5)
+        L2A_STAGE_S(aA, bA, aC, bC, soff, 0, g + 2)
+        L2A_STAGE_S(aB, bB, aD, bD, soff, 1024, g + 3)
+        L2A_STAGE_S(aC, bC, aA, bA, soff, 2048, g + 4)
+        L2A_STAGE_S(aD, bD, aB, bB, soff, 3072, g + 5)
     }
     // ---- peeled last iteration (k-groups HT-4 .. HT-1) ------------------------------------
-    L2A_STAGE(aA, bA, aC, bC, (HT - 2) * 1024, 0, HT - 2)
-    L2A_STAGE(aB, bB, aD, bD, (HT - 2) * 1024, 1024, HT - 1)
+    L2A_STAGE_S(aA, bA, aC, bC, (HT - 2) * 1024, 0, HT - 2)
+    L2A_STAGE_S(aB, bB, aD, bD, (HT - 2) * 1024, 1024, HT - 1)
     {   // stage 2: consume C; aA is free -> next phase's first operands
+        int so_ = LAST ? tile0 * 1024 : sbn;
+        L2A_OPAQUE_S(so_);
         if (LAST) {     // output layer: A fragment (obs tile c, k-group = hidden tile tile0 + tt)
 #pragma unroll
             for (int tt = 0; tt < L2A_PFT(TW, OT); ++tt)
 #pragma unroll
                 for (int c = 0; c < OT; ++c)
                     if (((tt * OT + c) & 1) == 0)
-                        pfO[tt][c] = l2a_ldw(rsn, olane[c] + (tile0 + tt) * 1024, c * HT * 1024);
+                        pfO[tt][c] = l2a_ldw(rsn, olane[c], so_ + (tt + c * HT) * 1024);
         } else {
 #pragma unroll
             for (int tt = 0; tt < TPW; ++tt)
-                if (tt < twn) aA[tt] = l2a_ldw(rsn, voffn[tt], 0);
+                if (tt < twn) aA[tt] = l2a_ldw(rsn, lane16, so_ + tt * (HT * 1024));
         }
         L2A_STAGE_MFMA(aC, bC)
         __builtin_amdgcn_sched_barrier(0);
@@ -254,17 +276,19 @@ __device__ __forceinline__ void l2a_hidden_gemm(__amdgpu_buffer_rsrc_t rs, __amd
         // read where they are used they cost one exposed LDS round trip per tile (~1k clocks per GEMM, timeline r03)
 #pragma unroll
         for (int tt = 0; tt < TW; ++tt) bias[tt] = *reinterpret_cast<const f32x4*>(bias_lds + 16 * tt);
+        int so_ = LAST ? tile0 * 1024 : sbn;
+        L2A_OPAQUE_S(so_);
         if (LAST) {
 #pragma unroll
             for (int tt = 0; tt < L2A_PFT(TW, OT); ++tt)
 #pragma unroll
                 for (int c = 0; c < OT; ++c)
                     if (((tt * OT + c) & 1) == 1)
-                        pfO[tt][c] = l2a_ldw(rsn, olane[c] + (tile0 + tt) * 1024, c * HT * 1024);
+                        pfO[tt][c] = l2a_ldw(rsn, olane[c], so_ + (tt + c * HT) * 1024);
         } else {
 #pragma unroll
             for (int tt = 0; tt < TPW; ++tt)
-                if (tt < twn) aB[tt] = l2a_ldw(rsn, voffn[tt] + 1024, 0);
+                if (tt < twn) aB[tt] = l2a_ldw(rsn, lane16 + 1024, so_ + tt * (HT * 1024));
         }
         L2A_STAGE_MFMA(aD, bD)
         __builtin_amdgcn_sched_barrier(0);
@@ -294,12 +318,14 @@ __device__ __forceinline__ void l2a_out_phase(const f32x4 (&hreg)[NT][TPW], f32x
     constexpr int CS = TPW / 2;         // tiles per chunk
     constexpr int NCH = TW / CS;        // chunks this wave owns (2 = full member, 1 = half member)
     f32x4 a[TW][OT];
+    int so_ = tile0 * 1024;
+    L2A_OPAQUE_S(so_);
 #pragma unroll
     for (int tt = 0; tt < TW; ++tt)
 #pragma unroll
         for (int c = 0; c < OT; ++c)
             a[tt][c] = (tt < L2A_PFT(TW, OT)) ? pfO[tt][c]
-                                              : l2a_ldw(rs_out, olane[c] + (tile0 + tt) * 1024, c * HT * 1024);
+                                              : l2a_ldw(rs_out, olane[c], so_ + (tt + c * HT) * 1024);
     prefetch();
     f32x4 acc[NCH][NT][OT];
 #pragma unroll
@@ -567,23 +593,25 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
 
     // Operands every phase receives preloaded from the phase before it (issued ahead of the
     // barrier that separates them, so a phase never starts with an exposed L2 round trip).
-    // (every layer-0 k-group a phase ahead was measured neutral for 21 more registers: profiles/r03_ab_kernel_variants.jsonl)
-    // Layer-0 k-groups fetched a phase ahead: the first one; in the fan instances (110 VGPRs below the tile-split ones) both
-    // k-groups of an input of at most 32 features - config-5 shard 0.6008 -> 0.5932 ms (round 6 A/B, tools/ab_fan.sh; the same
-    // prefetch was neutral in the tile-split instances at 442 VGPRs: profiles/r03_ab_kernel_variants.jsonl)
-    constexpr int KG0P = (FAN && KG0 <= 2) ? KG0 : 1;
+    // Layer-0 k-groups fetched a phase ahead: every k-group of an input of at most 32 features, else the first one (wider
+    // inputs: no registers to spare).  Round 6 had this in the fan instances only (config-5 shard 0.6008 -> 0.5932 ms); in the
+    // tile-split instances, then at 442 - 488 VGPRs, it measured neutral (profiles/r03_ab_kernel_variants.jsonl): the loads
+    // of the next set were issued IN FRONT of the MFMAs, so the arrived fragments had to be copied out of `pfL0` first (10
+    // v_mov_b64 + 8 v_accvgpr_read) and sixteen loads went out back to back.
+    // L0RF (round 7, general and whole-tile instances): a layer 0 that is followed by another REFILLS each fragment register
+    // after the last MFMA that reads it - k-group 0's under the MFMAs of k-group 1, the last k-group's behind the MFMAs - so
+    // the prefetched fragments are multiplied where they arrived.  Config 2 1.3978 -> 1.3799 ms (profiles/r07_ab_prefetch.jsonl).
+    constexpr int KG0P = (KG0 <= 2) ? KG0 : 1;
+    constexpr bool L0RF = !FAN && KG0P == KG0;
     f32x4 pfL0[KG0P][TPW];      // layer-0 A fragments of the upcoming (step, set)
     f32x4 pfA[TPW], pfB[TPW];   // k-groups 0 / 1 of the upcoming hidden->hidden layer
     f32x4 pfO[TPW][OT];         // output-layer A fragments of this wave's k-groups
-    // this lane's byte offset of its tiles in a hidden matrix (full member / half member) and in layer 0
-    int voff[TPW], voffh[TPW], voff0[TPW];
-    const int tile0h = grp * (HT / 2) + wave * TH;          // first tile of this wave in a half member
-#pragma unroll
-    for (int tt = 0; tt < TPW; ++tt) {
-        voff[tt] = lane * 16 + (c0 + tt) * HT * 1024;
-        voffh[tt] = lane * 16 + (tile0h + (tt < TH ? tt : 0)) * HT * 1024;
-        voff0[tt] = lane * 16 + (c0 + tt) * KG0 * 1024;
-    }
+    // A weight fragment's address = descriptor + lane16 (the one per-lane VGPR) + a wave-uniform byte offset of (tile,
+    // k-group) on the SALU: sbf / sbh = this wave's first tile in a hidden matrix as a full / half member, sb0 = in layer 0
+    const int lane16 = lane * 16;
+    const int tile0h = __builtin_amdgcn_readfirstlane(grp * (HT / 2) + wave * TH);      // first tile of this wave in a half member
+    const int sbf = c0 * (HT * 1024), sbh = tile0h * (HT * 1024), sb0 = c0 * (KG0 * 1024);
+    auto sbase = [](int v) { L2A_OPAQUE_S(v); return v; };      // (the base of one group of loads: see L2A_OPAQUE_S)
     const long long w0_bytes = (long long)HT * KG0 * 1024, wm_bytes = (long long)HT * HT * 1024,
                     wo_bytes = (long long)OT * HT * 1024;
     {
@@ -591,20 +619,18 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
 #pragma unroll
         for (int g = 0; g < KG0P; ++g)
 #pragma unroll
-            for (int tt = 0; tt < TPW; ++tt) pfL0[g][tt] = l2a_ldw(r0, voff0[tt] + g * 1024, 0);
+            for (int tt = 0; tt < TPW; ++tt) pfL0[g][tt] = l2a_ldw(r0, lane16, sb0 + (tt * KG0 + g) * 1024);
     }
 
     for (int t = 0; t < p.h; ++t) {
-        // dsum: finished group; dgrp: group being summed; qsh: this workgroup's half of the shared
-        // set's raw output sum (split == 2)
-        f32x4 dsum[NT][OT], dgrp[NT][OT], qsh[NT][OT];
+        // dsum: finished group; dgrp: group being summed
+        f32x4 dsum[NT][OT], dgrp[NT][OT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int c = 0; c < OT; ++c) {
                 dsum[nt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 dgrp[nt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                qsh[nt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
 
         // Exchange records (split): region 0 = group sum of the full sets, region 1 = this half of
@@ -653,10 +679,104 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
         // hand-over instead of behind them.  The shared set adds nothing to `dgrp` in phase C (its term is formed in the
         // combine), so its place in wave 0's order changes no bit.  Config 2: 1.4153 -> 1.3997 ms (profiles/r06_ab_xsweep.jsonl;
         // the records leaving early WITHOUT the early request gained nothing: r06_ab_xord.jsonl).
-        bool xearly = false;        // this step's records left in phase C, wave 3 holds the requested partner records in `sw`
+        // Phase C of the step's LAST batch stands behind the batch loop, as a copy of its own: the shared set (always the last
+        // of the sequence) is reduced only there and the partner's records are requested only there, so `qsh` and `sw` - 8 OT
+        // and 16 OT registers - are born after the last GEMM.  Written inside the loop they were loop-carried values and held
+        // their registers through phases A and B of every batch.
+        // qsh: this workgroup's half of the shared set's raw output sum (split == 2); sw: the partner records wave 3 requested
+        f32x4 qsh[NT][OT];
         u32x4 sw[2][NT][OT][2];
-        for (int b0 = 0; b0 < n_seq; b0 += LB) {
-            const int nb = (n_seq - b0 < LB) ? n_seq - b0 : LB;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int c = 0; c < OT; ++c) qsh[nt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        int b0 = 0, nb;
+        auto phase_c = [&](auto last_tag) {
+            constexpr bool last_batch = decltype(last_tag)::value;
+            // (the batch that ends with the shared set, if it holds another set too)
+            // (instances of up to 32 input features: the requested records are 16 VGPRs per obs tile, and the Ant's instance -
+            //  496 VGPRs without them - would spill)
+            constexpr bool XE_OK = L2A_XEARLY && !NOHALF && NT == 1 && OT <= 2 && KG0 <= 2;
+            const bool xe = last_batch && XE_OK && split == 2 && nb >= 2;
+            for (int jj = 0; jj < nb; ++jj) {
+                const int j = (xe && wave == 0) ? (jj == 0 ? nb - 1 : jj - 1) : jj;     // wave 0: the shared set first
+                const int i = b0 + j;
+                const int e = seq(i);
+                const bool is_half = last_batch && !NOHALF && (e == e_shared);
+                const float* nr = nrm + i * NRM_SET;
+                const f32x4* pb = (LB > 1) ? pbase + j * PS : hoth;
+                L2A_TS(5)
+                if (e == e_half && !split) {      // group A complete: park it, start group B
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                        for (int c = 0; c < OT; ++c) {
+                            dsum[nt][c] = dgrp[nt][c];
+                            dgrp[nt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                        }
+                }
+                // Sum the waves' partials in the canonical order - a balanced tree over the eight chunks of hidden units,
+                // ((c0+c1)+(c2+c3)) + ((c4+c5)+(c6+c7)): a full member's wave w wrote c_2w + c_2w+1, so (p0+p1)+(p2+p3) is the
+                // whole tree; a half member's wave w wrote chunk w of ITS half, so the same expression is its half of the
+                // tree, and the other half arrives at the end of the step from the partner workgroup.  (Until round 3 the
+                // order was ((c0+c1)+c2)+c3 + ((c4+c5)+c6)+c7, which forced a full member to keep its two chunks apart: eight
+                // partials per set to write and to read back instead of four.)
+                // All LDS reads of an obs tile are issued before the first add: left to itself the compiler,
+                // which is out of registers kernel-wide, serialises them read-wait-add (~120 cycles each, 22 of
+                // them: the reduce measured 1.4k cycles per set in tools/timeline.py).
+                // (reading all obs tiles of a set up front - one exposed round trip instead of OT - was measured and lost:
+                // 1.434 against 1.431 ms on config 2, profiles/r03_ab_kernel_variants.jsonl)
+#pragma unroll
+                for (int c = 0; c < OT; ++c) {
+                    f32x4 part[L2A_NW][NT];
+#pragma unroll
+                    for (int ch = 0; ch < L2A_NW; ++ch)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) part[ch][nt] = pb[((ch * NT + nt) * OT + c) * 64 + lane];
+                    const f32x4 bias = *reinterpret_cast<const f32x4*>(nr + CST_BOUT + 16 * c + 4 * qq);
+                    const f32x4 omu = *reinterpret_cast<const f32x4*>(nr + 32 * KG0 + 16 * c + 4 * qq);
+                    const f32x4 osd = *reinterpret_cast<const f32x4*>(nr + 32 * KG0 + 16 * OT + 16 * c + 4 * qq);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        static_assert(L2A_NW == 4, "the canonical tree below is written out for four waves");
+                        f32x4 s = (part[0][nt] + part[1][nt]) + (part[2][nt] + part[3][nt]);
+                        if (is_half) {
+                            qsh[nt][c] = s;
+                        } else {
+                            if (O4 && c == OT - 1) {        // the four quarters of the hidden units (l2a_out_phase)
+#pragma unroll
+                                for (int ii = 0; ii < 4; ++ii) s[ii] = l2a_sum_xor32(l2a_sum_xor16(s[ii]));
+                            }
+                            s = l2a_actv<GACT>(s + bias, p.output_act, p.out_floor);
+                            if (FAN) dgrp[nt][c] = s * osd + omu;      // this member's term as it stands: summed with the others' below
+                            else dgrp[nt][c] += s * osd + omu;
+                        }
+                    }
+                }
+                // the group sum of the full sets leaves as soon as it exists (LB == 1: it travels under the half set)
+                if (!NOHALF && split == 2 && i == n_full - 1 && wave == (XE_OK ? 1 : 0)) xput(0, dgrp);
+                if (xe && wave == 0 && jj == 0) xput(1, qsh);
+                if (xe && wave == 3 && jj == nb - 1) {
+                    // single model (E == 1): there are no full sets, region 0 is never written - not requested
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                            for (int c = 0; c < OT; ++c)
+#pragma unroll
+                                for (int hh = 0; hh < 2; ++hh)
+                                    sw[r][nt][c][hh] = (r == 1 || e_loop > 1)
+                                        ? __builtin_amdgcn_raw_buffer_load_b128(xrs, xbase(grp ^ 1, r) + ((nt * OT + c) * 2 + hh) * 1024, 0, L2A_SC1)
+                                        : (u32x4){xtag, 0u, xtag, 0u};
+                }
+                L2A_TS(6)
+            }
+            return xe;
+        };
+        for (;; b0 += LB) {
+            nb = (n_seq - b0 < LB) ? n_seq - b0 : LB;
             f32x4 hreg[NT][TPW];    // activations of the LAST hidden layer (stay in registers)
 
             // ======== phase A: layer 0 of every set of the batch ==================================
@@ -675,11 +795,12 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                 // k-group 0 arrived with the previous phase; the others land under its MFMAs
                 const __amdgpu_buffer_rsrc_t r0 = l2a_rsrc(wb + p.pk_w0, w0_bytes);
                 f32x4 a[KG0][TPW];
+                const int s0 = sbase(sb0);
 #pragma unroll
                 for (int g = 0; g < KG0; ++g)
 #pragma unroll
                     for (int tt = 0; tt < TPW; ++tt)
-                        a[g][tt] = (g < KG0P) ? pfL0[g < KG0P ? g : 0][tt] : l2a_ldw(r0, voff0[tt] + g * 1024, 0);
+                        a[g][tt] = (g < KG0P) ? pfL0[g < KG0P ? g : 0][tt] : l2a_ldw(r0, lane16, s0 + (tt * KG0 + g) * 1024);
                 L2A_TS(8)
                 // normalised inputs of every k-group up front: all 2 KG0 constant reads are issued together (the
                 // register-starved scheduler otherwise puts each LDS round trip right in front of its MFMAs)
@@ -751,6 +872,23 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                                     acc[nt][tt] = L2A_MFMA(a[g][tt][ii], xg[nt][ii], acc[nt][tt]);
                         }
                     }
+                    if constexpr (NPF < 0) {
+                        // refill order: k-group 0's MFMAs, then per later k-group one refill load of the group before per
+                        // share of its MFMAs, then the last group's refills
+                        __builtin_amdgcn_sched_group_barrier(0x008, (KG0 > 1 ? 4 : K0L) * NT * TPW, 0);
+#pragma unroll
+                        for (int k = 0; k < (KG0 - 2) * TPW; ++k) {         // the middle k-groups
+                            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT, 0);
+                        }
+#pragma unroll
+                        for (int k = 0; k < (KG0 > 1 ? TPW : 0); ++k) {     // the last one (K0L MFMAs per tile)
+                            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x008, K0L * NT, 0);
+                        }
+                        __builtin_amdgcn_sched_group_barrier(0x020, TPW, 0);
+                        return;
+                    }
                     // hint: the a[g >= 1] loads first, then one prefetch load per few MFMAs
                     constexpr int NM = ((KG0 - 1) * 4 + K0L) * NT * TPW;
                     constexpr int PER = NM / (NPF > 0 ? NPF : 1) > 0 ? NM / (NPF > 0 ? NPF : 1) : 1;
@@ -763,37 +901,40 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                 };
                 // operands of the phase after this one
                 if (N1) {
+                    const int so = sbase(c0 * 1024);
 #pragma unroll
                     for (int tt = 0; tt < L2A_PFT(TPW, OT); ++tt)
 #pragma unroll
                         for (int c = 0; c < OT; ++c)
-                            pfO[tt][c] = l2a_ldw(rs_out, olane[c] + (c0 + tt) * 1024, c * HT * 1024);
+                            pfO[tt][c] = l2a_ldw(rs_out, olane[c], so + (tt + c * HT) * 1024);
                     l0_mfma(std::integral_constant<int, L2A_PFT(TPW, OT) * OT>{});
                 } else if (!last_l0) {
                     // the next set's layer 0 follows: its k-group 0
                     const __amdgpu_buffer_rsrc_t r0n = l2a_rsrc(set_base(seq(i + 1)) + p.pk_w0, w0_bytes);
+                    if (L0RF) l0_mfma(std::integral_constant<int, -1>{});
 #pragma unroll
                     for (int g = 0; g < KG0P; ++g)
 #pragma unroll
-                        for (int tt = 0; tt < TPW; ++tt) pfL0[g][tt] = l2a_ldw(r0n, voff0[tt] + g * 1024, 0);
-                    l0_mfma(std::integral_constant<int, KG0P * TPW>{});
+                        for (int tt = 0; tt < TPW; ++tt) pfL0[g][tt] = l2a_ldw(r0n, lane16, s0 + (tt * KG0 + g) * 1024);
+                    if (!L0RF) l0_mfma(std::integral_constant<int, KG0P * TPW>{});
                 } else {
                     // the first hidden GEMM of the batch follows (set seq(b0))
                     const int e0 = seq(b0);
                     const __amdgpu_buffer_rsrc_t rs1 = l2a_rsrc(set_base(e0) + p.pk_wmid, wm_bytes);
                     const bool next_half = !NOHALF && (e0 == e_shared) && n_hidden == 2;
+                    const int s1 = sbase(next_half ? sbh : sbf);
                     if (next_half) {
 #pragma unroll
                         for (int tt = 0; tt < TH; ++tt) {
-                            pfA[tt] = l2a_ldw(rs1, voffh[tt], 0);
-                            pfB[tt] = l2a_ldw(rs1, voffh[tt] + 1024, 0);
+                            pfA[tt] = l2a_ldw(rs1, lane16, s1 + tt * (HT * 1024));
+                            pfB[tt] = l2a_ldw(rs1, lane16 + 1024, s1 + tt * (HT * 1024));
                         }
                         l0_mfma(std::integral_constant<int, 2 * TH>{});
                     } else {
 #pragma unroll
                         for (int tt = 0; tt < TPW; ++tt) {
-                            pfA[tt] = l2a_ldw(rs1, voff[tt], 0);
-                            pfB[tt] = l2a_ldw(rs1, voff[tt] + 1024, 0);
+                            pfA[tt] = l2a_ldw(rs1, lane16, s1 + tt * (HT * 1024));
+                            pfB[tt] = l2a_ldw(rs1, lane16 + 1024, s1 + tt * (HT * 1024));
                         }
                         l0_mfma(std::integral_constant<int, 2 * TPW>{});
                     }
@@ -836,8 +977,8 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                         const float* wl = wb + p.pk_wmid + (long long)(l - 1) * p.pk_wmid_stride;
                         const bool next_half = is_half && (l == n_hidden - 2);
                         l2a_hidden_gemm<NT, TPW, TPW, OT, false>(l2a_rsrc(wl, wm_bytes), l2a_rsrc(wl + p.pk_wmid_stride, wm_bytes),
-                                                                 voff, next_half ? voffh : voff, next_half ? TH : TPW, 0,
-                                                                 hcur, pfA, pfB, pfO, acc, lane,
+                                                                 sbf, next_half ? sbh : sbf, next_half ? TH : TPW, 0,
+                                                                 hcur, pfA, pfB, pfO, acc, lane, lane16,
                                                                  nr + CST_BHID + l * (16 * HT) + 16 * c0 + 4 * qq, bias, olane);
 #pragma unroll
                         for (int tt = 0; tt < TPW; ++tt) {
@@ -855,8 +996,8 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                         l2a_rsrc(wb + p.pk_wmid + (long long)(n_hidden - 2) * p.pk_wmid_stride, wm_bytes);
                     const float* bl = nr + CST_BHID + (n_hidden - 1) * (16 * HT);
                     if (!is_half) {
-                        l2a_hidden_gemm<NT, TPW, TPW, OT, true>(rs_last, rs_out, voff, voff, TPW, c0, hin, pfA, pfB, pfO,
-                                                                acc, lane, bl + 16 * c0 + 4 * qq, bias, olane);
+                        l2a_hidden_gemm<NT, TPW, TPW, OT, true>(rs_last, rs_out, sbf, sbf, TPW, c0, hin, pfA, pfB, pfO,
+                                                                acc, lane, lane16, bl + 16 * c0 + 4 * qq, bias, olane);
 #pragma unroll
                         for (int tt = 0; tt < TPW; ++tt) {
 #pragma unroll
@@ -864,8 +1005,8 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                                 hreg[nt][tt] = l2a_actv<GACT>(acc[nt][tt] + bias[tt], p.hidden_act, p.hid_floor);
                         }
                     } else {
-                        l2a_hidden_gemm<NT, TH, TPW, OT, true>(rs_last, rs_out, voffh, voffh, TH, tile0h, hin, pfA, pfB,
-                                                               pfO, acc, lane, bl + 16 * tile0h + 4 * qq, bias, olane);
+                        l2a_hidden_gemm<NT, TH, TPW, OT, true>(rs_last, rs_out, sbh, sbh, TH, tile0h, hin, pfA, pfB,
+                                                               pfO, acc, lane, lane16, bl + 16 * tile0h + 4 * qq, bias, olane);
 #pragma unroll
                         for (int tt = 0; tt < TH; ++tt) {
 #pragma unroll
@@ -880,10 +1021,11 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                 if (last_set) {
                     const __amdgpu_buffer_rsrc_t r0n = l2a_rsrc(set_base(seq((i + 1 < n_seq) ? i + 1 : 0)) + p.pk_w0, w0_bytes);
                     auto pf_l0 = [&]() {
+                        const int s0 = sbase(sb0);
 #pragma unroll
                         for (int g = 0; g < KG0P; ++g)
 #pragma unroll
-                            for (int tt = 0; tt < TPW; ++tt) pfL0[g][tt] = l2a_ldw(r0n, voff0[tt] + g * 1024, 0);
+                            for (int tt = 0; tt < TPW; ++tt) pfL0[g][tt] = l2a_ldw(r0n, lane16, s0 + (tt * KG0 + g) * 1024);
                     };
                     if (is_half) l2a_out_phase<NT, TH, TPW, OT, KG0P * TPW, O4>(hreg, pfO, rs_out, tile0h, pf_l0, pb, wave, lane, olane);
                     else l2a_out_phase<NT, TPW, TPW, OT, KG0P * TPW, O4>(hreg, pfO, rs_out, c0, pf_l0, pb, wave, lane, olane);
@@ -892,18 +1034,20 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                     const __amdgpu_buffer_rsrc_t rsn = l2a_rsrc(set_base(en) + p.pk_wmid, wm_bytes);   // nb > 1: two hidden layers
                     if (!NOHALF && en == e_shared) {
                         l2a_out_phase<NT, TPW, TPW, OT, 2 * TH, O4>(hreg, pfO, rs_out, c0, [&]() {
+                            const int s1 = sbase(sbh);
 #pragma unroll
                             for (int tt = 0; tt < TH; ++tt) {
-                                pfA[tt] = l2a_ldw(rsn, voffh[tt], 0);
-                                pfB[tt] = l2a_ldw(rsn, voffh[tt] + 1024, 0);
+                                pfA[tt] = l2a_ldw(rsn, lane16, s1 + tt * (HT * 1024));
+                                pfB[tt] = l2a_ldw(rsn, lane16 + 1024, s1 + tt * (HT * 1024));
                             }
                         }, pb, wave, lane, olane);
                     } else {
                         l2a_out_phase<NT, TPW, TPW, OT, 2 * TPW, O4>(hreg, pfO, rs_out, c0, [&]() {
+                            const int s1 = sbase(sbf);
 #pragma unroll
                             for (int tt = 0; tt < TPW; ++tt) {
-                                pfA[tt] = l2a_ldw(rsn, voff[tt], 0);
-                                pfB[tt] = l2a_ldw(rsn, voff[tt] + 1024, 0);
+                                pfA[tt] = l2a_ldw(rsn, lane16, s1 + tt * (HT * 1024));
+                                pfB[tt] = l2a_ldw(rsn, lane16 + 1024, s1 + tt * (HT * 1024));
                             }
                         }, pb, wave, lane, olane);
                     }
@@ -920,88 +1064,9 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
 
             // ======== phase C: canonical reduce of every set of the batch ===========================
             __syncthreads();
-            // (the batch that ends with the shared set, if it holds another set too)
-            // (instances of up to 32 input features: the requested records are 16 VGPRs per obs tile, and the Ant's instance -
-            //  496 VGPRs without them - would spill)
-            constexpr bool XE_OK = L2A_XEARLY && !NOHALF && NT == 1 && OT <= 2 && KG0 <= 2;
-            const bool xe = XE_OK && split == 2 && nb >= 2 && b0 + nb == n_seq;
-            for (int jj = 0; jj < nb; ++jj) {
-                const int j = (xe && wave == 0) ? (jj == 0 ? nb - 1 : jj - 1) : jj;     // wave 0: the shared set first
-                const int i = b0 + j;
-                const int e = seq(i);
-                const bool is_half = !NOHALF && (e == e_shared);
-                const float* nr = nrm + i * NRM_SET;
-                const f32x4* pb = (LB > 1) ? pbase + j * PS : hoth;
-                L2A_TS(5)
-                if (e == e_half && !split) {      // group A complete: park it, start group B
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int c = 0; c < OT; ++c) {
-                            dsum[nt][c] = dgrp[nt][c];
-                            dgrp[nt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                        }
-                }
-                // Sum the waves' partials in the canonical order - a balanced tree over the eight chunks of hidden units,
-                // ((c0+c1)+(c2+c3)) + ((c4+c5)+(c6+c7)): a full member's wave w wrote c_2w + c_2w+1, so (p0+p1)+(p2+p3) is the
-                // whole tree; a half member's wave w wrote chunk w of ITS half, so the same expression is its half of the
-                // tree, and the other half arrives at the end of the step from the partner workgroup.  (Until round 3 the
-                // order was ((c0+c1)+c2)+c3 + ((c4+c5)+c6)+c7, which forced a full member to keep its two chunks apart: eight
-                // partials per set to write and to read back instead of four.)
-                // All LDS reads of an obs tile are issued before the first add: left to itself the compiler,
-                // which is out of registers kernel-wide, serialises them read-wait-add (~120 cycles each, 22 of
-                // them: the reduce measured 1.4k cycles per set in tools/timeline.py).
-                // (reading all obs tiles of a set up front - one exposed round trip instead of OT - was measured and lost:
-                // 1.434 against 1.431 ms on config 2, profiles/r03_ab_kernel_variants.jsonl)
-#pragma unroll
-                for (int c = 0; c < OT; ++c) {
-                    f32x4 part[L2A_NW][NT];
-#pragma unroll
-                    for (int ch = 0; ch < L2A_NW; ++ch)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) part[ch][nt] = pb[((ch * NT + nt) * OT + c) * 64 + lane];
-                    const f32x4 bias = *reinterpret_cast<const f32x4*>(nr + CST_BOUT + 16 * c + 4 * qq);
-                    const f32x4 omu = *reinterpret_cast<const f32x4*>(nr + 32 * KG0 + 16 * c + 4 * qq);
-                    const f32x4 osd = *reinterpret_cast<const f32x4*>(nr + 32 * KG0 + 16 * OT + 16 * c + 4 * qq);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        static_assert(L2A_NW == 4, "the canonical tree below is written out for four waves");
-                        f32x4 s = (part[0][nt] + part[1][nt]) + (part[2][nt] + part[3][nt]);
-                        if (is_half) {
-                            qsh[nt][c] = s;
-                        } else {
-                            if (O4 && c == OT - 1) {        // the four quarters of the hidden units (l2a_out_phase)
-#pragma unroll
-                                for (int ii = 0; ii < 4; ++ii) s[ii] = l2a_sum_xor32(l2a_sum_xor16(s[ii]));
-                            }
-                            s = l2a_actv<GACT>(s + bias, p.output_act, p.out_floor);
-                            if (FAN) dgrp[nt][c] = s * osd + omu;      // this member's term as it stands: summed with the others' below
-                            else dgrp[nt][c] += s * osd + omu;
-                        }
-                    }
-                }
-                // the group sum of the full sets leaves as soon as it exists (LB == 1: it travels under the half set)
-                if (!NOHALF && split == 2 && i == n_full - 1 && wave == (XE_OK ? 1 : 0)) xput(0, dgrp);
-                if (xe && wave == 0 && jj == 0) xput(1, qsh);
-                if (xe && wave == 3 && jj == nb - 1) {
-                    // single model (E == 1): there are no full sets, region 0 is never written - not requested
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                            for (int c = 0; c < OT; ++c)
-#pragma unroll
-                                for (int hh = 0; hh < 2; ++hh)
-                                    sw[r][nt][c][hh] = (r == 1 || e_loop > 1)
-                                        ? __builtin_amdgcn_raw_buffer_load_b128(xrs, xbase(grp ^ 1, r) + ((nt * OT + c) * 2 + hh) * 1024, 0, L2A_SC1)
-                                        : (u32x4){xtag, 0u, xtag, 0u};
-                }
-                L2A_TS(6)
-            }
-            if (xe) xearly = true;
-            // LDS hazards.  LB == 1: the partial sums live in `hoth`; `hcur` was last read by the final
+            if (b0 + nb >= n_seq) break;        // (n_seq >= 1: a workgroup always has a last batch)
+            phase_c(std::false_type{});     // (touches neither `qsh` nor `sw`: no shared set, no request before the last batch)
+            // LDS hazards. LB == 1: the partial sums live in `hoth`; `hcur` was last read by the final
             // hidden layer, before the barrier above.  n_hidden >= 2: the next writes are layer 0
             // -> `hcur` (free) and, only after the layer-0 barrier, `hoth` again (every wave has
             // finished these reads by then).  n_hidden == 1: there is no layer-0 barrier, the next
@@ -1010,6 +1075,9 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
             // barriers, which every wave reaches after these reads.
             if (N1) { f32x4* tmp = hcur; hcur = hoth; hoth = tmp; }
         }
+        // xearly: this step's records left in phase C, wave 3 holds the requested partner records in `sw`
+        const bool xearly = phase_c(std::true_type{});
+        if (N1) { f32x4* tmp = hcur; hcur = hoth; hoth = tmp; }
 
         // ---- combine the two workgroups of a tile ---------------------------------------------
         { const int e = 7; L2A_TS(9) }
