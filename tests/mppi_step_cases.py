@@ -10,7 +10,8 @@ import cases
 from learning_to_adapt_amd.policies.native_mppi_step import NativeMppiStep
 
 MODELS = {"mlp": dict(cases.CASES["hc_rs_m3_n64_h5"]),
-          "ens5": dict(cases.CASES["c2_hc_rs_n2000_h30_e5"], n=96, h=6)}        # the 5-member mean ensemble on a small plan
+          "ens5": dict(cases.CASES["c2_hc_rs_n2000_h30_e5"], n=96, h=6),        # the 5-member mean ensemble on a small plan
+          "long": dict(cases.CASES["hc_rs_m3_n64_h5"], h=90)}   # l2a_mppi_sample_k walks this horizon in two passes (85 + 5 at A = 6)
 
 
 def bits(a):

@@ -18,7 +18,7 @@ from learning_to_adapt_amd.dynamics.native_lstm import NativeLSTM
 from learning_to_adapt_amd.dynamics.native_model import NativeModel
 from learning_to_adapt_amd.envs import RewardSpec
 from learning_to_adapt_amd.utils import synthetic
-from oracle import LSTMStateTuple, OracleLSTMDynamics, OracleMLPDynamics
+from oracle import LSTMStateTuple, OracleLSTMDynamics, OracleMLPDynamics, OracleRNNStackDynamics
 from oracle.planner import rollout_returns
 from oracle.rnn_planner import rnn_rollout_returns
 
@@ -44,9 +44,13 @@ def _norm(rs, obs_dim, act_dim, low, high):
     return synthetic.make_norm(obs_dim, act_dim, low, high, int(rs.randint(1 << 30)))
 
 
+def _err(got, want):
+    """The largest error as a fraction of ``max(1, max |want|)``; the sweep's bar on it is 1e-4."""
+    return float(np.max(np.abs(got - want))) / max(1.0, float(np.max(np.abs(want))))
+
+
 def _check(got, want, keys, n, offset):
-    scale = max(1.0, float(np.max(np.abs(want))))
-    assert float(np.max(np.abs(got - want))) / scale < 1e-4
+    assert _err(got, want) < 1e-4
     for i in range(got.shape[0]):
         ret, idx = _lib.key_decode(keys[i])
         assert idx - offset == int(np.argmax(got[i])) and ret == got[i, idx - offset]
@@ -143,11 +147,50 @@ def test_random_lstm_shapes_match_oracle(seed):
     native.close()
 
 
+ORACLE_ROWS = 12000         # m * n * h above which the float64 oracle rolls a subset of every env's candidates
+ORACLE_EDGE, ORACLE_DRAWN = 16, 224
+
+
+def _unpack_hidden(sizes, cell, c, h):
+    """The (c, h) rows a launch takes - the layers' states side by side - as the oracle structures a hidden state: per layer an
+    ``LSTMStateTuple`` (LSTM) or the plain ``h`` (GRU / BasicRNN, which have no c), a list of those for a stack."""
+    layers, o = [], 0
+    for u in sizes:
+        layers.append(LSTMStateTuple(c[:, o:o + u], h[:, o:o + u]) if cell == "lstm" else h[:, o:o + u])
+        o += u
+    assert o == c.shape[1] == h.shape[1]
+    return layers if len(layers) > 1 else layers[0]
+
+
+def _oracle_columns(rs, m, n, h):
+    """The candidates of every env the oracle rolls: all of them up to ``ORACLE_ROWS`` plan rows, else the first 16, the last 16 and
+    224 drawn in between (rows are independent: a candidate's return does not depend on its neighbours)."""
+    if m * n * h <= ORACLE_ROWS:
+        return np.arange(n)
+    assert n >= 2 * ORACLE_EDGE + ORACLE_DRAWN
+    drawn = rs.choice(np.arange(ORACLE_EDGE, n - ORACLE_EDGE), ORACLE_DRAWN, replace=False)
+    cols = np.concatenate([np.arange(ORACLE_EDGE), np.sort(drawn), np.arange(n - ORACLE_EDGE, n)])
+    assert cols.size == 2 * ORACLE_EDGE + ORACLE_DRAWN == 256 and np.unique(cols).size == cols.size
+    return cols
+
+
+def _stack_oracle_returns(obs_dim, act_dim, sizes, cell, act, params, norm, spec, obs0, c0, h0, acts, m, n, discount, cols):
+    """Float64 returns ``[m, len(cols)]`` of ``OracleRNNStackDynamics`` on the fp32 inputs the launches get (host arrays)."""
+    dyn = OracleRNNStackDynamics(obs_dim, act_dim, sizes, cell, params, norm, hidden_nonlinearity=act, dtype=np.float64)
+    h = acts.shape[0]
+    sub = np.ascontiguousarray(acts.reshape(h, m, n, act_dim)[:, :, cols]).reshape(h, m * cols.size, act_dim)
+    want = rnn_rollout_returns(dyn, spec.evaluate, obs0.astype(np.float64), _unpack_hidden(sizes, cell, c0, h0),
+                               sub.astype(np.float64), cols.size, discount).reshape(m, cols.size)
+    assert np.all(np.isfinite(want)), "oracle returns are not finite: lower the weight scale of this shape"
+    return want
+
+
 @pytest.mark.parametrize("seed", range(max(10, _EXTRA)))
 def test_random_recurrent_stacks_matrix_core_matches_valu(seed):
     """GRU / BasicRNN / LSTM stacks of odd widths (units that are no multiple of 16 or of 4, inputs that straddle k-groups,
     action vectors wider than the prefetch registers): the matrix-core kernel (l2a_rnn_mfma.h) against the VALU kernel
-    (l2a_rnn_valu.h) - every return, the arg-max keys' consistency, and the states `predict` writes."""
+    (l2a_rnn_valu.h) - every return, the arg-max keys' consistency, and the states `predict` writes; and both kernels' returns
+    against `OracleRNNStackDynamics` in float64 (a mistake the two share would cancel between them)."""
     rs = np.random.RandomState(900 + seed)
     cell = str(rs.choice(["gru", "lstm", "rnn"]))
     n_layers = int(rs.choice([1, 2, 3])) if cell != "lstm" else int(rs.choice([2, 3]))
@@ -169,9 +212,13 @@ def test_random_recurrent_stacks_matrix_core_matches_valu(seed):
     native.set_norm(norm)
     dev = native.device
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
-    obs0, acts = up(rs.randn(m, obs_dim)), up(rs.uniform(low, high, (h, m * n, act_dim)))
-    c0 = up(rs.randn(m, U) * (1.0 if cell == "lstm" else 0.0))
-    h0 = up(np.tanh(rs.randn(m, U)))
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    host_obs, host_acts = f32(rs.randn(m, obs_dim)), f32(rs.uniform(low, high, (h, m * n, act_dim)))
+    host_c = f32(rs.randn(m, U) * (1.0 if cell == "lstm" else 0.0))
+    host_h = f32(np.tanh(rs.randn(m, U)))
+    want = _stack_oracle_returns(obs_dim, act_dim, sizes, cell, act, params, norm, spec, host_obs, host_c, host_h, host_acts, m, n,
+                                 discount, np.arange(n))
+    obs0, acts, c0, h0 = up(host_obs), up(host_acts), up(host_c), up(host_h)
     ctx = _lib.Context.get(0)
     got = {}
     try:
@@ -186,6 +233,10 @@ def test_random_recurrent_stacks_matrix_core_matches_valu(seed):
         ctx.set_kernel("auto")
     (r_m, k_m, s_m), (r_v, k_v, s_v) = got["mfma"], got["valu"]
     _check(r_m, r_v, k_m, n, 3)
+    print("\n[stacks %d] %s %s: returns against the float64 oracle: mfma %.2e, valu %.2e of max(1, max |want|) (bar 1e-4)"
+          % (seed, cell, sizes, _err(r_m, want), _err(r_v, want)))
+    _check(r_m, want, k_m, n, 3)
+    _check(r_v, want, k_v, n, 3)
     for a, b in zip(s_m, s_v):
         np.testing.assert_allclose(a, b, rtol=2e-5, atol=2e-6)
     native.close()
@@ -196,7 +247,9 @@ def test_random_recurrent_micro_tile_shapes_match_valu(seed):
     """The micro-tile form of the generic recurrent kernel (csrc/l2a_rnn_micro.h; layers of 256 - GRU / BasicRNN also 512 - units)
     against the VALU kernel on random input shapes: observation / action widths that end anywhere in a 16-feature group - an ODD
     number of input groups takes the zero-padded one of the eight-deep operand ring -, 1 - 3 layers, every cell type and reward
-    family, plans of one micro tile up to several rounds of four-tile workgroups, ragged last tiles, discount."""
+    family, plans of one micro tile up to several rounds of four-tile workgroups, ragged last tiles, discount.  Both matrix-core
+    forms are also held to `OracleRNNStackDynamics` in float64 - above 12000 plan rows, where the VALU run is dropped and the two
+    would only be compared with each other, on 256 candidates of every env (`_oracle_columns`)."""
     rs = np.random.RandomState(1700 + seed)
     cell = str(rs.choice(["gru", "lstm", "rnn"]))
     U = 512 if (cell != "lstm" and rs.rand() < 0.25) else 256
@@ -220,9 +273,14 @@ def test_random_recurrent_micro_tile_shapes_match_valu(seed):
     native.set_norm(norm)
     dev = native.device
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
-    obs0, acts = up(rs.randn(m, obs_dim)), up(rs.uniform(low, high, (h, m * n, act_dim)))
-    c0 = up(rs.randn(m, W) * (1.0 if cell == "lstm" else 0.0))
-    h0 = up(np.tanh(rs.randn(m, W)))
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    host_obs, host_acts = f32(rs.randn(m, obs_dim)), f32(rs.uniform(low, high, (h, m * n, act_dim)))
+    host_c = f32(rs.randn(m, W) * (1.0 if cell == "lstm" else 0.0))
+    host_h = f32(np.tanh(rs.randn(m, W)))
+    cols = _oracle_columns(rs, m, n, h)
+    want = _stack_oracle_returns(obs_dim, act_dim, sizes, cell, act, params, norm, spec, host_obs, host_c, host_h, host_acts, m, n,
+                                 0.95, cols)
+    obs0, acts, c0, h0 = up(host_obs), up(host_acts), up(host_c), up(host_h)
     ctx = _lib.Context.get(0)
     got = {}
     try:
@@ -245,6 +303,10 @@ def test_random_recurrent_micro_tile_shapes_match_valu(seed):
     _check(got["micro"][0], got["tiles16"][0], got["micro"][1], n, 3)
     if "valu" in got:
         _check(got["micro"][0], got["valu"][0], got["micro"][1], n, 3)
+    errs = {name: _err(got[name][0][:, cols], want) for name in ("micro", "tiles16")}
+    print("\n[micro tiles %d] %s %s n=%d (%d of them rolled by the oracle): returns against the float64 oracle: micro %.2e, tiles16 %.2e "
+          "of max(1, max |want|) (bar 1e-4)" % (seed, cell, sizes, n, cols.size, errs["micro"], errs["tiles16"]))
+    assert errs["micro"] < 1e-4 and errs["tiles16"] < 1e-4
     native.close()
 
 

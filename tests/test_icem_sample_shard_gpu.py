@@ -3,21 +3,24 @@ same inputs: one rank of a sharded plan fetches, draws and clips ALL ``n_it`` ro
 bit the unsharded call's - and keeps the rollout tensor of its window ``[lo, hi)`` only, ``seq_local [h, m (hi - lo), A]``; kept rows
 and the mean row inside the window are rows like any other.  Every output starts from a sentinel and sits between guard words
 (``test_cem_kernels_gpu._Out``): ``seq_local`` is allocated at exactly ``h * m * (hi - lo) * A`` floats, so a store behind it trips
-the guard.  Bit equality throughout: the two calls run the same arithmetic."""
+the guard.  Bit equality throughout: the two calls run the same arithmetic.  The two calls are one kernel body, so with injected
+normals the unsharded call is also held to ``icem_reference.sample_f32`` (``test_icem_kernels_gpu.check_sample``), bit for bit."""
 
 import numpy as np
 import pytest
 
 from learning_to_adapt_amd import _lib
 from test_cem_kernels_gpu import _Out, _ull, _up
-from test_icem_kernels_gpu import NAN, SAMPLE_KEYS, _bits, run_sample, sample_inputs
+from test_icem_kernels_gpu import NAN, SAMPLE_KEYS, _bits, check_sample, run_sample, sample_inputs
 
 pytestmark = pytest.mark.gpu
 
 KK = 4
 # (n_it, m, h, A): 39 sample rows in workgroups of four - a partial last workgroup, three envs, one of them fresh | D = 32: four rows
-# per workgroup again, two envs that both hold kept rows
-SHAPES = [(13, 3, 5, 6), (40, 2, 4, 8)]
+# per workgroup again, two envs that both hold kept rows | D = 2080: one row per workgroup and two passes of the LDS tile (128 + 2
+# steps at A = 16) - seq_local is stored at step t0 + tt with the window's row index in the second one; n_it = 3 is below the inner
+# windows of ``windows``, so this shape gets its own
+SHAPES = [(13, 3, 5, 6), (40, 2, 4, 8), (3, 2, 130, 16)]
 KC = {3: [3, 4, 2], 2: [2, 4]}
 SHIFT = {3: [1, 0, -1], 2: [1, 0]}
 
@@ -25,6 +28,8 @@ SHIFT = {3: [1, 0, -1], 2: [1, 0]}
 def windows(n):
     """name -> [lo, hi): all rows, an inner window, one row, an empty window, kept rows only (hi <= kc of every running env), the
     window that holds the add_mean row."""
+    if n < 13:
+        return dict(full=(0, n), one=(1, 2), empty=(2, 2), kept=(0, 2), mean=(n - 1, n), tail=(1, n))
     return dict(full=(0, n), inner=(4, 9), one=(5, 6), empty=(7, 7), kept=(0, 2), mean=(n - 3, n))
 
 
@@ -72,6 +77,8 @@ def test_every_window_matches_the_unsharded_sample(shape, inject):
     inp = _inputs(shape, inject)
     full = run_sample(ctx, inp)
     assert not np.isnan(full["seq"]).any()
+    if inject:
+        check_sample(full, inp, True, "the unsharded call against the reference, n=%d m=%d h=%d ad=%d" % shape)
     seq_rows = full["seq"].reshape(h, m, n, ad)
     # the rows the windows are about are what they are named after: kept rows differ from drawn ones, the mean row is clip(mu')
     running = [i for i in range(m) if SHIFT[m][i] >= 0]

@@ -22,7 +22,8 @@ pytestmark = pytest.mark.gpu
 
 RTOL = 1e-4         # returns against the float64 oracle, |got - want| / max(1, |want|): the bar of tests/test_gpu_parity.py
 MODELS = {"mlp": dict(cases.CASES["hc_rs_m3_n64_h5"]),
-          "ens5": dict(cases.CASES["c2_hc_rs_n2000_h30_e5"], n=96, h=6)}        # the 5-member mean ensemble on a small plan
+          "ens5": dict(cases.CASES["c2_hc_rs_n2000_h30_e5"], n=96, h=6),        # the 5-member mean ensemble on a small plan
+          "long": dict(cases.CASES["hc_rs_m3_n64_h5"], h=90)}   # l2a_mppi_sample_k walks this horizon in two passes (85 + 5 at A = 6)
 
 
 def rel_err(got, want):
@@ -84,7 +85,7 @@ def _sample_bound(mean_shifted, z64, sigma, beta, h):
 
 
 # ------------------------------------------------------------------------------------------------- injected normals, one step
-@pytest.mark.parametrize("which", ["mlp", "ens5"])
+@pytest.mark.parametrize("which", ["mlp", "ens5", "long"])
 def test_single_step_with_injected_normals(which):
     case, ctrl = _controller(which)
     obs = _obs(which)
@@ -110,13 +111,11 @@ def test_single_step_with_injected_normals(which):
 
 
 # ----------------------------------------------------------------------------------------------------- three consecutive steps
-def test_three_steps_replayed_with_the_philox_normals():
-    """Step ``s`` draws at offset ``s n m D`` under ``torch.initial_seed()`` and samples around the previous step's mean moved on
-    one step."""
+def _replay_steps(which, steps):
     seed = 1234
     torch.manual_seed(seed)
-    case, ctrl = _controller("mlp", mppi_kappa=0.5)
-    obs = _obs("mlp")
+    case, ctrl = _controller(which, mppi_kappa=0.5)
+    obs = _obs(which)
     n, m, h = case["n"], case["m"], case["h"]
     ad = ctrl.action_space.shape[0]
     D = h * ad
@@ -124,7 +123,8 @@ def test_three_steps_replayed_with_the_philox_normals():
     low, high = ctrl.action_space.low.astype(np.float32), ctrl.action_space.high.astype(np.float32)
     mean = np.zeros((m, D), dtype=np.float32)
     rs = np.random.RandomState(0)
-    for s in range(3):
+    means = []
+    for s in range(steps):
         action, _ = ctrl.get_actions(obs)
         a_clip, seq = _samples(ctrl)
         z64 = mr.philox_normal(seed, mr.philox_indices(s * n * m * D, n * m * D)).reshape(n, m, D)
@@ -135,11 +135,34 @@ def test_three_steps_replayed_with_the_philox_normals():
         print("\n[mppi] step %d: sample error / bound %.3f" % (s, r))
         assert r <= 1.0, "step %d does not sample the shifted mean at offset %d" % (s, s * n * m * D)
         assert np.array_equal(_bits(seq), _bits(a_clip).reshape(-1)[mr.seq_index(n, m, h, ad)])
-        assert rel_err(ctrl.last_plan["returns"], _oracle_returns(case, obs, seq)) < RTOL
-        _check_update(ctrl, action, shifted.astype(np.float32), a_clip, 0.5, "step %d" % s)
+        err = rel_err(ctrl.last_plan["returns"], _oracle_returns(case, obs, seq))
+        print("[mppi] %s step %d: returns against the float64 oracle %.2e" % (which, s, err))
+        assert err < RTOL
+        _check_update(ctrl, action, shifted.astype(np.float32), a_clip, 0.5, "%s step %d" % (which, s))
         mean = ctrl.last_plan["mppi_mean"]
+        means.append(mean.copy())
         obs = obs + 0.01 * rs.randn(*obs.shape)
-    assert ctrl._bufs["mppi_calls"] == 3
+    assert ctrl._bufs["mppi_calls"] == steps
+    return means
+
+
+def test_three_steps_replayed_with_the_philox_normals():
+    """Step ``s`` draws at offset ``s n m D`` under ``torch.initial_seed()`` and samples around the previous step's mean moved on
+    one step."""
+    _replay_steps("mlp", 3)
+
+
+def test_two_steps_replayed_with_the_philox_normals_over_several_passes():
+    """The same at h = 90: step 1 samples around step 0's mean shifted ACROSS the pass boundary - the last step of the first pass
+    (t = 84) takes the mean of t = 85 -, draws its second pass at element index ``t0 * A`` onwards and hands the rollout a
+    candidate tensor stored in two passes; the update then refits a mean of 540 elements per env."""
+    case = MODELS["long"]
+    tc = 512 // 6
+    assert case["h"] > tc
+    mean = _replay_steps("long", 2)[0]
+    assert mean.shape == (case["m"], case["h"] * 6)
+    # the step-0 mean that step 1 shifted is not constant over the boundary: a clamp at the pass end would have shown
+    assert np.all(np.abs(mean[:, (tc - 1) * 6:tc * 6] - mean[:, tc * 6:(tc + 1) * 6]).max(axis=1) > 0)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ reset

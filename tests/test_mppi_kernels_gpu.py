@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import mppi_pass_cases as pc
 import mppi_reference as mr
 from learning_to_adapt_amd import _lib
 from test_cem_kernels_gpu import PHILOX_ATOL, Worst, _Out, _ull, _up, returns_pattern
@@ -158,6 +159,33 @@ def test_sample_with_injected_normals_bit_for_bit(h, ad, beta):
     assert on_low and on_high, "no sub-case put a sample on each bound"
 
 
+@pytest.mark.parametrize("h,ad", pc.SHAPES)
+def test_sample_over_a_horizon_of_several_passes(h, ad):
+    """The horizon goes through the LDS tiles in passes of ``512 // A`` steps; the filter state, the normal's element index, the
+    shifted mean's read ahead and the three stores all cross the pass boundary.  Every case of ``mppi_pass_cases.CASES`` at this
+    ``(h, A)`` - the table ``tests/test_mppi_pass_cases.py`` proves to reject a reset state, a clamp at the pass end and a dropped
+    ``t0 * A`` - with the table's own seeds: ``mean_out``, ``a_clip`` and ``seq`` equal ``sample_f32`` bit for bit."""
+    ctx = _lib.Context.get(0)
+    assert h > pc.PASS_STEPS(ad)
+    on_low = on_high = False
+    mine = [k for k, c in enumerate(pc.CASES) if (c[0], c[1]) == (h, ad)]
+    assert len(mine) == pc.PER_SHAPE
+    for k in mine:
+        _, _, n, m, shift, beta, zero_sigma, with_seq = pc.CASES[k]
+        inp = pc.inputs(k)
+        got = run_sample(ctx, inp, with_seq=with_seq)
+        want_mean, want_a, want_seq = mr.sample_f32(inp["mean"], inp["shift"], inp["z"], inp["sigma"], beta, inp["low"], inp["high"],
+                                                    n, m, h, ad)
+        what = "case %d: n=%d m=%d h=%d ad=%d beta=%g shift=%s zero_sigma=%s" % (k, n, m, h, ad, beta, shift, zero_sigma)
+        assert np.array_equal(_bits(got["mean_out"]), _bits(want_mean)), "mean_out: " + what
+        assert np.array_equal(_bits(got["a_clip"]), _bits(want_a)), "a_clip: " + what
+        if with_seq:
+            assert np.array_equal(_bits(got["seq"]), _bits(want_seq)), "seq: " + what
+        on_low = on_low or bool((want_a == np.tile(inp["low"], h)).any())
+        on_high = on_high or bool((want_a == np.tile(inp["high"], h)).any())
+    assert on_low and on_high, "no sub-case put a sample on each bound"
+
+
 # ---------------------------------------------------------------------------------------------------- sample with Philox normals
 @pytest.mark.parametrize("off", [0, (1 << 32) - 1000, (1 << 40) + 12345])
 def test_sample_with_philox_normals(off):
@@ -190,6 +218,46 @@ def test_sample_with_philox_normals(off):
                 halves.append(g2["a_clip"])
             assert np.array_equal(_bits(np.concatenate(halves)), _bits(got["a_clip"])), "two half launches differ from one: " + what
     worst.report("mppi Philox offset=%#x" % off)
+
+
+@pytest.mark.parametrize("off", [0, (1 << 32) - 1000, (1 << 40) + 12345])
+@pytest.mark.parametrize("n,m,h,ad", [(6, 2, 40, 16), (5, 3, 90, 6)])
+def test_sample_with_philox_normals_over_several_passes(n, m, h, ad, off):
+    """Two passes (32 + 8 steps at A = 16, 85 + 5 at A = 6): the Philox counter of an element picks up ``t0 * A`` in the second
+    one.  Against the float64 restatement fed the float64 Box-Muller normals under two seeds, within the bound of
+    ``test_sample_with_philox_normals``, which does not depend on ``h``: a step's normal is off by at most ``PHILOX_ATOL sigma_k``
+    and the filter's weights ``beta (1 - beta)^(t - s)`` sum to at most 1, so that term does not grow; the recurrence
+    ``nz = beta u + (1 - beta) nz`` rounds three times per step (``|nz| <= U``), and the roundings of earlier steps are damped by
+    ``1 - beta`` per step - a geometric sum of at most ``2 2^-24 U / beta``; the last add and ``mu'`` itself take the rest.  Two
+    launches over the candidates' halves equal one launch, bit for bit."""
+    ctx = _lib.Context.get(0)
+    worst = Worst()
+    D = h * ad
+    assert h > pc.PASS_STEPS(ad)
+    shift = [1, 0, -1][:m]
+    for seed in (0x5EED0000ABCD1234, 1):
+        for beta in (0.6, 1.0):
+            rs = np.random.RandomState(7)
+            inp = sample_inputs(rs, n, m, h, ad, beta, shift, inject=False, zero_sigma=3, seed=seed, off=off)
+            got = run_sample(ctx, inp)
+            what = "n=%d m=%d h=%d ad=%d seed=%#x offset=%#x beta=%g" % (n, m, h, ad, seed, off, beta)
+            z = mr.philox_normal(seed, mr.philox_indices(off, n * m * D)).reshape(n, m, D)
+            want_mean, want_a, want_seq = mr.sample(inp["mean"], inp["shift"], z, inp["sigma"], beta, inp["low"], inp["high"], n, m, h, ad)
+            assert np.array_equal(got["mean_out"].astype(np.float64), want_mean), what
+            sig = np.tile(inp["sigma"].astype(np.float64), h)
+            U = float(np.max(np.abs(z * sig)))
+            bound = PHILOX_ATOL * sig[None, None] + 4 * 2.0 ** -24 * (np.abs(want_mean)[None] + U / float(np.float32(beta)))
+            r = worst.note("a_clip", np.abs(got["a_clip"].astype(np.float64) - want_a), np.broadcast_to(bound, want_a.shape))
+            assert r <= 1.0, "a_clip off by %.3f of its bound: %s" % (r, what)
+            assert np.array_equal(_bits(got["seq"]), _bits(got["a_clip"]).reshape(-1)[mr.seq_index(n, m, h, ad)]), what
+            halves = []
+            for lo, hi in ((0, n // 2), (n // 2, n)):           # offsets advance by rows
+                half = dict(inp, n=hi - lo, off=off + lo * m * D)
+                g2 = run_sample(ctx, half)
+                assert np.array_equal(_bits(g2["mean_out"]), _bits(got["mean_out"])), what
+                halves.append(g2["a_clip"])
+            assert np.array_equal(_bits(np.concatenate(halves)), _bits(got["a_clip"])), "two half launches differ from one: " + what
+    worst.report("mppi Philox several passes n=%d m=%d h=%d ad=%d offset=%#x" % (n, m, h, ad, off))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ update

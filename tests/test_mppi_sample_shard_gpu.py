@@ -1,11 +1,14 @@
 """``l2a_mppi_sample_shard`` (``csrc/l2a_mppi.hip``: the SHARD instance of ``l2a_mppi_sample_k``) against ``l2a_mppi_sample`` on the
 same inputs: one rank of a sharded plan samples ALL candidates - ``a_clip`` and ``mean_out`` bit for bit the unsharded call's - and
 keeps the rollout tensor of its window ``[lo, hi)`` only, ``seq_local [h, m (hi - lo), A]``.  Every output starts from a sentinel
-and sits between guard words (``test_cem_kernels_gpu._Out``).  Bit equality throughout: the two calls run the same arithmetic."""
+and sits between guard words (``test_cem_kernels_gpu._Out``).  Bit equality throughout: the two calls run the same arithmetic.
+The two calls are one kernel body, so with injected normals both are also held to ``mppi_reference.sample_f32``, bit for bit - a
+mistake they share would cancel in the comparison above."""
 
 import numpy as np
 import pytest
 
+import mppi_reference as mr
 from learning_to_adapt_amd import _lib
 from test_cem_kernels_gpu import _Out, _ull, _up
 from test_mppi_kernels_gpu import NAN, _bits, run_sample, sample_inputs
@@ -13,8 +16,9 @@ from test_mppi_kernels_gpu import NAN, _bits, run_sample, sample_inputs
 pytestmark = pytest.mark.gpu
 
 # (n, m, h, A, world): 26 rows - a partial last workgroup - in uneven shards | two passes of the LDS tile (32 steps per pass at
-# A = 16) and an empty shard (8 ranks, 7 candidates) | more than one workgroup per candidate row group, three envs
-SHAPES = [(13, 2, 5, 3, 3), (7, 1, 40, 16, 8), (96, 3, 6, 6, 4)]
+# A = 16) and an empty shard (8 ranks, 7 candidates) | more than one workgroup per candidate row group, three envs | three passes
+# (32 + 32 + 6), three envs with the three shifts, windows of 2 and 3 | two passes at A = 6 (85 + 1), windows of 2, 2, 2 and 3
+SHAPES = [(13, 2, 5, 3, 3), (7, 1, 40, 16, 8), (96, 3, 6, 6, 4), (5, 3, 70, 16, 2), (9, 2, 86, 6, 4)]
 
 
 def _window(n, rank, world):
@@ -61,6 +65,13 @@ def test_every_rank_matches_the_unsharded_sample(shape, inject):
     full = run_sample(ctx, inp)
     assert not np.isnan(full["seq"]).any()
     seq_rows = full["seq"].reshape(h, m, n, ad)
+    if inject:
+        want_mean, want_a, want_seq = mr.sample_f32(inp["mean"], inp["shift"], inp["z"], inp["sigma"], inp["beta"], inp["low"],
+                                                    inp["high"], n, m, h, ad)
+        assert np.array_equal(_bits(full["mean_out"]), _bits(want_mean)), "mean_out against the reference"
+        assert np.array_equal(_bits(full["a_clip"]), _bits(want_a)), "a_clip against the reference"
+        assert np.array_equal(_bits(full["seq"]), _bits(want_seq)), "seq against the reference"
+        ref_rows = want_seq.reshape(h, m, n, ad)
     widths = []
     for rank in range(world):
         lo, hi = _window(n, rank, world)
@@ -74,6 +85,9 @@ def test_every_rank_matches_the_unsharded_sample(shape, inject):
         # plan row i * (hi - lo) + (j - lo) of every step t holds row i * n + j of the full tensor
         want = np.ascontiguousarray(seq_rows[:, :, lo:hi, :]).reshape(h, m * (hi - lo), ad)
         assert np.array_equal(_bits(got["seq"]), _bits(want)), (rank, lo, hi)
+        if inject:
+            want = np.ascontiguousarray(ref_rows[:, :, lo:hi, :]).reshape(h, m * (hi - lo), ad)
+            assert np.array_equal(_bits(got["seq"]), _bits(want)), ("seq_local against the reference", rank, lo, hi)
     assert sum(widths) == n
     if world == 3:
         assert len(set(widths)) > 1                                     # uneven shards

@@ -62,6 +62,20 @@ def test_three_consecutive_steps_equal_the_python_loop(which, iters, ctx):
         assert bits(got[0]["rets"][0]) != bits(got[0]["rets"][1])
 
 
+def test_two_consecutive_steps_over_several_passes_equal_the_python_loop(ctx):
+    """h = 90 at A = 6: ``l2a_mppi_sample_k`` walks the horizon in two passes (85 + 5 steps); step 1 samples around step 0's mean
+    shifted across the pass boundary, and the update refits 540 elements per env."""
+    setup = Setup("long", mppi_kappa=0.5)
+    assert setup.h == 90 and setup.h > 512 // 6
+    want = setup.python_steps(1234, 2)
+    got = _c_steps(setup, 1234, 2)
+    assert bits(want[0]["plan"]["mppi_mean"]) != bits(want[1]["plan"]["mppi_mean"])
+    for k in range(2):
+        assert got[k]["rc"] == _lib.L2A_OK and got[k]["rets"].shape == (1, setup.m, setup.n)
+        same_step(got[k], want[k], "long, step %d" % k)
+        assert got[k]["stats"]["steps"] == k + 1 and got[k]["stats"]["relaunches"] == 0
+
+
 def test_reset_of_one_env_between_two_steps(ctx):
     """Env 1 is reset in front of step 2 on both sides: its plan starts from zeros, the others move on one step."""
     setup = Setup("mlp")

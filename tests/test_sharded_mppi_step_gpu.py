@@ -23,7 +23,7 @@ import cases
 from learning_to_adapt_amd import _lib
 from learning_to_adapt_amd.policies.mpc_controller import MPCController
 from loopback_world import LoopbackWorld
-from mppi_step_cases import Setup, bits, restore_context, same_snapshot
+from mppi_step_cases import Setup, bits, restore_context, same_snapshot, same_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DIGEST_MASK = 0x7FFFFFFFFFFF
@@ -150,6 +150,24 @@ def test_every_rank_equals_the_unsharded_step_over_two_steps(world_size, n, ctx)
         for k in range(2):
             assert out[k]["rc"] == _lib.L2A_OK, (rank, k)
             same_snapshot(out[k], wants[k], "rank %d, step %d" % (rank, k))
+        assert out[1]["stats"]["steps"] == 2 and out[1]["stats"]["relaunches"] == 0 and not out[1]["degraded"]
+
+
+def test_two_ranks_over_several_passes_equal_the_python_loop_over_two_steps(ctx):
+    """h = 90 at A = 6: the SHARD instance of ``l2a_mppi_sample_k`` stores ``seq_local`` of its window in two passes (85 + 5
+    steps, the second at step ``t0 + tt`` with the window's row index), and step 1 samples around a mean shifted across the pass
+    boundary.  Both loopback ranks against ONE process's Python loop under the same seed, bit for bit."""
+    setup = Setup("long", mppi_kappa=0.5)
+    assert setup.h == 90 and setup.h > 512 // 6
+    want = setup.python_steps(31, 2)
+    assert bits(want[0]["plan"]["mppi_mean"]) != bits(want[1]["plan"]["mppi_mean"])
+    world, outs = _run_world(ctx, setup, 2, 31)
+    assert world.passes == 3 and world.calls == [2, 2]
+    _assert_collectives(world, setup.m, setup.n, 2, [w["plan"]["returns"] for w in want])
+    for rank, out in enumerate(outs):
+        for k in range(2):
+            assert out[k]["rc"] == _lib.L2A_OK, (rank, k)
+            same_step(out[k], want[k], "long, rank %d, step %d" % (rank, k))
         assert out[1]["stats"]["steps"] == 2 and out[1]["stats"]["relaunches"] == 0 and not out[1]["degraded"]
 
 
