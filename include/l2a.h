@@ -25,6 +25,7 @@ typedef struct l2a_ctx l2a_ctx;
 typedef struct l2a_model l2a_model;
 typedef struct l2a_lstm l2a_lstm;
 typedef struct l2a_reward_model l2a_reward_model;
+typedef struct l2a_value_model l2a_value_model;
 typedef struct l2a_controller l2a_controller;
 
 /* ---- error codes --------------------------------------------------------------------- */
@@ -358,6 +359,73 @@ int l2a_score_trajectory_model(l2a_reward_model* rm, const float* obs0, const fl
 int l2a_plan_rs_reward_model(l2a_model* model, l2a_reward_model* rm, const float* obs0, const float* actions, int m, int n,
                              int h, double discount, int cand_offset, float* returns_out, unsigned long long* best_key,
                              float* traj_out, void* stream);
+
+/* ---- plans with a learned terminal value --------------------------------------------------------
+ * A planner stops counting reward at the last horizon step; a learned value of the last predicted state added to the return
+ * is the usual remedy for a short horizon (POLO, Lowrey et al. 2019; TD-MPC, Hansen et al. 2022).  Not in the reference: the
+ * semantics are build-defined.  The value is an MLP of the observation, evaluated on the matrix cores (csrc/l2a_value.hip).
+ * Per row (one candidate's state after the last horizon step), all in fp32, round to nearest, nothing contracted outside the
+ * MFMAs:
+ *   x  = (s_h - mean_obs) * inv_obs, inv_obs = fp32(1 / (std_obs + 1e-10)); obs_dim features
+ *   z  = MLP(x): n_hidden = 1 .. 3 hidden layers with `hidden_act` (L2A_ACT_*), a linear scalar output layer
+ *   v  = z * fp32(std_v + 1e-10) + fp32(mean_v); v = NaN when any value of the row's state is not finite
+ *   w  = fp32(value_coef * d_h), d_h = discount ** h carried in float64 by h repeated multiplications from 1.0 (the rollout's
+ *        own recurrence), multiplied by the float64 value_coef and rounded to fp32 ONCE
+ *   R' = R + w * v, a separate multiply and add; w == 0 leaves R' = R bit for bit (v is not looked at)
+ * Keys over R' are packed as l2a_plan_rs packs them (index cand_offset + j, the lowest index wins ties, NaN sorts highest);
+ * best_key is zeroed on `stream` before the launch and every workgroup makes one integer atomicMax per env it touches - no
+ * float atomics.  A row's value bits depend on that row's state only - not on m, n, cand_offset, the shard, the row's place in
+ * a tile or the launch geometry.  Non-finite values follow IEEE through the formula; the planners' rules then apply unchanged.
+ *
+ * l2a_value_model_check: host only, needs no GPU.  L2A_EINVAL - with a message through l2a_last_error(NULL) - unless
+ * 1 <= obs_dim <= 64, 1 <= n_hidden <= 3, every hidden width a multiple of 64 up to 512 and hidden_act one of L2A_ACT_*.
+ * l2a_value_model_create calls it first; a new model has identity statistics.
+ * l2a_value_model_geometry: host only, needs no GPU - the launcher's decision (its own function, on plain integers) for `rows`
+ * states on a device of `num_cu` CUs (<= 0: 256) and `lds_per_block` bytes of LDS per workgroup: the smallest RT in 1 | 2 | 4 | 8
+ * row tiles of 16 rows per workgroup that leaves at most `num_cu` workgroups, capped by the accumulators (RT * widest / 64
+ * <= 32) and the LDS image (RT * max(ceil(obs_dim / 16), widest / 16) KiB + 4 KiB).  out[8] = { RT, workgroups =
+ * ceil(rows / (16 RT)), dynamic LDS bytes, 0 .. }.  L2A_EINVAL for a NULL out, rows < 1, a model l2a_value_model_check
+ * refuses, or an LDS size that no RT fits.  Any RT gives the same bits.
+ * l2a_value_model_set_weights: fp32 DEVICE arrays { hidden_0/kernel [obs_dim, h0], hidden_0/bias [h0], ..., output/kernel
+ * [hL, 1], output/bias [1] }, kernels row-major [in, out]; re-packed on `stream`.
+ * l2a_value_model_set_norm: float64 HOST vectors mean_obs / std_obs [obs_dim], mean_v / std_v (one value each); all four
+ * NULL = identity.
+ * l2a_value_model_predict: states [rows, obs_dim] -> values_out [rows] (device fp32), the same kernel without the fold.
+ * l2a_value_terminal: the kernel alone.  final_state [m*n, obs_dim], returns_in [m, n] -> returns_out [m, n] (or NULL;
+ * returns_out == returns_in is allowed: the work is row-local) and best_key [m] (or NULL).  L2A_EINVAL, nothing launched and
+ * no output touched: a NULL final_state / returns_in, both outputs NULL, m, n or h < 1, a non-finite value_coef or discount,
+ * m * n > 2^30 - 1, cand_offset < 0 or cand_offset + n > 2^31 - 1.
+ *
+ * The plan steps - all stream-ordered, no host synchronisation unless a model-owned buffer grows (freed with the model); `vm`
+ * and `model` must live on the same context and agree on obs_dim (L2A_EINVAL); a flagged tile-split launch flags the call
+ * (l2a_launch_status); arguments otherwise as the entry each one extends:
+ * l2a_plan_rs_value: ONE rollout launch as l2a_plan_rs_chunk makes it (t0 = 0, h_chunk = h, state_out into the model's own
+ * buffer, no keys), then l2a_value_terminal.  The rollout kernels and their launch decisions are untouched: a state-writing
+ * request takes the geometry it takes today (micro tiles decline it).
+ * l2a_plan_rs_program_value / l2a_plan_rs_reward_model_value: l2a_plan_rs_program / l2a_plan_rs_reward_model with the keys
+ * not requested, then l2a_value_terminal on traj[h - 1].                                                                  */
+int l2a_value_model_check(int obs_dim, int n_hidden, const int* hidden, int hidden_act);
+int l2a_value_model_geometry(int obs_dim, int n_hidden, const int* hidden, long long rows, int num_cu, int lds_per_block,
+                             int* out);
+int l2a_value_model_create(l2a_ctx* ctx, int obs_dim, int n_hidden, const int* hidden, int hidden_act, l2a_value_model** out);
+void l2a_value_model_destroy(l2a_value_model* vm);
+int l2a_value_model_set_weights(l2a_value_model* vm, const void* const* device_ptrs, void* stream);
+int l2a_value_model_set_norm(l2a_value_model* vm, const double* mean_obs, const double* std_obs, const double* mean_v,
+                             const double* std_v, void* stream);
+int l2a_value_model_predict(l2a_value_model* vm, const float* states, int rows, float* values_out, void* stream);
+int l2a_value_terminal(l2a_value_model* vm, const float* final_state, const float* returns_in, int m, int n, int h,
+                       double discount, double value_coef, int cand_offset, float* returns_out, unsigned long long* best_key,
+                       void* stream);
+int l2a_plan_rs_value(l2a_model* model, l2a_value_model* vm, const float* obs0, const float* actions, int m, int n, int h,
+                      double discount, const l2a_reward* reward, double value_coef, int cand_offset, float* returns_out,
+                      unsigned long long* best_key, void* stream);
+int l2a_plan_rs_program_value(l2a_model* model, l2a_value_model* vm, const float* obs0, const float* actions, int m, int n,
+                              int h, double discount, const l2a_reward_program* program, double value_coef, int cand_offset,
+                              float* returns_out, unsigned long long* best_key, float* traj_out, void* stream);
+int l2a_plan_rs_reward_model_value(l2a_model* model, l2a_reward_model* rm, l2a_value_model* vm, const float* obs0,
+                                   const float* actions, int m, int n, int h, double discount, double value_coef,
+                                   int cand_offset, float* returns_out, unsigned long long* best_key, float* traj_out,
+                                   void* stream);
 
 /* ---- the MLP planner's trajectory rollout -------------------------------------------------------
  * What l2a_plan_rs_program and l2a_plan_rs_reward_model put in front of their scoring launch, and the MLP counterpart of

@@ -50,6 +50,9 @@ EXPORTED_SYMBOLS = (
     "l2a_lstm_predict", "l2a_lstm_advance", "l2a_lstm_mfma_eligible",
     "l2a_lstm_rollout_traj", "l2a_lstm_plan_rs_program", "l2a_lstm_plan_rs_reward_model", "l2a_lstm_traj_geometry", "l2a_lstm_plan_geometry",
     "l2a_rollout_traj", "l2a_mlp_traj_geometry",
+    "l2a_value_model_check", "l2a_value_model_geometry", "l2a_value_model_create", "l2a_value_model_destroy", "l2a_value_model_set_weights",
+    "l2a_value_model_set_norm", "l2a_value_model_predict", "l2a_value_terminal", "l2a_plan_rs_value", "l2a_plan_rs_program_value",
+    "l2a_plan_rs_reward_model_value",
     "l2a_particle_score", "l2a_plan_rs_particles", "l2a_plan_rs_particles_program", "l2a_plan_rs_particles_reward_model",
     "l2a_particle_perm", "l2a_particle_shuffle", "l2a_plan_rs_particles_ts1",
     "l2a_particle_step", "l2a_plan_rs_particles_ts1_program", "l2a_plan_rs_particles_ts1_reward_model",
@@ -163,6 +166,30 @@ def reward_model_geometry(obs_dim, act_dim, hidden, rows, h, cus=0, lds_per_bloc
     return dict(RT=v[0], CT=v[1], S=v[2], workgroups=v[3], passes=v[4], lds_bytes=v[5])
 
 
+def value_model_check(obs_dim, hidden, hidden_act):
+    """``l2a_value_model_check`` (host only, no GPU): ``None`` when the terminal-value kernel takes this network, else the
+    library's reason.  ``hidden_act``: a nonlinearity name (``ACT_CODES``) or an integer code."""
+    lib = load()
+    hid = (ctypes.c_int * max(len(hidden), 1))(*[int(x) for x in hidden])
+    code = hidden_act if isinstance(hidden_act, int) else ACT_CODES.get(hidden_act, -1)
+    rc = lib.l2a_value_model_check(int(obs_dim), len(hidden), hid, int(code))
+    return None if rc == L2A_OK else lib.l2a_last_error(None).decode()
+
+
+def value_model_geometry(obs_dim, hidden, rows, cus=0, lds_per_block=160 * 1024):
+    """The launch geometry of the terminal-value kernel (``l2a_value_model_geometry``: the launcher's own decision function, no
+    GPU needed) for ``rows`` states on ``cus`` CUs (0: 256) with ``lds_per_block`` bytes of LDS.  Returns a dict: RT (row tiles
+    of 16 rows per workgroup), workgroups, lds_bytes."""
+    lib = load()
+    hid = (ctypes.c_int * max(len(hidden), 1))(*[int(x) for x in hidden])
+    out = (ctypes.c_int * 8)()
+    rc = lib.l2a_value_model_geometry(int(obs_dim), len(hidden), hid, int(rows), int(cus), int(lds_per_block), out)
+    if rc != L2A_OK:
+        raise L2AError("l2a_value_model_geometry failed (%d): %s" % (rc, lib.l2a_last_error(None).decode()))
+    v = list(out)
+    return dict(RT=v[0], workgroups=v[1], lds_bytes=v[2])
+
+
 _lib = None
 
 
@@ -261,6 +288,30 @@ def load():
     lib.l2a_score_trajectory.restype = i32
     lib.l2a_plan_rs_program.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), i32, vp, vp, vp, vp]
     lib.l2a_plan_rs_program.restype = i32
+    if hasattr(lib, "l2a_value_model_create"):          # (absent from older variant libraries selected with L2A_LIB_PATH)
+        dbl = c.c_double
+        lib.l2a_value_model_check.argtypes = [i32, i32, c.POINTER(i32), i32]
+        lib.l2a_value_model_check.restype = i32
+        lib.l2a_value_model_geometry.argtypes = [i32, i32, c.POINTER(i32), c.c_longlong, i32, i32, c.POINTER(i32)]
+        lib.l2a_value_model_geometry.restype = i32
+        lib.l2a_value_model_create.argtypes = [vp, i32, i32, c.POINTER(i32), i32, c.POINTER(vp)]
+        lib.l2a_value_model_create.restype = i32
+        lib.l2a_value_model_destroy.argtypes = [vp]
+        lib.l2a_value_model_destroy.restype = None
+        lib.l2a_value_model_set_weights.argtypes = [vp, c.POINTER(vp), vp]
+        lib.l2a_value_model_set_weights.restype = i32
+        lib.l2a_value_model_set_norm.argtypes = [vp, dp, dp, dp, dp, vp]
+        lib.l2a_value_model_set_norm.restype = i32
+        lib.l2a_value_model_predict.argtypes = [vp, vp, i32, vp, vp]
+        lib.l2a_value_model_predict.restype = i32
+        lib.l2a_value_terminal.argtypes = [vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp]
+        lib.l2a_value_terminal.restype = i32
+        lib.l2a_plan_rs_value.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, c.POINTER(RewardSpec), dbl, i32, vp, vp, vp]
+        lib.l2a_plan_rs_value.restype = i32
+        lib.l2a_plan_rs_program_value.argtypes = [vp, vp, vp, vp, i32, i32, i32, dbl, c.POINTER(RewardProgram), dbl, i32, vp, vp, vp, vp]
+        lib.l2a_plan_rs_program_value.restype = i32
+        lib.l2a_plan_rs_reward_model_value.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, vp]
+        lib.l2a_plan_rs_reward_model_value.restype = i32
     if hasattr(lib, "l2a_reward_model_create"):         # (absent from older variant libraries selected with L2A_LIB_PATH)
         lib.l2a_reward_model_check.argtypes = [i32, i32, i32, c.POINTER(i32), i32]
         lib.l2a_reward_model_check.restype = i32

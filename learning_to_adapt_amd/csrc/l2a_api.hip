@@ -63,6 +63,8 @@ struct l2a_model : l2a_mlp_shape {
     long long adapt_scratch_floats = 0;
     float* prog_buf = nullptr;                    // l2a_plan_rs_program: [returns of the carry launches (rows) | trajectory (h x rows x obs_dim)]
     long long prog_buf_floats = 0;
+    float* value_buf = nullptr;                   // l2a_plan_rs_value and its siblings: [last states (rows x obs_dim) | returns before the fold (rows)]
+    long long value_buf_floats = 0;
     float* part_buf = nullptr;                    // l2a_plan_rs_particles: [obs_x (m E obs_dim) | act_x (h m E n act_dim) | member returns (m E n)]
     long long part_buf_floats = 0;
     // l2a_model_adapt_sgd_host: two staging slots (host-mapped, read by the kernels directly)
@@ -892,6 +894,7 @@ void l2a_model_destroy(l2a_model* md) {
     if (md->adapt_scratch) (void)hipFree(md->adapt_scratch);
     if (md->prog_buf) (void)hipFree(md->prog_buf);
     if (md->part_buf) (void)hipFree(md->part_buf);
+    if (md->value_buf) (void)hipFree(md->value_buf);
     for (auto& sl : md->aslot) {
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.stage_host) (void)hipHostFree(sl.stage_host);
@@ -1592,6 +1595,106 @@ int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* o
     const int rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
     if (rc != L2A_OK) return rc;
     return l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, returns_out, best_key, stream_v);
+}
+
+// ---- plans with a learned terminal value (l2a_value.hip) --------------------------------------------------------------------
+// The checks the three entries share, made before the model's buffer is grown and before the first launch, and the buffer:
+// [last states (rows x obs_dim) | returns before the fold (rows)], grown on demand (which synchronises the stream).
+static int value_plan_begin(l2a_model* md, l2a_value_model* vm, const char* who_c, const float* obs0, const float* actions, int m, int n,
+                            int h, double discount, double value_coef, int cand_offset, const float* returns_out,
+                            const unsigned long long* best_key, hipStream_t stream) {
+    l2a_ctx* ctx = md->ctx;
+    const std::string who(who_c);
+    if (!vm) return fail(ctx, L2A_EINVAL, who + ": null value model");
+    l2a_ctx* vm_ctx = nullptr;
+    int vm_obs = 0;
+    l2a_value_model_facts(vm, &vm_ctx, &vm_obs);
+    if (vm_ctx != ctx) return fail(ctx, L2A_EINVAL, who + ": the value model lives on another context");
+    if (vm_obs != md->obs_dim)
+        return fail(ctx, L2A_EINVAL, who + ": the value model is for obs_dim " + std::to_string(vm_obs) + ", the dynamics model for " +
+                    std::to_string(md->obs_dim));
+    if (!obs0 || !actions) return fail(ctx, L2A_EINVAL, who + ": null obs0/actions");
+    if (!best_key && !returns_out) return fail(ctx, L2A_EINVAL, who + ": nothing to write (best_key and returns_out are null)");
+    if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, who + ": m, n and h must be >= 1");
+    if (!std::isfinite(discount) || !std::isfinite(value_coef))
+        return fail(ctx, L2A_EINVAL, who + ": discount and value_coef must be finite");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, who + ": too many candidates");
+    const long long rows = (long long)m * n, need = rows * md->obs_dim + rows;
+    if (need > md->value_buf_floats) {
+        l2a_device_guard guard(ctx->device);
+        if (md->value_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->value_buf)); md->value_buf = nullptr; md->value_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->value_buf), (size_t)need * sizeof(float)));
+        md->value_buf_floats = need;
+    }
+    return L2A_OK;
+}
+
+// The fused rollout with a terminal value: ONE rollout launch that hands out every candidate's last state, then the fold.
+int l2a_plan_rs_value(l2a_model* md, l2a_value_model* vm, const float* obs0, const float* actions, int m, int n, int h,
+                      double discount, const l2a_reward* reward, double value_coef, int cand_offset, float* returns_out,
+                      unsigned long long* best_key, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    if (!reward) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_value: null reward");
+    int rc = value_plan_begin(md, vm, "l2a_plan_rs_value", obs0, actions, m, n, h, discount, value_coef, cand_offset, returns_out,
+                              best_key, reinterpret_cast<hipStream_t>(stream_v));
+    if (rc != L2A_OK) return rc;
+    float* state = md->value_buf;
+    float* R = returns_out ? returns_out : md->value_buf + (long long)m * n * md->obs_dim;
+    rc = plan_rs_chunk_as(md, md->mode, obs0, 0, actions, m, n, h, 0, discount, reward, cand_offset, nullptr, R, state, nullptr, stream_v);
+    if (rc != L2A_OK) return rc;
+    return l2a_value_terminal(vm, state, R, m, n, h, discount, value_coef, cand_offset, returns_out, best_key, stream_v);
+}
+
+int l2a_plan_rs_program_value(l2a_model* md, l2a_value_model* vm, const float* obs0, const float* actions, int m, int n, int h,
+                              double discount, const l2a_reward_program* program, double value_coef, int cand_offset,
+                              float* returns_out, unsigned long long* best_key, float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    int rc = l2a_reward_program_check(program, md->obs_dim, md->act_dim);
+    if (rc != L2A_OK) return fail(ctx, rc, l2a_last_error(nullptr));
+    rc = value_plan_begin(md, vm, "l2a_plan_rs_program_value", obs0, actions, m, n, h, discount, value_coef, cand_offset, returns_out,
+                          best_key, reinterpret_cast<hipStream_t>(stream_v));
+    if (rc != L2A_OK) return rc;
+    const long long rows = (long long)m * n;
+    float* R = returns_out ? returns_out : md->value_buf + rows * md->obs_dim;
+    float* traj = nullptr;
+    rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
+    rc = l2a_score_trajectory(ctx, obs0, traj, actions, m, n, h, md->obs_dim, md->act_dim, discount, program, cand_offset, R, nullptr,
+                              stream_v);
+    if (rc != L2A_OK) return rc;
+    return l2a_value_terminal(vm, traj + (long long)(h - 1) * rows * md->obs_dim, R, m, n, h, discount, value_coef, cand_offset,
+                              returns_out, best_key, stream_v);
+}
+
+int l2a_plan_rs_reward_model_value(l2a_model* md, l2a_reward_model* rm, l2a_value_model* vm, const float* obs0, const float* actions,
+                                   int m, int n, int h, double discount, double value_coef, int cand_offset, float* returns_out,
+                                   unsigned long long* best_key, float* traj_out, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    if (!rm) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model_value: null reward model");
+    l2a_ctx* rm_ctx = nullptr;
+    int rm_obs = 0, rm_act = 0;
+    l2a_reward_model_facts(rm, &rm_ctx, &rm_obs, &rm_act);
+    if (rm_ctx != ctx) return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model_value: the reward model lives on another context");
+    if (rm_obs != md->obs_dim || rm_act != md->act_dim)
+        return fail(ctx, L2A_EINVAL, "l2a_plan_rs_reward_model_value: the reward model is for obs_dim " + std::to_string(rm_obs) +
+                    " / act_dim " + std::to_string(rm_act) + ", the dynamics model for " + std::to_string(md->obs_dim) + " / " +
+                    std::to_string(md->act_dim));
+    int rc = value_plan_begin(md, vm, "l2a_plan_rs_reward_model_value", obs0, actions, m, n, h, discount, value_coef, cand_offset,
+                              returns_out, best_key, reinterpret_cast<hipStream_t>(stream_v));
+    if (rc != L2A_OK) return rc;
+    const long long rows = (long long)m * n;
+    float* R = returns_out ? returns_out : md->value_buf + rows * md->obs_dim;
+    float* traj = nullptr;
+    rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
+    rc = l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, R, nullptr, stream_v);
+    if (rc != L2A_OK) return rc;
+    return l2a_value_terminal(vm, traj + (long long)(h - 1) * rows * md->obs_dim, R, m, n, h, discount, value_coef, cand_offset,
+                              returns_out, best_key, stream_v);
 }
 
 // ---- particle plans of a mean ensemble (l2a_particles.hip) ------------------------------------------------------------------

@@ -181,6 +181,7 @@ extern "C" L2A_HIDDEN int l2a_lstm_advance_keys(l2a_lstm* md, const float* obs, 
 extern "C" L2A_HIDDEN void l2a_model_facts(const l2a_model* md, l2a_ctx** ctx, int* obs_dim, int* act_dim);
 extern "C" L2A_HIDDEN void l2a_lstm_facts(const l2a_lstm* md, l2a_ctx** ctx, int* obs_dim, int* act_dim, int* units);
 extern "C" L2A_HIDDEN void l2a_reward_model_facts(const l2a_reward_model* rm, l2a_ctx** ctx, int* obs_dim, int* act_dim);
+extern "C" L2A_HIDDEN void l2a_value_model_facts(const l2a_value_model* vm, l2a_ctx** ctx, int* obs_dim);
 // The expansion launch of a particle plan (l2a_particles.hip; arguments validated by the caller, l2a_api.hip): obs0 [m, O] and
 // actions [h, m n, A] -> obs_x [m, E, O] and act_x [m, h, E n, A], each env's per-block request contiguous.
 // l2a_particle_expand_check: host only - the launch's own size refusals (L2A_EINVAL) for a destination in the model's aligned buffer,

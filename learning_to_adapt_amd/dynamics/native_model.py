@@ -54,6 +54,7 @@ class NativeModel(object):
         self._keep = {}     # source tensors kept alive until the stream has consumed them
         self.program_plans = 0      # calls of plan_rs_program (diagnostics: which plan path a controller took)
         self.reward_model_plans = 0     # calls of plan_rs_reward_model
+        self.value_plans = 0        # calls of plan_rs_value
 
     def close(self):
         if getattr(self, "handle", None):
@@ -278,6 +279,48 @@ class NativeModel(object):
                                                float(discount), int(cand_offset), _ptr(returns_out), _ptr(best_key),
                                                _ptr(traj_out), _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_plan_rs_reward_model")
+
+    def plan_rs_value(self, obs0, actions, m, n, h, discount, reward, value_model, value_coef=1.0, cand_offset=0,
+                      returns_out=None, best_key=None, traj_out=None):
+        """Plan step with a learned terminal value: ``R' = R + value_coef * discount ** h * V(s_h)`` (include/l2a.h, "plans with
+        a learned terminal value").  ``reward``: a ``RewardSpec`` (``l2a_plan_rs_value``: the fused rollout hands out the last
+        states), a ``RewardProgram`` (``l2a_plan_rs_program_value``) or a ``NativeRewardModel``
+        (``l2a_plan_rs_reward_model_value``); ``value_model``: a ``NativeValueModel``.  Other arguments as ``plan_rs`` /
+        ``plan_rs_program`` (``traj_out`` only with the latter two)."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if traj_out is not None:
+            assert not isinstance(reward, RewardSpec), "the fused rollout writes no trajectory"
+            assert traj_out.is_cuda and traj_out.dtype == torch.float32 and traj_out.is_contiguous()
+            assert traj_out.numel() == h * m * n * self.obs_dim
+        assert isinstance(value_model, NativeValueModel)
+        self.value_plans += 1
+        head = (_ptr(obs0), _ptr(actions), int(m), int(n), int(h), float(discount))
+        outs = (int(cand_offset), _ptr(returns_out), _ptr(best_key))
+        stream = _stream_ptr(self.device)
+        if isinstance(reward, RewardSpec):
+            what = "l2a_plan_rs_value"
+            rc = self.lib.l2a_plan_rs_value(self.handle, value_model.handle, *(head + (ctypes.byref(reward), float(value_coef)) + outs +
+                                                                               (stream,)))
+        elif isinstance(reward, RewardProgram):
+            what = "l2a_plan_rs_program_value"
+            self.program_plans += 1
+            rc = self.lib.l2a_plan_rs_program_value(self.handle, value_model.handle, *(head + (ctypes.byref(reward), float(value_coef)) +
+                                                                                       outs + (_ptr(traj_out), stream)))
+        elif isinstance(reward, NativeRewardModel):
+            what = "l2a_plan_rs_reward_model_value"
+            self.reward_model_plans += 1
+            rc = self.lib.l2a_plan_rs_reward_model_value(self.handle, reward.handle, value_model.handle,
+                                                         *(head + (float(value_coef),) + outs + (_ptr(traj_out), stream)))
+        else:
+            raise _lib.L2AError("plans with a terminal value take a RewardSpec, a RewardProgram or a NativeRewardModel, not %s"
+                                % type(reward).__name__)
+        self.ctx.check(rc, what)
 
     def plan_rs_particles(self, obs0, actions, m, n, h, discount, reward, risk_coef=0.0, cand_offset=0, score_out=None,
                           spread_out=None, member_returns_out=None, best_key=None):
@@ -566,3 +609,100 @@ class NativeRewardModel(object):
                                                  float(discount), int(cand_offset), _ptr(returns_out), _ptr(best_key),
                                                  _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_score_trajectory_model")
+
+
+class NativeValueModel(object):
+    """Python handle on an ``l2a_value_model``: a value MLP over the observation that the planner adds, evaluated on every
+    candidate's last predicted state, to the returns on the matrix cores (``csrc/l2a_value.hip``).  Raises ``L2AError`` on any
+    failure."""
+
+    def __init__(self, obs_dim, hidden_sizes, hidden_act, device=None):
+        if not torch.cuda.is_available():
+            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the value kernel is HIP-only (there is no CPU fallback)")
+        if device is None:
+            device = torch.cuda.current_device()
+        self.ctx = _lib.Context.get(device)
+        self.lib = self.ctx.lib
+        self.device = torch.device("cuda", device)
+        self.obs_dim = int(obs_dim)
+        self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
+        if hidden_act not in _lib.ACT_CODES:
+            raise _lib.L2AError("nonlinearity %r is not supported by the HIP kernels" % (hidden_act,))
+        hid = (ctypes.c_int * len(self.hidden_sizes))(*self.hidden_sizes)
+        handle = ctypes.c_void_p()
+        rc = self.lib.l2a_value_model_create(self.ctx.handle, self.obs_dim, len(self.hidden_sizes), hid,
+                                             _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
+        self.ctx.check(rc, "l2a_value_model_create")
+        self.handle = handle
+        self._keep = {}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.l2a_value_model_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, params):
+        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]``; the first ``in`` is ``obs_dim``, the last ``out`` is 1."""
+        dev = []
+        for p in params:
+            t = torch.as_tensor(p) if not torch.is_tensor(p) else p
+            dev.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        sizes = (self.obs_dim,) + self.hidden_sizes + (1,)
+        assert len(dev) == 2 * (len(sizes) - 1), "expected %d parameter arrays" % (2 * (len(sizes) - 1))
+        for li in range(len(sizes) - 1):
+            assert tuple(dev[2 * li].shape) == (sizes[li], sizes[li + 1]), \
+                "kernel %d has shape %s, expected %s" % (li, tuple(dev[2 * li].shape), (sizes[li], sizes[li + 1]))
+            assert tuple(dev[2 * li + 1].shape) == (sizes[li + 1],)
+        ptrs = (ctypes.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
+        rc = self.lib.l2a_value_model_set_weights(self.handle, ptrs, _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_value_model_set_weights")
+        self._keep["w"] = dev
+
+    def set_norm(self, norm):
+        """``norm``: dict ``'obs' / 'value' -> (mean, std)`` (value: scalars), or ``None`` for identity."""
+        if norm is None:
+            null = ctypes.POINTER(ctypes.c_double)()
+            rc = self.lib.l2a_value_model_set_norm(self.handle, null, null, null, null, _stream_ptr(self.device))
+        else:
+            keep, args = [], []
+            for key in ("obs", "value"):
+                for j in (0, 1):
+                    arr, p = _dvec(np.reshape(norm[key][j], -1))
+                    expect = 1 if key == "value" else self.obs_dim
+                    assert arr.shape == (expect,), "normalization[%r] has shape %s" % (key, arr.shape)
+                    keep.append(arr)
+                    args.append(p)
+            rc = self.lib.l2a_value_model_set_norm(self.handle, *args, _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_value_model_set_norm")
+
+    def predict(self, states, out=None):
+        """fp32 CUDA ``[rows, obs_dim]`` -> fp32 CUDA ``[rows]``."""
+        assert states.is_cuda and states.dtype == torch.float32
+        rows = int(states.shape[0])
+        assert tuple(states.shape) == (rows, self.obs_dim)
+        if out is None:
+            out = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        rc = self.lib.l2a_value_model_predict(self.handle, _ptr(states.contiguous()), rows, _ptr(out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_value_model_predict")
+        return out
+
+    def terminal(self, final_state, returns_in, m, n, h, discount, value_coef=1.0, cand_offset=0, returns_out=None, best_key=None):
+        """The fold alone (``l2a_value_terminal``): ``final_state`` ``[m * n, obs_dim]`` and ``returns_in`` ``[m, n]`` fp32 CUDA
+        tensors -> ``returns_out`` (may be ``returns_in``) and / or ``best_key``."""
+        for t in (final_state, returns_in):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert final_state.numel() == m * n * self.obs_dim and returns_in.numel() == m * n
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        rc = self.lib.l2a_value_terminal(self.handle, _ptr(final_state), _ptr(returns_in), int(m), int(n), int(h), float(discount),
+                                         float(value_coef), int(cand_offset), _ptr(returns_out), _ptr(best_key),
+                                         _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_value_terminal")

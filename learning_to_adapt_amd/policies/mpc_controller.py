@@ -64,7 +64,11 @@ permutation, ``l2a_plan_rs_particles_ts1``; seeded by ``torch.initial_seed()`` u
 ``horizon * m`` permutation slots; one rank only, and the fused reward formula only unless the next keyword is set),
 ``ts1_step_rewards`` (off by default: ``particle_sampling="ts1"`` refuses an env with a ``RewardProgram`` and ``use_reward_model``
 at construction; on: such a plan takes every step's reward where the particles are dealt, ``l2a_plan_rs_particles_ts1_program`` /
-``_reward_model`` - random shooting, CEM, MPPI and iCEM alike; with a ``RewardSpec`` env the keyword changes nothing).
+``_reward_model`` - random shooting, CEM, MPPI and iCEM alike; with a ``RewardSpec`` env the keyword changes nothing),
+``value_model`` / ``terminal_value_coef`` (a learned terminal value, ``MLPValueModel``: every planner scores
+``R' = R + terminal_value_coef * discount ** h * V(s_h)``, the value of each candidate's last predicted state folded into returns and
+keys by one launch behind the rollout - ``l2a_plan_rs_value`` / ``_program_value`` / ``_reward_model_value``; no host fallback, not
+with ``ensemble_planning="particles"`` or an explicit C controller step, which raise at construction).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -126,8 +130,12 @@ class MPCController(Policy, Serializable):
             icem_beta=2.0,
             particle_sampling="tsinf",
             ts1_step_rewards=False,
+            value_model=None,
+            terminal_value_coef=1.0,
     ):
         self.dynamics_model = dynamics_model
+        self.value_model = value_model
+        self.terminal_value_coef = float(terminal_value_coef)
         self.reward_model = reward_model
         self.discount = discount
         self.n_candidates = n_candidates
@@ -228,6 +236,8 @@ class MPCController(Policy, Serializable):
                 (use_reward_model or isinstance(self._reward_spec, RewardProgram)):
             raise _lib.L2AError("particle_sampling='ts1' scores the fused reward formula only: a reward program or a reward model "
                                 "reads a step's two states from one trajectory row, which the shuffle between steps breaks")
+        if value_model is not None:
+            self._check_value_model()
         self._ts1_calls = 0         # `_rollout` calls under particle_sampling="ts1" since the seed below was first seen
         self._ts1_seed = None       # torch.initial_seed() the count belongs to: a changed seed restarts it
         self._bufs = {}
@@ -261,6 +271,31 @@ class MPCController(Policy, Serializable):
         if self.native_cem_step or self.native_mppi_step:
             raise _lib.L2AError("ensemble_planning='particles' plans through the Python loop: the C controller steps "
                                 "(native_cem_step, native_mppi_step) roll the mean ensemble out - leave them off")
+
+    def _check_value_model(self):
+        """``value_model=...``: the plan is scored on ``R' = R + terminal_value_coef * discount ** h * V(s_h)`` by a launch of its
+        own behind the rollout (``l2a_value_terminal``) - there is no host fallback, and the plan goes through ``_rollout``, which
+        the C controller steps bypass."""
+        vm = self.value_model
+        if not np.isfinite(self.terminal_value_coef):
+            raise ValueError("terminal_value_coef must be finite")
+        if not hasattr(vm, "planner_value_model"):
+            raise _lib.L2AError("value_model must be a value model the library evaluates on the GPU (MLPValueModel): there is no "
+                                "host fallback")
+        why = vm.native_eligible() if hasattr(vm, "native_eligible") else None
+        if why is not None:
+            raise _lib.L2AError("value_model is not eligible for the terminal-value kernel (there is no host fallback): %s" % why)
+        if self.ensemble_planning == "particles":
+            raise _lib.L2AError("ensemble_planning='particles' with a value_model is not built: a particle plan scores every "
+                                "member's rollout, the terminal value is folded into the mean ensemble's plan only")
+        if self.native_cem_step or self.native_mppi_step or self.native_icem_step:
+            raise _lib.L2AError("a value_model plans through the Python loop: the C controller steps (native_cem_step, "
+                                "native_mppi_step, native_icem_step) score the plain return - leave them off")
+        if self._reward_spec is None and self._native_reward_model() is None:
+            raise _lib.L2AError("a value_model needs a plan the library scores: an env reward it knows (a RewardSpec or a "
+                                "RewardProgram) or, with use_reward_model, a reward model it scores (MLPRewardModel)")
+        if not hasattr(self.dynamics_model, "planner_model"):
+            raise _lib.L2AError("a value_model needs a dynamics model with a native planner (MLPDynamicsModel)")
 
     # ------------------------------------------------------------------ reference API
     def get_action(self, observation):
@@ -425,9 +460,10 @@ class MPCController(Policy, Serializable):
         ``RewardProgram`` (``l2a_plan_rs_program``) or a native reward model stands in for it (``l2a_plan_rs_reward_model``) -
         through ``_rollout``, and every path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking
         launch, the horizon-chunked pipelines, the C controllers - declines.  A particle plan (``ensemble_planning="particles"``)
-        is scored behind its rollouts too, whatever its reward, and stays on ``_rollout`` the same way."""
+        is scored behind its rollouts too, whatever its reward, and stays on ``_rollout`` the same way; so does a plan with a
+        ``value_model``: its terminal value is folded in by a launch behind the rollout (``l2a_plan_rs_value`` and its siblings)."""
         return (self.ensemble_planning == "particles" or isinstance(self._reward_spec, RewardProgram)
-                or self._native_reward_model() is not None)
+                or self._native_reward_model() is not None or self.__dict__.get("value_model") is not None)
 
     def _buf(self, key, shape, dtype, device):
         t = self._bufs.get(key)
@@ -577,6 +613,13 @@ class MPCController(Policy, Serializable):
                                      cand_offset=cand_offset, score_out=rets, spread_out=spread, member_returns_out=members,
                                      best_key=best)
             self._particles = dict(members=members, spread=spread, score=rets, best=best, cand_offset=cand_offset)
+            return best, rets
+        if self.__dict__.get("value_model") is not None:
+            # R' = R + terminal_value_coef * discount ** h * V(s_h): one branch per reward kind, the planners see R' only
+            native.plan_rs_value(obs0, actions_local, m, n_local, self.horizon, self.discount,
+                                 rm.planner_reward_model() if rm is not None else self._reward_spec,
+                                 self.value_model.planner_value_model(), value_coef=self.terminal_value_coef,
+                                 cand_offset=cand_offset, returns_out=rets, best_key=best)
             return best, rets
         if rm is not None:
             native.plan_rs_reward_model(obs0, actions_local, m, n_local, self.horizon, self.discount, rm.planner_reward_model(),
