@@ -427,6 +427,76 @@ int l2a_plan_rs_reward_model_value(l2a_model* model, l2a_reward_model* rm, l2a_v
                                    int cand_offset, float* returns_out, unsigned long long* best_key, float* traj_out,
                                    void* stream);
 
+/* ---- plans on envs that terminate: termination programs ---------------------------------------------
+ * Hopper, Walker2d, gym's Ant and Humanoid end an episode when the state leaves a healthy range; PETS and MBPO carry a per-env
+ * termination function for that reason.  Not in the reference (its five envs never set `done`): the semantics are build-defined.
+ * A termination program is 1 .. 8 guards over the NEXT observation of a step.  Guard g = { index, len, lo, hi } holds iff every
+ * x in next_obs[index : index + len] satisfies lo <= x <= hi (a NaN is outside, as L2A_TERM_INRANGE has it; lo = -inf and
+ * hi = +inf are allowed).  A transition is terminal iff any guard fails.  Per candidate row, in fp32, round to nearest, nothing
+ * contracted, disc = discount ** t carried in float64 and rounded once per step exactly as l2a_score_trajectory does:
+ *   alive = true; R = 0; steps_alive = h
+ *   for t in 0 .. h-1, while alive:
+ *       R = R + fp32(disc) * r_t                        r_t: the reward program on (obs, act, next), or step_rewards[t][row]
+ *       if any guard fails on next_obs:
+ *           if terminal_reward != 0: R = R + fp32(disc) * terminal_reward         a separate multiply and add; skipped at 0
+ *           alive = false; steps_alive = t + 1
+ *   if alive and terminal_values given and w != 0: R = R + w * terminal_values[row]       w as l2a_value_terminal defines it
+ * The terminating transition's reward counts, as in gym; nothing after it is looked at - a selection, not a multiplication by
+ * zero: a NaN that appears in the trajectory (or in step_rewards) after a row's terminal step does not reach R.  Non-finite
+ * values otherwise follow IEEE.  Keys are packed as everywhere: lowest index wins ties, NaN sorts highest, the index is
+ * cand_offset + j; one integer atomicMax per (workgroup, env touched), no float atomics.  For a row whose guards never fire, R
+ * is bit-equal to l2a_score_trajectory's; with step rewards taken from a reward model as l2a_plan_rs_term takes them, to
+ * l2a_score_trajectory_model's; with terminal values, to l2a_plan_rs_program_value's / _reward_model_value's.
+ *
+ * l2a_termination_check: host only, needs no GPU.  L2A_EINVAL - with a message through l2a_last_error(NULL) - for a NULL program,
+ * n_guards outside 1 .. 8, a non-finite terminal_reward, a guard with len < 1 or a range outside obs_dim, a NaN bound, lo > hi.
+ *
+ * l2a_score_trajectory_term: the kernel alone (l2a_score_term_k, csrc/l2a_score.hip), on trajectories that are already in HBM.
+ * Exactly one of `program` / `step_rewards` (device fp32 [h, m*n]) is given; with step_rewards, obs0 and actions are not read
+ * and may be NULL.  obs0 / traj / actions as l2a_score_trajectory.  terminal_values: device fp32 [m*n], or NULL.  returns_out
+ * [m, n] or NULL, steps_alive_out int32 [m, n] or NULL, best_key [m] or NULL (zeroed on `stream` in front of the launch).
+ * Every refusal (L2A_EINVAL) is made before the memset and the launch: both or neither of program / step_rewards, a program or
+ * a termination its check refuses, a NULL traj (or obs0 / actions with a program), all three outputs NULL, m, n or h < 1, a
+ * non-finite discount or value_coef, m * n > 2^30 - 1, cand_offset < 0 or cand_offset + n > 2^31 - 1, and the LDS bound:
+ * l2a_score_trajectory's with a program, 256 * (obs_dim | 1) bytes <= 63 KiB with step_rewards.
+ *
+ * l2a_plan_rs_term: the plan step - stream-ordered, no host synchronisation unless a model-owned buffer grows (freed with the
+ * model).  Exactly one of `rm` / `program` is given; `vm` may be NULL (value_coef is then not looked at beyond its finiteness).
+ *   1. the rollout of l2a_rollout_traj (single launch or carry chain; the launch status word keeps its meaning);
+ *   2. with a reward model, the per-step rewards from the scorer kernel of l2a_score_trajectory_model, unchanged: step 0 is one
+ *      l2a_score_trajectory_model call with h = 1 and discount 1 into rewards[0]; steps 1 .. h - 1 are ONE
+ *      l2a_reward_model_predict over the (h - 1) * m * n contiguous rows obs = traj[0 .. h-2], act = actions[1 ..], next =
+ *      traj[1 ..] (refused when (h - 1) * m * n > 2^30 - 1);
+ *   3. with a value model, one l2a_value_model_predict on traj[h - 1];
+ *   4. one launch of l2a_score_term_k.
+ * Launches: rollout + 1 for a program, rollout + 3 for a reward model (+ 2 at h = 1), + 1 with a value model.  `rm`, `vm` and
+ * `model` must live on the same context and agree on obs_dim / act_dim (L2A_EINVAL).  A fused l2a_reward reaches this entry as
+ * a program (RewardProgram.from_spec on the Python side).  traj_out as l2a_plan_rs_program.                               */
+#define L2A_TERMINATION_MAX_GUARDS 8
+typedef struct l2a_guard {
+    int index;                   /* next_obs[index : index + len]                                       */
+    int len;
+    float lo;                    /* the guard holds iff lo <= x <= hi for every element                 */
+    float hi;
+} l2a_guard;
+typedef struct l2a_termination {
+    int n_guards;                /* 1 .. L2A_TERMINATION_MAX_GUARDS                                     */
+    int reserved;
+    float terminal_reward;       /* added, discounted, at the terminating step; 0: nothing is added     */
+    float reserved2;
+    l2a_guard guards[L2A_TERMINATION_MAX_GUARDS];
+} l2a_termination;
+int l2a_termination_check(const l2a_termination* termination, int obs_dim);
+int l2a_score_trajectory_term(l2a_ctx* ctx, const float* obs0, const float* traj, const float* actions, const float* step_rewards,
+                              int m, int n, int h, int obs_dim, int act_dim, double discount, const l2a_reward_program* program,
+                              const l2a_termination* termination, const float* terminal_values, double value_coef,
+                              int cand_offset, float* returns_out, int* steps_alive_out, unsigned long long* best_key,
+                              void* stream);
+int l2a_plan_rs_term(l2a_model* model, l2a_reward_model* rm, l2a_value_model* vm, const float* obs0, const float* actions, int m,
+                     int n, int h, double discount, const l2a_reward_program* program, const l2a_termination* termination,
+                     double value_coef, int cand_offset, float* returns_out, int* steps_alive_out, unsigned long long* best_key,
+                     float* traj_out, void* stream);
+
 /* ---- the MLP planner's trajectory rollout -------------------------------------------------------
  * What l2a_plan_rs_program and l2a_plan_rs_reward_model put in front of their scoring launch, and the MLP counterpart of
  * l2a_lstm_rollout_traj.  Stream-ordered; no host synchronisation unless the model's own buffer grows.

@@ -10,6 +10,7 @@ import json
 import os
 
 from .envs.reward_spec import RewardProgram, RewardSpec
+from .envs.termination import TerminationProgram
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # L2A_LIB_PATH: developer override for kernel A/B runs (tools/build_variant.py); the product loads the in-tree build
@@ -53,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "l2a_value_model_check", "l2a_value_model_geometry", "l2a_value_model_create", "l2a_value_model_destroy", "l2a_value_model_set_weights",
     "l2a_value_model_set_norm", "l2a_value_model_predict", "l2a_value_terminal", "l2a_plan_rs_value", "l2a_plan_rs_program_value",
     "l2a_plan_rs_reward_model_value",
+    "l2a_termination_check", "l2a_score_trajectory_term", "l2a_plan_rs_term",
     "l2a_particle_score", "l2a_plan_rs_particles", "l2a_plan_rs_particles_program", "l2a_plan_rs_particles_reward_model",
     "l2a_particle_perm", "l2a_particle_shuffle", "l2a_plan_rs_particles_ts1",
     "l2a_particle_step", "l2a_plan_rs_particles_ts1_program", "l2a_plan_rs_particles_ts1_reward_model",
@@ -288,6 +290,16 @@ def load():
     lib.l2a_score_trajectory.restype = i32
     lib.l2a_plan_rs_program.argtypes = [vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), i32, vp, vp, vp, vp]
     lib.l2a_plan_rs_program.restype = i32
+    if hasattr(lib, "l2a_termination_check"):           # (absent from older variant libraries selected with L2A_LIB_PATH)
+        tp = c.POINTER(TerminationProgram)
+        lib.l2a_termination_check.argtypes = [tp, i32]
+        lib.l2a_termination_check.restype = i32
+        lib.l2a_score_trajectory_term.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), tp,
+                                                  vp, c.c_double, i32, vp, vp, vp, vp]
+        lib.l2a_score_trajectory_term.restype = i32
+        lib.l2a_plan_rs_term.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, c.c_double, c.POINTER(RewardProgram), tp, c.c_double, i32,
+                                         vp, vp, vp, vp, vp]
+        lib.l2a_plan_rs_term.restype = i32
     if hasattr(lib, "l2a_value_model_create"):          # (absent from older variant libraries selected with L2A_LIB_PATH)
         dbl = c.c_double
         lib.l2a_value_model_check.argtypes = [i32, i32, c.POINTER(i32), i32]
@@ -726,6 +738,46 @@ class Context(object):
                                            act_dim, float(discount), ctypes.byref(program), int(cand_offset), ptr(returns_out),
                                            ptr(best_key), stream_ptr)
         self.check(rc, "l2a_score_trajectory")
+
+    def score_trajectory_term(self, obs0, traj, actions, m, n, h, discount, termination, program=None, step_rewards=None,
+                              terminal_values=None, value_coef=1.0, cand_offset=0, returns_out=None, steps_alive_out=None,
+                              best_key=None, stream_ptr=None):
+        """Score trajectories that are already on the device under a termination program (``l2a_score_trajectory_term``): exactly
+        one of ``program`` (a ``RewardProgram``; ``obs0`` / ``actions`` as ``score_trajectory``) and ``step_rewards`` (fp32 CUDA
+        ``[h, m * n]``; ``obs0`` and ``actions`` may be ``None``).  ``terminal_values``: fp32 CUDA ``[m * n]`` or ``None``;
+        ``steps_alive_out``: int32 CUDA ``[m, n]`` or ``None``."""
+        import torch
+        assert isinstance(termination, TerminationProgram)
+        assert program is None or isinstance(program, RewardProgram)
+        assert traj.is_cuda and traj.dtype == torch.float32 and traj.is_contiguous()
+        obs_dim = int(traj.shape[-1])
+        assert traj.numel() == h * m * n * obs_dim
+        act_dim = int(actions.shape[-1]) if actions is not None else 1
+        if program is not None:
+            for t in (obs0, actions):
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+            assert obs0.numel() == m * obs_dim and actions.numel() == h * m * n * act_dim
+        if step_rewards is not None:
+            assert step_rewards.is_cuda and step_rewards.dtype == torch.float32 and step_rewards.is_contiguous()
+            assert step_rewards.numel() == h * m * n
+        if terminal_values is not None:
+            assert terminal_values.is_cuda and terminal_values.dtype == torch.float32 and terminal_values.is_contiguous()
+            assert terminal_values.numel() == m * n
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if steps_alive_out is not None:
+            assert steps_alive_out.is_cuda and steps_alive_out.dtype == torch.int32 and steps_alive_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if stream_ptr is None:
+            stream_ptr = ctypes.c_void_p(torch.cuda.current_stream(traj.device).cuda_stream)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)    # noqa: E731
+        rc = self.lib.l2a_score_trajectory_term(self.handle, ptr(obs0), ptr(traj), ptr(actions), ptr(step_rewards), int(m), int(n),
+                                                int(h), obs_dim, act_dim, float(discount),
+                                                ctypes.byref(program) if program is not None else None, ctypes.byref(termination),
+                                                ptr(terminal_values), float(value_coef), int(cand_offset), ptr(returns_out),
+                                                ptr(steps_alive_out), ptr(best_key), stream_ptr)
+        self.check(rc, "l2a_score_trajectory_term")
 
     def set_spin_limit(self, polls):
         """Developer / test knob: polls a split workgroup waits for its partner per launch (0 = default)."""

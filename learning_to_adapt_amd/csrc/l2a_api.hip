@@ -65,6 +65,8 @@ struct l2a_model : l2a_mlp_shape {
     long long prog_buf_floats = 0;
     float* value_buf = nullptr;                   // l2a_plan_rs_value and its siblings: [last states (rows x obs_dim) | returns before the fold (rows)]
     long long value_buf_floats = 0;
+    float* term_buf = nullptr;                    // l2a_plan_rs_term: [step rewards (h x rows, reward model only) | terminal values (rows, value model only)]
+    long long term_buf_floats = 0;
     float* part_buf = nullptr;                    // l2a_plan_rs_particles: [obs_x (m E obs_dim) | act_x (h m E n act_dim) | member returns (m E n)]
     long long part_buf_floats = 0;
     // l2a_model_adapt_sgd_host: two staging slots (host-mapped, read by the kernels directly)
@@ -895,6 +897,7 @@ void l2a_model_destroy(l2a_model* md) {
     if (md->prog_buf) (void)hipFree(md->prog_buf);
     if (md->part_buf) (void)hipFree(md->part_buf);
     if (md->value_buf) (void)hipFree(md->value_buf);
+    if (md->term_buf) (void)hipFree(md->term_buf);
     for (auto& sl : md->aslot) {
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.stage_host) (void)hipHostFree(sl.stage_host);
@@ -1695,6 +1698,86 @@ int l2a_plan_rs_reward_model_value(l2a_model* md, l2a_reward_model* rm, l2a_valu
     if (rc != L2A_OK) return rc;
     return l2a_value_terminal(vm, traj + (long long)(h - 1) * rows * md->obs_dim, R, m, n, h, discount, value_coef, cand_offset,
                               returns_out, best_key, stream_v);
+}
+
+// ---- plans on envs that terminate (l2a_score.hip: l2a_score_term_k) ---------------------------------------------------------
+// The checks this entry makes itself - its arguments, the program, the termination, the models' contexts and dimensions, the row
+// limit of the one reward-model launch, the scoring kernel's LDS bound - come before the model's buffer is grown and before the
+// first launch.  What the launches behind them check for themselves (weights or statistics never set, a HIP error) can still end
+// the call after the buffer was grown or the rollout was launched; no output is complete then.
+// The buffer: [step rewards (h x rows) with a reward model | terminal values (rows) with a value model].
+int l2a_plan_rs_term(l2a_model* md, l2a_reward_model* rm, l2a_value_model* vm, const float* obs0, const float* actions, int m, int n,
+                     int h, double discount, const l2a_reward_program* program, const l2a_termination* termination, double value_coef,
+                     int cand_offset, float* returns_out, int* steps_alive_out, unsigned long long* best_key, float* traj_out,
+                     void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    const std::string who("l2a_plan_rs_term");
+    if ((rm != nullptr) == (program != nullptr)) return fail(ctx, L2A_EINVAL, who + ": exactly one of a reward model and a program must be given");
+    int rc = program ? l2a_reward_program_check(program, md->obs_dim, md->act_dim) : L2A_OK;
+    if (rc != L2A_OK) return fail(ctx, rc, l2a_last_error(nullptr));
+    rc = l2a_termination_check(termination, md->obs_dim);
+    if (rc != L2A_OK) return fail(ctx, rc, l2a_last_error(nullptr));
+    if (rm) {
+        l2a_ctx* rm_ctx = nullptr;
+        int rm_obs = 0, rm_act = 0;
+        l2a_reward_model_facts(rm, &rm_ctx, &rm_obs, &rm_act);
+        if (rm_ctx != ctx) return fail(ctx, L2A_EINVAL, who + ": the reward model lives on another context");
+        if (rm_obs != md->obs_dim || rm_act != md->act_dim)
+            return fail(ctx, L2A_EINVAL, who + ": the reward model is for obs_dim " + std::to_string(rm_obs) + " / act_dim " +
+                        std::to_string(rm_act) + ", the dynamics model for " + std::to_string(md->obs_dim) + " / " + std::to_string(md->act_dim));
+    }
+    if (vm) {
+        l2a_ctx* vm_ctx = nullptr;
+        int vm_obs = 0;
+        l2a_value_model_facts(vm, &vm_ctx, &vm_obs);
+        if (vm_ctx != ctx) return fail(ctx, L2A_EINVAL, who + ": the value model lives on another context");
+        if (vm_obs != md->obs_dim)
+            return fail(ctx, L2A_EINVAL, who + ": the value model is for obs_dim " + std::to_string(vm_obs) + ", the dynamics model for " +
+                        std::to_string(md->obs_dim));
+    }
+    if (!obs0 || !actions) return fail(ctx, L2A_EINVAL, who + ": null obs0/actions");
+    if (!best_key && !returns_out && !steps_alive_out)
+        return fail(ctx, L2A_EINVAL, who + ": nothing to write (best_key, returns_out and steps_alive_out are null)");
+    if (m < 1 || n < 1 || h < 1) return fail(ctx, L2A_EINVAL, who + ": m, n and h must be >= 1");
+    if (!std::isfinite(discount) || !std::isfinite(value_coef)) return fail(ctx, L2A_EINVAL, who + ": discount and value_coef must be finite");
+    if ((long long)m * n > 0x3fffffffLL || cand_offset < 0 || (long long)cand_offset + n > 0x7fffffffLL)
+        return fail(ctx, L2A_EINVAL, who + ": too many candidates");
+    const long long rows = (long long)m * n;
+    if (rm && (h - 1) * rows > 0x3fffffffLL) return fail(ctx, L2A_EINVAL, who + ": (h - 1) * m * n rows are too many for one reward-model launch");
+    const long long so = md->obs_dim | 1, sa = md->act_dim | 1;
+    if (256LL * (rm ? so : 2 * so + sa) > 63 * 1024)
+        return fail(ctx, L2A_EINVAL, who + ": 64 rows of obs_dim " + std::to_string(md->obs_dim) + " / act_dim " + std::to_string(md->act_dim) +
+                    " do not fit the scoring kernel's LDS");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    const long long rew_floats = rm ? (long long)h * rows : 0, need = rew_floats + (vm ? rows : 0);
+    if (need > md->term_buf_floats) {
+        l2a_device_guard guard(ctx->device);
+        if (md->term_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->term_buf)); md->term_buf = nullptr; md->term_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->term_buf), (size_t)need * sizeof(float)));
+        md->term_buf_floats = need;
+    }
+    float* const rewards = rm ? md->term_buf : nullptr;
+    float* const values = vm ? md->term_buf + rew_floats : nullptr;
+    float* traj = nullptr;
+    rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
+    if (rc != L2A_OK) return rc;
+    if (rm) {
+        rc = l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, 1, 1.0, cand_offset, rewards, nullptr, stream_v);
+        if (rc != L2A_OK) return rc;
+        if (h > 1) {
+            rc = l2a_reward_model_predict(rm, traj, actions + rows * md->act_dim, traj + rows * md->obs_dim, (int)((h - 1) * rows),
+                                          rewards + rows, stream_v);
+            if (rc != L2A_OK) return rc;
+        }
+    }
+    if (vm) {
+        rc = l2a_value_model_predict(vm, traj + (long long)(h - 1) * rows * md->obs_dim, (int)rows, values, stream_v);
+        if (rc != L2A_OK) return rc;
+    }
+    return l2a_score_trajectory_term(ctx, program ? obs0 : nullptr, traj, program ? actions : nullptr, rewards, m, n, h, md->obs_dim,
+                                     md->act_dim, discount, program, termination, values, vm ? value_coef : 0.0, cand_offset,
+                                     returns_out, steps_alive_out, best_key, stream_v);
 }
 
 // ---- particle plans of a mean ensemble (l2a_particles.hip) ------------------------------------------------------------------

@@ -12,6 +12,7 @@ import torch
 
 from .. import _lib
 from ..envs.reward_spec import RewardProgram, RewardSpec
+from ..envs.termination import TerminationProgram
 
 
 def _stream_ptr(device=None):
@@ -55,6 +56,8 @@ class NativeModel(object):
         self.program_plans = 0      # calls of plan_rs_program (diagnostics: which plan path a controller took)
         self.reward_model_plans = 0     # calls of plan_rs_reward_model
         self.value_plans = 0        # calls of plan_rs_value
+        self.term_plans = 0         # calls of plan_rs_term
+        self._spec_programs = {}    # RewardSpec -> its RewardProgram.from_spec (plan_rs_term scores a spec as a program)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -321,6 +324,50 @@ class NativeModel(object):
             raise _lib.L2AError("plans with a terminal value take a RewardSpec, a RewardProgram or a NativeRewardModel, not %s"
                                 % type(reward).__name__)
         self.ctx.check(rc, what)
+
+    def plan_rs_term(self, obs0, actions, m, n, h, discount, reward, termination, value_model=None, value_coef=1.0, cand_offset=0,
+                     returns_out=None, steps_alive_out=None, best_key=None, traj_out=None):
+        """Plan step of an env that terminates (``l2a_plan_rs_term``; include/l2a.h, "plans on envs that terminate"): every
+        candidate's return stops at its first step whose next observation fails a guard of ``termination`` (a
+        ``TerminationProgram``).  ``reward``: a ``RewardProgram``, a ``RewardSpec`` (scored as ``RewardProgram.from_spec``) or a
+        ``NativeRewardModel``; ``value_model``: an optional ``NativeValueModel`` whose value of the last state is folded into the
+        rows that survive.  ``steps_alive_out``: optional int32 CUDA ``[m, n]``.  Other arguments as ``plan_rs_program``."""
+        assert obs0.is_cuda and actions.is_cuda and obs0.dtype == torch.float32 and actions.dtype == torch.float32
+        assert obs0.is_contiguous() and actions.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and actions.numel() == h * m * n * self.act_dim
+        if returns_out is not None:
+            assert returns_out.is_cuda and returns_out.dtype == torch.float32 and returns_out.numel() == m * n
+        if steps_alive_out is not None:
+            assert steps_alive_out.is_cuda and steps_alive_out.dtype == torch.int32 and steps_alive_out.numel() == m * n
+        if best_key is not None:
+            assert best_key.is_cuda and best_key.dtype == torch.int64 and best_key.numel() == m
+        if traj_out is not None:
+            assert traj_out.is_cuda and traj_out.dtype == torch.float32 and traj_out.is_contiguous()
+            assert traj_out.numel() == h * m * n * self.obs_dim
+        assert isinstance(termination, TerminationProgram)
+        assert value_model is None or isinstance(value_model, NativeValueModel)
+        if not hasattr(self.lib, "l2a_plan_rs_term"):
+            raise _lib.L2AError("this libl2a_hip.so has no termination kernel (l2a_plan_rs_term): rebuild it")
+        rm, program = None, None
+        if isinstance(reward, NativeRewardModel):
+            rm = reward.handle
+        elif isinstance(reward, RewardProgram):
+            program = reward
+        elif isinstance(reward, RewardSpec):
+            program = self._spec_programs.get(id(reward))
+            if program is None or program[0] is not reward:
+                program = self._spec_programs[id(reward)] = (reward, RewardProgram.from_spec(reward, self.obs_dim, self.act_dim))
+            program = program[1]
+        else:
+            raise _lib.L2AError("plans with a termination program take a RewardSpec, a RewardProgram or a NativeRewardModel, not %s"
+                                % type(reward).__name__)
+        self.term_plans += 1
+        rc = self.lib.l2a_plan_rs_term(self.handle, rm, value_model.handle if value_model is not None else None, _ptr(obs0),
+                                       _ptr(actions), int(m), int(n), int(h), float(discount),
+                                       ctypes.byref(program) if program is not None else None, ctypes.byref(termination),
+                                       float(value_coef), int(cand_offset), _ptr(returns_out), _ptr(steps_alive_out),
+                                       _ptr(best_key), _ptr(traj_out), _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_plan_rs_term")
 
     def plan_rs_particles(self, obs0, actions, m, n, h, discount, reward, risk_coef=0.0, cand_offset=0, score_out=None,
                           spread_out=None, member_returns_out=None, best_key=None):

@@ -92,7 +92,9 @@ class SyntheticEnv(object):
         nxt = self.toy_dynamics(obs[None], np.asarray(action, dtype=np.float64)[None])[0]
         rew = float(self.reward(obs[None], np.asarray(action, dtype=np.float64)[None], nxt[None])[0])
         self._state = nxt
-        return nxt.copy(), rew, False, {}
+        term = getattr(self, "termination_spec", None)      # a TerminationProgram: the episode ends when a guard fails
+        done = False if term is None else not bool(term.alive(nxt[None])[0])
+        return nxt.copy(), rew, done, {}
 
     def log_diagnostics(self, paths, prefix=""):
         pass

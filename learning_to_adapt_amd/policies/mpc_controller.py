@@ -68,7 +68,12 @@ at construction; on: such a plan takes every step's reward where the particles a
 ``value_model`` / ``terminal_value_coef`` (a learned terminal value, ``MLPValueModel``: every planner scores
 ``R' = R + terminal_value_coef * discount ** h * V(s_h)``, the value of each candidate's last predicted state folded into returns and
 keys by one launch behind the rollout - ``l2a_plan_rs_value`` / ``_program_value`` / ``_reward_model_value``; no host fallback, not
-with ``ensemble_planning="particles"`` or an explicit C controller step, which raise at construction).
+with ``ensemble_planning="particles"`` or an explicit C controller step, which raise at construction),
+``termination`` (a ``TerminationProgram``; default: the env's ``termination_spec``: every candidate's return stops at its first step
+whose next observation leaves a guarded range, and a ``value_model`` is folded into the surviving candidates only - one scoring
+launch behind the trajectory rollout, ``l2a_plan_rs_term``; random shooting, CEM, MPPI and iCEM alike; no host fallback, not with
+``ensemble_planning="particles"``, an explicit C controller step or the recurrent planner, which raise at construction;
+``termination_diagnostics()`` copies the winner's ``steps_alive`` and the terminated share back on demand).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -82,6 +87,7 @@ import torch
 
 from .. import _lib
 from ..envs.reward_spec import RewardProgram, reward_spec_for_env
+from ..envs.termination import TerminationProgram, termination_spec_for_env
 from ..utils import fast_rng
 from ..utils.serializable import Serializable
 from .draw_ahead import DrawAhead
@@ -132,6 +138,7 @@ class MPCController(Policy, Serializable):
             ts1_step_rewards=False,
             value_model=None,
             terminal_value_coef=1.0,
+            termination=None,
     ):
         self.dynamics_model = dynamics_model
         self.value_model = value_model
@@ -238,6 +245,10 @@ class MPCController(Policy, Serializable):
                                 "reads a step's two states from one trajectory row, which the shuffle between steps breaks")
         if value_model is not None:
             self._check_value_model()
+        self._termination = termination if termination is not None else termination_spec_for_env(env)
+        if self._termination is not None:
+            self._check_termination()
+        self._term = None           # device tensors of the latest plan under a termination program (`termination_diagnostics`)
         self._ts1_calls = 0         # `_rollout` calls under particle_sampling="ts1" since the seed below was first seen
         self._ts1_seed = None       # torch.initial_seed() the count belongs to: a changed seed restarts it
         self._bufs = {}
@@ -296,6 +307,34 @@ class MPCController(Policy, Serializable):
                                 "RewardProgram) or, with use_reward_model, a reward model it scores (MLPRewardModel)")
         if not hasattr(self.dynamics_model, "planner_model"):
             raise _lib.L2AError("a value_model needs a dynamics model with a native planner (MLPDynamicsModel)")
+
+    _takes_termination = True       # (RNNMPCController: False - the recurrent planner scores no termination program)
+
+    def _check_termination(self):
+        """``termination=...`` (or the env's ``termination_spec``): every candidate's return stops at its first step whose next
+        observation fails a guard (``l2a_plan_rs_term``) - there is no host fallback, and the plan goes through ``_rollout``,
+        which the C controller steps bypass."""
+        term = self._termination
+        if not isinstance(term, TerminationProgram):
+            raise _lib.L2AError("termination must be a TerminationProgram (envs/termination.py), not %s" % type(term).__name__)
+        try:
+            term.check(int(self.env.observation_space.shape[0]))
+        except ValueError as e:
+            raise _lib.L2AError(str(e))
+        if not self._takes_termination:
+            raise _lib.L2AError("the recurrent planner scores no termination program: plan this env with an MLPDynamicsModel "
+                                "(MPCController)")
+        if self.ensemble_planning == "particles":
+            raise _lib.L2AError("ensemble_planning='particles' with a termination program is not built (either particle_sampling): "
+                                "a particle plan scores every member's rollout on the whole horizon")
+        if self.native_cem_step or self.native_mppi_step or self.native_icem_step:
+            raise _lib.L2AError("a termination program plans through the Python loop: the C controller steps (native_cem_step, "
+                                "native_mppi_step, native_icem_step) score the whole horizon - leave them off")
+        if self._reward_spec is None and self._native_reward_model() is None:
+            raise _lib.L2AError("a termination program needs a plan the library scores: an env reward it knows (a RewardSpec or a "
+                                "RewardProgram) or, with use_reward_model, a reward model it scores (MLPRewardModel)")
+        if not hasattr(self.dynamics_model, "planner_model"):
+            raise _lib.L2AError("a termination program needs a dynamics model with a native planner (MLPDynamicsModel)")
 
     # ------------------------------------------------------------------ reference API
     def get_action(self, observation):
@@ -461,9 +500,11 @@ class MPCController(Policy, Serializable):
         through ``_rollout``, and every path that would hand the spec to an entry point taking ``l2a_reward`` - the blocking
         launch, the horizon-chunked pipelines, the C controllers - declines.  A particle plan (``ensemble_planning="particles"``)
         is scored behind its rollouts too, whatever its reward, and stays on ``_rollout`` the same way; so does a plan with a
-        ``value_model``: its terminal value is folded in by a launch behind the rollout (``l2a_plan_rs_value`` and its siblings)."""
+        ``value_model``: its terminal value is folded in by a launch behind the rollout (``l2a_plan_rs_value`` and its siblings);
+        and so does a plan under a termination program, scored by ``l2a_plan_rs_term`` behind the trajectory rollout."""
         return (self.ensemble_planning == "particles" or isinstance(self._reward_spec, RewardProgram)
-                or self._native_reward_model() is not None or self.__dict__.get("value_model") is not None)
+                or self._native_reward_model() is not None or self.__dict__.get("value_model") is not None
+                or self.__dict__.get("_termination") is not None)
 
     def _buf(self, key, shape, dtype, device):
         t = self._bufs.get(key)
@@ -614,6 +655,17 @@ class MPCController(Policy, Serializable):
                                      best_key=best)
             self._particles = dict(members=members, spread=spread, score=rets, best=best, cand_offset=cand_offset)
             return best, rets
+        if self.__dict__.get("_termination") is not None:
+            # the return stops at a candidate's terminal step; a value model's V(s_h) is folded into the rows that survive
+            steps = self._buf("t_steps", (m, n_local), torch.int32, dev)
+            vm = self.__dict__.get("value_model")
+            native.plan_rs_term(obs0, actions_local, m, n_local, self.horizon, self.discount,
+                                rm.planner_reward_model() if rm is not None else self._reward_spec, self._termination,
+                                value_model=vm.planner_value_model() if vm is not None else None,
+                                value_coef=self.terminal_value_coef, cand_offset=cand_offset, returns_out=rets,
+                                steps_alive_out=steps, best_key=best)
+            self._term = dict(steps=steps, best=best, cand_offset=cand_offset, horizon=self.horizon)
+            return best, rets
         if self.__dict__.get("value_model") is not None:
             # R' = R + terminal_value_coef * discount ** h * V(s_h): one branch per reward kind, the planners see R' only
             native.plan_rs_value(obs0, actions_local, m, n_local, self.horizon, self.discount,
@@ -629,6 +681,24 @@ class MPCController(Policy, Serializable):
         plan(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
              cand_offset=cand_offset, returns_out=rets, best_key=best)
         return best, rets
+
+    def termination_diagnostics(self):
+        """What the latest plan under a termination program on this rank knew, copied back on demand (nothing of it is on the plan
+        step's own read-back): per env ``index`` (global candidate index of the best return in this rank's shard),
+        ``steps_alive [m]`` of that winner (``horizon``: it survived) and ``terminated [m]``, the share of this rank's candidates
+        that terminated before the horizon's end.  Under CEM, MPPI and iCEM it is the last iteration's rollout; ``None`` before
+        the first such plan."""
+        st = self._term
+        if st is None:
+            return None
+        keys = st["best"].cpu().numpy()
+        m = len(keys)
+        index = np.empty(m, dtype=np.int64)
+        for i in range(m):
+            _, index[i] = _lib.key_decode(keys[i])
+        steps = st["steps"].cpu().numpy()
+        return dict(index=index, steps_alive=steps[np.arange(m), index - st["cand_offset"]].astype(np.int32),
+                    terminated=(steps < st["horizon"]).mean(axis=1))
 
     def particle_diagnostics(self, tables=False):
         """What the latest particle rollout on this rank knew of its winner, copied back on demand (nothing of it is on the plan

@@ -34,6 +34,7 @@ class RNNMPCController(MPCController):
     _hid_stale = None       # which copy is out of date: None | "host" | "dev"
     _hid_next = None        # (c, h) already advanced with the chosen actions by the blocking plan launch
     _hid_flip = 0
+    _takes_termination = False      # an env with a `termination_spec` raises at construction: no recurrent termination scorer
     _takes_reward_models = False    # a reward model keeps the reference's loop unless the instance asks: `native_reward_model=True`
 
     def __init__(
