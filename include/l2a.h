@@ -26,6 +26,7 @@ typedef struct l2a_model l2a_model;
 typedef struct l2a_lstm l2a_lstm;
 typedef struct l2a_reward_model l2a_reward_model;
 typedef struct l2a_value_model l2a_value_model;
+typedef struct l2a_policy_model l2a_policy_model;
 typedef struct l2a_controller l2a_controller;
 
 /* ---- error codes --------------------------------------------------------------------- */
@@ -426,6 +427,54 @@ int l2a_plan_rs_reward_model_value(l2a_model* model, l2a_reward_model* rm, l2a_v
                                    const float* actions, int m, int n, int h, double discount, double value_coef,
                                    int cand_offset, float* returns_out, unsigned long long* best_key, float* traj_out,
                                    void* stream);
+
+/* ---- policy priors: candidates proposed by a learned policy ------------------------------------------
+ * TD-MPC, LOOP and POPLIN seed a share of every population from a learned policy rolled in closed loop through the dynamics
+ * model, a_t = pi(s_t) + sigma * eps, s_{t+1} = f(s_t, a_t).  l2a_policy_model is that policy: the value model's MLP with an
+ * act_dim-wide linear output.  Per row, fp32, nothing contracted:
+ *   x = (s - mu_obs) * inv_obs, inv = fp32(1 / (sd + 1e-10));   y = MLP(x), one accumulator chain per output element, k ascending,
+ *   K zero-padded;   a_k = y_k * fp32(sd_a,k + 1e-10) + fp32(mu_a,k);   where sigma_k != 0: a_k = a_k + sigma_k * z_k (a multiply
+ *   and an add; where sigma_k == 0 no z is read or drawn);   a_k = min(max(a_k, low_k), high_k), NaN propagating;   a row with a
+ *   non-finite state value gets NaN in every action.
+ * z is given, or the Philox4x32-10 + Box-Muller normal of l2a_cem_sample / l2a_mppi_sample at the counters stated below.
+ *
+ * l2a_policy_model_check: host only.  The limits of l2a_value_model_check and 1 <= act_dim <= 16 (one output tile); refuses with
+ * a message through l2a_last_error(NULL).
+ * l2a_policy_model_geometry: host only - l2a_value_model_geometry's contract and rule for this kernel's launcher.
+ * l2a_policy_model_set_weights: fp32 DEVICE arrays { hidden_l/kernel, hidden_l/bias, ..., output/kernel [hL, act_dim],
+ * output/bias [act_dim] }, kernels row-major [in, out].
+ * l2a_policy_model_set_norm: float64 HOST vectors mean_obs / std_obs [obs_dim], mean_act / std_act [act_dim]; all four NULL =
+ * identity.
+ * l2a_policy_act: the kernel alone.  states [rows, obs_dim] -> actions_out [rows, act_dim]; z [rows, act_dim] or NULL: the
+ * normal at counter offset + row * act_dim + k.  sigma / low / high: DEVICE fp32 [act_dim].  L2A_EINVAL for a NULL pointer or
+ * rows outside 1 .. 2^30 - 1.
+ * l2a_policy_propose: overwrites candidate j of env i, for every GLOBAL index gj = cand_offset + j < n_pi, in seq [h, m * n,
+ * act_dim] (row i * n + j) and, when given, in mirror [n_total, m, h * act_dim] (row gj * m + i: the a_clip layout of
+ * l2a_cem_refit / l2a_mppi_update / l2a_icem_refit) with the policy rolled in closed loop from obs0 [m, obs_dim]: per step one
+ * launch of the policy kernel over the shard's proposal rows and, for t < h - 1, one one-step launch of the unchanged rollout
+ * kernels (l2a_plan_rs_chunk's form: h_chunk = 1, an all-zero reward, state_out) - 2 h - 1 launches.  The normal of element
+ * (t, i, gj, k) sits at counter offset + ((t * m + i) * n_pi + gj) * act_dim + k - positional in the global index, so shards
+ * agree; an injected z [h, m, n_pi, act_dim] is indexed the same way.  Rows with gj >= n_pi are not touched; a shard without a
+ * proposal row returns L2A_OK and launches nothing.  Stream-ordered; no host synchronisation unless the model-owned buffer
+ * grows.  L2A_EINVAL before the first launch and before the buffer grows: a NULL pointer; m, n, h or n_pi < 1; n_pi > n_total;
+ * cand_offset < 0 or cand_offset + n > n_total; `pm` and `model` on different contexts or disagreeing on obs_dim / act_dim;
+ * per-block mode with m > n_sets; m * n > 2^30 - 1.  A flagged tile-split launch in the chain flags the call
+ * (l2a_launch_status).                                                                                                    */
+int l2a_policy_model_check(int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act);
+int l2a_policy_model_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, long long rows, int num_cu,
+                              int lds_per_block, int* out);
+int l2a_policy_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act,
+                            l2a_policy_model** out);
+void l2a_policy_model_destroy(l2a_policy_model* pm);
+int l2a_policy_model_set_weights(l2a_policy_model* pm, const void* const* device_ptrs, void* stream);
+int l2a_policy_model_set_norm(l2a_policy_model* pm, const double* mean_obs, const double* std_obs, const double* mean_act,
+                              const double* std_act, void* stream);
+int l2a_policy_act(l2a_policy_model* pm, const float* states, int rows, const float* z, unsigned long long seed,
+                   unsigned long long offset, const float* sigma, const float* low, const float* high, float* actions_out,
+                   void* stream);
+int l2a_policy_propose(l2a_model* model, l2a_policy_model* pm, const float* obs0, int m, int n, int n_pi, int h, int cand_offset,
+                       const float* z, unsigned long long seed, unsigned long long offset, const float* sigma, const float* low,
+                       const float* high, float* seq, float* mirror, int n_total, void* stream);
 
 /* ---- plans on envs that terminate: termination programs ---------------------------------------------
  * Hopper, Walker2d, gym's Ant and Humanoid end an episode when the state leaves a healthy range; PETS and MBPO carry a per-env

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = (
     "l2a_value_model_check", "l2a_value_model_geometry", "l2a_value_model_create", "l2a_value_model_destroy", "l2a_value_model_set_weights",
     "l2a_value_model_set_norm", "l2a_value_model_predict", "l2a_value_terminal", "l2a_plan_rs_value", "l2a_plan_rs_program_value",
     "l2a_plan_rs_reward_model_value",
+    "l2a_policy_model_check", "l2a_policy_model_geometry", "l2a_policy_model_create", "l2a_policy_model_destroy",
+    "l2a_policy_model_set_weights", "l2a_policy_model_set_norm", "l2a_policy_act", "l2a_policy_propose",
     "l2a_termination_check", "l2a_score_trajectory_term", "l2a_plan_rs_term",
     "l2a_particle_score", "l2a_plan_rs_particles", "l2a_plan_rs_particles_program", "l2a_plan_rs_particles_reward_model",
     "l2a_particle_perm", "l2a_particle_shuffle", "l2a_plan_rs_particles_ts1",
@@ -192,6 +194,37 @@ def value_model_geometry(obs_dim, hidden, rows, cus=0, lds_per_block=160 * 1024)
     return dict(RT=v[0], workgroups=v[1], lds_bytes=v[2])
 
 
+def _policy_symbols(lib):
+    if not hasattr(lib, "l2a_policy_model_create"):
+        raise L2AError("the loaded library (%s) has no l2a_policy_model_* entries: it predates policy priors - rebuild it" % LIB_PATH)
+
+
+def policy_model_check(obs_dim, act_dim, hidden, hidden_act):
+    """``l2a_policy_model_check`` (host only, no GPU): ``None`` when the policy kernel takes this network, else the library's
+    reason.  ``hidden_act``: a nonlinearity name (``ACT_CODES``) or an integer code."""
+    lib = load()
+    _policy_symbols(lib)
+    hid = (ctypes.c_int * max(len(hidden), 1))(*[int(x) for x in hidden])
+    code = hidden_act if isinstance(hidden_act, int) else ACT_CODES.get(hidden_act, -1)
+    rc = lib.l2a_policy_model_check(int(obs_dim), int(act_dim), len(hidden), hid, int(code))
+    return None if rc == L2A_OK else lib.l2a_last_error(None).decode()
+
+
+def policy_model_geometry(obs_dim, act_dim, hidden, rows, cus=0, lds_per_block=160 * 1024):
+    """The launch geometry of the policy kernel (``l2a_policy_model_geometry``: the launcher's own decision function, no GPU
+    needed) for ``rows`` states on ``cus`` CUs (0: 256) with ``lds_per_block`` bytes of LDS.  Returns a dict: RT (row tiles of 16
+    rows per workgroup), workgroups, lds_bytes."""
+    lib = load()
+    _policy_symbols(lib)
+    hid = (ctypes.c_int * max(len(hidden), 1))(*[int(x) for x in hidden])
+    out = (ctypes.c_int * 8)()
+    rc = lib.l2a_policy_model_geometry(int(obs_dim), int(act_dim), len(hidden), hid, int(rows), int(cus), int(lds_per_block), out)
+    if rc != L2A_OK:
+        raise L2AError("l2a_policy_model_geometry failed (%d): %s" % (rc, lib.l2a_last_error(None).decode()))
+    v = list(out)
+    return dict(RT=v[0], workgroups=v[1], lds_bytes=v[2])
+
+
 _lib = None
 
 
@@ -324,6 +357,24 @@ def load():
         lib.l2a_plan_rs_program_value.restype = i32
         lib.l2a_plan_rs_reward_model_value.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, vp]
         lib.l2a_plan_rs_reward_model_value.restype = i32
+    if hasattr(lib, "l2a_policy_model_create"):         # (absent from older variant libraries selected with L2A_LIB_PATH)
+        u64 = c.c_ulonglong
+        lib.l2a_policy_model_check.argtypes = [i32, i32, i32, c.POINTER(i32), i32]
+        lib.l2a_policy_model_check.restype = i32
+        lib.l2a_policy_model_geometry.argtypes = [i32, i32, i32, c.POINTER(i32), c.c_longlong, i32, i32, c.POINTER(i32)]
+        lib.l2a_policy_model_geometry.restype = i32
+        lib.l2a_policy_model_create.argtypes = [vp, i32, i32, i32, c.POINTER(i32), i32, c.POINTER(vp)]
+        lib.l2a_policy_model_create.restype = i32
+        lib.l2a_policy_model_destroy.argtypes = [vp]
+        lib.l2a_policy_model_destroy.restype = None
+        lib.l2a_policy_model_set_weights.argtypes = [vp, c.POINTER(vp), vp]
+        lib.l2a_policy_model_set_weights.restype = i32
+        lib.l2a_policy_model_set_norm.argtypes = [vp, dp, dp, dp, dp, vp]
+        lib.l2a_policy_model_set_norm.restype = i32
+        lib.l2a_policy_act.argtypes = [vp, vp, i32, vp, u64, u64, vp, vp, vp, vp, vp]
+        lib.l2a_policy_act.restype = i32
+        lib.l2a_policy_propose.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, u64, u64, vp, vp, vp, vp, vp, i32, vp]
+        lib.l2a_policy_propose.restype = i32
     if hasattr(lib, "l2a_reward_model_create"):         # (absent from older variant libraries selected with L2A_LIB_PATH)
         lib.l2a_reward_model_check.argtypes = [i32, i32, i32, c.POINTER(i32), i32]
         lib.l2a_reward_model_check.restype = i32

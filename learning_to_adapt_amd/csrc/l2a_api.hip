@@ -65,6 +65,8 @@ struct l2a_model : l2a_mlp_shape {
     long long prog_buf_floats = 0;
     float* value_buf = nullptr;                   // l2a_plan_rs_value and its siblings: [last states (rows x obs_dim) | returns before the fold (rows)]
     long long value_buf_floats = 0;
+    float* pol_buf = nullptr;                     // l2a_policy_propose: [actions (rows x act_dim) | two state slots (rows x obs_dim each) | carry returns (rows)]
+    long long pol_buf_floats = 0;
     float* term_buf = nullptr;                    // l2a_plan_rs_term: [step rewards (h x rows, reward model only) | terminal values (rows, value model only)]
     long long term_buf_floats = 0;
     float* part_buf = nullptr;                    // l2a_plan_rs_particles: [obs_x (m E obs_dim) | act_x (h m E n act_dim) | member returns (m E n)]
@@ -897,6 +899,7 @@ void l2a_model_destroy(l2a_model* md) {
     if (md->prog_buf) (void)hipFree(md->prog_buf);
     if (md->part_buf) (void)hipFree(md->part_buf);
     if (md->value_buf) (void)hipFree(md->value_buf);
+    if (md->pol_buf) (void)hipFree(md->pol_buf);
     if (md->term_buf) (void)hipFree(md->term_buf);
     for (auto& sl : md->aslot) {
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -1598,6 +1601,65 @@ int l2a_plan_rs_reward_model(l2a_model* md, l2a_reward_model* rm, const float* o
     const int rc = rollout_traj_launch(md, md->mode, obs0, actions, m, n, h, discount, cand_offset, traj_out, stream_v, &traj);
     if (rc != L2A_OK) return rc;
     return l2a_score_trajectory_model(rm, obs0, traj, actions, m, n, h, discount, cand_offset, returns_out, best_key, stream_v);
+}
+
+// ---- policy proposals (l2a_policy.hip) ---------------------------------------------------------------------------------------
+// Candidates gj = cand_offset + j < n_pi of every env are overwritten, in seq and in mirror, by the policy rolled in closed loop
+// through the model: per horizon step one launch of the policy kernel over the m * npl proposal rows (npl = this shard's share)
+// and, for t < h - 1, ONE one-step launch of the unchanged rollout kernels on the compact action slice - the carry chain's own
+// form (all-zero reward, state_out).  2 h - 1 launches, stream-ordered; the model-owned pol_buf grows on demand (which
+// synchronises the stream).  Every refusal is made before the buffer grows and before the first launch.
+int l2a_policy_propose(l2a_model* md, l2a_policy_model* pm, const float* obs0, int m, int n, int n_pi, int h, int cand_offset,
+                       const float* z, unsigned long long seed, unsigned long long offset, const float* sigma, const float* low,
+                       const float* high, float* seq, float* mirror, int n_total, void* stream_v) {
+    if (!md) return L2A_EINVAL;
+    l2a_ctx* ctx = md->ctx;
+    const std::string who = "l2a_policy_propose";
+    if (!pm) return fail(ctx, L2A_EINVAL, who + ": null policy model");
+    if (!obs0 || !sigma || !low || !high || !seq) return fail(ctx, L2A_EINVAL, who + ": null obs0/sigma/low/high/seq");
+    l2a_ctx* pm_ctx = nullptr;
+    int pm_obs = 0, pm_act = 0;
+    l2a_policy_model_facts(pm, &pm_ctx, &pm_obs, &pm_act);
+    if (pm_ctx != ctx) return fail(ctx, L2A_EINVAL, who + ": the policy model lives on another context");
+    if (pm_obs != md->obs_dim || pm_act != md->act_dim)
+        return fail(ctx, L2A_EINVAL, who + ": the policy model is for obs_dim " + std::to_string(pm_obs) + " / act_dim " +
+                    std::to_string(pm_act) + ", the dynamics model for " + std::to_string(md->obs_dim) + " / " + std::to_string(md->act_dim));
+    if (m < 1 || n < 1 || h < 1 || n_pi < 1) return fail(ctx, L2A_EINVAL, who + ": m, n, h and n_pi must be >= 1");
+    if (n_pi > n_total) return fail(ctx, L2A_EINVAL, who + ": n_pi " + std::to_string(n_pi) + " exceeds n_total " + std::to_string(n_total));
+    if (cand_offset < 0 || (long long)cand_offset + n > (long long)n_total)
+        return fail(ctx, L2A_EINVAL, who + ": cand_offset " + std::to_string(cand_offset) + " + n " + std::to_string(n) +
+                    " lies outside the n_total " + std::to_string(n_total) + " candidates");
+    if (md->mode == L2A_MODE_PER_BLOCK && m > md->n_sets)
+        return fail(ctx, L2A_EINVAL, who + ": per-block mode with m " + std::to_string(m) + " > n_sets " + std::to_string(md->n_sets));
+    if ((long long)m * n > 0x3fffffffLL || (long long)m * n_total * h * md->act_dim > 0x7fffffffffLL)
+        return fail(ctx, L2A_EINVAL, who + ": too many candidates");
+    const int npl = n_pi - cand_offset < n ? n_pi - cand_offset : n;       // this shard's proposal rows per env
+    if (npl < 1) return L2A_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    l2a_device_guard guard(ctx->device);
+    const long long rows = (long long)m * npl;
+    const long long need = rows * md->act_dim + 2 * rows * md->obs_dim + rows;
+    if (need > md->pol_buf_floats) {
+        if (md->pol_buf) { L2A_HIP(ctx, hipStreamSynchronize(stream)); L2A_HIP(ctx, hipFree(md->pol_buf)); md->pol_buf = nullptr; md->pol_buf_floats = 0; }
+        L2A_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&md->pol_buf), (size_t)need * sizeof(float)));
+        md->pol_buf_floats = need;
+    }
+    float* act_c = md->pol_buf;
+    float* st[2] = {act_c + rows * md->act_dim, act_c + rows * md->act_dim + rows * md->obs_dim};
+    float* carry_returns = st[1] + rows * md->obs_dim;
+    l2a_reward zero;
+    std::memset(&zero, 0, sizeof(zero));
+    for (int t = 0; t < h; ++t) {
+        const float* s_in = t == 0 ? obs0 : st[(t - 1) & 1];
+        int rc = l2a_policy_step_launch(pm, s_in, t > 0, m, npl, n, n_pi, h, t, cand_offset, z, seed, offset, sigma, low, high, act_c,
+                                        seq, mirror, stream);
+        if (rc != L2A_OK) return rc;
+        if (t == h - 1) break;
+        rc = plan_rs_chunk_as(md, md->mode, s_in, t > 0, act_c, m, npl, 1, 0, 1.0, &zero, cand_offset, nullptr, carry_returns, st[t & 1],
+                              nullptr, stream_v);
+        if (rc != L2A_OK) return rc;
+    }
+    return L2A_OK;
 }
 
 // ---- plans with a learned terminal value (l2a_value.hip) --------------------------------------------------------------------

@@ -182,6 +182,12 @@ extern "C" L2A_HIDDEN void l2a_model_facts(const l2a_model* md, l2a_ctx** ctx, i
 extern "C" L2A_HIDDEN void l2a_lstm_facts(const l2a_lstm* md, l2a_ctx** ctx, int* obs_dim, int* act_dim, int* units);
 extern "C" L2A_HIDDEN void l2a_reward_model_facts(const l2a_reward_model* rm, l2a_ctx** ctx, int* obs_dim, int* act_dim);
 extern "C" L2A_HIDDEN void l2a_value_model_facts(const l2a_value_model* vm, l2a_ctx** ctx, int* obs_dim);
+extern "C" L2A_HIDDEN void l2a_policy_model_facts(const l2a_policy_model* pm, l2a_ctx** ctx, int* obs_dim, int* act_dim);
+// l2a_policy.hip: one launch of the policy kernel for horizon step t of a proposal (l2a_policy_propose validates the arguments)
+extern "C" L2A_HIDDEN int l2a_policy_step_launch(l2a_policy_model* pm, const float* states, int state_per_row, int m, int npl, int n,
+                                                 int n_pi, int h, int t, int cand_offset, const float* z, unsigned long long seed,
+                                                 unsigned long long offset, const float* sigma, const float* low, const float* high,
+                                                 float* out, float* seq, float* mirror, hipStream_t stream);
 // The expansion launch of a particle plan (l2a_particles.hip; arguments validated by the caller, l2a_api.hip): obs0 [m, O] and
 // actions [h, m n, A] -> obs_x [m, E, O] and act_x [m, h, E n, A], each env's per-block request contiguous.
 // l2a_particle_expand_check: host only - the launch's own size refusals (L2A_EINVAL) for a destination in the model's aligned buffer,

@@ -57,6 +57,7 @@ class NativeModel(object):
         self.reward_model_plans = 0     # calls of plan_rs_reward_model
         self.value_plans = 0        # calls of plan_rs_value
         self.term_plans = 0         # calls of plan_rs_term
+        self.policy_proposals = 0   # calls of policy_propose
         self._spec_programs = {}    # RewardSpec -> its RewardProgram.from_spec (plan_rs_term scores a spec as a program)
 
     def close(self):
@@ -324,6 +325,33 @@ class NativeModel(object):
             raise _lib.L2AError("plans with a terminal value take a RewardSpec, a RewardProgram or a NativeRewardModel, not %s"
                                 % type(reward).__name__)
         self.ctx.check(rc, what)
+
+    def policy_propose(self, policy_model, obs0, m, n, n_pi, h, seq, sigma, low, high, mirror=None, n_total=None, cand_offset=0, z=None,
+                       seed=0, offset=0):
+        """Overwrite the first ``n_pi`` (global index ``cand_offset + j``) candidates of every env in ``seq`` ``[h, m * n, act_dim]``
+        - and in ``mirror`` ``[n_total, m, h * act_dim]`` when given - with ``policy_model`` (a ``NativePolicyModel``) rolled in
+        closed loop through this model from ``obs0`` ``[m, obs_dim]`` (``l2a_policy_propose``; include/l2a.h, "policy priors").
+        ``sigma`` / ``low`` / ``high``: fp32 CUDA ``[act_dim]``; ``z``: optional injected normals ``[h, m, n_pi, act_dim]``, else
+        the Philox stream of (``seed``, ``offset``).  Stream-ordered."""
+        if not hasattr(self.lib, "l2a_policy_propose"):
+            raise _lib.L2AError("this libl2a_hip.so has no policy kernel (l2a_policy_propose): rebuild it")
+        assert isinstance(policy_model, NativePolicyModel)
+        n_total = int(n) if n_total is None else int(n_total)
+        for t in (obs0, seq, sigma, low, high):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert obs0.numel() == m * self.obs_dim and seq.numel() == h * m * n * self.act_dim
+        assert sigma.numel() == self.act_dim and low.numel() == self.act_dim and high.numel() == self.act_dim
+        if mirror is not None:
+            assert mirror.is_cuda and mirror.dtype == torch.float32 and mirror.is_contiguous()
+            assert mirror.numel() == n_total * m * h * self.act_dim
+        if z is not None:
+            assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.numel() == h * m * n_pi * self.act_dim
+        self.policy_proposals += 1
+        rc = self.lib.l2a_policy_propose(self.handle, policy_model.handle, _ptr(obs0), int(m), int(n), int(n_pi), int(h),
+                                         int(cand_offset), _ptr(z), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                         _ptr(sigma), _ptr(low), _ptr(high), _ptr(seq), _ptr(mirror), n_total,
+                                         _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_policy_propose")
 
     def plan_rs_term(self, obs0, actions, m, n, h, discount, reward, termination, value_model=None, value_coef=1.0, cand_offset=0,
                      returns_out=None, steps_alive_out=None, best_key=None, traj_out=None):
@@ -656,6 +684,98 @@ class NativeRewardModel(object):
                                                  float(discount), int(cand_offset), _ptr(returns_out), _ptr(best_key),
                                                  _stream_ptr(self.device))
         self.ctx.check(rc, "l2a_score_trajectory_model")
+
+
+class NativePolicyModel(object):
+    """Python handle on an ``l2a_policy_model``: a policy MLP over the observation that proposes planning candidates, evaluated
+    on the matrix cores (``csrc/l2a_policy.hip``).  Raises ``L2AError`` on any failure."""
+
+    def __init__(self, obs_dim, act_dim, hidden_sizes, hidden_act, device=None):
+        if not torch.cuda.is_available():
+            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the policy kernel is HIP-only (there is no CPU fallback)")
+        if device is None:
+            device = torch.cuda.current_device()
+        self.ctx = _lib.Context.get(device)
+        self.lib = self.ctx.lib
+        if not hasattr(self.lib, "l2a_policy_model_create"):
+            raise _lib.L2AError("this libl2a_hip.so has no policy kernel (l2a_policy_model_create): rebuild it")
+        self.device = torch.device("cuda", device)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
+        if hidden_act not in _lib.ACT_CODES:
+            raise _lib.L2AError("nonlinearity %r is not supported by the HIP kernels" % (hidden_act,))
+        hid = (ctypes.c_int * len(self.hidden_sizes))(*self.hidden_sizes)
+        handle = ctypes.c_void_p()
+        rc = self.lib.l2a_policy_model_create(self.ctx.handle, self.obs_dim, self.act_dim, len(self.hidden_sizes), hid,
+                                              _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
+        self.ctx.check(rc, "l2a_policy_model_create")
+        self.handle = handle
+        self._keep = {}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.l2a_policy_model_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, params):
+        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]``; the first ``in`` is ``obs_dim``, the last ``out`` is
+        ``act_dim``."""
+        dev = []
+        for p in params:
+            t = torch.as_tensor(p) if not torch.is_tensor(p) else p
+            dev.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        sizes = (self.obs_dim,) + self.hidden_sizes + (self.act_dim,)
+        assert len(dev) == 2 * (len(sizes) - 1), "expected %d parameter arrays" % (2 * (len(sizes) - 1))
+        for li in range(len(sizes) - 1):
+            assert tuple(dev[2 * li].shape) == (sizes[li], sizes[li + 1]), \
+                "kernel %d has shape %s, expected %s" % (li, tuple(dev[2 * li].shape), (sizes[li], sizes[li + 1]))
+            assert tuple(dev[2 * li + 1].shape) == (sizes[li + 1],)
+        ptrs = (ctypes.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
+        rc = self.lib.l2a_policy_model_set_weights(self.handle, ptrs, _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_policy_model_set_weights")
+        self._keep["w"] = dev
+
+    def set_norm(self, norm):
+        """``norm``: dict ``'obs' / 'act' -> (mean, std)``, or ``None`` for identity."""
+        if norm is None:
+            null = ctypes.POINTER(ctypes.c_double)()
+            rc = self.lib.l2a_policy_model_set_norm(self.handle, null, null, null, null, _stream_ptr(self.device))
+        else:
+            keep, args = [], []
+            for key in ("obs", "act"):
+                for j in (0, 1):
+                    arr, p = _dvec(np.reshape(norm[key][j], -1))
+                    expect = self.act_dim if key == "act" else self.obs_dim
+                    assert arr.shape == (expect,), "normalization[%r] has shape %s" % (key, arr.shape)
+                    keep.append(arr)
+                    args.append(p)
+            rc = self.lib.l2a_policy_model_set_norm(self.handle, *args, _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_policy_model_set_norm")
+
+    def act(self, states, sigma, low, high, z=None, seed=0, offset=0, out=None):
+        """The kernel alone (``l2a_policy_act``): fp32 CUDA ``[rows, obs_dim]`` -> fp32 CUDA ``[rows, act_dim]``.  ``sigma`` /
+        ``low`` / ``high``: fp32 CUDA ``[act_dim]``; ``z``: optional normals ``[rows, act_dim]``, else the Philox stream."""
+        rows = int(states.shape[0])
+        for t in (states, sigma, low, high):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert tuple(states.shape) == (rows, self.obs_dim)
+        assert sigma.numel() == self.act_dim and low.numel() == self.act_dim and high.numel() == self.act_dim
+        if z is not None:
+            assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.numel() == rows * self.act_dim
+        if out is None:
+            out = torch.empty((rows, self.act_dim), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == rows * self.act_dim
+        rc = self.lib.l2a_policy_act(self.handle, _ptr(states), rows, _ptr(z), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(sigma), _ptr(low), _ptr(high), _ptr(out),
+                                     _stream_ptr(self.device))
+        self.ctx.check(rc, "l2a_policy_act")
+        return out
 
 
 class NativeValueModel(object):

@@ -73,7 +73,14 @@ with ``ensemble_planning="particles"`` or an explicit C controller step, which r
 whose next observation leaves a guarded range, and a ``value_model`` is folded into the surviving candidates only - one scoring
 launch behind the trajectory rollout, ``l2a_plan_rs_term``; random shooting, CEM, MPPI and iCEM alike; no host fallback, not with
 ``ensemble_planning="particles"``, an explicit C controller step or the recurrent planner, which raise at construction;
-``termination_diagnostics()`` copies the winner's ``steps_alive`` and the terminated share back on demand).
+``termination_diagnostics()`` copies the winner's ``steps_alive`` and the terminated share back on demand),
+``policy_model`` / ``policy_candidates`` / ``policy_fraction`` / ``policy_noise`` (a learned policy prior, ``MLPPolicyModel``: the first
+``n_pi = policy_candidates or max(1, round(policy_fraction * n))`` candidates of every env are the policy rolled in closed loop through
+the dynamics model, ``a_t = pi(s_t) + policy_noise * eps``, clipped to the action box - ``l2a_policy_propose``, written into the
+candidate tensor (and CEM's / MPPI's sample memory) in front of the unchanged rollout, so it composes with every scoring path;
+random shooting under ``rng="device"``, CEM in ``cem_mode="fixed"`` and MPPI; ``last_plan["policy_candidates"]`` is ``n_pi``, so
+``best_index < n_pi`` says the policy's proposal won; no host fallback, not with ``use_icem``, ``cem_mode="reference"``,
+``rng="numpy"``, an explicit C controller step or more than one rank, which raise).
 
 A tile-split launch whose exchange partner was not co-resident (another process on the GPU) flags a status
 word instead of hanging; the controller then switches the context to the unsplit geometry (bit-identical
@@ -139,9 +146,17 @@ class MPCController(Policy, Serializable):
             value_model=None,
             terminal_value_coef=1.0,
             termination=None,
+            policy_model=None,
+            policy_candidates=None,
+            policy_fraction=0.05,
+            policy_noise=0.0,
     ):
         self.dynamics_model = dynamics_model
         self.value_model = value_model
+        self.policy_model = policy_model
+        self.policy_candidates = policy_candidates
+        self.policy_fraction = float(policy_fraction)
+        self.policy_noise = policy_noise
         self.terminal_value_coef = float(terminal_value_coef)
         self.reward_model = reward_model
         self.discount = discount
@@ -248,6 +263,10 @@ class MPCController(Policy, Serializable):
         self._termination = termination if termination is not None else termination_spec_for_env(env)
         if self._termination is not None:
             self._check_termination()
+        if policy_model is not None:
+            self._check_policy_model()
+        self._pol_calls = 0         # `_policy_fill` calls since the seed below was first seen
+        self._pol_seed = None       # torch.initial_seed() the count belongs to: a changed seed restarts it
         self._term = None           # device tensors of the latest plan under a termination program (`termination_diagnostics`)
         self._ts1_calls = 0         # `_rollout` calls under particle_sampling="ts1" since the seed below was first seen
         self._ts1_seed = None       # torch.initial_seed() the count belongs to: a changed seed restarts it
@@ -307,6 +326,69 @@ class MPCController(Policy, Serializable):
                                 "RewardProgram) or, with use_reward_model, a reward model it scores (MLPRewardModel)")
         if not hasattr(self.dynamics_model, "planner_model"):
             raise _lib.L2AError("a value_model needs a dynamics model with a native planner (MLPDynamicsModel)")
+
+    def _check_policy_model(self):
+        """``policy_model=...``: the first ``n_pi`` candidates of every env are the policy rolled in closed loop through the
+        dynamics model on the GPU (``l2a_policy_propose``), written into the tensors the planner already holds directly in front
+        of ``_rollout`` - there is no host fallback, and the C controller steps, which draw and score in one call, do not apply."""
+        pm = self.policy_model
+        n = int(self.n_candidates)
+        if self.policy_candidates is not None:
+            n_pi = int(self.policy_candidates)
+        else:
+            if not (np.isfinite(self.policy_fraction) and 0.0 <= self.policy_fraction <= 1.0):
+                raise ValueError("policy_fraction must lie in [0, 1]")
+            n_pi = max(1, int(round(self.policy_fraction * n)))
+        if n_pi < 1:
+            raise ValueError("policy_candidates must be at least 1")
+        if n_pi > n:
+            raise _lib.L2AError("policy_candidates %d exceeds n_candidates %d" % (n_pi, n))
+        self._n_pi = n_pi
+        self._policy_sigma = self._sigma_vector(self.policy_noise, "policy_noise")
+        if self.rng != "device":
+            raise _lib.L2AError("a policy_model proposes its candidates on the device: pass rng='device' (the parity path returns "
+                                "the winner's action from the host copy of the candidates, which the proposal never reaches)")
+        if self.use_icem:
+            raise _lib.L2AError("a policy_model with use_icem is not built: the kept elites and the added mean own candidate slots")
+        if self.use_cem and self.cem_mode == "reference":
+            raise _lib.L2AError("a policy_model needs cem_mode='fixed': cem_mode='reference' rolls out the unclipped samples in "
+                                "candidate-major rows, which the proposal does not write")
+        if self.native_cem_step or self.native_mppi_step or self.native_icem_step:
+            raise _lib.L2AError("a policy_model plans through the Python loop: the C controller steps (native_cem_step, "
+                                "native_mppi_step, native_icem_step) draw and score in one call - leave them off")
+        if not hasattr(pm, "planner_policy_model"):
+            raise _lib.L2AError("policy_model must be a policy the library evaluates on the GPU (MLPPolicyModel): there is no "
+                                "host fallback")
+        why = pm.native_eligible() if hasattr(pm, "native_eligible") else None
+        if why is not None:
+            raise _lib.L2AError("policy_model is not eligible for the policy kernel (there is no host fallback): %s" % why)
+        if not self._fusable():
+            raise _lib.L2AError("a policy_model needs a plan the library scores: an env reward it knows (a RewardSpec or a "
+                                "RewardProgram) or, with use_reward_model, a reward model it scores (MLPRewardModel), and a "
+                                "dynamics model with a native planner (MLPDynamicsModel)")
+
+    def _policy_fill(self, obs_dev, seq, mirror, n_local, cand_offset):
+        """Overwrite candidates ``cand_offset + j < n_pi`` of every env in ``seq`` ``[h, m * n_local, act_dim]`` (and in ``mirror``,
+        the planner's ``a_clip`` ``[n, m, h * act_dim]``) with the policy's closed-loop proposal (``l2a_policy_propose``, 2 h - 1
+        launches, stream-ordered).  Every call - an RS step, a CEM / MPPI iteration, a relaunch after a flagged tile split - takes
+        the next ``h * m * n_pi * act_dim`` counters of a Philox stream of its own under ``torch.initial_seed()``."""
+        if self._dist()[1] > 1:
+            raise _lib.L2AError("a policy_model is not sharded at the controller level (the sharded CEM keeps a full a_clip on every "
+                                "rank): plan on one rank (shard_candidates=False), or call l2a_policy_propose per shard")
+        native = self.dynamics_model.planner_model()
+        dev = native.device
+        m, h, act_dim = int(obs_dev.shape[0]), self.horizon, self.action_space.shape[0]
+        const = self._bufs.get("pol_const")
+        if const is None or const[0].device != dev:
+            up = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)  # noqa: E731
+            const = self._bufs["pol_const"] = (up(self._policy_sigma), up(self.action_space.low), up(self.action_space.high))
+        seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        if seed != self._pol_seed:
+            self._pol_seed, self._pol_calls = seed, 0
+        offset = self._pol_calls * h * m * self._n_pi * act_dim
+        self._pol_calls += 1
+        native.policy_propose(self.policy_model.planner_policy_model(), obs_dev, m, n_local, self._n_pi, h, seq, const[0], const[1],
+                              const[2], mirror=mirror, n_total=self.n_candidates, cand_offset=cand_offset, seed=seed, offset=offset)
 
     _takes_termination = True       # (RNNMPCController: False - the recurrent planner scores no termination program)
 
@@ -501,10 +583,11 @@ class MPCController(Policy, Serializable):
         launch, the horizon-chunked pipelines, the C controllers - declines.  A particle plan (``ensemble_planning="particles"``)
         is scored behind its rollouts too, whatever its reward, and stays on ``_rollout`` the same way; so does a plan with a
         ``value_model``: its terminal value is folded in by a launch behind the rollout (``l2a_plan_rs_value`` and its siblings);
-        and so does a plan under a termination program, scored by ``l2a_plan_rs_term`` behind the trajectory rollout."""
+        and so does a plan under a termination program, scored by ``l2a_plan_rs_term`` behind the trajectory rollout; and so does a
+        plan with a ``policy_model``, whose proposal is written into the candidate tensor in front of ``_rollout``."""
         return (self.ensemble_planning == "particles" or isinstance(self._reward_spec, RewardProgram)
                 or self._native_reward_model() is not None or self.__dict__.get("value_model") is not None
-                or self.__dict__.get("_termination") is not None)
+                or self.__dict__.get("_termination") is not None or self.__dict__.get("policy_model") is not None)
 
     def _buf(self, key, shape, dtype, device):
         t = self._bufs.get(key)
@@ -677,7 +760,8 @@ class MPCController(Policy, Serializable):
             native.plan_rs_reward_model(obs0, actions_local, m, n_local, self.horizon, self.discount, rm.planner_reward_model(),
                                         cand_offset=cand_offset, returns_out=rets, best_key=best)
             return best, rets
-        plan = native.plan_rs_program if self._program() else native.plan_rs
+        # (a policy prior holds `_program()` with any reward kind: the fused formula keeps its own entry)
+        plan = native.plan_rs_program if isinstance(self._reward_spec, RewardProgram) else native.plan_rs
         plan(obs0, actions_local, m, n_local, self.horizon, self.discount, self._reward_spec,
              cand_offset=cand_offset, returns_out=rets, best_key=best)
         return best, rets
@@ -980,6 +1064,8 @@ class MPCController(Policy, Serializable):
                 a_dev.mul_(high - low).add_(low)
 
             def relaunch():
+                if self.__dict__.get("policy_model") is not None and n_local > 0:
+                    self._policy_fill(self._upload_obs(observations), a_dev, None, n_local, lo)
                 return self._plan_keys(observations, a_dev, n_local, lo, world)
             best = relaunch()
 
@@ -989,6 +1075,8 @@ class MPCController(Policy, Serializable):
         for i in range(m):
             best_ret[i], idx[i] = _lib.key_decode(keys[i])
         self.last_plan = dict(best_index=idx, best_return=best_ret, n_local=n_local, shard=(lo, hi))
+        if self.__dict__.get("policy_model") is not None:
+            self.last_plan["policy_candidates"] = self._n_pi
 
         if cand_a is not None:
             return cand_a[range(m), idx]
@@ -1404,6 +1492,8 @@ class MPCController(Policy, Serializable):
                                          1 if reference else 0, lo, hi, _ptr(a_clip), _ptr(a_raw),
                                          _ptr(seq) if n_local > 0 else None, _stream_ptr(dev)), "l2a_cem_sample")
             if n_local > 0:
+                if self.__dict__.get("policy_model") is not None:
+                    self._policy_fill(obs_dev, seq, a_clip, n_local, lo)
                 _, r_loc = self._rollout(observations, seq, n_local, lo, want_returns=True, obs_dev=obs_dev)
             else:
                 r_loc = torch.zeros((m, 0), dtype=torch.float32, device=dev)
@@ -1449,6 +1539,8 @@ class MPCController(Policy, Serializable):
             return self.get_cem_action_device(observations, retry=True)      # same counters: the same normals again
         self._bufs["cem_calls"] = call0 + self.num_cem_iters
         self.last_plan = dict(best_index=best_index, best_return=best_return, cem_mean=mean_h, cem_std=std_h)
+        if self.__dict__.get("policy_model") is not None:
+            self.last_plan["policy_candidates"] = self._n_pi
         return out
 
     def _native_cem_step(self, observations):
@@ -1781,6 +1873,8 @@ class MPCController(Policy, Serializable):
                                           _ptr(means[src]), _ptr(first if it == 0 else shifts[1]), _ptr(sigma), self.mppi_beta,
                                           _ptr(low), _ptr(high), n, m, h, act_dim, _ptr(means[dst]), _ptr(a_clip), _ptr(seq),
                                           _stream_ptr(dev)), "l2a_mppi_sample")
+            if self.__dict__.get("policy_model") is not None:
+                self._policy_fill(obs_dev, seq, a_clip, n, 0)
             _, rets = self._rollout(observations, seq, n, 0, want_returns=True, obs_dev=obs_dev)
             ctx.check(lib.l2a_mppi_update(ctx.handle, _ptr(rets), _ptr(a_clip), n, m, h, act_dim, self.mppi_kappa, _ptr(means[dst]),
                                           _ptr(packed), _stream_ptr(dev)), "l2a_mppi_update")
@@ -1798,6 +1892,8 @@ class MPCController(Policy, Serializable):
                               mppi_mean=host[m * width:m * width + m * D].reshape(m, D).copy(),
                               mppi_ess=head[:, act_dim + 2].copy(),
                               mppi_valid=head[:, act_dim + 3].copy().view(np.int32).astype(np.int64))
+        if self.__dict__.get("policy_model") is not None:
+            self.last_plan["policy_candidates"] = self._n_pi
         return head[:, :act_dim].astype(np.float64)
 
     # ------------------------------------------------------------------ iCEM (Pinneri et al. 2020: CEM with memory and coloured noise)
