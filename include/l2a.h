@@ -183,6 +183,12 @@ int l2a_set_fan(l2a_ctx* ctx, int on);
  * weight set per candidate (single model, per-block sets), 3 - 4 % faster per round than the general instances.
  * 1 (default) = wherever they apply, 0 = never (general instances only).  Geometry only: results are bit-identical.   */
 int l2a_set_double_rounds(l2a_ctx* ctx, int on);
+/* Static three-set step of the tile split (hidden width 512, two hidden layers, up to 32 inputs, relu / identity).  Under the
+ * shared-set tile split a mean ensemble of FIVE sets gives every workgroup the same sequence per horizon step - two full
+ * sets, then its half of the shared one, in one batch (BASELINE config 2).  Kernel instances that know this sequence at compile
+ * time run the step as straight-line code; every other plan keeps the general instances.  1 (default) = wherever the plan is
+ * exactly that sequence, 0 = never (environment default: L2A_SEQ3).  Schedule only: results are bit-identical.           */
+int l2a_set_seq3(l2a_ctx* ctx, int on);
 /* Micro tiles (csrc/l2a_micro.h).  A plan whose 16-candidate tiles would leave CUs idle - e.g. the reference's own default
  * plans, run_grbal.py:84-85 / run_rebal.py:77-78: 5 x 500 candidates = 160 tiles on 256 CUs - can run in candidate tiles of
  * FOUR on v_mfma_f32_4x4x1_16b_f32 instead: workgroups of 4, 8 or 12 candidates, every CU busy, no exchange between
@@ -1479,6 +1485,11 @@ int l2a_controller_stats(l2a_controller* controller, double* out, int cap);
  * on the geometry (bit-identical); this is how tests/test_host_logic.py pins the routing table without a GPU.          */
 int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, int n_sets, int mode, int m, int n, int h,
                       const int* policy, int* out);
+/* The same with counted arrays: policy[n_policy <= 7] = the five above, then {sets per batch (l2a_set_batch; negative = the
+ * default 0), static three-set step (l2a_set_seq3; negative = the default 1)}; out[n_out = 12 | 13] = the twelve above, then 1
+ * when the described launch runs on a static three-set-step instance (the other twelve do not depend on that switch).     */
+int l2a_plan_geometry_ex(int obs_dim, int act_dim, int n_hidden, const int* hidden, int n_sets, int mode, int m, int n, int h,
+                         const int* policy, int n_policy, int* out, int n_out);
 /* The same for the recurrent launcher: which launch the library picks for a request of m envs x n candidates x h steps on the
  * model l2a_rnn_create builds from (obs_dim, act_dim, n_layers, units[], cell_type) - n_layers == 0: the model of
  * l2a_lstm_create with units[0] units - as the launcher's own plan function decides it, without a HIP call.

@@ -30,13 +30,13 @@ KERNEL_CODES = {"auto": 0, "mfma": 1, "valu": 2}
 CELL_CODES = {"lstm": 0, "gru": 1, "rnn": 2}
 
 EXPORTED_SYMBOLS = (
-    "l2a_init", "l2a_destroy", "l2a_last_error", "l2a_device_info", "l2a_set_kernel", "l2a_set_split", "l2a_set_batch", "l2a_set_xcd_align", "l2a_set_fan", "l2a_set_double_rounds", "l2a_set_micro",
+    "l2a_init", "l2a_destroy", "l2a_last_error", "l2a_device_info", "l2a_set_kernel", "l2a_set_split", "l2a_set_batch", "l2a_set_xcd_align", "l2a_set_fan", "l2a_set_double_rounds", "l2a_set_seq3", "l2a_set_micro",
     "l2a_launch_status", "l2a_set_debug_buffer", "l2a_set_spin_limit", "l2a_inject_status",
     "l2a_model_create", "l2a_model_destroy", "l2a_model_set_weights", "l2a_model_set_weights_strided",
     "l2a_model_set_norm", "l2a_model_adapt_sgd", "l2a_model_adapt_sgd_host", "l2a_model_adapt_sgd_raw", "l2a_model_get_weights",
     "l2a_plan_rs", "l2a_plan_rs_sync", "l2a_plan_rs_chunk", "l2a_reward_program_check", "l2a_score_trajectory", "l2a_plan_rs_program",
     "l2a_reward_model_check", "l2a_reward_model_geometry", "l2a_reward_model_create", "l2a_reward_model_destroy", "l2a_reward_model_set_weights", "l2a_reward_model_set_norm",
-    "l2a_reward_model_predict", "l2a_score_trajectory_model", "l2a_plan_rs_reward_model", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry",
+    "l2a_reward_model_predict", "l2a_score_trajectory_model", "l2a_plan_rs_reward_model", "l2a_predict", "l2a_key_encode", "l2a_key_decode", "l2a_mfma_eligible", "l2a_plan_geometry", "l2a_plan_geometry_ex",
     "l2a_packed_layer_floats", "l2a_pack_layer_host", "l2a_micro_layout_floats", "l2a_micro_pack_layer_host",
     "l2a_comm_unique_id", "l2a_comm_init", "l2a_comm_destroy", "l2a_allreduce_best", "l2a_plan_payload",
     "l2a_cem_sample", "l2a_cem_refit", "l2a_cem_pick", "l2a_cem_refit_sample", "l2a_cem_refit_sample_fused",
@@ -104,23 +104,28 @@ def mlp_traj_geometry(obs_dim, act_dim, n_hidden, hidden, mode, n_sets, m, n, h,
     return dict(single=bool(v[0]), launches=v[1], workgroups=v[2], workgroups_per_env=v[3], micro_tiles=v[4], full_workgroups=v[5])
 
 
-def plan_geometry(obs_dim, act_dim, hidden, n_sets, mode, m, n, h, split=-1, fan=-1, micro=-1, cus=0, double=-1):
+def plan_geometry(obs_dim, act_dim, hidden, n_sets, mode, m, n, h, split=-1, fan=-1, micro=-1, cus=0, double=-1, batch=-1, seq3=-1):
     """The launch geometry the library would pick for this plan (``l2a_plan_geometry``: the launcher's own decision code, no
     GPU needed).  Returns a dict: kernel ('valu' | 'mfma16' | 'micro'), nt, split (0 none, 1 whole sets, 2 shared half member,
     3 member fan), split_from, fan, workgroups, lds_bytes, sets_per_batch, micro_tiles, placement_units, front_workgroups
     (double-tile workgroups of a launch IN FRONT of the described one: ``l2a_set_double_rounds``), whole_instance (the
-    described launch runs on a whole-tiles-only kernel instance)."""
+    described launch runs on a whole-tiles-only kernel instance), seq3 (it runs on a static three-set-step instance:
+    ``l2a_set_seq3``).  ``batch`` / ``seq3``: the policies of ``l2a_set_batch`` / ``l2a_set_seq3`` (-1 = their defaults)."""
     lib = load()
     hid = (ctypes.c_int * len(hidden))(*[int(x) for x in hidden])
-    pol = (ctypes.c_int * 5)(int(split), int(fan), int(micro), int(cus), int(double))
-    out = (ctypes.c_int * 12)()
-    rc = lib.l2a_plan_geometry(int(obs_dim), int(act_dim), len(hidden), hid, int(n_sets), MODE_CODES[mode], int(m), int(n), int(h), pol, out)
+    pol = (ctypes.c_int * 7)(int(split), int(fan), int(micro), int(cus), int(double), int(batch), int(seq3))
+    out = (ctypes.c_int * 13)()
+    if hasattr(lib, "l2a_plan_geometry_ex"):
+        rc = lib.l2a_plan_geometry_ex(int(obs_dim), int(act_dim), len(hidden), hid, int(n_sets), MODE_CODES[mode], int(m), int(n), int(h),
+                                      pol, 7, out, 13)
+    else:       # (an older variant library selected with L2A_LIB_PATH: neither the two policies nor the field)
+        rc = lib.l2a_plan_geometry(int(obs_dim), int(act_dim), len(hidden), hid, int(n_sets), MODE_CODES[mode], int(m), int(n), int(h), pol, out)
     if rc != L2A_OK:
         raise L2AError("l2a_plan_geometry failed (%d)" % rc)
     v = list(out)
     return dict(kernel=("valu", "mfma16", "micro")[v[0]], nt=v[1], split=v[2], split_from=v[3], fan=bool(v[4]), workgroups=v[5],
                 lds_bytes=v[6], sets_per_batch=v[7], micro_tiles=v[8], placement_units=v[9], front_workgroups=v[10],
-                whole_instance=bool(v[11]))
+                whole_instance=bool(v[11]), seq3=bool(v[12]))
 
 
 LSTM_FAMILIES = ("lstm_valu", "lstm_mfma16", "lstm_micro", "lstm_micro_traj", "generic_valu", "generic_mfma16", "generic_micro")
@@ -274,6 +279,11 @@ def load():
     else:
         lib.l2a_set_fan.argtypes = [vp, i32]
         lib.l2a_set_fan.restype = i32
+    if os.environ.get("L2A_LIB_PATH") and not hasattr(lib, "l2a_set_seq3"):
+        lib.l2a_set_seq3 = lambda handle, on: 0
+    else:
+        lib.l2a_set_seq3.argtypes = [vp, i32]
+        lib.l2a_set_seq3.restype = i32
     if os.environ.get("L2A_LIB_PATH") and not hasattr(lib, "l2a_set_double_rounds"):
         lib.l2a_set_double_rounds = lambda handle, on: 0
     else:
@@ -405,6 +415,9 @@ def load():
     lib.l2a_mfma_eligible.restype = i32
     lib.l2a_plan_geometry.argtypes = [i32, i32, i32, c.POINTER(i32), i32, i32, i32, i32, i32, c.POINTER(i32), c.POINTER(i32)]
     lib.l2a_plan_geometry.restype = i32
+    if hasattr(lib, "l2a_plan_geometry_ex") or not os.environ.get("L2A_LIB_PATH"):
+        lib.l2a_plan_geometry_ex.argtypes = [i32, i32, i32, c.POINTER(i32), i32, i32, i32, i32, i32, c.POINTER(i32), i32, c.POINTER(i32), i32]
+        lib.l2a_plan_geometry_ex.restype = i32
     lib.l2a_packed_layer_floats.argtypes = [i32, i32]
     lib.l2a_packed_layer_floats.restype = c.c_longlong
     lib.l2a_pack_layer_host.argtypes = [c.POINTER(f32), i32, i32, c.POINTER(f32)]
@@ -712,6 +725,11 @@ class Context(object):
     def set_fan(self, on):
         """Member fan: small mean-ensemble plans on one workgroup per (candidate tile, member) - default on; bit-identical."""
         self.check(self.lib.l2a_set_fan(self.handle, int(bool(on))), "l2a_set_fan")
+
+    def set_seq3(self, on):
+        """Static three-set step: five-set mean ensembles under the shared-set tile split (2 x 512) run kernel instances that know
+        the full, full, shared sequence at compile time - default on; bit-identical."""
+        self.check(self.lib.l2a_set_seq3(self.handle, int(bool(on))), "l2a_set_seq3")
 
     def set_double_rounds(self, on):
         """Double rounds: multi-round plans at width 512 run their first rounds on two-tile workgroups - default on; bit-identical."""

@@ -2,8 +2,8 @@
 
     python learning_to_adapt_amd/csrc/build.py [--force]
 
-The MFMA kernel template is instantiated in ten translation units (one per (NT, TPW) pair, the four
-member-fan units and the whole-tiles unit), the LSTM kernel in three (one per units / 64), the micro-tile kernels in four (the
+The MFMA kernel template is instantiated in twelve translation units (one per (NT, TPW) pair, the four
+member-fan units, the two whole-tiles units and the static three-set step), the LSTM kernel in three (one per units / 64), the micro-tile kernels in four (the
 fused instances, the two trajectory-writing units, the generic recurrent cells); all are compiled in parallel and linked with the
 API units.
 """
@@ -29,6 +29,8 @@ FAN_INSTANCES = [(1, 2), (1, 4), (1, 8), (2, 8)]
 # whole-tiles-only instances (-DL2A_INST_FAN=2: neither exchange nor half-member code): two candidate tiles per workgroup at
 # width 512 - the double rounds launch_rollout puts in front of a multi-round plan
 WHOLE_INSTANCES = [(2, 8), (1, 8)]
+# the static three-set step of the tile split (-DL2A_INST_FAN=3: full, full, shared written out; l2a_mfma.h SEQ3)
+SEQ3_INSTANCES = [(1, 8)]
 LSTM_INSTANCES = [2, 4, 8]          # UTW = units / 64
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # Rollout kernels: MFMA accumulators in architectural VGPRs where the allocator can afford it - every epilogue reads its
@@ -142,6 +144,9 @@ def unit_table():
     for nt, tpw in WHOLE_INSTANCES:
         t["l2a_mfma_whole_%d_%d.o" % (nt, tpw)] = ("l2a_mfma_inst.hip", ["-DL2A_INST_NT=%d" % nt, "-DL2A_INST_TPW=%d" % tpw,
                                                                           "-DL2A_INST_FAN=2"] + KERNEL_FLAGS)
+    for nt, tpw in SEQ3_INSTANCES:
+        t["l2a_mfma_seq3_%d_%d.o" % (nt, tpw)] = ("l2a_mfma_inst.hip", ["-DL2A_INST_NT=%d" % nt, "-DL2A_INST_TPW=%d" % tpw,
+                                                                         "-DL2A_INST_FAN=3"] + KERNEL_FLAGS)
     return t
 
 
@@ -196,7 +201,7 @@ def build(force=False, verbose=True, only=None):
     for o, (src, flags) in table.items():
         obj = os.path.join(OBJ_DIR, o)
         if only is not None and o.startswith("l2a_mfma_") and os.path.exists(obj) and \
-                tuple(int(x) for x in o[len("l2a_mfma_"):-2].replace("fan_", "").replace("whole_", "").split("_")) not in only:
+                tuple(int(x) for x in o[len("l2a_mfma_"):-2].replace("fan_", "").replace("whole_", "").replace("seq3_", "").split("_")) not in only:
             continue
         if not force and only is None and _obj_fresh(obj):
             continue

@@ -119,7 +119,7 @@ int allow_big_lds(const l2a_ctx* ctx, K kernel, int bytes) {
 // What the decision depends on beside the model and the request: the context's policies and device facts, and the two
 // developer switches of the environment (read once, here).
 struct l2a_rollout_policy {
-    int kernel_kind, split_policy, fan_policy, double_policy, micro_policy, batch_sets, xcd_align;
+    int kernel_kind, split_policy, fan_policy, double_policy, micro_policy, batch_sets, xcd_align, seq3_policy;
     int num_cu, lds_per_block;
     int force_nt;           // L2A_FORCE_NT=1 | 2: developer A/B of the NT choice (tools/ab_nt.py); 0 = choose_nt decides
     bool dbg_front;         // L2A_DBG_FRONT=1: of two launches the double tiles in front write the phase stamps (launch_rollout)
@@ -129,7 +129,7 @@ l2a_rollout_policy rollout_policy(const l2a_ctx* ctx) {
     static const int force_nt = [] { const char* e = std::getenv("L2A_FORCE_NT"); return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }();
     static const bool dbg_front = [] { const char* e = std::getenv("L2A_DBG_FRONT"); return e && e[0] == '1'; }();
     return {ctx->kernel_kind, ctx->split_policy, ctx->fan_policy, ctx->double_policy, ctx->micro_policy, ctx->batch_sets,
-            ctx->xcd_align, ctx->num_cu > 0 ? ctx->num_cu : 256, ctx->lds_per_block, force_nt, dbg_front};
+            ctx->xcd_align, ctx->seq3_policy, ctx->num_cu > 0 ? ctx->num_cu : 256, ctx->lds_per_block, force_nt, dbg_front};
 }
 
 struct l2a_rollout_request {
@@ -402,7 +402,13 @@ int plan_rollout(const l2a_mlp_shape& md, const l2a_rollout_policy& pol, const l
     // general instances (config 5's iteration, five sets in batches of three: +3.4 % on the whole-tiles-only one)
     const bool whole1 = !fan && pol.double_policy != 0 && e_loop == 1 && nt == 1 && md.TPW == 8 && md.OT <= 3 &&
                         d.split == 0 && d.split_from < 0;
-    d.geo = fan ? 1 : whole1 ? 2 : 0;
+    // The static three-set step (l2a_mfma.h SEQ3): a uniform tile split with a shared set whose every workgroup runs exactly
+    // full, full, shared in ONE batch - a mean ensemble of five sets with two hidden layers of 512 (config 2: A = 0, 1, 2;
+    // B = 3, 4, 2) - on the shapes of the early exchange (up to 32 inputs, relu / identity).  Its instances know the sequence at
+    // compile time; same arithmetic in the same order: bit-identical.
+    const bool seq3 = pol.seq3_policy != 0 && !fan && !whole1 && !gact && nt == 1 && md.TPW == 8 && md.OT <= 2 && md.KG0 <= 2 &&
+                      md.n_hidden == 2 && rq.mode == L2A_MODE_MEAN && e_loop == 5 && d.split == 2 && d.split_from < 0 && d.lb == 3;
+    d.geo = fan ? 1 : whole1 ? 2 : seq3 ? 3 : 0;
     // what the mailbox counts: one per workgroup that owns a tile's (or micro-tile group's) key, over both launches
     if (front_k) plan->done_total = (int)(front.grid + pairs);
     return L2A_OK;
@@ -637,6 +643,8 @@ int l2a_init(int device, l2a_ctx** out) {
     if (fn && (fn[0] == '0' || fn[0] == '1')) ctx->fan_policy = fn[0] - '0';
     const char* db = std::getenv("L2A_DOUBLE");
     if (db && (db[0] == '0' || db[0] == '1')) ctx->double_policy = db[0] - '0';
+    const char* s3 = std::getenv("L2A_SEQ3");
+    if (s3 && (s3[0] == '0' || s3[0] == '1')) ctx->seq3_policy = s3[0] - '0';
     const char* bs = std::getenv("L2A_BATCH");
     if (bs && bs[0] >= '0' && bs[0] <= '4') ctx->batch_sets = bs[0] - '0';
     const char* mc = std::getenv("L2A_MICRO");
@@ -657,18 +665,24 @@ void l2a_destroy(l2a_ctx* ctx) {
 
 int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, int n_sets, int mode, int m, int n, int h,
                       const int* policy, int* out) {
+    return l2a_plan_geometry_ex(obs_dim, act_dim, n_hidden, hidden, n_sets, mode, m, n, h, policy, policy ? 5 : 0, out, 12);
+}
+
+int l2a_plan_geometry_ex(int obs_dim, int act_dim, int n_hidden, const int* hidden, int n_sets, int mode, int m, int n, int h,
+                         const int* policy, int n_policy, int* out, int n_out) {
+    if (n_policy < 0 || n_policy > 7 || n_out < 12 || n_out > 13 || (n_policy > 0 && !policy)) return L2A_EINVAL;
     if (!hidden || !out || obs_dim < 1 || act_dim < 1 || n_hidden < 1 || n_hidden > L2A_MAX_LAYERS - 1 || n_sets < 1 || m < 1 || n < 1 || h < 1)
         return L2A_EINVAL;
     l2a_ctx ctx;                                    // (its default policies; never touches a device)
     ctx.num_cu = 256;
     ctx.lds_per_block = 160 * 1024;
-    if (policy) {
-        if (policy[0] >= 0) ctx.split_policy = policy[0];
-        if (policy[1] >= 0) ctx.fan_policy = policy[1];
-        if (policy[2] >= 0) ctx.micro_policy = policy[2];
-        if (policy[3] > 0) ctx.num_cu = policy[3];
-        if (policy[4] >= 0) ctx.double_policy = policy[4];
-    }
+    if (n_policy > 0 && policy[0] >= 0) ctx.split_policy = policy[0];
+    if (n_policy > 1 && policy[1] >= 0) ctx.fan_policy = policy[1];
+    if (n_policy > 2 && policy[2] >= 0) ctx.micro_policy = policy[2];
+    if (n_policy > 3 && policy[3] > 0) ctx.num_cu = policy[3];
+    if (n_policy > 4 && policy[4] >= 0) ctx.double_policy = policy[4];
+    if (n_policy > 5 && policy[5] >= 0) ctx.batch_sets = policy[5];
+    if (n_policy > 6 && policy[6] >= 0) ctx.seq3_policy = policy[6];
     l2a_mlp_shape md;
     model_shape(&md, obs_dim, act_dim, n_hidden, hidden, L2A_ACT_RELU, L2A_ACT_IDENTITY, n_sets, mode);
     l2a_rollout_plan plan;
@@ -678,9 +692,9 @@ int l2a_plan_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden,
     // the plan's last launch, and the workgroups of the double tiles in front of it if there are any
     const l2a_rollout_launch& d = plan.launch[plan.n_launch - 1];
     const bool mfma16 = d.family == L2A_FAMILY_MFMA16;
-    const int g[12] = {d.family, d.nt, d.split, mfma16 ? d.split_from : -1, d.geo == 1, (int)d.grid, d.smem, mfma16 ? d.lb : 1,
-                       d.mc_hi, d.pl_units, plan.n_launch == 2 ? (int)plan.launch[0].grid : 0, d.geo == 2};
-    std::memcpy(out, g, sizeof(g));
+    const int g[13] = {d.family, d.nt, d.split, mfma16 ? d.split_from : -1, d.geo == 1, (int)d.grid, d.smem, mfma16 ? d.lb : 1,
+                       d.mc_hi, d.pl_units, plan.n_launch == 2 ? (int)plan.launch[0].grid : 0, d.geo == 2, d.geo == 3};
+    std::memcpy(out, g, sizeof(int) * n_out);
     return L2A_OK;
 }
 
@@ -723,6 +737,13 @@ int l2a_set_fan(l2a_ctx* ctx, int on) {
     if (!ctx) return L2A_EINVAL;
     if (on != 0 && on != 1) return fail(ctx, L2A_EINVAL, "member fan must be 0 or 1");
     ctx->fan_policy = on;
+    return L2A_OK;
+}
+
+int l2a_set_seq3(l2a_ctx* ctx, int on) {
+    if (!ctx) return L2A_EINVAL;
+    if (on != 0 && on != 1) return fail(ctx, L2A_EINVAL, "static three-set step must be 0 or 1");
+    ctx->seq3_policy = on;
     return L2A_OK;
 }
 

@@ -62,7 +62,13 @@
 // own instances: compile-time, so that neither path keeps the other's operand registers alive - with the run-time
 // test the register allocator carried the GEMM's prefetch registers through the whole kernel, 475 instead of ~410
 // VGPRs on the HalfCheetah instance), O4 = the last obs tile has at most four live units (HalfCheetah: 20 = 16 + 4):
-// it is computed with the 4x4x1 MFMA instead of a 16-row tile that is three quarters padding (l2a_out_phase).
+// it is computed with the 4x4x1 MFMA instead of a 16-row tile that is three quarters padding (l2a_out_phase), SEQ3 (last: profile
+// tools find the headline kernel by the leading parameters) = the static three-set step: a uniformly tile-split workgroup whose
+// sequence is full, full, shared in ONE batch (mean ensemble of five, two hidden layers of 512, up to 32 inputs; plan_rollout
+// selects it) - p.lb, p.split, the set roles and the ensemble size are compile-time facts, so phases A and B are straight-line
+// code over the three sets (no back-edge or uniform branch between them for the scheduler to stop at), the half member's GEMM
+// runs four k-groups ahead (l2a_half_gemm_ring) and phase C is one pass.  Same arithmetic in the same order: same bits.  Config 2
+// 1.3771 -> 1.3360 ms (profiles/r08_ab_seq3.jsonl).
 #pragma once
 
 #include <type_traits>
@@ -295,6 +301,84 @@ __device__ __forceinline__ void l2a_hidden_gemm(__amdgpu_buffer_rsrc_t rs, __amd
     }
 }
 
+// The half member's last hidden layer in the static three-set step (SEQ3): TPW / 2 tiles per wave, so a stage holds half the
+// MFMAs of a full member's and a prefetch distance of two k-groups is half as long in clocks.  Here the weights run FOUR
+// k-groups ahead through a ring of eight buffers (a buffer is refilled four stages after its last use; five are alive at any
+// time: +32 VGPRs), the activations two ahead through four as before.  pfA / pfB arrive with k-groups 0 | 2 and 1 | 3 of this
+// wave's tiles (the previous set's output phase issued them); the last two stages request the output layer's fragments and the
+// epilogue's bias vectors, like l2a_hidden_gemm<LAST>.  Same MFMAs in the same order per accumulator: same bits.
+template <int NT, int TPW, int OT>
+__device__ __forceinline__ void l2a_half_gemm_ring(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rsn, int sb, int tile0,
+                                                   const f32x4* hin, const f32x4 (&pfA)[TPW], const f32x4 (&pfB)[TPW],
+                                                   f32x4 (&pfO)[TPW][OT], f32x4 (&acc)[NT][TPW], int lane, int lane16,
+                                                   const float* bias_lds, f32x4 (&bias)[TPW], const int (&olane)[OT]) {
+    constexpr int HT = L2A_NW * TPW;
+    constexpr int TW = TPW / 2;
+    static_assert(HT % 8 == 0 && HT >= 16, "the ring is unrolled by 8 and its last iteration is peeled");
+    f32x4 a[8][TW], b[4][NT];
+#pragma unroll
+    for (int tt = 0; tt < TW; ++tt) {
+        a[0][tt] = pfA[tt]; a[1][tt] = pfB[tt];
+        a[2][tt] = pfA[TW + tt]; a[3][tt] = pfB[TW + tt];
+    }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        b[0][nt] = hin[(nt * HT + 0) * 64 + lane];
+        b[1][nt] = hin[(nt * HT + 1) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < TW; ++tt) acc[nt][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) { L2A_OPAQUE(b[0][nt]); L2A_OPAQUE(b[1][nt]); }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // stage k of an iteration: MFMAs of k-group g + k (a[k], b[k & 3]); weights of g + k + 4 -> a[(k + 4) & 7], activations of
+    // g + k + 2 -> b[(k + 2) & 3].  (the k-group inside four stages is the load's 12-bit immediate: two scalar bases)
+#pragma unroll 1
+    for (int g = 0; g < HT - 8; g += 8) {
+        const int soff = (g + 4) * 1024;
+        L2A_STAGE_S(a[0], b[0], a[4], b[2], soff, 0, g + 2)
+        L2A_STAGE_S(a[1], b[1], a[5], b[3], soff, 1024, g + 3)
+        L2A_STAGE_S(a[2], b[2], a[6], b[0], soff, 2048, g + 4)
+        L2A_STAGE_S(a[3], b[3], a[7], b[1], soff, 3072, g + 5)
+        L2A_STAGE_S(a[4], b[0], a[0], b[2], soff + 4096, 0, g + 6)
+        L2A_STAGE_S(a[5], b[1], a[1], b[3], soff + 4096, 1024, g + 7)
+        L2A_STAGE_S(a[6], b[2], a[2], b[0], soff + 4096, 2048, g + 8)
+        L2A_STAGE_S(a[7], b[3], a[3], b[1], soff + 4096, 3072, g + 9)
+    }
+    // ---- peeled last iteration (k-groups HT-8 .. HT-1): the last four weight groups, the last six activation groups ----
+    L2A_STAGE_S(a[0], b[0], a[4], b[2], (HT - 4) * 1024, 0, HT - 6)
+    L2A_STAGE_S(a[1], b[1], a[5], b[3], (HT - 4) * 1024, 1024, HT - 5)
+    L2A_STAGE_S(a[2], b[2], a[6], b[0], (HT - 4) * 1024, 2048, HT - 4)
+    L2A_STAGE_S(a[3], b[3], a[7], b[1], (HT - 4) * 1024, 3072, HT - 3)
+    { L2A_STAGE_REST(a[4], b[0], b[2], HT - 2, 0) }
+    { L2A_STAGE_REST(a[5], b[1], b[3], HT - 1, 0) }
+    {   // the output layer's A fragments (obs tile c, k-group = hidden tile tile0 + tt), half of them per stage
+        int so_ = tile0 * 1024;
+        L2A_OPAQUE_S(so_);
+#pragma unroll
+        for (int tt = 0; tt < L2A_PFT(TW, OT); ++tt)
+#pragma unroll
+            for (int c = 0; c < OT; ++c)
+                if (((tt * OT + c) & 1) == 0) pfO[tt][c] = l2a_ldw(rsn, olane[c], so_ + (tt + c * HT) * 1024);
+        L2A_STAGE_MFMA(a[6], b[2])
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    {   // and the epilogue's bias vectors (LDS), under the last MFMAs
+#pragma unroll
+        for (int tt = 0; tt < TW; ++tt) bias[tt] = *reinterpret_cast<const f32x4*>(bias_lds + 16 * tt);
+        int so_ = tile0 * 1024;
+        L2A_OPAQUE_S(so_);
+#pragma unroll
+        for (int tt = 0; tt < L2A_PFT(TW, OT); ++tt)
+#pragma unroll
+            for (int c = 0; c < OT; ++c)
+                if (((tt * OT + c) & 1) == 1) pfO[tt][c] = l2a_ldw(rsn, olane[c], so_ + (tt + c * HT) * 1024);
+        L2A_STAGE_MFMA(a[7], b[3])
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // Output layer for the TW hidden tiles whose activations `hreg` this wave holds in registers
 // (hidden tile == k-group of the output layer, D fragment == B fragment: no LDS round trip).
 // The K reduction is cut into chunks of TPW / 2 k-groups, each its own MFMA chain, written to
@@ -372,9 +456,13 @@ __device__ __forceinline__ void l2a_out_phase(const f32x4 (&hreg)[NT][TPW], f32x
             pbuf[((chunk0 * NT + nt) * OT + c) * 64 + lane] = (NCH == 2) ? acc[0][nt][c] + acc[NCH - 1][nt][c] : acc[0][nt][c];
 }
 
-template <int NT, int TPW, int OT, int KG0, bool GACT, int K0L = 4, bool N1 = false, bool O4 = false, bool FAN = false, bool WHOLE = false>
+template <int NT, int TPW, int OT, int KG0, bool GACT, int K0L = 4, bool N1 = false, bool O4 = false, bool FAN = false, bool WHOLE = false,
+          bool SEQ3 = false>
 __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKParams p) {
     static_assert(!(FAN && WHOLE), "an instance is general, member fan or whole-tiles-only");
+    // (a -DL2A_XEARLY=0 variant library builds no SEQ3 instance: l2a_mfma_inst.hip hands those plans to the general ones)
+    static_assert(!SEQ3 || (L2A_XEARLY && !FAN && !WHOLE && !N1 && NT == 1 && TPW == 8 && OT <= 2 && KG0 <= 2),
+                  "the static three-set step exists for the (1, 8) tile-split shapes of the early exchange");
     constexpr bool NOHALF = FAN || WHOLE;   // instances without the half-member paths (they cost ~110 VGPRs at width 512)
     constexpr int HT = L2A_NW * TPW;
     constexpr int TH = TPW / 2;         // tiles per wave of a half member
@@ -392,7 +480,7 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
     // ONE barrier, then every set's hidden GEMM + output layer back to back (partials -> their own area), ONE
     // barrier, all reduces - two barriers per batch instead of two per set, and the MFMA-light phases of
     // consecutive sets overlap each other's latencies.  Same arithmetic in the same order: bit-identical.
-    const int LB = p.lb;
+    const int LB = SEQ3 ? 3 : p.lb;
     extern __shared__ __attribute__((aligned(16))) char l2a_smem[];
     f32x4* buf0 = reinterpret_cast<f32x4*>(l2a_smem);
     f32x4* buf1 = buf0 + p.sa_elems;
@@ -413,9 +501,9 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
     // remapped XCD-aware.  Tail split (p.split_from >= 0): the first split_from hardware workgroups run whole
     // tiles, the remaining ones - dispatched last - are pairs that share the left-over tiles of a multi-round
     // plan (e.g. 625 tiles on 256 CUs: 512 whole + 113 shared instead of a third, 44 %-filled round).
-    const int tail = p.split_from >= 0;
+    const int tail = SEQ3 ? 0 : p.split_from >= 0;
     const int in_tail = tail && (int)blockIdx.x >= p.split_from;
-    const int split = FAN ? 3 : WHOLE ? 0 : (tail ? (in_tail ? p.split : 0) : p.split);   // this workgroup's split mode (3 = member fan)
+    const int split = SEQ3 ? 2 : FAN ? 3 : WHOLE ? 0 : (tail ? (in_tail ? p.split : 0) : p.split);   // this workgroup's split mode (3 = member fan)
     const int n_tiles = p.m * p.tiles_per_env;
     const int n_pairs = tail ? n_tiles - p.split_from : n_tiles;       // tiles that are shared by two workgroups
     int bid, grp, lpair, pairid;
@@ -467,7 +555,7 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
     const int obs_dim = p.obs_dim, act_dim = p.act_dim;
     // N1: the model has ONE hidden layer (its own instances: no hidden->hidden GEMM, layer 0 feeds the output layer from
     // registers) - a compile-time fact, so that neither path keeps the other's operand registers alive
-    const int n_hidden = N1 ? 1 : p.n_hidden;
+    const int n_hidden = N1 ? 1 : SEQ3 ? 2 : p.n_hidden;
 
     int cand[NT], row[NT];
     bool valid[NT];
@@ -483,13 +571,14 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
     // inner hidden layers in full, the last hidden layer and the output layer for one half of the
     // hidden tiles each - which balances odd ensembles and lets a single model use two CUs).
     // Both workgroups run their full sets first and the shared one last.
-    const bool per_block = (p.mode == L2A_MODE_PER_BLOCK);
-    const int e_loop = (p.mode == L2A_MODE_MEAN) ? p.n_sets : 1;
+    const bool per_block = !SEQ3 && (p.mode == L2A_MODE_PER_BLOCK);
+    const int e_loop = SEQ3 ? 5 : (p.mode == L2A_MODE_MEAN) ? p.n_sets : 1;
     const int e_half = (e_loop + 1) >> 1;                   // group A = [0, e_half), B = [e_half, e_loop)
     // Member fan (FAN instances, split == 3): workgroup `grp` of a tile runs set `grp` alone, as a full member.
     const int e_shared = (!NOHALF && split == 2) ? e_half - 1 : -1;
-    const int n_full = FAN ? 1 : (!split ? e_loop : (grp == 0 ? e_half - (split == 2 ? 1 : 0) : e_loop - e_half));
-    const int n_seq = FAN ? 1 : n_full + (split == 2 ? 1 : 0);
+    // (SEQ3: two full sets and the shared one whichever the group - literals, so that the batch loop below folds to one pass)
+    const int n_full = SEQ3 ? 2 : FAN ? 1 : (!split ? e_loop : (grp == 0 ? e_half - (split == 2 ? 1 : 0) : e_loop - e_half));
+    const int n_seq = SEQ3 ? 3 : FAN ? 1 : n_full + (split == 2 ? 1 : 0);
     const int full0 = FAN ? grp : ((split && grp == 1) ? e_half : 0);       // first full set of this workgroup
     auto seq = [&](int i) { return (i < n_full) ? full0 + i : e_shared; };
     auto set_base = [&](int e) { return p.wblk + (long long)(per_block ? env : e) * p.set_stride; };
@@ -775,6 +864,8 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
             }
             return xe;
         };
+        // (SEQ3: LB = n_seq = nb = 3 are compile-time literals - the loop runs once, leaves at its `break`, and its
+        //  phase_c(false_type) is dead code; the host sends only plans with p.lb == 3 and five sets there, plan_rollout)
         for (;; b0 += LB) {
             nb = (n_seq - b0 < LB) ? n_seq - b0 : LB;
             f32x4 hreg[NT][TPW];    // activations of the LAST hidden layer (stay in registers)
@@ -921,7 +1012,7 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                     // the first hidden GEMM of the batch follows (set seq(b0))
                     const int e0 = seq(b0);
                     const __amdgpu_buffer_rsrc_t rs1 = l2a_rsrc(set_base(e0) + p.pk_wmid, wm_bytes);
-                    const bool next_half = !NOHALF && (e0 == e_shared) && n_hidden == 2;
+                    const bool next_half = !SEQ3 && !NOHALF && (e0 == e_shared) && n_hidden == 2;    // (SEQ3: a full set comes first)
                     const int s1 = sbase(next_half ? sbh : sbf);
                     if (next_half) {
 #pragma unroll
@@ -965,7 +1056,7 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                 constexpr bool last_set = decltype(last_tag)::value;
                 const int i = b0 + j;
                 const int e = seq(i);
-                const bool is_half = !NOHALF && last_set && (e == e_shared);
+                const bool is_half = SEQ3 ? last_set : (!NOHALF && last_set && (e == e_shared));      // (SEQ3: full, full, half)
                 const float* wb = set_base(e);
                 const float* nr = nrm + i * NRM_SET;
                 const __amdgpu_buffer_rsrc_t rs_out = l2a_rsrc(wb + p.pk_wout, wo_bytes);
@@ -1005,6 +1096,10 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                                 hreg[nt][tt] = l2a_actv<GACT>(acc[nt][tt] + bias[tt], p.hidden_act, p.hid_floor);
                         }
                     } else {
+                        if constexpr (SEQ3)
+                            l2a_half_gemm_ring<NT, TPW, OT>(rs_last, rs_out, sbh, tile0h, hin, pfA, pfB,
+                                                            pfO, acc, lane, lane16, bl + 16 * tile0h + 4 * qq, bias, olane);
+                        else
                         l2a_hidden_gemm<NT, TH, TPW, OT, true>(rs_last, rs_out, sbh, sbh, TH, tile0h, hin, pfA, pfB,
                                                                pfO, acc, lane, lane16, bl + 16 * tile0h + 4 * qq, bias, olane);
 #pragma unroll
@@ -1032,7 +1127,29 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
                 } else {
                     const int en = seq(i + 1);
                     const __amdgpu_buffer_rsrc_t rsn = l2a_rsrc(set_base(en) + p.pk_wmid, wm_bytes);   // nb > 1: two hidden layers
-                    if (!NOHALF && en == e_shared) {
+                    if constexpr (SEQ3) {
+                        // (SEQ3, compile-time roles: set 0 hands over to a full member, set 1 to the half member's ring)
+                        if (j == 1) {
+                            // the ring runs four k-groups ahead: k-groups 0 .. 3 of the half member's TH tiles, in the sixteen
+                            // registers a full member's k-groups 0 / 1 would take (pfA = groups 0 | 2, pfB = groups 1 | 3)
+                            l2a_out_phase<NT, TPW, TPW, OT, 4 * TH, O4>(hreg, pfO, rs_out, c0, [&]() {
+                                const int s1 = sbase(sbh);
+#pragma unroll
+                                for (int tt = 0; tt < TH; ++tt) {
+                                    pfA[tt] = l2a_ldw(rsn, lane16, s1 + tt * (HT * 1024));
+                                    pfB[tt] = l2a_ldw(rsn, lane16 + 1024, s1 + tt * (HT * 1024));
+                                }
+#pragma unroll
+                                for (int tt = 0; tt < TH; ++tt) {
+                                    pfA[TH + tt] = l2a_ldw(rsn, lane16 + 2048, s1 + tt * (HT * 1024));
+                                    pfB[TH + tt] = l2a_ldw(rsn, lane16 + 3072, s1 + tt * (HT * 1024));
+                                }
+                            }, pb, wave, lane, olane);
+                            L2A_TS(4)
+                            return;
+                        }
+                    }
+                    if (!SEQ3 && !NOHALF && en == e_shared) {      // (SEQ3: set 0 hands over to the full set 1, below)
                         l2a_out_phase<NT, TPW, TPW, OT, 2 * TH, O4>(hreg, pfO, rs_out, c0, [&]() {
                             const int s1 = sbase(sbh);
 #pragma unroll
@@ -1056,11 +1173,22 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
             };
             // (layer 0 of a batch's later sets carried inside the previous set's GEMM - one hidden tile per loop iteration - was
             // measured and lost: it lengthens the host GEMM by what the phase of its own costs, profiles/r03_ab_kernel_variants.jsonl)
+            if constexpr (SEQ3) {
+                // the static three-set step: full, full, shared - one batch, written out (no back-edge between the sets)
+                layer0(0, std::false_type{});
+                layer0(1, std::false_type{});
+                layer0(2, std::true_type{});
+                __syncthreads();
+                member(0, std::false_type{});
+                member(1, std::false_type{});
+                member(2, std::true_type{});
+            } else {
             for (int j = 0; j + 1 < nb; ++j) layer0(j, std::false_type{});
             layer0(nb - 1, std::true_type{});
             if (!N1) __syncthreads();
             for (int j = 0; j + 1 < nb; ++j) member(j, std::false_type{});
             member(nb - 1, std::true_type{});
+            }
 
             // ======== phase C: canonical reduce of every set of the batch ===========================
             __syncthreads();
@@ -1076,7 +1204,75 @@ __global__ void __launch_bounds__(64 * L2A_NW) l2a_rollout_mfma_k(const L2AKPara
             if (N1) { f32x4* tmp = hcur; hcur = hoth; hoth = tmp; }
         }
         // xearly: this step's records left in phase C, wave 3 holds the requested partner records in `sw`
-        const bool xearly = phase_c(std::true_type{});
+        bool xearly;
+        if constexpr (SEQ3) {
+            // Phase C of the static step in ONE pass: the partials of all three sets and the constants of the two full ones are
+            // requested together (one exposed LDS round trip instead of six), then the adds in the order that lets the records
+            // leave earliest - the shared set's raw sum (wave 0 publishes it), the group sum of the full sets (wave 1), wave 3's
+            // request for the partner's records.  Every wave runs the same order: wave 0's permutation only ever chose addresses.
+            f32x4 part[3][OT][L2A_NW][NT], cb[2][OT], cm[2][OT], cs[2][OT];
+            // (timeline: the one pass is stamped as every set's reduce start; a set's reduce end = its record's publish point)
+            { const int e = 2; L2A_TS(5) } { const int e = seq(0); L2A_TS(5) } { const int e = seq(1); L2A_TS(5) }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int j = (k == 0) ? 2 : k - 1;         // the shared set's partials first
+#pragma unroll
+                for (int c = 0; c < OT; ++c)
+#pragma unroll
+                    for (int ch = 0; ch < L2A_NW; ++ch)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) part[j][c][ch][nt] = pbase[j * PS + ((ch * NT + nt) * OT + c) * 64 + lane];
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float* nr = nrm + j * NRM_SET;
+#pragma unroll
+                for (int c = 0; c < OT; ++c) {
+                    cb[j][c] = *reinterpret_cast<const f32x4*>(nr + CST_BOUT + 16 * c + 4 * qq);
+                    cm[j][c] = *reinterpret_cast<const f32x4*>(nr + 32 * KG0 + 16 * c + 4 * qq);
+                    cs[j][c] = *reinterpret_cast<const f32x4*>(nr + 32 * KG0 + 16 * OT + 16 * c + 4 * qq);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < OT; ++c)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    qsh[nt][c] = (part[2][c][0][nt] + part[2][c][1][nt]) + (part[2][c][2][nt] + part[2][c][3][nt]);
+            if (wave == 0) xput(1, qsh);
+            { const int e = 2; L2A_TS(6) }
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int c = 0; c < OT; ++c)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        f32x4 s = (part[j][c][0][nt] + part[j][c][1][nt]) + (part[j][c][2][nt] + part[j][c][3][nt]);
+                        if (O4 && c == OT - 1) {        // the four quarters of the hidden units (l2a_out_phase)
+#pragma unroll
+                            for (int ii = 0; ii < 4; ++ii) s[ii] = l2a_sum_xor32(l2a_sum_xor16(s[ii]));
+                        }
+                        s = l2a_actv<GACT>(s + cb[j][c], p.output_act, p.out_floor);
+                        dgrp[nt][c] += s * cs[j][c] + cm[j][c];
+                    }
+            if (wave == 1) xput(0, dgrp);
+            if (wave == 3) {
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                        for (int c = 0; c < OT; ++c)
+#pragma unroll
+                            for (int hh = 0; hh < 2; ++hh)
+                                sw[r][nt][c][hh] = __builtin_amdgcn_raw_buffer_load_b128(
+                                    xrs, xbase(grp ^ 1, r) + ((nt * OT + c) * 2 + hh) * 1024, 0, L2A_SC1);
+            }
+            { const int e = seq(0); L2A_TS(6) } { const int e = seq(1); L2A_TS(6) }
+            xearly = true;
+        } else {
+            xearly = phase_c(std::true_type{});
+        }
         if (N1) { f32x4* tmp = hcur; hcur = hoth; hoth = tmp; }
 
         // ---- combine the two workgroups of a tile ---------------------------------------------
