@@ -20,8 +20,8 @@ OUT = os.path.join(PKG, "libl2a_hip.so")
 RNG_OUT = os.path.join(PKG, "libl2a_rng.so")        # host-only helper (gcc), see l2a_rng.c
 OBJ_DIR = os.path.join(HERE, "_obj")
 HEADERS = ["l2a_host.h", "l2a_kernels.h", "l2a_valu.h", "l2a_adapt.h", "l2a_mfma.h", "l2a_mfma_launch.h", "l2a_lstm.h",
-           "l2a_lstm_valu.h", "l2a_rnn_valu.h", "l2a_rnn_mfma.h", "l2a_lstm_launch.h", "l2a_micro.h", "l2a_rnn_micro.h", "l2a_micro_pack.h", "l2a_rm_layer.h", "l2a_micro_launch.h", "l2a_rng.h", os.path.join("..", "..", "include", "l2a.h")]
-SOURCES = ["l2a_api.hip", "l2a_mfma_inst.hip", "l2a_lstm_api.hip", "l2a_lstm_inst.hip", "l2a_micro_inst.hip", "l2a_micro_traj_inst.hip", "l2a_mlp_micro_traj_inst.hip", "l2a_rnn_micro_inst.hip", "l2a_comm.hip", "l2a_cem.hip", "l2a_mppi.hip", "l2a_icem.hip", "l2a_step.hip", "l2a_score.hip", "l2a_score_mlp.hip", "l2a_value.hip", "l2a_policy.hip", "l2a_particles.hip", "l2a_particle_step.hip", "l2a_rng.c"]
+           "l2a_lstm_valu.h", "l2a_rnn_valu.h", "l2a_rnn_mfma.h", "l2a_lstm_launch.h", "l2a_micro.h", "l2a_rnn_micro.h", "l2a_micro_pack.h", "l2a_rm_layer.h", "l2a_rm_net.h", "l2a_philox.h", "l2a_micro_launch.h", "l2a_rng.h", os.path.join("..", "..", "include", "l2a.h")]
+SOURCES = ["l2a_api.hip", "l2a_mfma_inst.hip", "l2a_lstm_api.hip", "l2a_lstm_inst.hip", "l2a_micro_inst.hip", "l2a_micro_traj_inst.hip", "l2a_mlp_micro_traj_inst.hip", "l2a_rnn_micro_inst.hip", "l2a_comm.hip", "l2a_cem.hip", "l2a_mppi.hip", "l2a_icem.hip", "l2a_step.hip", "l2a_score.hip", "l2a_score_mlp.hip", "l2a_value.hip", "l2a_policy.hip", "l2a_rm_net.hip", "l2a_particles.hip", "l2a_particle_step.hip", "l2a_rng.c"]
 INSTANCES = [(1, 2), (1, 4), (1, 8), (2, 2), (2, 4)]
 # member-fan instances of the same template (-DL2A_INST_FAN=1): NT = 1 at every width, NT = 2 at width 512 (the fan instances
 # carry no half-member code: (2, 8) keeps its registers - 456 VGPRs, no scratch - where the tile-split (2, 8) instances spilled)
@@ -121,10 +121,12 @@ def unit_table():
          "l2a_step.o": ("l2a_step.hip", []),
          "l2a_score.o": ("l2a_score.hip", SCORE_FLAGS),
          "l2a_score_mlp.o": ("l2a_score_mlp.hip", SCORE_FLAGS),
-         # (the terminal-value kernel: the scorer's layer routine, l2a_rm_layer.h, and the same unfused fp32 fold)
+         # (the terminal-value kernel: the scorer's device routines, l2a_rm_layer.h, and the same unfused fp32 fold)
          "l2a_value.o": ("l2a_value.hip", SCORE_FLAGS),
-         # (the policy-prior kernel: the same layer routine, an epilogue restated bit for bit on the host, tests/policy_reference.py)
+         # (the policy-prior kernel: the same routines, an epilogue restated bit for bit on the host, tests/policy_reference.py)
          "l2a_policy.o": ("l2a_policy.hip", SCORE_FLAGS),
+         # (the model core the three heads above derive from, and their weight pack kernel)
+         "l2a_rm_net.o": ("l2a_rm_net.hip", SCORE_FLAGS),
          # (the particle scorer's mean - lambda * std is restated bit for bit on the host, tests/particle_reference.py)
          "l2a_particles.o": ("l2a_particles.hip", SCORE_FLAGS),
          # (the TS1 step kernel restates l2a_score.o's reward arithmetic; a unit of its own so that neither of those changes)

@@ -22,35 +22,13 @@
 // permute / contiguous, argsort, compare, transpose, masked sums, topk / gather, mean, std).
 
 #include "l2a_host.h"
+#include "l2a_philox.h"      // above every `#pragma clang fp contract(off)` of this unit: see the note at l2a_philox_normal
 
 #include <atomic>
 #include <cstring>
 #include <string>
 
 namespace {
-
-// ---- Philox4x32-10 (Salmon et al., SC'11): counter-based, so every element's normal is a pure function of
-//      (seed, offset + element index) - all ranks of a sharded plan generate the same numbers without talking ----------
-__device__ __forceinline__ void philox_round(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned int hi0 = (unsigned int)(p0 >> 32), lo0 = (unsigned int)p0;
-    const unsigned int hi1 = (unsigned int)(p1 >> 32), lo1 = (unsigned int)p1;
-    c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
-}
-
-__device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned long long index) {
-    unsigned int c[4] = {(unsigned int)index, (unsigned int)(index >> 32), 0x4c32614du, 0u};
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    // Box-Muller on two uniforms in (0, 1]
-    const float u1 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
 
 struct CemSampleParams {
     const float* z;             // [n, m, D] or null (generate)
@@ -73,7 +51,7 @@ __global__ void __launch_bounds__(256) l2a_cem_sample_k(const CemSampleParams p)
     const long long g = e / D;                  // flat sample row j * m + i (the draw's [n, m, D] order, :85)
     const int d = (int)(e - g * D);
     const int i = (int)(g % p.m);
-    const float z = p.z ? p.z[e] : philox_normal(p.seed, p.offset + (unsigned long long)e);
+    const float z = p.z ? p.z[e] : l2a_philox_normal(p.seed, p.offset + (unsigned long long)e);
     const float a = p.mean[i * D + d] + z * p.std[i * D + d];                      // :86
     const int k = d % p.act_dim, t = d / p.act_dim;
     const float c = fminf(fmaxf(a, p.low[k]), p.high[k]);                           // :87
@@ -414,7 +392,7 @@ __global__ void __launch_bounds__(L2A_CRS_THREADS) l2a_cem_refit_sample_k(const 
         const long long g = (long long)j * m + i;
         const int d = t * A + kk;
         const long long e = g * D + d;
-        const float z = p.z ? p.z[e] : philox_normal(p.seed, p.offset + (unsigned long long)e);
+        const float z = p.z ? p.z[e] : l2a_philox_normal(p.seed, p.offset + (unsigned long long)e);
         const float a = nm[ii * A + kk] + z * ns[kk];                                 // :86
         const float c = fminf(fmaxf(a, p.low[kk]), p.high[kk]);                         // :87
         p.a_clip[e] = c;

@@ -46,39 +46,13 @@
 // its weight pass, which is n operations, not n^2 / 64 ballots).  No atomics anywhere: the same inputs give the same bits.
 
 #include "l2a_host.h"
+#include "l2a_philox.h"      // above every `#pragma clang fp contract(off)` of this unit: see the note at l2a_philox_normal
 
 #include <cmath>
 #include <cstring>
 #include <string>
 
 namespace {
-
-// ---- Philox4x32-10 + Box-Muller: l2a_cem.hip's normal stream restated (that file and l2a_mppi.hip keep their own copies; the three
-//      must stay the same function of (seed, index): tests/test_icem_kernels_gpu.py holds this one to l2a_cem_sample bit for bit) ------
-//      MAINTENANCE: these two functions must NOT carry `#pragma clang fp contract(off)` - they are compiled as l2a_cem.hip compiles
-//      its copy, or the normals move by an ulp.  EVERYTHING ELSE in this unit that does floating-point arithmetic - every kernel
-//      body, every device helper a kernel calls, the host arithmetic that forms `c` in l2a_icem_sample - MUST open with it: the
-//      unit's flags do not switch contraction off, and a helper without the pragma would fuse silently.
-__device__ __forceinline__ void icem_philox_round(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned int hi0 = (unsigned int)(p0 >> 32), lo0 = (unsigned int)p0;
-    const unsigned int hi1 = (unsigned int)(p1 >> 32), lo1 = (unsigned int)p1;
-    c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
-}
-
-__device__ __forceinline__ float icem_philox_normal(unsigned long long seed, unsigned long long index) {
-    unsigned int c[4] = {(unsigned int)index, (unsigned int)(index >> 32), 0x4c32614du, 0u};
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        icem_philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    // Box-Muller on two uniforms in (0, 1]
-    const float u1 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
 
 struct IcemSampleParams {
     const float* z;             // [n, m, D] or null (generate)
@@ -166,7 +140,7 @@ __global__ void __launch_bounds__(256) l2a_icem_sample_k(const IcemSampleParams 
             else if (kind == 1) v = p.kept_in[((long long)i * p.Kk + j) * D + ts * A + k];
             else {
                 const long long e = g * D + t0 * A + rem;
-                v = p.z ? p.z[e] : icem_philox_normal(p.seed, p.offset + (unsigned long long)e);
+                v = p.z ? p.z[e] : l2a_philox_normal(p.seed, p.offset + (unsigned long long)e);
             }
             tile[q] = v;
         }
@@ -322,7 +296,7 @@ __global__ void __launch_bounds__(256) l2a_icem_sample_noise_k(const IcemNoisePa
         else if (kind == 1) v = p.kept_in[((long long)i * p.Kk + j) * D + ts * A + k];
         else {
             const long long e = g * D + rem;
-            v = p.z ? p.z[e] : icem_philox_normal(p.seed, p.offset + (unsigned long long)e);
+            v = p.z ? p.z[e] : l2a_philox_normal(p.seed, p.offset + (unsigned long long)e);
         }
         tile[q] = v;
     }

@@ -35,35 +35,13 @@
 // permute, isfinite, max, sub, mul, exp, two sums, a matrix product, div) and the host round trip of returns and samples.
 
 #include "l2a_host.h"
+#include "l2a_philox.h"      // above every `#pragma clang fp contract(off)` of this unit: see the note at l2a_philox_normal
 
 #include <cmath>
 #include <cstring>
 #include <string>
 
 namespace {
-
-// ---- Philox4x32-10 + Box-Muller: l2a_cem.hip's normal stream restated (that file keeps its own copy; the two must stay the same
-//      function of (seed, index): tests/test_cem_kernels_gpu.py and tests/test_mppi_kernels_gpu.py hold both to cem_reference) ------
-__device__ __forceinline__ void mppi_philox_round(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned int hi0 = (unsigned int)(p0 >> 32), lo0 = (unsigned int)p0;
-    const unsigned int hi1 = (unsigned int)(p1 >> 32), lo1 = (unsigned int)p1;
-    c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
-}
-
-__device__ __forceinline__ float mppi_philox_normal(unsigned long long seed, unsigned long long index) {
-    unsigned int c[4] = {(unsigned int)index, (unsigned int)(index >> 32), 0x4c32614du, 0u};
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        mppi_philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    // Box-Muller on two uniforms in (0, 1]
-    const float u1 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
 
 struct MppiSampleParams {
     const float* z;             // [n, m, D] or null (generate)
@@ -118,7 +96,7 @@ __global__ void __launch_bounds__(256) l2a_mppi_sample_k(const MppiSampleParams 
             const int ts = (sh > 0) ? (t + 1 < p.h ? t + 1 : p.h - 1) : t;
             mtile[q] = (sh < 0) ? 0.0f : p.mean_in[(long long)i * D + ts * A + k];
             const long long e = g * D + t0 * A + rem;
-            const float z = p.z ? p.z[e] : mppi_philox_normal(p.seed, p.offset + (unsigned long long)e);
+            const float z = p.z ? p.z[e] : l2a_philox_normal(p.seed, p.offset + (unsigned long long)e);
             tile[q] = z * p.sigma[k];
         }
         __syncthreads();

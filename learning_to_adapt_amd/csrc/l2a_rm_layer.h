@@ -1,7 +1,9 @@
-// l2a_rm_layer.h - the layer routine of the matrix-core MLP scorers, shared by the reward-model scorer (l2a_score_mlp.hip) and the
-// terminal-value kernel (l2a_value.hip): the weight pack kernel, one hidden layer in place in the LDS image, and its dispatch on
-// the layer's width.  Both units are compiled with contraction off.  The text is l2a_score_mlp.hip's own, moved here unchanged
-// (the pack kernel is `static`, as the pack kernels of l2a_micro_pack.h are: two units of one library hold it).
+// l2a_rm_layer.h - the device side of the matrix-core MLP heads: the learned reward model (l2a_score_mlp.hip), the terminal value
+// (l2a_value.hip) and the policy prior (l2a_policy.hip).  The network descriptor the three kernels take, the place of an input
+// feature in the LDS image, one hidden layer in place in the image with its dispatch on the layer's width and its activation pass, and the
+// output tile's accumulator chain.  Each kernel keeps its own prologue (what the features are) and its own consumer of the output
+// tile.  The three units are compiled with contraction off and include this header below their `#pragma clang fp contract(off)`.
+// The host side of the heads - the model object, its weight block and the launcher - is l2a_rm_net.h / l2a_rm_net.hip.
 #pragma once
 
 #include "l2a_kernels.h"
@@ -11,17 +13,25 @@
 #define L2A_RM_MAX_ROWS 128         // 16 * RT, RT <= 8
 #define L2A_RM_MAX_ACC 32           // TPW * RT accumulators of four registers per wave
 
-static __global__ void l2a_rm_pack_k(const float* __restrict__ w, int k_in, int n_out, int KG, long long total, float* __restrict__ out) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    int k, u;
-    l2a_pack_decode(idx, KG, &k, &u);
-    out[idx] = (k < k_in && u < n_out) ? w[(long long)k * n_out + u] : 0.0f;
+// The network as a kernel sees it (filled by l2a_rm_core_net, l2a_rm_net.hip): plain data, a member of the kernel's parameters.
+struct L2ARmNet {
+    const float* wblk;              // the model's device block
+    long long pk[L2A_RM_MAX_HIDDEN + 1];    // packed kernels (floats from wblk); [n_hidden] = the output layer
+    long long bias[L2A_RM_MAX_HIDDEN + 1];  // biases
+    long long nm;                   // [mu KG0*16][inv KG0*16] in feature order, then the head's own tail
+    int tpw[L2A_RM_MAX_HIDDEN];     // hidden width / 64
+    int n_hidden, d_in, KG0, kgs;   // d_in input features in KG0 k-groups; kgs: k-groups between the row tiles of the LDS image
+    int act;
+};
+
+// Float index of feature k of row j (0 .. 15) of row tile rt in the image [row tile][k-group][lane] of f32x4: the B fragment
+__device__ __forceinline__ int l2a_rm_image_index(int rt, int kgs, int k, int j) {
+    return (((rt * kgs + (k >> 4)) * 64) + ((k >> 2) & 3) * 16 + j) * 4 + (k & 3);
 }
 
 // One hidden layer for the pass's RT row tiles, in place: this wave's TPW unit tiles.  `live`: bit rt = row tile rt holds rows.
 // The epilogue applies max(x, floor) - relu (0) or nothing (-inf; the max propagates NaN, l2a_max_nan) - and the other
-// activations follow in a pass of their own over the image (l2a_score_mlp_k): inlined into every instance here their code
+// activations follow in a pass of their own over the image (l2a_rm_hidden_layer): inlined into every instance here their code
 // cost registers (spills at RT = 4) and a minute of compile time.
 template <int TPW, int RT>
 __device__ __forceinline__ void l2a_rm_layer(const f32x4* __restrict__ wp, const float* __restrict__ bias, int KGin, int kgs,
@@ -88,4 +98,46 @@ __device__ __forceinline__ void l2a_rm_layer_any(int tpw, const f32x4* wp, const
         case 7: l2a_rm_layer<7, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
         default: l2a_rm_layer<8, RT>(wp, bias, KGin, kgs, act, floor, live, wave, lane); break;
     }
+}
+
+// Hidden layer l, in place, with its elementwise activation pass: the image holds the layer's input in KGin k-groups on entry
+// (every thread's stores made visible by a barrier) and its activations on return.  Returns the next layer's KGin.  The kernels
+// keep the loop over l themselves: with the loop inside a shared routine the register allocator schedules the widest
+// instances' MFMA loops differently from the loop written out in the kernel (one LDS read in flight instead of eight).
+template <int RT>
+__device__ __forceinline__ int l2a_rm_hidden_layer(const L2ARmNet& net, int l, int KGin, f32x4* act, unsigned live, int tid, int wave,
+                                                   int lane) {
+    const float floor = (net.act == L2A_ACT_RELU) ? 0.0f : -__builtin_inff();
+    l2a_rm_layer_any<RT>(net.tpw[l], reinterpret_cast<const f32x4*>(net.wblk + net.pk[l]), net.wblk + net.bias[l], KGin, net.kgs,
+                         act, floor, live, wave, lane);
+    KGin = 4 * net.tpw[l];
+    if (net.act != L2A_ACT_RELU && net.act != L2A_ACT_IDENTITY) {       // tanh / sigmoid / swish: elementwise over the live tiles
+        for (int e = tid; e < RT * KGin * 64; e += L2A_RM_THREADS) {
+            const int rt = e / (KGin * 64);
+            if ((live >> rt) & 1u) {
+                f32x4* q = act + (rt * net.kgs) * 64 + (e - rt * KGin * 64);
+                f32x4 v = *q;
+                v.x = l2a_act1(v.x, net.act); v.y = l2a_act1(v.y, net.act); v.z = l2a_act1(v.z, net.act); v.w = l2a_act1(v.w, net.act);
+                *q = v;
+            }
+        }
+        __syncthreads();
+    }
+    return KGin;
+}
+
+// The output layer's ONE 16-unit tile for row tile rt, without the bias: the single accumulator chain over k.  Unit 4 (lane >> 4)
+// + c of row lane & 15 is register c - a scalar head's unit 0 is .x of lanes 0 .. 15.  The kernels deal the row tiles to the waves.
+__device__ __forceinline__ f32x4 l2a_rm_out_chain(const L2ARmNet& net, const f32x4* act, int rt, int KGin, int lane) {
+    const f32x4* wo = reinterpret_cast<const f32x4*>(net.wblk + net.pk[net.n_hidden]) + lane;
+    f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int g = 0; g < KGin; ++g) {
+        const f32x4 a = wo[g * 64];
+        const f32x4 b = act[(rt * net.kgs + g) * 64 + lane];
+        acc = L2A_MFMA(a.x, b.x, acc);
+        acc = L2A_MFMA(a.y, b.y, acc);
+        acc = L2A_MFMA(a.z, b.z, acc);
+        acc = L2A_MFMA(a.w, b.w, acc);
+    }
+    return acc;
 }

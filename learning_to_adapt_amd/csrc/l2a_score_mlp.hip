@@ -22,27 +22,23 @@
 // k-group 0, 1, .. and inside a group MFMA 0 .. 3, i.e. (l2a_kernels.h) features 16g + 4kk + ii for ii = 0 .. 3 (outer), kk = 0 .. 3
 // (inside the instruction) - whichever row tile, workgroup geometry (RT, CT, S), shard or cand_offset the row falls into.  K is
 // padded with zeros to a multiple of 16.  The scalar output layer is the same chain on a unit tile whose rows 1 .. 15 are zero.
-// No float atomics.
+// No float atomics.  The descriptor, the hidden-layer routine and the output chain are shared with the value and policy kernels
+// (l2a_rm_layer.h), the model object with their models (l2a_rm_net.hip); the pass prologue, the discounted sum, the keys and the
+// geometry search are this unit's own.
 #pragma clang fp contract(off)
 
 #include "l2a_host.h"
 #include "l2a_kernels.h"
-#include "l2a_rm_layer.h"
+#include "l2a_rm_net.h"
 
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <vector>
 
 struct L2ARMParams {
-    const float* wblk;              // the model's device block
-    long long pk[L2A_RM_MAX_HIDDEN + 1];    // packed kernels (floats from wblk); [n_hidden] = the output layer
-    long long bias[L2A_RM_MAX_HIDDEN + 1];  // biases
-    long long nm;                   // [mu KG0*16][inv KG0*16] in feature order
-    int tpw[L2A_RM_MAX_HIDDEN];     // hidden width / 64
-    int n_hidden, obs_dim, act_dim, d_in, KG0, kgs;     // kgs: k-groups between the row tiles of the LDS image
-    int act;
+    L2ARmNet net;                   // d_in = 2 * obs_dim + act_dim
+    int obs_dim, act_dim;
     float sr, mur;                  // fp32(sd_r + 1e-10), fp32(mu_r)
     const float* obs0;              // [m, obs_dim], or [rows, obs_dim] when obs_per_row
     const float* traj;              // [h, rows, obs_dim]
@@ -67,9 +63,9 @@ __global__ __launch_bounds__(L2A_RM_THREADS) void l2a_score_mlp_k(const L2ARMPar
     const int CT = p.CT, S = p.S;
     const int r0 = (int)blockIdx.x * 16 * CT;
     const int nr = min(16 * CT, p.rows - r0);           // candidates of this workgroup
-    const float* __restrict__ mu = p.wblk + p.nm;
-    const float* __restrict__ inv = mu + 16 * p.KG0;
-    const int kpad = 16 * p.KG0;
+    const float* __restrict__ mu = p.net.wblk + p.net.nm;
+    const float* __restrict__ inv = mu + 16 * p.net.KG0;
+    const int kpad = 16 * p.net.KG0;
     float* actf = reinterpret_cast<float*>(act);
 
     if (tid < L2A_RM_MAX_ROWS) sbad[tid] = 0;
@@ -86,7 +82,7 @@ __global__ __launch_bounds__(L2A_RM_THREADS) void l2a_score_mlp_k(const L2ARMPar
             const int rt = i >> 4, j = i & 15;
             const int ci = 16 * (rt / S) + j, t = t0 + rt % S;
             float x = 0.0f;
-            if (ci < nr && t < p.h && k < p.d_in) {
+            if (ci < nr && t < p.h && k < p.net.d_in) {
                 const size_t r = (size_t)(r0 + ci);
                 const float* o = p.obs_per_row ? p.obs0 + r * p.obs_dim
                                  : (t == 0)    ? p.obs0 + (r / (size_t)p.n) * p.obs_dim
@@ -109,46 +105,20 @@ __global__ __launch_bounds__(L2A_RM_THREADS) void l2a_score_mlp_k(const L2ARMPar
                 if (!fin) sbad[i] = 1;
                 x = (v - mu[k]) * inv[k];
             }
-            actf[(((rt * p.kgs + (k >> 4)) * 64) + ((k >> 2) & 3) * 16 + j) * 4 + (k & 3)] = x;
+            actf[l2a_rm_image_index(rt, p.net.kgs, k, j)] = x;
         }
         __syncthreads();
         // ---- hidden layers, in place ----
-        int KGin = p.KG0;
-        const float floor = (p.act == L2A_ACT_RELU) ? 0.0f : -__builtin_inff();
-        for (int l = 0; l < p.n_hidden; ++l) {
-            l2a_rm_layer_any<RT>(p.tpw[l], reinterpret_cast<const f32x4*>(p.wblk + p.pk[l]), p.wblk + p.bias[l], KGin, p.kgs, act,
-                                 floor, live, wave, lane);
-            KGin = 4 * p.tpw[l];
-            if (p.act != L2A_ACT_RELU && p.act != L2A_ACT_IDENTITY) {       // tanh / sigmoid / swish: elementwise over the live tiles
-                for (int e = tid; e < RT * KGin * 64; e += L2A_RM_THREADS) {
-                    const int rt = e / (KGin * 64);
-                    if ((live >> rt) & 1u) {
-                        f32x4* q = act + (rt * p.kgs) * 64 + (e - rt * KGin * 64);
-                        f32x4 v = *q;
-                        v.x = l2a_act1(v.x, p.act); v.y = l2a_act1(v.y, p.act); v.z = l2a_act1(v.z, p.act); v.w = l2a_act1(v.w, p.act);
-                        *q = v;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        int KGin = p.net.KG0;
+        for (int l = 0; l < p.net.n_hidden; ++l) KGin = l2a_rm_hidden_layer<RT>(p.net, l, KGin, act, live, tid, wave, lane);
         // ---- the scalar output layer: row tiles dealt to the waves; unit 0 = register 0 of lanes 0 .. 15 ----
         {
-            const f32x4* wo = reinterpret_cast<const f32x4*>(p.wblk + p.pk[p.n_hidden]) + lane;
-            const float bo = p.wblk[p.bias[p.n_hidden]];
+            const float bo = p.net.wblk[p.net.bias[p.net.n_hidden]];
 #pragma unroll
             for (int q = 0; q < (RT + 3) / 4; ++q) {
                 const int rt = wave + 4 * q;
                 if (rt < RT && ((live >> rt) & 1u)) {
-                    f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                    for (int g = 0; g < KGin; ++g) {
-                        const f32x4 a = wo[g * 64];
-                        const f32x4 b = act[(rt * p.kgs + g) * 64 + lane];
-                        acc = L2A_MFMA(a.x, b.x, acc);
-                        acc = L2A_MFMA(a.y, b.y, acc);
-                        acc = L2A_MFMA(a.z, b.z, acc);
-                        acc = L2A_MFMA(a.w, b.w, acc);
-                    }
+                    const f32x4 acc = l2a_rm_out_chain(p.net, act, rt, KGin, lane);
                     if (lane < 16) sz[rt * 16 + lane] = acc.x + bo;
                 }
             }
@@ -183,16 +153,9 @@ __global__ __launch_bounds__(L2A_RM_THREADS) void l2a_score_mlp_k(const L2ARMPar
     }
 }
 
-struct l2a_reward_model {
-    l2a_ctx* ctx = nullptr;
-    int obs_dim = 0, act_dim = 0, d_in = 0, KG0 = 0, kgs = 0;
-    int n_hidden = 0, hidden[L2A_RM_MAX_HIDDEN] = {0}, act = L2A_ACT_RELU;
-    float* wblk = nullptr;
-    long long blk_floats = 0;
-    long long pk[L2A_RM_MAX_HIDDEN + 1] = {0}, bias[L2A_RM_MAX_HIDDEN + 1] = {0}, nm = 0;
+struct l2a_reward_model : l2a_rm_core {          // d_in = 2 * obs_dim + act_dim, one output
+    int obs_dim = 0, act_dim = 0;
     float sr = 1.0f, mur = 0.0f;
-    bool weights_set = false;
-    std::vector<float> norm_stage;              // host staging, kept alive for the async H2D
 };
 
 namespace {
@@ -200,17 +163,11 @@ namespace {
 // Launch geometry: RT row tiles per pass (accumulator and LDS budget), of them S steps x CT candidate tiles.  Any choice gives
 // the same bits; this one minimises (rounds of workgroups) x (passes) x (pass cost ~ RT + 2).  Plain integers, no context and
 // no HIP call: launch() and l2a_reward_model_geometry share it.  False (outputs untouched) when no RT fits the LDS.
-int rm_kgs(int n_hidden, const int* hidden, int obs_dim, int act_dim) {
-    int kgs = l2a_ceil_div(2 * obs_dim + act_dim, 16);
-    for (int l = 0; l < n_hidden; ++l) kgs = hidden[l] / 16 > kgs ? hidden[l] / 16 : kgs;
-    return kgs;
-}
-
 bool choose_geometry(int n_hidden, const int* hidden, int obs_dim, int act_dim, long long rows, int h, int num_cu,
                      int lds_per_block, int* rt_out, int* ct_out, int* s_out) {
     int tpw_max = 1;
     for (int l = 0; l < n_hidden; ++l) tpw_max = hidden[l] / 64 > tpw_max ? hidden[l] / 64 : tpw_max;
-    const int kgs = rm_kgs(n_hidden, hidden, obs_dim, act_dim);
+    const int kgs = l2a_rm_kgs(n_hidden, hidden, 2 * obs_dim + act_dim);
     const int cus = num_cu > 0 ? num_cu : 256;
     long long best_cost = -1;
     for (int rt = 8; rt >= 1; rt >>= 1) {
@@ -227,41 +184,16 @@ bool choose_geometry(int n_hidden, const int* hidden, int obs_dim, int act_dim, 
     return best_cost >= 0;
 }
 
-// The function attribute is per (device, instance), not per model: it is raised ONCE to all the LDS a workgroup may take, so
-// that models of different widths do not lower it under each other.
-template <int RT>
-int launch_rt(l2a_reward_model* rm, const L2ARMParams& p, unsigned blocks, hipStream_t stream) {
-    static bool allowed[64] = {false};
-    const size_t bytes = (size_t)RT * rm->kgs * 1024;
-    const int dev = rm->ctx->device;
-    if (bytes > 48 * 1024 && !(dev >= 0 && dev < 64 && allowed[dev])) {
-        L2A_HIP(rm->ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l2a_score_mlp_k<RT>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, rm->ctx->lds_per_block - 4096));
-        if (dev >= 0 && dev < 64) allowed[dev] = true;
-    }
-    hipLaunchKernelGGL(l2a_score_mlp_k<RT>, dim3(blocks), dim3(L2A_RM_THREADS), bytes, stream, p);
-    L2A_HIP(rm->ctx, hipGetLastError());
-    return L2A_OK;
-}
-
 int launch(l2a_reward_model* rm, L2ARMParams& p, hipStream_t stream) {
-    p.wblk = rm->wblk;
-    for (int l = 0; l <= rm->n_hidden; ++l) { p.pk[l] = rm->pk[l]; p.bias[l] = rm->bias[l]; }
-    p.nm = rm->nm;
-    for (int l = 0; l < L2A_RM_MAX_HIDDEN; ++l) p.tpw[l] = l < rm->n_hidden ? rm->hidden[l] / 64 : 0;
-    p.n_hidden = rm->n_hidden; p.obs_dim = rm->obs_dim; p.act_dim = rm->act_dim; p.d_in = rm->d_in; p.KG0 = rm->KG0; p.kgs = rm->kgs;
-    p.act = rm->act; p.sr = rm->sr; p.mur = rm->mur;
+    l2a_rm_core_net(rm, &p.net);
+    p.obs_dim = rm->obs_dim; p.act_dim = rm->act_dim;
+    p.sr = rm->sr; p.mur = rm->mur;
     int rt = 1, ct = 1, s = 1;
     (void)choose_geometry(rm->n_hidden, rm->hidden, rm->obs_dim, rm->act_dim, p.rows, p.h, rm->ctx->num_cu, rm->ctx->lds_per_block,
                           &rt, &ct, &s);
     p.CT = ct; p.S = s;
     const unsigned blocks = (unsigned)(((long long)p.rows + 16 * ct - 1) / (16 * ct));
-    switch (rt) {
-        case 8: return launch_rt<8>(rm, p, blocks, stream);
-        case 4: return launch_rt<4>(rm, p, blocks, stream);
-        case 2: return launch_rt<2>(rm, p, blocks, stream);
-        default: return launch_rt<1>(rm, p, blocks, stream);
-    }
+    return L2A_RM_LAUNCH_RT(l2a_score_mlp_k, L2ARMParams, rm, rt, p, blocks, stream);
 }
 
 }  // namespace
@@ -269,20 +201,7 @@ int launch(l2a_reward_model* rm, L2ARMParams& p, hipStream_t stream) {
 extern "C" {
 
 int l2a_reward_model_check(int obs_dim, int act_dim, int n_hidden, const int* hidden, int hidden_act) {
-    const std::string who = "reward model: ";
-    if (obs_dim < 1 || obs_dim > 16 * L2A_OTMAX)
-        return l2a_fail(nullptr, L2A_EINVAL, who + "obs_dim " + std::to_string(obs_dim) + " (1 .. " + std::to_string(16 * L2A_OTMAX) + ")");
-    if (act_dim < 1 || act_dim > 16)
-        return l2a_fail(nullptr, L2A_EINVAL, who + "act_dim " + std::to_string(act_dim) + " (1 .. 16)");
-    if (n_hidden < 1 || n_hidden > L2A_RM_MAX_HIDDEN)
-        return l2a_fail(nullptr, L2A_EINVAL, who + std::to_string(n_hidden) + " hidden layers (1 .. " + std::to_string(L2A_RM_MAX_HIDDEN) + ")");
-    if (!hidden) return l2a_fail(nullptr, L2A_EINVAL, who + "null hidden sizes");
-    for (int l = 0; l < n_hidden; ++l)
-        if (hidden[l] < 64 || hidden[l] > 512 || hidden[l] % 64 != 0)
-            return l2a_fail(nullptr, L2A_EINVAL, who + "hidden width " + std::to_string(hidden[l]) + " (a multiple of 64 up to 512)");
-    if (hidden_act < L2A_ACT_IDENTITY || hidden_act > L2A_ACT_SWISH)
-        return l2a_fail(nullptr, L2A_EINVAL, who + "unknown activation " + std::to_string(hidden_act));
-    return L2A_OK;
+    return l2a_rm_check("reward model: ", obs_dim, &act_dim, "1 .. 16", n_hidden, hidden, hidden_act);
 }
 
 int l2a_reward_model_geometry(int obs_dim, int act_dim, int n_hidden, const int* hidden, long long rows, int h, int num_cu,
@@ -299,7 +218,7 @@ int l2a_reward_model_geometry(int obs_dim, int act_dim, int n_hidden, const int*
     out[0] = rt; out[1] = ct; out[2] = s;
     out[3] = (int)wgs;
     out[4] = (h + s - 1) / s;
-    out[5] = rt * rm_kgs(n_hidden, hidden, obs_dim, act_dim) * 1024;
+    out[5] = rt * l2a_rm_kgs(n_hidden, hidden, 2 * obs_dim + act_dim) * 1024;
     return L2A_OK;
 }
 
@@ -309,66 +228,27 @@ int l2a_reward_model_create(l2a_ctx* ctx, int obs_dim, int act_dim, int n_hidden
     const int rc = l2a_reward_model_check(obs_dim, act_dim, n_hidden, hidden, hidden_act);
     if (rc != L2A_OK) return l2a_fail(ctx, rc, l2a_last_error(nullptr));
     l2a_reward_model* rm = new l2a_reward_model();
-    rm->ctx = ctx;
-    rm->obs_dim = obs_dim; rm->act_dim = act_dim; rm->d_in = 2 * obs_dim + act_dim; rm->KG0 = l2a_ceil_div(rm->d_in, 16);
-    rm->n_hidden = n_hidden; rm->act = hidden_act;
-    rm->kgs = rm_kgs(n_hidden, hidden, obs_dim, act_dim);
-    long long off = 0;
-    int kg = rm->KG0;
-    for (int l = 0; l <= n_hidden; ++l) {
-        const int n_out = l < n_hidden ? hidden[l] : 1;
-        if (l < n_hidden) rm->hidden[l] = hidden[l];
-        rm->pk[l] = off;
-        off += (long long)l2a_ceil_div(n_out, 16) * kg * 256;
-        rm->bias[l] = off;
-        off += (n_out + 63) / 64 * 64;
-        kg = n_out / 16;
-    }
-    rm->nm = off;
-    off += 32 * rm->KG0;
-    rm->blk_floats = off;
+    rm->obs_dim = obs_dim; rm->act_dim = act_dim;
     l2a_device_guard guard(ctx->device);
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&rm->wblk), (size_t)off * sizeof(float));
-    if (e != hipSuccess) {
-        delete rm;
-        return l2a_fail(ctx, L2A_EHIP, std::string("l2a_reward_model_create: hipMalloc: ") + hipGetErrorString(e));
-    }
+    int rc_c = l2a_rm_core_create(rm, ctx, "l2a_reward_model_create", 2 * obs_dim + act_dim, 1, n_hidden, hidden, hidden_act, 0);
     // identity statistics until l2a_reward_model_set_norm is called (on the null stream, drained here)
-    const int rc_n = l2a_reward_model_set_norm(rm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (rc_n == L2A_OK && hipStreamSynchronize(nullptr) == hipSuccess) { *out = rm; return L2A_OK; }
-    l2a_reward_model_destroy(rm);
-    return rc_n != L2A_OK ? rc_n : l2a_fail(ctx, L2A_EHIP, "l2a_reward_model_create: hipStreamSynchronize failed");
+    if (rc_c == L2A_OK)
+        rc_c = l2a_reward_model_set_norm(rm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc_c == L2A_OK && hipStreamSynchronize(nullptr) != hipSuccess)
+        rc_c = l2a_fail(ctx, L2A_EHIP, "l2a_reward_model_create: hipStreamSynchronize failed");
+    if (rc_c == L2A_OK) *out = rm;
+    else l2a_reward_model_destroy(rm);
+    return rc_c;
 }
 
 void l2a_reward_model_destroy(l2a_reward_model* rm) {
     if (!rm) return;
-    l2a_device_guard guard(rm->ctx->device);
-    if (rm->wblk) (void)hipFree(rm->wblk);
+    l2a_rm_core_free(rm);
     delete rm;
 }
 
 int l2a_reward_model_set_weights(l2a_reward_model* rm, const void* const* device_ptrs, void* stream_v) {
-    if (!rm) return L2A_EINVAL;
-    l2a_ctx* ctx = rm->ctx;
-    if (!device_ptrs) return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_set_weights: null pointer table");
-    for (int i = 0; i < 2 * (rm->n_hidden + 1); ++i)
-        if (!device_ptrs[i]) return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_set_weights: null parameter " + std::to_string(i));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    l2a_device_guard guard(ctx->device);
-    int k_in = rm->d_in, kg = rm->KG0;
-    for (int l = 0; l <= rm->n_hidden; ++l) {
-        const int n_out = l < rm->n_hidden ? rm->hidden[l] : 1;
-        const long long total = (long long)l2a_ceil_div(n_out, 16) * kg * 256;
-        hipLaunchKernelGGL(l2a_rm_pack_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                           static_cast<const float*>(device_ptrs[2 * l]), k_in, n_out, kg, total, rm->wblk + rm->pk[l]);
-        L2A_HIP(ctx, hipGetLastError());
-        L2A_HIP(ctx, hipMemcpyAsync(rm->wblk + rm->bias[l], device_ptrs[2 * l + 1], sizeof(float) * (size_t)n_out,
-                                    hipMemcpyDeviceToDevice, stream));
-        k_in = n_out;
-        kg = n_out / 16;
-    }
-    rm->weights_set = true;
-    return L2A_OK;
+    return l2a_rm_core_set_weights(rm, "l2a_reward_model_set_weights", device_ptrs, stream_v);
 }
 
 int l2a_reward_model_set_norm(l2a_reward_model* rm, const double* mean_obs, const double* std_obs, const double* mean_act,
@@ -381,10 +261,9 @@ int l2a_reward_model_set_norm(l2a_reward_model* rm, const double* mean_obs, cons
         return l2a_fail(ctx, L2A_EINVAL, "l2a_reward_model_set_norm: pass all eight statistics, or none for identity");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     l2a_device_guard guard(ctx->device);
-    // a previous async copy from the staging buffer must have drained before it is overwritten
-    if (!rm->norm_stage.empty()) L2A_HIP(ctx, hipStreamSynchronize(stream));
-    rm->norm_stage.assign((size_t)32 * rm->KG0, 0.0f);
-    float* mu = rm->norm_stage.data();
+    float* mu = nullptr;
+    const int rc = l2a_rm_core_norm_stage(rm, stream, &mu);
+    if (rc != L2A_OK) return rc;
     float* inv = mu + 16 * rm->KG0;
     const double eps = 1e-10;
     for (int k = 0; k < rm->d_in; ++k) {
@@ -397,8 +276,7 @@ int l2a_reward_model_set_norm(l2a_reward_model* rm, const double* mean_obs, cons
     }
     rm->mur = n_null ? 0.0f : (float)*mean_r;
     rm->sr = n_null ? 1.0f : (float)(*std_r + eps);
-    L2A_HIP(ctx, hipMemcpyAsync(rm->wblk + rm->nm, mu, rm->norm_stage.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    return L2A_OK;
+    return l2a_rm_core_norm_upload(rm, stream);
 }
 
 int l2a_reward_model_predict(l2a_reward_model* rm, const float* obs, const float* act, const float* next_obs, int rows,

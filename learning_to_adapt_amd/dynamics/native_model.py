@@ -585,33 +585,42 @@ class NativeModel(object):
         return out
 
 
-class NativeRewardModel(object):
-    """Python handle on an ``l2a_reward_model``: a reward MLP over ``[obs | act | next_obs - obs]`` that the planner scores
-    trajectories with on the matrix cores (``csrc/l2a_score_mlp.hip``).  Raises ``L2AError`` on any failure."""
+class _NativeHead(object):
+    """What the handles on the three matrix-core MLP heads share (``csrc/l2a_rm_net.hip``): construction, ``close``, and the
+    marshalling of ``set_weights`` and ``set_norm``.  A subclass names its C entry points (``_prefix`` + ``_create`` /
+    ``_destroy`` / ``_set_weights`` / ``_set_norm``) and itself in messages (``_what``), and supplies ``_sizes()`` - the layer
+    widths, input first - and ``_norm_spec()`` - the ``(key, length)`` pairs of its normalisation dict, in the C argument order."""
 
-    def __init__(self, obs_dim, act_dim, hidden_sizes, hidden_act, device=None):
+    _prefix = None
+    _what = None
+
+    def __init__(self, dims, hidden_sizes, hidden_act, device=None):
         if not torch.cuda.is_available():
-            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the reward scorer is HIP-only (there is no CPU fallback)")
+            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the %s is HIP-only (there is no CPU fallback)" % self._what)
         if device is None:
             device = torch.cuda.current_device()
         self.ctx = _lib.Context.get(device)
         self.lib = self.ctx.lib
+        if not hasattr(self.lib, self._prefix + "_create"):
+            raise _lib.L2AError("this libl2a_hip.so has no %s (%s_create): rebuild it" % (self._what, self._prefix))
         self.device = torch.device("cuda", device)
-        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
         self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
         if hidden_act not in _lib.ACT_CODES:
             raise _lib.L2AError("nonlinearity %r is not supported by the HIP kernels" % (hidden_act,))
         hid = (ctypes.c_int * len(self.hidden_sizes))(*self.hidden_sizes)
         handle = ctypes.c_void_p()
-        rc = self.lib.l2a_reward_model_create(self.ctx.handle, self.obs_dim, self.act_dim, len(self.hidden_sizes), hid,
-                                              _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
-        self.ctx.check(rc, "l2a_reward_model_create")
+        args = tuple(dims) + (len(self.hidden_sizes), hid, _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
+        self._call("_create", self.ctx.handle, *args)
         self.handle = handle
         self._keep = {}
 
+    def _call(self, suffix, *args):
+        """``l2a_<head>_model<suffix>(*args)``, checked."""
+        self.ctx.check(getattr(self.lib, self._prefix + suffix)(*args), self._prefix + suffix)
+
     def close(self):
         if getattr(self, "handle", None):
-            self.lib.l2a_reward_model_destroy(self.handle)
+            getattr(self.lib, self._prefix + "_destroy")(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -621,40 +630,54 @@ class NativeRewardModel(object):
             pass
 
     def set_weights(self, params):
-        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]``; the first ``in`` is ``2 * obs_dim + act_dim``, the last
-        ``out`` is 1."""
+        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]`` of the widths ``_sizes()``."""
         dev = []
         for p in params:
             t = torch.as_tensor(p) if not torch.is_tensor(p) else p
             dev.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
-        sizes = (2 * self.obs_dim + self.act_dim,) + self.hidden_sizes + (1,)
+        sizes = self._sizes()
         assert len(dev) == 2 * (len(sizes) - 1), "expected %d parameter arrays" % (2 * (len(sizes) - 1))
         for li in range(len(sizes) - 1):
             assert tuple(dev[2 * li].shape) == (sizes[li], sizes[li + 1]), \
                 "kernel %d has shape %s, expected %s" % (li, tuple(dev[2 * li].shape), (sizes[li], sizes[li + 1]))
             assert tuple(dev[2 * li + 1].shape) == (sizes[li + 1],)
         ptrs = (ctypes.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
-        rc = self.lib.l2a_reward_model_set_weights(self.handle, ptrs, _stream_ptr(self.device))
-        self.ctx.check(rc, "l2a_reward_model_set_weights")
+        self._call("_set_weights", self.handle, ptrs, _stream_ptr(self.device))
         self._keep["w"] = dev
 
     def set_norm(self, norm):
-        """``norm``: dict ``'obs' / 'act' / 'delta' / 'reward' -> (mean, std)`` (reward: scalars), or ``None`` for identity."""
+        """``norm``: dict ``key -> (mean, std)`` over the keys of ``_norm_spec()``, or ``None`` for identity."""
+        spec = self._norm_spec()
         if norm is None:
-            null = ctypes.POINTER(ctypes.c_double)()
-            rc = self.lib.l2a_reward_model_set_norm(self.handle, null, null, null, null, null, null, null, null,
-                                                    _stream_ptr(self.device))
+            args = [ctypes.POINTER(ctypes.c_double)()] * (2 * len(spec))
         else:
             keep, args = [], []
-            for key in ("obs", "act", "delta", "reward"):
+            for key, expect in spec:
                 for j in (0, 1):
                     arr, p = _dvec(np.reshape(norm[key][j], -1))
-                    expect = {"act": self.act_dim, "reward": 1}.get(key, self.obs_dim)
                     assert arr.shape == (expect,), "normalization[%r] has shape %s" % (key, arr.shape)
                     keep.append(arr)
                     args.append(p)
-            rc = self.lib.l2a_reward_model_set_norm(self.handle, *args, _stream_ptr(self.device))
-        self.ctx.check(rc, "l2a_reward_model_set_norm")
+        self._call("_set_norm", self.handle, *(args + [_stream_ptr(self.device)]))
+
+
+class NativeRewardModel(_NativeHead):
+    """Python handle on an ``l2a_reward_model``: a reward MLP over ``[obs | act | next_obs - obs]`` that the planner scores
+    trajectories with on the matrix cores (``csrc/l2a_score_mlp.hip``).  Raises ``L2AError`` on any failure.  ``set_weights``:
+    the first ``in`` is ``2 * obs_dim + act_dim``, the last ``out`` is 1.  ``set_norm``: ``'obs' / 'act' / 'delta' / 'reward' ->
+    (mean, std)`` (reward: scalars)."""
+
+    _prefix, _what = "l2a_reward_model", "reward scorer"
+
+    def __init__(self, obs_dim, act_dim, hidden_sizes, hidden_act, device=None):
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        _NativeHead.__init__(self, (self.obs_dim, self.act_dim), hidden_sizes, hidden_act, device)
+
+    def _sizes(self):
+        return (2 * self.obs_dim + self.act_dim,) + self.hidden_sizes + (1,)
+
+    def _norm_spec(self):
+        return (("obs", self.obs_dim), ("act", self.act_dim), ("delta", self.obs_dim), ("reward", 1))
 
     def predict(self, obs, act, next_obs, out=None):
         """fp32 CUDA ``[rows, obs_dim]``, ``[rows, act_dim]``, ``[rows, obs_dim]`` -> fp32 CUDA ``[rows]``."""
@@ -686,77 +709,22 @@ class NativeRewardModel(object):
         self.ctx.check(rc, "l2a_score_trajectory_model")
 
 
-class NativePolicyModel(object):
+class NativePolicyModel(_NativeHead):
     """Python handle on an ``l2a_policy_model``: a policy MLP over the observation that proposes planning candidates, evaluated
-    on the matrix cores (``csrc/l2a_policy.hip``).  Raises ``L2AError`` on any failure."""
+    on the matrix cores (``csrc/l2a_policy.hip``).  Raises ``L2AError`` on any failure.  ``set_weights``: the first ``in`` is
+    ``obs_dim``, the last ``out`` is ``act_dim``.  ``set_norm``: ``'obs' / 'act' -> (mean, std)``."""
+
+    _prefix, _what = "l2a_policy_model", "policy kernel"
 
     def __init__(self, obs_dim, act_dim, hidden_sizes, hidden_act, device=None):
-        if not torch.cuda.is_available():
-            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the policy kernel is HIP-only (there is no CPU fallback)")
-        if device is None:
-            device = torch.cuda.current_device()
-        self.ctx = _lib.Context.get(device)
-        self.lib = self.ctx.lib
-        if not hasattr(self.lib, "l2a_policy_model_create"):
-            raise _lib.L2AError("this libl2a_hip.so has no policy kernel (l2a_policy_model_create): rebuild it")
-        self.device = torch.device("cuda", device)
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-        self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
-        if hidden_act not in _lib.ACT_CODES:
-            raise _lib.L2AError("nonlinearity %r is not supported by the HIP kernels" % (hidden_act,))
-        hid = (ctypes.c_int * len(self.hidden_sizes))(*self.hidden_sizes)
-        handle = ctypes.c_void_p()
-        rc = self.lib.l2a_policy_model_create(self.ctx.handle, self.obs_dim, self.act_dim, len(self.hidden_sizes), hid,
-                                              _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
-        self.ctx.check(rc, "l2a_policy_model_create")
-        self.handle = handle
-        self._keep = {}
+        _NativeHead.__init__(self, (self.obs_dim, self.act_dim), hidden_sizes, hidden_act, device)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.l2a_policy_model_destroy(self.handle)
-            self.handle = None
+    def _sizes(self):
+        return (self.obs_dim,) + self.hidden_sizes + (self.act_dim,)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_weights(self, params):
-        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]``; the first ``in`` is ``obs_dim``, the last ``out`` is
-        ``act_dim``."""
-        dev = []
-        for p in params:
-            t = torch.as_tensor(p) if not torch.is_tensor(p) else p
-            dev.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
-        sizes = (self.obs_dim,) + self.hidden_sizes + (self.act_dim,)
-        assert len(dev) == 2 * (len(sizes) - 1), "expected %d parameter arrays" % (2 * (len(sizes) - 1))
-        for li in range(len(sizes) - 1):
-            assert tuple(dev[2 * li].shape) == (sizes[li], sizes[li + 1]), \
-                "kernel %d has shape %s, expected %s" % (li, tuple(dev[2 * li].shape), (sizes[li], sizes[li + 1]))
-            assert tuple(dev[2 * li + 1].shape) == (sizes[li + 1],)
-        ptrs = (ctypes.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
-        rc = self.lib.l2a_policy_model_set_weights(self.handle, ptrs, _stream_ptr(self.device))
-        self.ctx.check(rc, "l2a_policy_model_set_weights")
-        self._keep["w"] = dev
-
-    def set_norm(self, norm):
-        """``norm``: dict ``'obs' / 'act' -> (mean, std)``, or ``None`` for identity."""
-        if norm is None:
-            null = ctypes.POINTER(ctypes.c_double)()
-            rc = self.lib.l2a_policy_model_set_norm(self.handle, null, null, null, null, _stream_ptr(self.device))
-        else:
-            keep, args = [], []
-            for key in ("obs", "act"):
-                for j in (0, 1):
-                    arr, p = _dvec(np.reshape(norm[key][j], -1))
-                    expect = self.act_dim if key == "act" else self.obs_dim
-                    assert arr.shape == (expect,), "normalization[%r] has shape %s" % (key, arr.shape)
-                    keep.append(arr)
-                    args.append(p)
-            rc = self.lib.l2a_policy_model_set_norm(self.handle, *args, _stream_ptr(self.device))
-        self.ctx.check(rc, "l2a_policy_model_set_norm")
+    def _norm_spec(self):
+        return (("obs", self.obs_dim), ("act", self.act_dim))
 
     def act(self, states, sigma, low, high, z=None, seed=0, offset=0, out=None):
         """The kernel alone (``l2a_policy_act``): fp32 CUDA ``[rows, obs_dim]`` -> fp32 CUDA ``[rows, act_dim]``.  ``sigma`` /
@@ -778,75 +746,23 @@ class NativePolicyModel(object):
         return out
 
 
-class NativeValueModel(object):
+class NativeValueModel(_NativeHead):
     """Python handle on an ``l2a_value_model``: a value MLP over the observation that the planner adds, evaluated on every
     candidate's last predicted state, to the returns on the matrix cores (``csrc/l2a_value.hip``).  Raises ``L2AError`` on any
-    failure."""
+    failure.  ``set_weights``: the first ``in`` is ``obs_dim``, the last ``out`` is 1.  ``set_norm``: ``'obs' / 'value' ->
+    (mean, std)`` (value: scalars)."""
+
+    _prefix, _what = "l2a_value_model", "value kernel"
 
     def __init__(self, obs_dim, hidden_sizes, hidden_act, device=None):
-        if not torch.cuda.is_available():
-            raise _lib.L2AError("no MI355X visible to PyTorch-ROCm: the value kernel is HIP-only (there is no CPU fallback)")
-        if device is None:
-            device = torch.cuda.current_device()
-        self.ctx = _lib.Context.get(device)
-        self.lib = self.ctx.lib
-        self.device = torch.device("cuda", device)
         self.obs_dim = int(obs_dim)
-        self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
-        if hidden_act not in _lib.ACT_CODES:
-            raise _lib.L2AError("nonlinearity %r is not supported by the HIP kernels" % (hidden_act,))
-        hid = (ctypes.c_int * len(self.hidden_sizes))(*self.hidden_sizes)
-        handle = ctypes.c_void_p()
-        rc = self.lib.l2a_value_model_create(self.ctx.handle, self.obs_dim, len(self.hidden_sizes), hid,
-                                             _lib.ACT_CODES[hidden_act], ctypes.byref(handle))
-        self.ctx.check(rc, "l2a_value_model_create")
-        self.handle = handle
-        self._keep = {}
+        _NativeHead.__init__(self, (self.obs_dim,), hidden_sizes, hidden_act, device)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.l2a_value_model_destroy(self.handle)
-            self.handle = None
+    def _sizes(self):
+        return (self.obs_dim,) + self.hidden_sizes + (1,)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_weights(self, params):
-        """``params``: [W0, b0, ..., Wout, bout], kernels ``[in, out]``; the first ``in`` is ``obs_dim``, the last ``out`` is 1."""
-        dev = []
-        for p in params:
-            t = torch.as_tensor(p) if not torch.is_tensor(p) else p
-            dev.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
-        sizes = (self.obs_dim,) + self.hidden_sizes + (1,)
-        assert len(dev) == 2 * (len(sizes) - 1), "expected %d parameter arrays" % (2 * (len(sizes) - 1))
-        for li in range(len(sizes) - 1):
-            assert tuple(dev[2 * li].shape) == (sizes[li], sizes[li + 1]), \
-                "kernel %d has shape %s, expected %s" % (li, tuple(dev[2 * li].shape), (sizes[li], sizes[li + 1]))
-            assert tuple(dev[2 * li + 1].shape) == (sizes[li + 1],)
-        ptrs = (ctypes.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
-        rc = self.lib.l2a_value_model_set_weights(self.handle, ptrs, _stream_ptr(self.device))
-        self.ctx.check(rc, "l2a_value_model_set_weights")
-        self._keep["w"] = dev
-
-    def set_norm(self, norm):
-        """``norm``: dict ``'obs' / 'value' -> (mean, std)`` (value: scalars), or ``None`` for identity."""
-        if norm is None:
-            null = ctypes.POINTER(ctypes.c_double)()
-            rc = self.lib.l2a_value_model_set_norm(self.handle, null, null, null, null, _stream_ptr(self.device))
-        else:
-            keep, args = [], []
-            for key in ("obs", "value"):
-                for j in (0, 1):
-                    arr, p = _dvec(np.reshape(norm[key][j], -1))
-                    expect = 1 if key == "value" else self.obs_dim
-                    assert arr.shape == (expect,), "normalization[%r] has shape %s" % (key, arr.shape)
-                    keep.append(arr)
-                    args.append(p)
-            rc = self.lib.l2a_value_model_set_norm(self.handle, *args, _stream_ptr(self.device))
-        self.ctx.check(rc, "l2a_value_model_set_norm")
+    def _norm_spec(self):
+        return (("obs", self.obs_dim), ("value", 1))
 
     def predict(self, states, out=None):
         """fp32 CUDA ``[rows, obs_dim]`` -> fp32 CUDA ``[rows]``."""

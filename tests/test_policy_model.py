@@ -120,6 +120,36 @@ def test_geometry_refusals():
         _lib.policy_model_geometry(20, 6, (96,), 100)
 
 
+@pytest.mark.parametrize("hidden", [(64,), (256, 64), (512, 512, 512)])
+@pytest.mark.parametrize("obs", [1, 17, 64])
+def test_value_and_policy_kernels_share_one_geometry_rule(hidden, obs):
+    """``l2a_value_model_geometry`` and ``l2a_policy_model_geometry`` go through one ``choose_rt``: the same network and row count
+    give the same (RT, workgroups, LDS bytes), whatever the policy's ``act_dim``."""
+    for rows in (1, 16, 17, 16 * 256, 16 * 256 * 8 + 1):
+        for cus in (256, 1):
+            for lds in (65536, 163840):
+                v = _lib.value_model_geometry(obs, hidden, rows, cus=cus, lds_per_block=lds)
+                p = _lib.policy_model_geometry(obs, 6, hidden, rows, cus=cus, lds_per_block=lds)
+                assert v == p and set(v) == {"RT", "workgroups", "lds_bytes"}, (rows, cus, lds, v, p)
+                assert v["workgroups"] == (rows + 16 * v["RT"] - 1) // (16 * v["RT"])
+
+
+@pytest.mark.parametrize("hidden,code,word", [
+    ((0,), 1, "hidden width 0 "), ((32,), 1, "hidden width 32 "), ((96,), 1, "hidden width 96 "), ((576,), 1, "hidden width 576 "),
+    ((64, 96), 1, "hidden width 96 "), ((), 1, "0 hidden layers"), ((64, 64, 64, 64), 1, "4 hidden layers"),
+    ((64,), -1, "unknown activation -1"), ((64,), 5, "unknown activation 5"), ((64,), 100, "unknown activation 100")])
+def test_the_three_model_checks_reject_the_same_networks_with_the_same_words(hidden, code, word):
+    """The reward, value and policy model checks are one function behind three prefixes."""
+    msgs = {"reward model: ": _lib.reward_model_check(20, 6, hidden, code),
+            "value model: ": _lib.value_model_check(20, hidden, code),
+            "policy model: ": _lib.policy_model_check(20, 6, hidden, code)}
+    tails = set()
+    for prefix, msg in msgs.items():
+        assert msg is not None and msg.startswith(prefix), (prefix, msg)
+        tails.add(msg[len(prefix):])
+    assert len(tails) == 1 and tails.pop().startswith(word), msgs
+
+
 # ------------------------------------------------------------------------------------------
 # 3. MLPPolicyModel
 # ------------------------------------------------------------------------------------------
